@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — env-steps/sec/GPU on the BASELINE.json workload (3 jammers / 4 radars, batch_envs=4096).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode env|rollout|train] [--sweep]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode env|rollout|train] [--dump-outputs DIR] [--full] [--sweep]
 
 One "step" = one pass of the hot path over one batch of E environments per GPU.  Modes:
   env      the HIP env-step kernel alone (Philox uniforms in-kernel, synthetic actions resident in HBM)
@@ -10,8 +10,10 @@ One "step" = one pass of the hot path over one batch of E environments per GPU. 
 For N>1 launch through torch.distributed.run (one rank per GPU, RCCL); envs shard across ranks with
 no data-path collective in env/rollout mode ("weak" scaling); train mode all-reduces the gradients.
 
-Prints ONE JSON line (rank 0) with the contract keys plus `roofline` (env-step kernel, HBM bound,
-timed with HIP events on the launch stream) and `cpu_baseline` (the C oracle timed on host cores).
+Prints ONE JSON line (rank 0) with the contract keys.  A plain run sets up, warms up, times the K steps and
+reports them.  --full adds the other modes, `roofline` (env-step kernel, HBM bound, timed with HIP events on
+the launch stream), the MFMA rooflines and `cpu_baseline` (the C oracle timed on host cores).
+--dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy (float32).
 """
 import argparse
 import json
@@ -114,7 +116,7 @@ def pmc_traffic(J, R, E, per_env=False, many=False):
 
 def profiled_kernel_time(kernel_substr, per_env=False, pattern=None):
     """(average us, min us, calls, file) of a kernel in the latest committed rocprofv3 --kernel-trace --stats summary of
-    the env-roofline replay (scripts/collect_profiles.sh: `bench.py --mode env --steps 1 --warmup 0`, i.e. the 200-launch
+    the env-roofline replay (scripts/collect_profiles.sh: `bench.py --mode env --steps 1 --warmup 0 --full`, i.e. the 200-launch
     graph of macjd_env_step_timed, warm + timed); None when no such file."""
     import csv
     import glob
@@ -155,6 +157,63 @@ def time_graph_replay(fn, dev, calls=20, replays=10):
     return e0.elapsed_time(e1) / (calls * replays) * 1e3
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def last_step_outputs(mode, step_fn, steps, episode_limit):
+    """What the timed path handed its caller in the last timed step: {name: (tensor, index of its env axis or None)}.
+    env: the env step's outputs.  rollout / train: the staging rows of the episode batch that holds the last step (the
+    rollout writes all of them when the batch starts), the recurrent state after the last step; train adds the
+    statistics of the updates the last step issued (loss, eval_qtot_avg, target_qtot_avg, grad_norm) and the weights
+    they left behind."""
+    import torch
+    if mode == "env":
+        rew, ter, info = step_fn.last
+        return {"reward": (rew, 0), "terminated": (ter, 0),
+                "r_dpj": (torch.stack([info["r_d"], info["r_p"], info["r_j"]], 1), 0),
+                "radar_tracking": (info["radar_tracking"], 0), "step_count": (info["step_count"], 0),
+                "radar_pds": (info["radar_pds"], 0), "snr_with_jamming": (info["snr_with_jamming"], 0)}
+    n = (steps - 1) % episode_limit + 1
+    st = step_fn.runner.stage
+    out = {"reward": (st["reward"][:n, :, 0], 1), "terminated": (st["terminated"][:n, :, 0], 1),
+           "actions_discrete": (st["actions_discrete"][:n, :, :, 0], 1),
+           "actions_continuous": (st["actions_continuous"][:n, :, :, 0], 1),
+           "hidden_state": (st["hidden_state"][n - 1], 0)}
+    if mode == "train":
+        keys = ("loss", "eval_qtot_avg", "target_qtot_avg", "grad_norm")
+        rows = [torch.stack([torch.as_tensor(u[k]).reshape(()).float().cpu() for k in keys]) if isinstance(u, dict)
+                else u.reshape(4).float().cpu() for u in step_fn.state["updates"]]
+        out["update_stats"] = (torch.stack(rows), None)
+        learner = step_fn.learner
+        for prefix, net in (("agent.", learner.mac.agent), ("mixer.", learner.eval_qmix_net)):
+            for k, p in net.named_parameters():
+                out[prefix + k] = (p, None)
+    return out
+
+
+def dump_outputs(out_dir, arrays, n_envs):
+    """Writes ``arrays`` (see last_step_outputs) as out_dir/<name>.npy in float32.  When they come to more than
+    DUMP_MAX_BYTES, every per-env array keeps the same fixed, seeded sample of envs, whose indices go to env_index.npy."""
+    import numpy as np
+    import torch
+    per_env = sum(t.numel() // n_envs for t, ax in arrays.values() if ax is not None) * 4
+    shared = sum(t.numel() for t, ax in arrays.values() if ax is None) * 4
+    keep = None
+    if shared + per_env * n_envs > DUMP_MAX_BYTES:
+        k = (DUMP_MAX_BYTES - shared) // (per_env + 8)
+        if k < 1:
+            raise RuntimeError(f"--dump-outputs: the shared outputs alone exceed {DUMP_MAX_BYTES} bytes")
+        keep = np.sort(np.random.default_rng(0).choice(n_envs, int(k), replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    if keep is not None:
+        np.save(os.path.join(out_dir, "env_index.npy"), keep.astype(np.float64))
+    for name, (t, ax) in arrays.items():
+        t = t.detach()
+        if keep is not None and ax is not None:
+            t = t.index_select(ax, torch.as_tensor(keep, device=t.device))
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -167,10 +226,15 @@ def main():
     ap.add_argument("--hidden", type=int, default=64)
     ap.add_argument("--mixer-dtype", dest="mixer_dtype", default="fp32", choices=["fp32", "bf16"],
                     help="bf16: BASELINE.json config 5's hyper-network option (library GEMMs with bf16 inputs; outside the 1e-5 bar)")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the other modes, the env-step and MFMA rooflines and the CPU baseline "
+                         "(default: only the timed steps of --mode)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32, <= 64 MB)")
     ap.add_argument("--sweep", action="store_true", help="also print an E-sweep of the env kernel (stderr)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-other-modes", dest="no_other_modes", action="store_true",
-                    help="measure only --mode (default: the other two modes of SURVEY.md 8(d) are timed briefly as well)")
+                    help="--full without the other two modes of SURVEY.md 8(d) (timed briefly otherwise)")
     ap.add_argument("--per-env-scenarios", dest="per_env", action="store_true",
                     help="every env gets its own randomised scenario (positions / threat / powers): tables streamed from HBM")
     ap.add_argument("--no-graphs", dest="no_graphs", action="store_true", help="eager launches (A/B against HIP graphs)")
@@ -239,7 +303,7 @@ def main():
             def fn(i):
                 if i % sc.episode_limit == 0:
                     env_.reset()
-                env_.step(T, P)
+                fn.last = env_.step(T, P)   # (views of the env's output buffers: no copy, no sync)
             return fn, {}
         if which == "env_many_step":
             # the env kernel as the rollout launches it: all steps of an episode batch in ONE launch (macjd_env_step_many),
@@ -277,152 +341,154 @@ def main():
     step_fn, extra = build_step(mode, env, args)
     dt = timed(step_fn, args.warmup, args.steps)
 
-    # ---- the other two modes of SURVEY.md 8(d) in the same run (single process; shorter regions) ----
     modes = {mode: round(dt / args.steps * 1e3, 4)}
-    if world == 1 and bench_mod is not None and not args.no_other_modes:
-        for which in ("env", "env_many_step", "rollout", "train"):
-            if which in modes or (which == "env_many_step" and (args.per_env or E * sc.episode_limit > (1 << 24))):
-                continue
-            e2 = make_env()
-            e2.reset()
-            cli2 = argparse.Namespace(**vars(args))
-            cli2.steps, cli2.warmup = (300, 100) if which in ("rollout", "train") else (1000, 100)
-            fn2, _ = build_step(which, e2, cli2)
-            modes[which] = round(timed(fn2, cli2.warmup, cli2.steps) / cli2.steps * 1e3, 5 if which == "env_many_step" else 4)
-            del fn2
-            torch.cuda.synchronize()
-
-    # ---- roofline of the env-step kernel: HIP events on the launch stream ----
-    # (1) the launch the rollout / train modes actually issue: ONE launch for the T = episode_limit steps of all E envs
-    #     (macjd_env_step_many: T x E independent work items in the streaming lane kernel; no pd / snr_with outputs,
-    #     `track` and the counters written once per env).  (2) the single-step launch of the step-by-step API at the
-    #     same E (what `mode: env` issues; launch-latency bound).  (3) below: the 2^22-env streaming point.
-    ms = env.time_step_kernel(T, P, iters=200)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_step_outputs(mode, step_fn, args.steps, sc.episode_limit), E)
     B_step = algorithmic_bytes_per_env_step(J, R, uniforms_supplied=False) + (per_env_table_bytes(J, R) if args.per_env else 0)
-    achieved = E * B_step / (ms * 1e-3) / 1e9
-    kname = (f"env_step_kernel<{J},{R},per-env tables>" if args.per_env else
-             f"env_step_slots_kernel<{J},{R}>" if E < (1 << 16) else f"env_step_kernel<{J},{R}>")
-    single = {"kernel": kname, "us_per_launch": round(ms * 1e3, 3), "achieved": round(achieved, 3),
-              "frac": round(achieved / HBM_PEAK_GBS, 6), "bytes_per_env_step": B_step, "envs_per_launch": E,
-              "traffic": pmc_traffic(J, R, E, args.per_env)[0], "traffic_source": pmc_traffic(J, R, E, args.per_env)[1]}
-    prof = profiled_kernel_time("env_step_kernel<" if (args.per_env or E >= (1 << 16)) else "env_step_slots_kernel<", args.per_env)
-    if prof is not None and E == 4096:
-        # the committed rocprofv3 summary of the same replay: its per-dispatch duration (start -> end timestamps of ONE
-        # dispatch, taken with the dispatches serialised by the profiler) is ~0.7 us above the back-to-back figure the
-        # HIP events give for a launch this short; both are stated, `frac` uses the live HIP-event time
-        single["profile"] = {"file": prof[3], "avg_us": round(prof[0], 3), "min_us": round(prof[1], 3), "calls": prof[2],
-                             "frac_from_avg": round(E * B_step / (prof[0] * 1e-6) / 1e9 / HBM_PEAK_GBS, 6)}
-    Tn = sc.episode_limit
-    Tm = torch.randint(0, 2 * R + 1, (Tn, E, J), generator=g, device=dev, dtype=torch.int32)
-    Pm = torch.rand((Tn, E, J), generator=g, device=dev)
-    rew_m = torch.zeros((Tn, E), device=dev)
-    ter_m = torch.zeros((Tn, E), dtype=torch.uint8, device=dev)
-    rd_m = torch.zeros((Tn, E, 3), device=dev)
-    env.time_step_many_kernel(Tm, Pm, rew_m, ter_m, rd_m, iters=3)
-    ms_m = env.time_step_many_kernel(Tm, Pm, rew_m, ter_m, rd_m, iters=50)
-    # algorithmic (compulsory) bytes per env-step of THIS launch: T 4J + P 4J read, reward 4 + (r_d,r_p,r_j) 12 +
-    # terminated 1 written by every work item; the env's step counter 4 + episode index 4 are read by each of its T work
-    # items but are ONE HBM read per env (the other T - 1 hit L2: PMC traffic = 1.01x this count), and track R is written
-    # once per env: (8 + R) / T per env-step; per-env tables likewise — an env's table column is read by each of its T work
-    # items but comes from HBM once
-    B_many = 8 * J + 4 + 12 + 1 + (8 + R + (per_env_table_bytes(J, R) if args.per_env else 0)) / Tn
-    ach_m = Tn * E * B_many / (ms_m * 1e-3) / 1e9
-    roofline = {"bound": "hbm", "achieved": round(ach_m, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(ach_m / HBM_PEAK_GBS, 6), "traffic": pmc_traffic(J, R, E, args.per_env, many=True)[0],
-                "traffic_source": pmc_traffic(J, R, E, args.per_env, many=True)[1],
-                "kernel": f"env_step_kernel<{J},{R}" + (",per-env tables" if args.per_env else "") +
-                          f"> as launched by the rollout: {Tn} steps x {E} envs = {Tn * E} work items per launch (macjd_env_step_many)",
-                "us_per_launch": round(ms_m * 1e3, 3),
-                "timing": "HIP events around 50 launches replayed from one HIP graph on their own stream (macjd_env_step_many_timed); "
-                          "the committed rocprofv3 kernel-trace summary of this launch alone is quoted under 'profile'",
-                "traffic_measured_in_run": False,
-                "limiter": "VALU issue, not HBM: ~735 VALU instructions per env-step at 3j/4r (~145 float64 for the power / received-power "
-                           "quotients, 2 Philox blocks = 40 quarter-rate 32 x 32 multiplies, float32 SNR / detection probabilities "
-                           "with a float64 fallback for compares within 4e-6) for 41 bytes; traffic = 1.01x algorithmic (DESIGN.md 4.1)",
-                "bytes_per_env_step": round(B_many, 2), "env_steps_per_launch": Tn * E,
-                "single_step_launch": single}
-    prof_m = profiled_kernel_time("env_step_kernel<", args.per_env, pattern=f"r*_env_many_step_{J}j{R}r_kernel_stats.csv")
-    if prof_m is not None and E == 4096 and not args.per_env:
-        roofline["profile"] = {"file": prof_m[3], "avg_us": round(prof_m[0], 3), "min_us": round(prof_m[1], 3), "calls": prof_m[2],
-                               "note": "rocprofv3 --kernel-trace --stats of scripts/replay_many_step.py: this launch alone"}
-    del Tm, Pm, rew_m, ter_m, rd_m
-    # large-batch point of the same kernel family (2^22 envs): the HBM-bound asymptote, measured every run so the
-    # launch-bound fraction at the benchmark's E is not mistaken for the kernel's streaming rate
-    if rank == 0:
-        Eb = 1 << 22
-        if args.per_env:   # the 4096 compiled scenarios, cycled
-            eb = BatchedElectromagneticEnvironment(scenario_batch=batch.tile(Eb), device=dev, seed=1)
-        else:
-            eb = BatchedElectromagneticEnvironment(scenario=sc, batch_envs=Eb, device=dev, seed=1)
-        Tb = torch.randint(0, 2 * R + 1, (J, Eb), generator=g, device=dev, dtype=torch.int32).t()
-        Pb = torch.rand((J, Eb), generator=g, device=dev).t()
-        eb.time_step_kernel(Tb, Pb, iters=3)
-        mb = eb.time_step_kernel(Tb, Pb, iters=20)
-        gb = Eb * B_step / (mb * 1e-3) / 1e9
-        roofline["large_batch"] = {"envs_per_launch": Eb, "us_per_launch": round(mb * 1e3, 2), "achieved": round(gb, 1),
-                                   "frac": round(gb / HBM_PEAK_GBS, 4),
-                                   "kernel": f"env_step_kernel<{J},{R}" + (",per-env tables>" if args.per_env else ">"),
-                                   "traffic": pmc_traffic(J, R, Eb, args.per_env)[0]}
-        eb.close()
-        del eb, Tb, Pb
-    # ---- MFMA-bound kernel of the path: the actor's fused dense chain (exact-f32 v_mfma_f32_16x16x4_f32) ----
-    roofline_mfma = None
-    if rank == 0:
-        try:
-            from macjd_amd import ops
-            A_, S_, N_rows = 2 * R + 1, sc.state_dim, E * J
-            dims = (S_, 128, 128, A_)
-            if ops.mlp_supported(list(dims)):
-                layers = [(torch.randn(dims[l + 1], dims[l], device=dev) / dims[l] ** 0.5,
-                           torch.randn(dims[l + 1], device=dev) * 0.1, (1, 1, 2)[l]) for l in range(3)]
+    roofline = roofline_mfma = roofline_mixer = None
+    if args.full:
+        # ---- the other two modes of SURVEY.md 8(d) in the same run (single process; shorter regions) ----
+        if world == 1 and bench_mod is not None and not args.no_other_modes:
+            for which in ("env", "env_many_step", "rollout", "train"):
+                if which in modes or (which == "env_many_step" and (args.per_env or E * sc.episode_limit > (1 << 24))):
+                    continue
+                e2 = make_env()
+                e2.reset()
+                cli2 = argparse.Namespace(**vars(args))
+                cli2.steps, cli2.warmup = (300, 100) if which in ("rollout", "train") else (1000, 100)
+                fn2, _ = build_step(which, e2, cli2)
+                modes[which] = round(timed(fn2, cli2.warmup, cli2.steps) / cli2.steps * 1e3, 5 if which == "env_many_step" else 4)
+                del fn2
+                torch.cuda.synchronize()
 
-                def time_chain(n_rows, calls=20, replays=10):
-                    xs = torch.randn(n_rows, S_, device=dev)
-                    with torch.no_grad():
-                        side = torch.cuda.Stream(device=dev)
-                        side.wait_stream(torch.cuda.current_stream(dev))
-                        with torch.cuda.stream(side):
-                            for _ in range(3):
-                                ops.mlp_forward(xs, layers)
-                        torch.cuda.current_stream(dev).wait_stream(side)
-                        gr = torch.cuda.CUDAGraph()
-                        with torch.cuda.graph(gr):
-                            for _ in range(calls):
-                                ops.mlp_forward(xs, layers)
-                        gr.replay()
-                        torch.cuda.synchronize()
-                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        e0.record()
-                        for _ in range(replays):
+        # ---- roofline of the env-step kernel: HIP events on the launch stream ----
+        # (1) the launch the rollout / train modes actually issue: ONE launch for the T = episode_limit steps of all E envs
+        #     (macjd_env_step_many: T x E independent work items in the streaming lane kernel; no pd / snr_with outputs,
+        #     `track` and the counters written once per env).  (2) the single-step launch of the step-by-step API at the
+        #     same E (what `mode: env` issues; launch-latency bound).  (3) below: the 2^22-env streaming point.
+        ms = env.time_step_kernel(T, P, iters=200)
+        achieved = E * B_step / (ms * 1e-3) / 1e9
+        kname = (f"env_step_kernel<{J},{R},per-env tables>" if args.per_env else
+                 f"env_step_slots_kernel<{J},{R}>" if E < (1 << 16) else f"env_step_kernel<{J},{R}>")
+        single = {"kernel": kname, "us_per_launch": round(ms * 1e3, 3), "achieved": round(achieved, 3),
+                  "frac": round(achieved / HBM_PEAK_GBS, 6), "bytes_per_env_step": B_step, "envs_per_launch": E,
+                  "traffic": pmc_traffic(J, R, E, args.per_env)[0], "traffic_source": pmc_traffic(J, R, E, args.per_env)[1]}
+        prof = profiled_kernel_time("env_step_kernel<" if (args.per_env or E >= (1 << 16)) else "env_step_slots_kernel<", args.per_env)
+        if prof is not None and E == 4096:
+            # the committed rocprofv3 summary of the same replay: its per-dispatch duration (start -> end timestamps of ONE
+            # dispatch, taken with the dispatches serialised by the profiler) is ~0.7 us above the back-to-back figure the
+            # HIP events give for a launch this short; both are stated, `frac` uses the live HIP-event time
+            single["profile"] = {"file": prof[3], "avg_us": round(prof[0], 3), "min_us": round(prof[1], 3), "calls": prof[2],
+                                 "frac_from_avg": round(E * B_step / (prof[0] * 1e-6) / 1e9 / HBM_PEAK_GBS, 6)}
+        Tn = sc.episode_limit
+        Tm = torch.randint(0, 2 * R + 1, (Tn, E, J), generator=g, device=dev, dtype=torch.int32)
+        Pm = torch.rand((Tn, E, J), generator=g, device=dev)
+        rew_m = torch.zeros((Tn, E), device=dev)
+        ter_m = torch.zeros((Tn, E), dtype=torch.uint8, device=dev)
+        rd_m = torch.zeros((Tn, E, 3), device=dev)
+        env.time_step_many_kernel(Tm, Pm, rew_m, ter_m, rd_m, iters=3)
+        ms_m = env.time_step_many_kernel(Tm, Pm, rew_m, ter_m, rd_m, iters=50)
+        # algorithmic (compulsory) bytes per env-step of THIS launch: T 4J + P 4J read, reward 4 + (r_d,r_p,r_j) 12 +
+        # terminated 1 written by every work item; the env's step counter 4 + episode index 4 are read by each of its T work
+        # items but are ONE HBM read per env (the other T - 1 hit L2: PMC traffic = 1.01x this count), and track R is written
+        # once per env: (8 + R) / T per env-step; per-env tables likewise — an env's table column is read by each of its T work
+        # items but comes from HBM once
+        B_many = 8 * J + 4 + 12 + 1 + (8 + R + (per_env_table_bytes(J, R) if args.per_env else 0)) / Tn
+        ach_m = Tn * E * B_many / (ms_m * 1e-3) / 1e9
+        roofline = {"bound": "hbm", "achieved": round(ach_m, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(ach_m / HBM_PEAK_GBS, 6), "traffic": pmc_traffic(J, R, E, args.per_env, many=True)[0],
+                    "traffic_source": pmc_traffic(J, R, E, args.per_env, many=True)[1],
+                    "kernel": f"env_step_kernel<{J},{R}" + (",per-env tables" if args.per_env else "") +
+                              f"> as launched by the rollout: {Tn} steps x {E} envs = {Tn * E} work items per launch (macjd_env_step_many)",
+                    "us_per_launch": round(ms_m * 1e3, 3),
+                    "timing": "HIP events around 50 launches replayed from one HIP graph on their own stream (macjd_env_step_many_timed); "
+                              "the committed rocprofv3 kernel-trace summary of this launch alone is quoted under 'profile'",
+                    "traffic_measured_in_run": False,
+                    "limiter": "VALU issue, not HBM: ~735 VALU instructions per env-step at 3j/4r (~145 float64 for the power / received-power "
+                               "quotients, 2 Philox blocks = 40 quarter-rate 32 x 32 multiplies, float32 SNR / detection probabilities "
+                               "with a float64 fallback for compares within 4e-6) for 41 bytes; traffic = 1.01x algorithmic (DESIGN.md 4.1)",
+                    "bytes_per_env_step": round(B_many, 2), "env_steps_per_launch": Tn * E,
+                    "single_step_launch": single}
+        prof_m = profiled_kernel_time("env_step_kernel<", args.per_env, pattern=f"r*_env_many_step_{J}j{R}r_kernel_stats.csv")
+        if prof_m is not None and E == 4096 and not args.per_env:
+            roofline["profile"] = {"file": prof_m[3], "avg_us": round(prof_m[0], 3), "min_us": round(prof_m[1], 3), "calls": prof_m[2],
+                                   "note": "rocprofv3 --kernel-trace --stats of scripts/replay_many_step.py: this launch alone"}
+        del Tm, Pm, rew_m, ter_m, rd_m
+        # large-batch point of the same kernel family (2^22 envs): the HBM-bound asymptote, measured every run so the
+        # launch-bound fraction at the benchmark's E is not mistaken for the kernel's streaming rate
+        if rank == 0:
+            Eb = 1 << 22
+            if args.per_env:   # the 4096 compiled scenarios, cycled
+                eb = BatchedElectromagneticEnvironment(scenario_batch=batch.tile(Eb), device=dev, seed=1)
+            else:
+                eb = BatchedElectromagneticEnvironment(scenario=sc, batch_envs=Eb, device=dev, seed=1)
+            Tb = torch.randint(0, 2 * R + 1, (J, Eb), generator=g, device=dev, dtype=torch.int32).t()
+            Pb = torch.rand((J, Eb), generator=g, device=dev).t()
+            eb.time_step_kernel(Tb, Pb, iters=3)
+            mb = eb.time_step_kernel(Tb, Pb, iters=20)
+            gb = Eb * B_step / (mb * 1e-3) / 1e9
+            roofline["large_batch"] = {"envs_per_launch": Eb, "us_per_launch": round(mb * 1e3, 2), "achieved": round(gb, 1),
+                                       "frac": round(gb / HBM_PEAK_GBS, 4),
+                                       "kernel": f"env_step_kernel<{J},{R}" + (",per-env tables>" if args.per_env else ">"),
+                                       "traffic": pmc_traffic(J, R, Eb, args.per_env)[0]}
+            eb.close()
+            del eb, Tb, Pb
+        # ---- MFMA-bound kernel of the path: the actor's fused dense chain (exact-f32 v_mfma_f32_16x16x4_f32) ----
+        if rank == 0:
+            try:
+                from macjd_amd import ops
+                A_, S_, N_rows = 2 * R + 1, sc.state_dim, E * J
+                dims = (S_, 128, 128, A_)
+                if ops.mlp_supported(list(dims)):
+                    layers = [(torch.randn(dims[l + 1], dims[l], device=dev) / dims[l] ** 0.5,
+                               torch.randn(dims[l + 1], device=dev) * 0.1, (1, 1, 2)[l]) for l in range(3)]
+
+                    def time_chain(n_rows, calls=20, replays=10):
+                        xs = torch.randn(n_rows, S_, device=dev)
+                        with torch.no_grad():
+                            side = torch.cuda.Stream(device=dev)
+                            side.wait_stream(torch.cuda.current_stream(dev))
+                            with torch.cuda.stream(side):
+                                for _ in range(3):
+                                    ops.mlp_forward(xs, layers)
+                            torch.cuda.current_stream(dev).wait_stream(side)
+                            gr = torch.cuda.CUDAGraph()
+                            with torch.cuda.graph(gr):
+                                for _ in range(calls):
+                                    ops.mlp_forward(xs, layers)
                             gr.replay()
-                        e1.record()
-                        torch.cuda.synchronize()
-                    us_ = e0.elapsed_time(e1) / (calls * replays) * 1e3
-                    fl = 2.0 * n_rows * (dims[0] * dims[1] + dims[1] * dims[2] + dims[2] * dims[3])
-                    return us_, fl, fl / (us_ * 1e-6) / 1e12
+                            torch.cuda.synchronize()
+                            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                            e0.record()
+                            for _ in range(replays):
+                                gr.replay()
+                            e1.record()
+                            torch.cuda.synchronize()
+                        us_ = e0.elapsed_time(e1) / (calls * replays) * 1e3
+                        fl = 2.0 * n_rows * (dims[0] * dims[1] + dims[1] * dims[2] + dims[2] * dims[3])
+                        return us_, fl, fl / (us_ * 1e-6) / 1e12
 
-                us, flops, tf = time_chain(N_rows)
-                roofline_mfma = {"bound": "mfma", "achieved": round(tf, 2), "peak": 157.3, "unit": "TFLOP/s",
-                                 "frac": round(tf / 157.3, 4), "traffic": None,
-                                 "kernel": "mlp_forward_kernel (actor %d-%d-%d-%d, %d rows)" % (*dims, N_rows),
-                                 "us_per_call": round(us, 2), "flops_per_call": int(flops), "dtype": "f32 (exact-f32 MFMA)"}
-                # streaming-size point of the same kernel (16x the rows: every workgroup stages the weights once and
-                # walks 12 tiles), so the launch / staging-bound fraction at the benchmark's size is not mistaken for
-                # the kernel's matrix-core rate
-                Nb = 16 * N_rows
-                usb, flb, tfb = time_chain(Nb, calls=5, replays=5)
-                roofline_mfma["large_batch"] = {"rows": Nb, "us_per_call": round(usb, 2), "achieved": round(tfb, 2),
-                                                "frac": round(tfb / 157.3, 4)}
-        except Exception as ex:  # the HBM roofline above is the contract item; this one is additional
-            roofline_mfma = {"error": str(ex)[:200]}
-    # ---- MFMA fraction of the mixer's hyper_w_1 network (2 M (S 128 + 128 J 64) flop over the learner's
-    # M = batch x (T + 1) rows) as the learner evaluates it ----
-    roofline_mixer = None
-    if rank == 0 and bench_mod is not None:
-        try:
-            roofline_mixer = bench_mod.mixer_hyper_w1_roofline(sc, args.hidden, dev, 32 * (sc.episode_limit + 1), time_graph_replay)
-        except Exception as ex:
-            roofline_mixer = {"error": str(ex)[:200]}
+                    us, flops, tf = time_chain(N_rows)
+                    roofline_mfma = {"bound": "mfma", "achieved": round(tf, 2), "peak": 157.3, "unit": "TFLOP/s",
+                                     "frac": round(tf / 157.3, 4), "traffic": None,
+                                     "kernel": "mlp_forward_kernel (actor %d-%d-%d-%d, %d rows)" % (*dims, N_rows),
+                                     "us_per_call": round(us, 2), "flops_per_call": int(flops), "dtype": "f32 (exact-f32 MFMA)"}
+                    # streaming-size point of the same kernel (16x the rows: every workgroup stages the weights once and
+                    # walks 12 tiles), so the launch / staging-bound fraction at the benchmark's size is not mistaken for
+                    # the kernel's matrix-core rate
+                    Nb = 16 * N_rows
+                    usb, flb, tfb = time_chain(Nb, calls=5, replays=5)
+                    roofline_mfma["large_batch"] = {"rows": Nb, "us_per_call": round(usb, 2), "achieved": round(tfb, 2),
+                                                    "frac": round(tfb / 157.3, 4)}
+            except Exception as ex:  # the HBM roofline above is the contract item; this one is additional
+                roofline_mfma = {"error": str(ex)[:200]}
+        # ---- MFMA fraction of the mixer's hyper_w_1 network (2 M (S 128 + 128 J 64) flop over the learner's
+        # M = batch x (T + 1) rows) as the learner evaluates it ----
+        if rank == 0 and bench_mod is not None:
+            try:
+                roofline_mixer = bench_mod.mixer_hyper_w1_roofline(sc, args.hidden, dev, 32 * (sc.episode_limit + 1), time_graph_replay)
+            except Exception as ex:
+                roofline_mixer = {"error": str(ex)[:200]}
     sweep = None
     if args.sweep and rank == 0:
         sweep = []
@@ -455,7 +521,7 @@ def main():
             "config": {"workload": f"{J} jammers / {R} radars, batch_envs={E} per GPU, GRU hidden={args.hidden}"
                                    + (", per-env randomised scenarios" if args.per_env else ""),
                        "mode": mode, "per_gpu_env_steps_per_s": round(E * args.steps / dt, 1), **extra},
-            "roofline": roofline,
+            **({"roofline": roofline} if roofline is not None else {}),
             # ms per batched step of each mode of SURVEY.md 8(d): (i) env kernel only — `env`: one launch per step through
             # the single-step API (host-enqueue bound), `env_many_step`: the launch the rollout issues, all steps of an
             # episode batch at once — (ii) rollout, (iii) rollout + training
@@ -476,7 +542,7 @@ def main():
             res["roofline_mfma_mixer"] = roofline_mixer
         if sweep:
             res["env_kernel_sweep"] = sweep
-        if not args.no_cpu_baseline and world == 1:   # reported baseline: rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:   # reported baseline: rank 0 at N=1 only
             cb = cpu_baseline(sc, E, seed=42)
             res["cpu_baseline"] = {
                 "value": round(cb["all"][0], 1), "unit": "env-steps/s", "cores": cb["all"][1], "kind": "port",

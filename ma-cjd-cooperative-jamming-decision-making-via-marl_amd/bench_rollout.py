@@ -74,13 +74,14 @@ def _make_step_fn(cli, runner, learner, buf, args, T, mode, use_graphs, tails):
                 # batch were launched at t = 0 anyway); the region's remainder goes one by one
                 state["owed"] = state.get("owed", 0) + 1
                 if state["owed"] == group or j == region - 1:
-                    learner.train_from_buffer_many(state["owed"])
+                    state["updates"] = learner.train_from_buffer_many(state["owed"])
                     state["owed"] = 0
             elif use_graphs:
-                learner.train_from_buffer(sync_stats=False)
+                state["updates"] = [learner.train_from_buffer(sync_stats=False)]
             else:
-                learner.train(buf.sample(args.batch_size), None, sync_stats=False)
+                state["updates"] = [learner.train(buf.sample(args.batch_size), None, sync_stats=False)]
 
+    step_fn.state = state   # "updates": the statistics of the updates issued by the latest step that issued any
     return step_fn
 
 

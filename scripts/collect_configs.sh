@@ -5,7 +5,7 @@ TAG=${1:-r03}
 ROOT=$(pwd); OUT=$ROOT/gpurun_out; mkdir -p $OUT
 run() {  # name, bench args...
   local name=$1; shift
-  ( cd $ROOT && timeout -k 10 500 python3 bench.py "$@" 2> $OUT/${TAG}_${name}_line.err | tail -1 > $OUT/${TAG}_${name}_line.json )
+  ( cd $ROOT && timeout -k 10 500 python3 bench.py --full "$@" 2> $OUT/${TAG}_${name}_line.err | tail -1 > $OUT/${TAG}_${name}_line.json )
   echo "[configs] $name line done"
   ( cd /tmp && export TMPDIR=/tmp && rm -rf $OUT/prof_$name && \
     timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$name -o p -- python3 $ROOT/bench.py "$@" --mode train --steps 300 --warmup 100 --no-cpu-baseline --no-other-modes > /dev/null 2> $OUT/${TAG}_${name}_prof.err )

@@ -20,7 +20,7 @@ per_env = len(sys.argv) > 3 and sys.argv[3] == "per-env"
 J, R = 3, 4
 B_ALG = 89 + ((8 * (6 * R + 3 * J + J * R) + J * R) if per_env else 0)   # bench.py: algorithmic bytes per env-step
 runs = {}
-# dispatches are told apart by kernel name AND grid size (threads): a per-env pass runs bench.py once at its default
+# dispatches are told apart by kernel name AND grid size (threads): a per-env pass runs bench.py --full once at its default
 # E = 4096 and picks up the 2^22-env launches of the same kernel from bench.py's large_batch section
 for E, kern in ((4096, "env_step_kernel" if per_env else "env_step_slots_kernel"), (4194304, "env_step_kernel")):
     rec = {}
