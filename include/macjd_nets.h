@@ -491,6 +491,15 @@ int macjd_mixer_fused_backward(const macjd_mixerf_io* io, void* hip_stream);
    (stats[0..2] = loss, mean(y), mean(target) — core/qmix.py:194, 212-213; stats[3] is left alone), so that they need neither
    a launch nor a stream of their own. */
 int macjd_mixer_fused_backward_td(const macjd_mixerf_io* io, const macjd_tdloss_io* td, const float* tot_m, void* hip_stream);
+/* The learner update's two mixers, the TD loss's gradient and the eval mixer's backward as ONE launch: `eval` (save = 1,
+   with the backward's outputs gq / gout1 / g_w1raw / g_wfraw / g_v; gy is not read) and `target` (save = 0) as in
+   macjd_mixer_fused_forward_pair, `td` and `tot_m` as in macjd_mixer_fused_backward_td with the rows the loss pairs up
+   kept on chip: td->y = eval->y, td->tq = target->y + 1, y_sb = tq_sb = gy_cols > Tm1 (eval row (b, t) against target row
+   (b, t + 1)).  Every output equals forward_pair + backward_td bit for bit, except target->y at row 0, which the loss
+   never reads and this launch does not write.  td->stats is not read: the logged sums are the caller's (macjd_td_loss
+   with td->gy = NULL after this launch).  J in {2, 3}; other J return MACJD_EINVAL. */
+int macjd_mixer_fused_train(const macjd_mixerf_io* eval, const macjd_mixerf_io* target, const macjd_tdloss_io* td,
+                            const float* tot_m, void* hip_stream);
 
 /*
  * The agent side of a WHOLE episode batch in one launch: for t = 0 .. T-1 and every (env, agent) row

@@ -29,7 +29,7 @@ EXPORTS = [
     "macjd_mixer_fused_supported", "macjd_mixer_fused_forward", "macjd_mixer_fused_backward", "macjd_mixer_fused_backward_td", "macjd_td_mask_sum",
     "macjd_agent_episode_supported", "macjd_agent_episode", "macjd_env_step_many", "macjd_env_step_many_timed",
     "macjd_qhead_double_q_supported", "macjd_qhead_double_q", "macjd_qhead_taken_supported", "macjd_qhead_taken",
-    "macjd_qheads_pair", "macjd_mixer_fused_forward_pair",
+    "macjd_qheads_pair", "macjd_mixer_fused_forward_pair", "macjd_mixer_fused_train",
 ]
 
 
@@ -349,6 +349,9 @@ def load() -> ctypes.CDLL:
         getattr(lib, name).argtypes = [ctypes.POINTER(MixerFusedIO), ctypes.c_void_p]
     lib.macjd_mixer_fused_backward_td.restype = ctypes.c_int
     lib.macjd_mixer_fused_backward_td.argtypes = [ctypes.POINTER(MixerFusedIO), ctypes.POINTER(TdLossIO), ctypes.c_void_p, ctypes.c_void_p]
+    lib.macjd_mixer_fused_train.restype = ctypes.c_int
+    lib.macjd_mixer_fused_train.argtypes = [ctypes.POINTER(MixerFusedIO), ctypes.POINTER(MixerFusedIO), ctypes.POINTER(TdLossIO),
+                                            ctypes.c_void_p, ctypes.c_void_p]
     lib.macjd_td_mask_sum.restype = ctypes.c_int
     lib.macjd_td_mask_sum.argtypes = [ctypes.POINTER(TdLossIO), ctypes.c_void_p, ctypes.c_void_p]
     lib.macjd_qhead_taken_supported.restype = ctypes.c_int

@@ -20,6 +20,8 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
+from . import options
+
 
 def make_args(sc, hidden, device, batch_size=32, buffer_size=None, batch_envs=4096, seed=42, mixer_dtype="fp32"):
     info = sc.env_info()
@@ -137,8 +139,10 @@ def make_step(cli, sc, env, dev, rank, world, mode):
              "hip_graphs": bool(use_graphs), "gemm_tuning": bool(gemm_tuning),
              "graph_launch": {"stream": hipgraph.launch_mode(), "GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES"),
                               "allreduce_in_graph": bool(getattr(learner, "_g_graphed_ar", False))},
-             "update": (("paired: Q-head launches as one grid, mixers as one grid, the chain on one queue"
-                         if learner._paired_heads_ok(st0, learner._g_T) else "target branch on the side stream")
+             "update": (((("paired: Q-head launches as one grid, both mixers + loss gradient + mixer backward as one launch, "
+                          "the chain on one queue") if (options.on("MIXER_TRAIN") and learner.n_agents in (2, 3)) else
+                         "paired: Q-head launches as one grid, mixers as one grid, the chain on one queue")
+                        if learner._paired_heads_ok(st0, learner._g_T) else "target branch on the side stream")
                         if (mode == "train" and use_graphs and st0 is not None) else None),
              "replay_capacity_episodes": args.buffer_size, "mixer_dtype": args.mixer_dtype,
              "mixer": ("one MFMA launch per direction (f32)" if (mode == "train" and learner.eval_qmix_net.fused_available(next(learner.eval_qmix_net.parameters())))

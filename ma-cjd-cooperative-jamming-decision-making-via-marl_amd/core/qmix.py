@@ -440,27 +440,39 @@ class QMixLearner:
                 side_work = lambda: after_join(fork_at)
             if prefetched[1] is not None:        # (None: a wait earlier on this stream already covers this update's prefetch)
                 origin.wait_event(prefetched[1])  # the prefetched scan (hence the gather before it on that stream) is there
-            with torch.no_grad():
-                bases = scan_chain()
-                p_eval = pre_actor[1]
-                params = [p_eval if shared else pre_actor[0], p_eval]
-                for t_ in list(bases) + [p for p in params if p is not None]:
-                    t_.record_stream(origin)
-                tq_agents = double_q(bases, params, paired=True)                                # launched with the next call
-            q_taken = self.mac.agent.get_q_value_for_action(
-                st["hidden_state"].view(n, H), st["actions_discrete"].view(n, 1), st["actions_continuous"].view(n, 1),
-                validate=False).view(B, T1, J)                                                  # qmix.py:138-147, 161-184
-            if after_join is not None:
-                # (the fork: behind the Q-head grid rather than in front of it — the prefetch's scan then runs beside the
-                # weight-gradient launches instead of the two mixer launches, which it slows more: 118.2 -> 116.7 us;
-                # behind the mixer grid the prefetch is late for the next update: 120.7 us)
-                fork_at.record(origin)
-            with torch.no_grad():
-                target_q_tot = self.target_qmix_net.forward_paired_with_next_fused(tq_agents, st["state"])
-            eval_q_tot = self.eval_qmix_net(q_taken, st["state"])                               # qmix.py:151, 187
-            ops.assert_pairs_launched()
-            return self._finish_update(st, T, eval_q_tot, target_q_tot, tot_m=prefetched[2] if len(prefetched) > 2 else None,
-                                       side_work=side_work, sums_in_backward=True)
+            tot_m = prefetched[2] if len(prefetched) > 2 else None
+            # both mixers, the loss's gradient and the eval mixer's backward as one launch (ops.pair_mixer_train_with_next_fused)
+            mixer_train = tot_m is not None and options.on("MIXER_TRAIN") and J in (2, 3)
+            train_gy = None
+            try:   # (an argument block that a raising call leaves behind must not ride in a later, unrelated launch)
+                with torch.no_grad():
+                    bases = scan_chain()
+                    p_eval = pre_actor[1]
+                    params = [p_eval if shared else pre_actor[0], p_eval]
+                    for t_ in list(bases) + [p for p in params if p is not None]:
+                        t_.record_stream(origin)
+                    tq_agents = double_q(bases, params, paired=True)                            # launched with the next call
+                q_taken = self.mac.agent.get_q_value_for_action(
+                    st["hidden_state"].view(n, H), st["actions_discrete"].view(n, 1), st["actions_continuous"].view(n, 1),
+                    validate=False).view(B, T1, J)                                              # qmix.py:138-147, 161-184
+                if after_join is not None:
+                    # (the fork: behind the Q-head grid rather than in front of it — the prefetch's scan then runs beside the
+                    # weight-gradient launches instead of the two mixer launches, which it slows more: 118.2 -> 116.7 us;
+                    # behind the mixer grid the prefetch is late for the next update: 120.7 us)
+                    fork_at.record(origin)
+                with torch.no_grad():
+                    if mixer_train:
+                        target_q_tot, train_gy = self.target_qmix_net.forward_paired_with_next_fused(
+                            tq_agents, st["state"], td=dict(reward=st["reward"], terminated=st["terminated"], filled=st["filled"],
+                                                            gamma=self.args.gamma, Tm1=T - 1, tot_m=tot_m))
+                    else:
+                        target_q_tot = self.target_qmix_net.forward_paired_with_next_fused(tq_agents, st["state"])
+                eval_q_tot = self.eval_qmix_net(q_taken, st["state"])                           # qmix.py:151, 187
+                ops.assert_pairs_launched()
+            finally:
+                ops.clear_pending_pairs()
+            return self._finish_update(st, T, eval_q_tot, target_q_tot, tot_m=tot_m, side_work=side_work, sums_in_backward=True,
+                                       train_gy=train_gy)
         elif target_beside_head:
             origin = torch.cuda.current_stream(dev)
             ts = self._target_stream
@@ -547,7 +559,8 @@ class QMixLearner:
                 and self.target_qmix_net.fused_available(st["state"]) and self.eval_qmix_net.fused_available(st["state"])
                 and ops.qhead_taken_supported(st["hidden_state"].view(n, H), head[0].weight, head[2].weight, A))
 
-    def _finish_update(self, st, T, eval_q_tot, target_q_tot, tot_m=None, side_work=None, sums_in_backward=False):
+    def _finish_update(self, st, T, eval_q_tot, target_q_tot, tot_m=None, side_work=None, sums_in_backward=False,
+                       train_gy=None):
         # loss over eval steps 0..T-2 against targets built from target steps 1..T-1 (qmix.py:155,190-194)
         for p in self.params:
             p.grad = None
@@ -555,8 +568,29 @@ class QMixLearner:
             # the loss kernel also produces dL/dQ_tot: it seeds the backward pass directly (no ones-fill / multiply).
             # (Measured and dropped: the loss inside the eval mixer's backward launch — its loads and reductions in front of
             # the kernel's chain cost the 7 us the separate launch does: 26.2 vs 7.5 + 17.8 us.)
-            stats_done = stats_branch = None
-            if tot_m is not None and ops.fused_mixer_backward_will_run(eval_q_tot):
+            stats_done = stats_branch = sums_late = None
+            if train_gy is not None:
+                # the mixer training launch (ops.pair_mixer_train_with_next_fused) has formed dL/dQ_tot and the mixer's
+                # backward already: the backward below records only the weight gradients.  The logged sums read both
+                # mixers' outputs, which other workgroups of that launch write, so they are one sums-only loss launch on
+                # the side stream, captured behind the chain's launches and behind the next update's prefetch (it forks
+                # from the end of the mixer launch; the optimiser writes the gradient norm into row[3], the sums row[0:3])
+                origin = torch.cuda.current_stream(eval_q_tot.device)
+                ts = self._target_stream
+                head_done = torch.cuda.Event()
+                head_done.record(origin)
+                row = self._last_stats4 = torch.empty(4, dtype=torch.float32, device=eval_q_tot.device)
+                loss, eval_mean, target_mean = row[0], row[1], row[2]
+                gy = train_gy
+
+                def sums_late():
+                    ts.wait_event(head_done)
+                    with torch.cuda.stream(ts):
+                        ops.td_loss_sums_into(row, eval_q_tot, target_q_tot, st["reward"], st["terminated"], st["filled"],
+                                              self.args.gamma, T - 1, 1)
+                    for t_ in (row, eval_q_tot, target_q_tot):
+                        t_.record_stream(ts)
+            elif tot_m is not None and ops.fused_mixer_backward_will_run(eval_q_tot):
                 # pipelined update: the batch's mask sum was computed behind its gather, so the eval mixer's backward
                 # launch forms dL/dQ_tot itself (5 loads per row) and the loss launch leaves the serial chain: it still runs
                 # — for the logged sums — on the side stream, ordered before the optimiser writes the gradient norm into
@@ -601,6 +635,8 @@ class QMixLearner:
                 # side-stream launches whose forks lie earlier (side_work: its own fork; the logged sums: head_done),
                 # captured behind the chain's launches so that the chain's nodes stay first dependents of each other
                 side_work()
+            if sums_late is not None:
+                sums_late()
             if stats_done is not None:
                 torch.cuda.current_stream(eval_q_tot.device).wait_event(stats_done)
                 for t_ in (self._last_stats4,):

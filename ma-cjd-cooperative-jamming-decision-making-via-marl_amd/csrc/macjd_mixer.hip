@@ -127,17 +127,27 @@ struct MixerFwdLds {
 // LATE2: the second layers' fragments (B2 / Bf, 32 (J + 1) registers) are requested behind the first layer's MFMAs
 // instead of at the top: ~130 fewer live registers at J = 3 — two workgroups per CU, which the paired launch (twice the
 // workgroups) needs to stay one round — for one exposed L2 latency, which the CU's other workgroup covers.
-template <int J, int SQ, bool SAVE, bool LATE2 = false>
-__device__ __forceinline__ void mixer_fused_forward_body(const macjd_mixerf_io& io, const int blk, MixerFwdLds<SQ>& L) {
+// What the training kernel's backward takes over from its eval half's forward instead of recomputing or reloading it:
+// the accumulator tiles of w1_raw / wf_raw (without bias), their biases, the rows of q and (wave 0) v_raw, and the
+// forward's Q_tot of row (lane & 15) (wave 0, g == 0).
+template <int J>
+struct MixerKeep {
+    f32x4 acc2[J], accf;
+    float qv[4][J], b2e[J], bfe, v_raw, y;
+};
+
+// m0 = first row of the tile, wave = this wave's index among the body's four (the training kernel runs two bodies side
+// by side in one eight-wave workgroup).  KEEP: hand the tiles / vectors above to the caller.
+template <int J, int SQ, bool SAVE, bool LATE2 = false, bool KEEP = false>
+__device__ __forceinline__ void mixer_fused_forward_body(const macjd_mixerf_io& io, const int64_t m0, const int wave,
+                                                         MixerFwdLds<SQ>& L, MixerKeep<J>* keep = nullptr) {
     constexpr int LDA = 16 * SQ + 8;
     constexpr int T1W = MX_N1 / 16 / 4;   // 6 first-layer column tiles per wave
     auto& As = L.As;
     auto& Hs = L.Hs;
     auto& part = L.part;
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int li = lane & 15, g = lane >> 4;
-    const int64_t m0 = (int64_t)blk * 16;
     const int S = io.S;
 
     // ---- loads, oldest first = needed first (s_waitcnt counts in issue order): the state rows of the LayerNorm, then
@@ -264,22 +274,38 @@ __device__ __forceinline__ void mixer_fused_forward_body(const macjd_mixerf_io& 
     __syncthreads();
     if (wave == 0 && g == 0) {
         const int64_t m = m0 + li;
-        if (m < io.M) io.y[m] = ((part[0][li] + part[1][li]) + (part[2][li] + part[3][li])) + mx_clamp(v_raw, -5.0f, 5.0f);
+        const float y = ((part[0][li] + part[1][li]) + (part[2][li] + part[3][li])) + mx_clamp(v_raw, -5.0f, 5.0f);
+        if (m < io.M) io.y[m] = y;
+        if (KEEP) keep->y = y;
+    }
+    if (KEEP) {
+#pragma unroll
+        for (int j = 0; j < J; ++j) {
+            keep->acc2[j] = acc2[j];
+            keep->b2e[j] = b2e[j];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) keep->qv[r][j] = qv[r][j];
+        }
+        keep->accf = accf;
+        keep->bfe = bfe;
+        keep->v_raw = v_raw;
     }
 }
 
 template <int J, int SQ, bool SAVE>
 __global__ void __launch_bounds__(256) mixer_fused_forward_kernel(const macjd_mixerf_io io) {
     __shared__ MixerFwdLds<SQ> L;
-    mixer_fused_forward_body<J, SQ, SAVE>(io, blockIdx.x, L);
+    mixer_fused_forward_body<J, SQ, SAVE>(io, (int64_t)blockIdx.x * 16, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), L);
 }
 
 // blockIdx.y = 0: the mixer whose activations are saved for a backward (io_a), 1: the plain one (io_b)
 template <int J, int SQ>
 __global__ void __launch_bounds__(256, (J <= 3) ? 2 : 1) mixer_fused_forward_pair_kernel(const macjd_mixerf_io io_a, const macjd_mixerf_io io_b) {
     __shared__ MixerFwdLds<SQ> L;
-    if (blockIdx.y == 0) mixer_fused_forward_body<J, SQ, true, (J <= 3)>(io_a, blockIdx.x, L);
-    else mixer_fused_forward_body<J, SQ, false, (J <= 3)>(io_b, blockIdx.x, L);
+    const int64_t m0 = (int64_t)blockIdx.x * 16;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (blockIdx.y == 0) mixer_fused_forward_body<J, SQ, true, (J <= 3)>(io_a, m0, wave, L);
+    else mixer_fused_forward_body<J, SQ, false, (J <= 3)>(io_b, m0, wave, L);
 }
 
 // Backward (see the header): recompute the second layers from `act`, tail gradients, transposed second layers.
@@ -473,6 +499,184 @@ __global__ void __launch_bounds__(256) mixer_fused_backward_kernel(const macjd_m
         const int row = idx / MX_EM, k = idx - row * MX_EM;
         if (m0 + row < io.M)
             io.gout1[(m0 + row) * MX_N1 + 2 * MX_HH + k] = (Hs[row * MX_LDH + 2 * MX_HH + k] > 0.0f) ? gv_s[row] * wvo[i] : 0.0f;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The learner update's mixers as ONE launch (macjd_mixer_fused_train): eval forward, target forward, the TD loss's
+// gradient and the eval mixer's backward.  One workgroup of eight waves owns the 16-row tile [m0, m0 + 16):
+//   waves 0-3  the eval mixer's forward body on rows [m0, m0 + 16) (activations saved, as the pair's saving half); its
+//              first-layer output stays in LDS (= `act`) and its w1_raw / wf_raw tiles stay in registers (MixerKeep)
+//   waves 4-7  the target mixer's forward body on rows [m0 + 1, m0 + 17) (loads clamped at M, as everywhere): eval row m's
+//              TD target reads the target mixer's row m + 1, so every target value the tile's loss needs is made here
+//   one barrier, then dL/dy of each row from LDS (td_loss_kernel's expression, see mixer_fused_backward_kernel<J, true>)
+//   waves 0-3  tail gradients of embed block `wave` (the backward's expressions on the kept tiles)
+//   waves 0-7  one column tile each of the transposed second-layer products (gout1's first 2 Hh columns; the backward
+//              kernel's four waves do two each), dL/dq, the V head's outer product.
+// Every output is the same expression in the same order as the pair + backward launches: bit-identical.
+template <int J>
+struct MixerTrainLds {
+    MixerFwdLds<J> ev, tg;
+    alignas(16) float G1[16 * (J * MX_EM + 8)];
+    alignas(16) float Gf[16 * (MX_EM + 8)];
+    float gq_part[4][16][J];
+    float gv_s[16];
+    float ys[16], tqs[16];   // eval Q_tot of row m0 + i, target Q_tot of row m0 + 1 + i
+};
+
+template <int J>
+__global__ void __launch_bounds__(512) mixer_fused_train_kernel(const macjd_mixerf_io io, const macjd_mixerf_io tio,
+                                                                 const macjd_tdloss_io td, const float* __restrict__ tot_m) {
+    constexpr int LDG = J * MX_EM + 8;
+    constexpr int LDF = MX_EM + 8;
+    constexpr int KQ1 = J * MX_EM / 16;
+    constexpr int KQF = MX_EM / 16;
+    __shared__ MixerTrainLds<J> L;
+    const int lane = threadIdx.x & 63;
+    const int wave8 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave = wave8 & 3;
+    const bool eval_half = wave8 < 4;
+    const int li = lane & 15, g = lane >> 4;
+    const int64_t m0 = (int64_t)blockIdx.x * 16;
+    const float* Hs = L.ev.Hs;   // the eval mixer's first-layer output of the tile = `act`
+
+    // the loss inputs of this lane's rows (4 g + r, and li for the V head), requested before the forward's loads
+    float rw[5], term[5], mk[5];
+    bool live[5];
+    if (eval_half) {
+#pragma unroll
+        for (int r = 0; r < 5; ++r) {
+            const int row = r < 4 ? 4 * g + r : li;
+            const int64_t mc = (m0 + row < io.M) ? m0 + row : io.M - 1;
+            const int cols = (int)td.gy_cols;
+            const int b = (int)(mc / cols), t = (int)(mc - (int64_t)b * cols);
+            const int tc = t < td.Tm1 ? t : td.Tm1 - 1;
+            term[r] = td.terminated[b * td.t_sb + tc * td.t_st] ? 1.0f : 0.0f;
+            mk[r] = td.filled[b * td.f_sb + tc * td.f_st] ? 1.0f : 0.0f;
+            rw[r] = td.reward[b * td.r_sb + tc * td.r_st];
+            live[r] = t < td.Tm1;
+        }
+    }
+
+    MixerKeep<J> K;
+    f32x4 D1[KQ1], Df[KQF];
+    if (eval_half) {
+        mixer_fused_forward_body<J, J, true, true, true>(io, m0, wave, L.ev, &K);
+        if (wave == 0 && g == 0) L.ys[li] = K.y;
+    } else {
+        MixerKeep<J> Kt;
+        mixer_fused_forward_body<J, J, false, true, true>(tio, m0 + 1, wave, L.tg, &Kt);
+        if (wave == 0 && g == 0) L.tqs[li] = Kt.y;
+    }
+    // transposed second-layer fragments of this wave's gout1 column tile n = 16 wave8 + li (B[k][n] = W2[k][n], k = 16 Q +
+    // 4 g + jj), requested while the tail gradients run
+    {
+        const int n = 16 * wave8 + li;
+#pragma unroll
+        for (int Q = 0; Q < KQ1; ++Q)
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj) D1[Q][jj] = io.W2[(int64_t)(16 * Q + 4 * g + jj) * MX_HH + n];
+#pragma unroll
+        for (int Q = 0; Q < KQF; ++Q)
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj) Df[Q][jj] = io.Wf2[(int64_t)(16 * Q + 4 * g + jj) * MX_HH + n];
+    }
+    float wvo[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) wvo[i] = io.wV2[(threadIdx.x + 512 * i) & (MX_EM - 1)];
+    __syncthreads();   // ys / tqs of the tile
+
+    if (eval_half) {
+        const float scale = 2.0f / tot_m[0];
+        float gyv[5];
+#pragma unroll
+        for (int r = 0; r < 5; ++r) {
+            const int row = r < 4 ? 4 * g + r : li;
+            const float target = rw[r] + td.gamma * (1.0f - term[r]) * L.tqs[row];
+            const float gv = scale * mk[r] * (L.ys[row] - target);
+            gyv[r] = live[r] ? gv : 0.0f;
+        }
+        const int e = 16 * wave + li;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = 4 * g + r;
+            const int64_t m = m0 + row;
+            const float b1r = Hs[row * MX_LDH + MX_RELU + e];
+            float hid = mx_clamp(b1r, -5.0f, 5.0f);
+            float w1r[J];
+#pragma unroll
+            for (int j = 0; j < J; ++j) {
+                w1r[j] = K.acc2[j][r] + K.b2e[j];
+                hid = fmaf(K.qv[r][j], mx_clamp(w1r[j], 0.0f, 5.0f), hid);
+            }
+            const float h = hid > 0.0f ? hid : expm1f(hid);
+            const float wfr = K.accf[r] + K.bfe;
+            const float ghid = gyv[r] * mx_clamp(wfr, 0.0f, 5.0f) * (hid > 0.0f ? 1.0f : h + 1.0f);
+            const float gwf = (wfr >= 0.0f && wfr <= 5.0f) ? gyv[r] * h : 0.0f;
+            const float gb1 = (b1r >= -5.0f && b1r <= 5.0f) ? ghid : 0.0f;
+            L.Gf[row * LDF + e] = gwf;
+            if (m < io.M) {
+                io.g_wfraw[m * MX_EM + e] = gwf;
+                io.gout1[m * MX_N1 + MX_RELU + e] = gb1;
+            }
+#pragma unroll
+            for (int j = 0; j < J; ++j) {
+                const float gw = (w1r[j] >= 0.0f && w1r[j] <= 5.0f) ? ghid * K.qv[r][j] : 0.0f;
+                L.G1[row * LDG + j * MX_EM + e] = gw;
+                if (m < io.M) io.g_w1raw[m * (J * MX_EM) + j * MX_EM + e] = gw;
+                const float t = mx_sum16(ghid * mx_clamp(w1r[j], 0.0f, 5.0f));
+                if (li == 0) L.gq_part[wave][row][j] = t;
+            }
+        }
+        if (wave == 0 && g == 0) {   // v = clamp(v_raw, -5, 5): row li
+            const int64_t m = m0 + li;
+            const float gv = (K.v_raw >= -5.0f && K.v_raw <= 5.0f) ? gyv[4] : 0.0f;
+            L.gv_s[li] = gv;
+            if (m < io.M) io.g_v[m] = gv;
+        }
+    }
+    __syncthreads();
+    // dL/dq: the four embed blocks' partial sums in fixed order
+    if (threadIdx.x < 16 * J) {
+        const int row = threadIdx.x / J, j = threadIdx.x - row * J;
+        if (m0 + row < io.M)
+            io.gq[(m0 + row) * J + j] = (L.gq_part[0][row][j] + L.gq_part[1][row][j]) + (L.gq_part[2][row][j] + L.gq_part[3][row][j]);
+    }
+    // input gradients of the second layers, masked by the first layer's ReLU: column tile n of [0, Hh) and of [Hh, 2 Hh)
+    {
+        f32x4 a1 = f32x4{0.f, 0.f, 0.f, 0.f}, af = f32x4{0.f, 0.f, 0.f, 0.f};
+        const float* gp = L.G1 + li * LDG + 4 * g;
+        const float* fp = L.Gf + li * LDF + 4 * g;
+#pragma unroll
+        for (int Q = 0; Q < KQ1; ++Q) {
+            const f32x4 a = *reinterpret_cast<const f32x4*>(gp + 16 * Q);
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj) a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[jj], D1[Q][jj], a1, 0, 0, 0);
+        }
+#pragma unroll
+        for (int Q = 0; Q < KQF; ++Q) {
+            const f32x4 a = *reinterpret_cast<const f32x4*>(fp + 16 * Q);
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj) af = __builtin_amdgcn_mfma_f32_16x16x4f32(a[jj], Df[Q][jj], af, 0, 0, 0);
+        }
+        const int n = 16 * wave8 + li;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = 4 * g + r;
+            const int64_t m = m0 + row;
+            if (m < io.M) {
+                io.gout1[m * MX_N1 + n] = (Hs[row * MX_LDH + n] > 0.0f) ? a1[r] : 0.0f;
+                io.gout1[m * MX_N1 + MX_HH + n] = (Hs[row * MX_LDH + MX_HH + n] > 0.0f) ? af[r] : 0.0f;
+            }
+        }
+    }
+    // the V head's one-output second layer: outer product g_v wV2, masked: columns [2 Hh, 2 Hh + Em)
+#pragma unroll
+    for (int i = 0; i < 16 * MX_EM / 512; ++i) {
+        const int idx = threadIdx.x + 512 * i;
+        const int row = idx / MX_EM, k = idx - row * MX_EM;
+        if (m0 + row < io.M)
+            io.gout1[(m0 + row) * MX_N1 + 2 * MX_HH + k] = (Hs[row * MX_LDH + 2 * MX_HH + k] > 0.0f) ? L.gv_s[row] * wvo[i] : 0.0f;
     }
 }
 
@@ -1014,5 +1218,35 @@ extern "C" int macjd_mixer_fused_backward_td(const macjd_mixerf_io* io, const ma
     else hipLaunchKernelGGL((mixer_fused_backward_wide_kernel<12, 4, true>), grid, block, 0, s, *io, *td, tot_m);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_mixer_fused_backward_td: %s", hipGetErrorString(err));
+    return MACJD_OK;
+}
+
+extern "C" int macjd_mixer_fused_train(const macjd_mixerf_io* eval, const macjd_mixerf_io* target, const macjd_tdloss_io* td,
+                                       const float* tot_m, void* hip_stream) {
+    using namespace macjd;
+    int rc = mixerf_check(eval, false);
+    if (rc != MACJD_OK) return rc;
+    rc = mixerf_check(eval, true, true);
+    if (rc != MACJD_OK) return rc;
+    rc = mixerf_check(target, false);
+    if (rc != MACJD_OK) return rc;
+    if (!eval->save || target->save) return set_err(MACJD_EINVAL, "%s", "macjd_mixer_fused_train: the eval mixer saves, the target mixer does not");
+    if (eval->J != target->J || eval->S != target->S || eval->M != target->M)
+        return set_err(MACJD_EINVAL, "%s", "macjd_mixer_fused_train: the two mixers differ in J / S / M");
+    if (eval->J != 2 && eval->J != 3) return set_err(MACJD_EINVAL, "%s", "macjd_mixer_fused_train: J must be 2 or 3");
+    if (!td || !tot_m || td->B < 1 || td->Tm1 < 1 || !td->y || !td->tq || !td->reward || !td->terminated || !td->filled)
+        return set_err(MACJD_EINVAL, "%s", "macjd_mixer_fused_train: bad TD-loss argument");
+    if (td->gy_cols < td->Tm1 + 1 || (int64_t)td->B * td->gy_cols != eval->M)
+        return set_err(MACJD_EINVAL, "%s", "macjd_mixer_fused_train: rows must be B x gy_cols with gy_cols > Tm1");
+    // the loss reads eval row (b, t) and target row (b, t + 1) of the two outputs, which this launch keeps in LDS
+    if (td->y != eval->y || td->y_sb != td->gy_cols || td->tq != target->y + 1 || td->tq_sb != td->gy_cols)
+        return set_err(MACJD_EINVAL, "%s", "macjd_mixer_fused_train: td->y / td->tq must be eval->y / target->y + 1 with row pitch gy_cols");
+    if (eval->M == 0) return MACJD_OK;
+    const dim3 grid((unsigned)((eval->M + 15) / 16)), block(512);
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (eval->J == 2) hipLaunchKernelGGL((mixer_fused_train_kernel<2>), grid, block, 0, s, *eval, *target, *td, tot_m);
+    else hipLaunchKernelGGL((mixer_fused_train_kernel<3>), grid, block, 0, s, *eval, *target, *td, tot_m);
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_mixer_fused_train: %s", hipGetErrorString(err));
     return MACJD_OK;
 }

@@ -152,6 +152,8 @@ def _doubleq_io(h_eval, P_eval, head_eval, h_tgt, P_tgt, head_tgt, H, A, want_ar
 # block built — and rides in the launch of the next autograd forward of the matching kind.
 _PAIRED_DQ = None      # (macjd_doubleq_io, tensors kept alive, out) waiting for the next _QheadTaken.forward
 _PAIRED_MIXER = None   # (macjd_mixerf_io, tensors kept alive, y) waiting for the next saving mixer_fused_forward
+_PAIRED_TRAIN = None   # (target macjd_mixerf_io, macjd_tdloss_io, tensors kept alive, placeholder) waiting for the next
+                       # _FusedMixer.forward (pair_mixer_train_with_next_fused)
 
 
 def pair_double_q_with_next_taken(h_eval, P_eval, head_eval, h_tgt, P_tgt, head_tgt, H: int, A: int, p_row_map=None):
@@ -177,11 +179,47 @@ def pair_mixer_forward_with_next_fused(q, s, params):
     return y
 
 
+def pair_mixer_train_with_next_fused(q, s, params, reward, terminated, filled, gamma, Tm1, tot_m):
+    """The target mixer ``mixer_fused_forward(q, s, params)``, the TD loss's gradient (``td_grad_in_mixer_backward``'s
+    inputs with tq_off = 1) and the eval mixer's backward, all inside the launch of the NEXT differentiable ``mixer_fused``
+    forward (macjd_mixer_fused_train): that forward's rows are [B, T1] with B = reward.shape[0].  Returns (target y [M, 1],
+    placeholder): y is valid once that forward has run; the placeholder [B, T1, 1] is what the eval output's backward must
+    be seeded with — its backward then only records the weight-gradient products.  The logged loss sums are the caller's
+    (``td_loss_sums_into``)."""
+    global _PAIRED_TRAIN
+    assert _PAIRED_TRAIN is None and _PAIRED_MIXER is None, "a paired mixer launch is already waiting"
+    q, s = q.detach().float().contiguous(), _f32c(s.detach())
+    M = s.shape[0]
+    B = reward.shape[0]
+    assert M % B == 0 and M // B > int(Tm1), "pair_mixer_train_with_next_fused: rows must be B x T1 with T1 > Tm1"
+    T1 = M // B
+    y = torch.empty((M, 1), dtype=torch.float32, device=q.device)
+    io = _mixerf_io(q, s, params)
+    io.y = y.data_ptr()
+    td = _native.TdLossIO()
+    td.B, td.Tm1, td.gamma = B, int(Tm1), float(gamma)
+    td.y_sb = T1                                   # td.y: the eval output, set by the forward that takes this block
+    td.tq, td.tq_sb = y.data_ptr() + 4, T1         # target row (b, t + 1)
+    td.gy, td.gy_sb, td.gy_cols = None, T1, T1
+    td.reward, td.r_sb, td.r_st = reward.data_ptr(), reward.stride(0), reward.stride(1)
+    td.terminated, td.t_sb, td.t_st = terminated.data_ptr(), terminated.stride(0), terminated.stride(1)
+    td.filled, td.f_sb, td.f_st = filled.data_ptr(), filled.stride(0), filled.stride(1)
+    placeholder = torch.empty((B, T1, 1), dtype=torch.float32, device=q.device)   # never read
+    _PAIRED_TRAIN = (io, td, (q, s, params, reward, terminated, filled, tot_m, y), placeholder)
+    return y, placeholder
+
+
+def clear_pending_pairs():
+    """Drop every argument block handed to ``pair_*`` and not launched (a forward that raised before taking it)."""
+    global _PAIRED_DQ, _PAIRED_MIXER, _PAIRED_TRAIN
+    _PAIRED_DQ = _PAIRED_MIXER = _PAIRED_TRAIN = None
+
+
 def assert_pairs_launched():
     """Every launch handed to ``pair_*`` has gone out (it has not if the autograd call took another code path)."""
-    global _PAIRED_DQ, _PAIRED_MIXER
-    left = [n for n, v in (("Double-DQN", _PAIRED_DQ), ("mixer", _PAIRED_MIXER)) if v is not None]
-    _PAIRED_DQ = _PAIRED_MIXER = None
+    left = [n for n, v in (("Double-DQN", _PAIRED_DQ), ("mixer", _PAIRED_MIXER), ("mixer training", _PAIRED_TRAIN))
+            if v is not None]
+    clear_pending_pairs()
     if left:
         raise RuntimeError("paired launch not taken by the autograd forward it was meant for: " + ", ".join(left))
 
@@ -586,7 +624,13 @@ class _FusedMixer(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, s, ln_w, ln_b, eps, w_cat, b_cat, W2, b2, Wf2, bf2, wV2, bV2, *first):
         params = _mixerf_params(ln_w, ln_b, eps, w_cat, b_cat, W2, b2, Wf2, bf2, wV2, bV2)
-        y, qc, (sn, xhat, act) = mixer_fused_forward(q, s, params, save=True)
+        global _PAIRED_TRAIN
+        train, _PAIRED_TRAIN = _PAIRED_TRAIN, None
+        ctx.train = None
+        if train is not None:   # target mixer, loss gradient and this mixer's backward in one launch (see _mixer_train)
+            y, qc, (sn, xhat, act), ctx.train = _mixer_train(q, s, params, train)
+        else:
+            y, qc, (sn, xhat, act) = mixer_fused_forward(q, s, params, save=True)
         ctx.save_for_backward(qc, sn, xhat, act, w_cat, W2, Wf2, wV2, ln_w, ln_b, b2, bf2, bV2)
         ctx.params = {k: v for k, v in params.items() if k in ("eps",)}
         ctx.sizes = [p.shape[0] for p in first[:len(first) // 2]]
@@ -602,6 +646,10 @@ class _FusedMixer(torch.autograd.Function):
         M, J = q.shape
         Hh, Em = W2.shape[1], Wf2.shape[0]
         dev = q.device
+        if ctx.train is not None:   # the forward's launch wrote every gradient below: only the weight gradients are left
+            placeholder, (gq, gout1, g_w1, g_wf, g_v) = ctx.train
+            assert gy.data_ptr() == placeholder.data_ptr(), "mixer training launch: backward not seeded with its placeholder"
+            return _FusedMixer._wgrads(ctx, q, sn, xhat, act, w_cat, W2, Wf2, wV2, ln_w, ln_b, gq, gout1, g_w1, g_wf, g_v)
         gy = gy.detach().float().contiguous()
         gq = torch.empty((M, J), dtype=torch.float32, device=dev)
         gout1 = torch.empty((M, 2 * Hh + 2 * Em), dtype=torch.float32, device=dev)
@@ -621,6 +669,12 @@ class _FusedMixer(torch.autograd.Function):
                                                                 _stream(q)), "macjd_mixer_fused_backward_td")
             else:
                 _native.check(lib.macjd_mixer_fused_backward(ctypes.byref(io), _stream(q)), "macjd_mixer_fused_backward")
+        return _FusedMixer._wgrads(ctx, q, sn, xhat, act, w_cat, W2, Wf2, wV2, ln_w, ln_b, gq, gout1, g_w1, g_wf, g_v)
+
+    @staticmethod
+    def _wgrads(ctx, q, sn, xhat, act, w_cat, W2, Wf2, wV2, ln_w, ln_b, gq, gout1, g_w1, g_wf, g_v):
+        Hh, Em = W2.shape[1], Wf2.shape[0]
+        dev = q.device
         nd = ctx.needs_input_grad
         # weight / bias gradients: split-K products of the matrices the kernel wrote (recorded inside deferred_wgrad)
         gW1, gb1 = linear_wgrad(gout1, sn, want_bias=True, w_key=grad_key(w_cat), b_key=ctx.keys["b_cat"])
@@ -653,6 +707,37 @@ class _FusedMixer(torch.autograd.Function):
             post()
         first = tuple(gW1.split(ctx.sizes, 0)) + tuple(gb1.split(ctx.sizes, 0))
         return (gq, None, dgamma, dbeta, None, None, None, gW2, gb2, gWf, gbf, gWv, gbv) + first
+
+
+def _mixer_train(q, s, params, train):
+    """macjd_mixer_fused_train with this (eval) mixer and the block of ``pair_mixer_train_with_next_fused``:
+    (y, q, (sn, xhat, act), (placeholder, (gq, gout1, g_w1raw, g_wfraw, g_v)))."""
+    lib = _native.load()
+    tio, td, keep, placeholder = train
+    q, s = q.detach().float().contiguous(), _f32c(s.detach())
+    M, S = s.shape
+    J, dev = q.shape[1], q.device
+    assert M == tio.M and td.B * td.gy_cols == M, "mixer training launch: the two mixers / the loss differ in rows"
+    y = torch.empty((M, 1), dtype=torch.float32, device=dev)
+    io = _mixerf_io(q, s, params)
+    width = 2 * io.Hh + 2 * io.Em
+    sn = torch.empty((M, S), dtype=torch.float32, device=dev)
+    xhat = torch.empty((M, S), dtype=torch.float32, device=dev)
+    act = torch.empty((M, width), dtype=torch.float32, device=dev)
+    gq = torch.empty((M, J), dtype=torch.float32, device=dev)
+    gout1 = torch.empty((M, width), dtype=torch.float32, device=dev)
+    g_w1 = torch.empty((M, J * io.Em), dtype=torch.float32, device=dev)
+    g_wf = torch.empty((M, io.Em), dtype=torch.float32, device=dev)
+    g_v = torch.empty((M, 1), dtype=torch.float32, device=dev)
+    io.y, io.save, io.sn, io.xhat, io.act = y.data_ptr(), 1, sn.data_ptr(), xhat.data_ptr(), act.data_ptr()
+    io.gq, io.gout1 = gq.data_ptr(), gout1.data_ptr()
+    io.g_w1raw, io.g_wfraw, io.g_v = g_w1.data_ptr(), g_wf.data_ptr(), g_v.data_ptr()
+    td.y = y.data_ptr()
+    tot_m = keep[6]
+    with torch.cuda.device(dev):
+        _native.check(lib.macjd_mixer_fused_train(ctypes.byref(io), ctypes.byref(tio), ctypes.byref(td), tot_m.data_ptr(),
+                                                  _stream(q)), "macjd_mixer_fused_train")
+    return y, q, (sn, xhat, act), (placeholder, (gq, gout1, g_w1, g_wf, g_v))
 
 
 def mixer_fused(q, s, ln_w, ln_b, eps, w_cat, b_cat, W2, b2, Wf2, bf2, wV2, bV2, first_params):

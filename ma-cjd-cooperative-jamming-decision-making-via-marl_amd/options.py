@@ -16,6 +16,8 @@ for normal operation.
     MACJD_QHEAD_TAKEN         1 | 0      taken-action Q-head as one launch / input rows + GEMM + row-dot
     MACJD_PAIRED_HEADS        1 | 0      pipelined update: both Q-head launches as one grid and both mixers as one grid on
                                          the chain's stream / target branch on the side stream beside the eval head
+    MACJD_MIXER_TRAIN         1 | 0      paired update at 2 / 3 agents: both mixers, the loss gradient and the mixer backward
+                                         as one launch / the mixer pair + the backward launch
     MACJD_GRAPHED_ALLREDUCE   0 | 1      with ranks: RCCL all-reduce captured inside the update graph
 """
 from __future__ import annotations
@@ -25,7 +27,7 @@ import os
 _DEFAULTS = {
     "UPDATE_STREAMS": "2", "UPDATES_PER_GRAPH": "1", "PIPELINED_GROUP": "1", "SHARED_BODY": "1",
     "LEARNER_STATIC_OBS": "1", "ACTOR_IN_SCAN": "1", "DEVICE_SAMPLER": "1", "LN_IN_SQNORM": "1", "WGRAD_OUTER": "1",
-    "QHEAD_TAKEN": "1", "PAIRED_HEADS": "1", "GRAPHED_ALLREDUCE": "0",
+    "QHEAD_TAKEN": "1", "PAIRED_HEADS": "1", "MIXER_TRAIN": "1", "GRAPHED_ALLREDUCE": "0",
 }
 _values = None
 
