@@ -449,6 +449,19 @@ int macjd_gru_gates(const macjd_grugates_io* io, void* hip_stream);
  * first layer `gout1` [M, 2 Hh + 2 Em].  No gradient flows to the state.  The weight / bias / LayerNorm-parameter
  * gradients are split-K products of these matrices (macjd_linear_wgrad_many, macjd_layernorm_param_grad).
  *
+ * Operand type (operand_dtype; the five entry points below dispatch on it, the two mixers of a pair / training call must
+ * agree, any other value returns MACJD_EINVAL).  0: the exact-f32 products above.  1: bf16 operands, i.e. round to
+ * nearest even at exactly these points, every accumulation in f32 (v_mfma_f32_16x16x32_bf16):
+ *   forward   LayerNorm f32; first layer bf16(s~) . bf16(W_first)^T, then + b_first in f32, then ReLU;
+ *             w1_raw = bf16(h_w1) . bf16(W2)^T + b2, wf_raw = bf16(h_wf) . bf16(Wf2)^T + bf2; v_raw (row-dot), the clamps,
+ *             the fmaf chain over the agents, ELU and the final products f32 as in the f32 kernels; sn / xhat / act are
+ *             saved in f32, unrounded.
+ *   backward  tail gradients (gq, g_w1raw, g_wfraw, g_v) f32; gout1[:, :Hh] = bf16(g_w1raw) . bf16(W2) and
+ *             gout1[:, Hh:2Hh] = bf16(g_wfraw) . bf16(Wf2), each masked by its ReLU; the V and b1 blocks f32.  w1_raw /
+ *             wf_raw are re-derived with the forward's bf16 instruction sequence (bit-identical: same clamp masks).
+ *   The weight, bias and LayerNorm-parameter gradients stay the f32 split-K products of the f32 saved matrices.  The
+ *   weights stay the f32 parameters: fragments are rounded in the kernel, so there is no bf16 copy to keep current.
+ *
  * Supported: hyper_hidden_dim Hh = 128, mixing_embed_dim Em = 64 (the reference's sizes), n_agents J in {2, 3, 6, 12},
  * state_dim S <= 16 J (the shipped 2j/2r, 3j/4r, 6j/8r and 12j/16r scenarios; J = 12 runs both layers in passes); everything else returns
  * MACJD_EUNSUPPORTED and the caller keeps the unfused kernels.
@@ -456,7 +469,8 @@ int macjd_gru_gates(const macjd_grugates_io* io, void* hip_stream);
 typedef struct macjd_mixerf_io {
     int64_t M;                 /* rows */
     int32_t J, S, Hh, Em;      /* agents, state_dim, hyper_hidden_dim, mixing_embed_dim */
-    int32_t save, reserved;    /* forward: != 0 stores sn / xhat / act */
+    int32_t save;              /* forward: != 0 stores sn / xhat / act */
+    int32_t operand_dtype;     /* 0: exact f32 products, 1: bf16 operands with f32 accumulation (see above); else MACJD_EINVAL */
     float ln_eps;  float reserved_f;
     const float* s;   int64_t s_ld;      /* [M,S] state rows */
     const float* q;            /* [M,J] agent Q-values (contiguous) */

@@ -14,7 +14,7 @@ LIB_NAME = "libmacjd_hip.so"
 # MACJD_LIB points at another build of the same sources (kernel A/B runs); the default is the in-tree library
 LIB_PATH = os.environ.get("MACJD_LIB") or os.path.join(_PKG_DIR, LIB_NAME)
 
-ABI_VERSION = 3
+ABI_VERSION = 4
 STEP_ARITH_F64 = 1
 STEP_LANE_KERNEL = 2
 STEP_SLOT_KERNEL = 4
@@ -112,7 +112,7 @@ class MixerFusedIO(ctypes.Structure):
     """ctypes mirror of ``macjd_mixerf_io`` (include/macjd_nets.h)."""
     _fields_ = [
         ("M", ctypes.c_int64), ("J", ctypes.c_int32), ("S", ctypes.c_int32), ("Hh", ctypes.c_int32), ("Em", ctypes.c_int32),
-        ("save", ctypes.c_int32), ("reserved", ctypes.c_int32), ("ln_eps", ctypes.c_float), ("reserved_f", ctypes.c_float),
+        ("save", ctypes.c_int32), ("operand_dtype", ctypes.c_int32), ("ln_eps", ctypes.c_float), ("reserved_f", ctypes.c_float),
         ("s", ctypes.c_void_p), ("s_ld", ctypes.c_int64), ("q", ctypes.c_void_p),
         ("ln_w", ctypes.c_void_p), ("ln_b", ctypes.c_void_p), ("W1", ctypes.c_void_p), ("b1", ctypes.c_void_p),
         ("W2", ctypes.c_void_p), ("b2", ctypes.c_void_p), ("Wf2", ctypes.c_void_p), ("bf2", ctypes.c_void_p),

@@ -145,7 +145,7 @@ def make_step(cli, sc, env, dev, rank, world, mode):
                         if learner._paired_heads_ok(st0, learner._g_T) else "target branch on the side stream")
                         if (mode == "train" and use_graphs and st0 is not None) else None),
              "replay_capacity_episodes": args.buffer_size, "mixer_dtype": args.mixer_dtype,
-             "mixer": ("one MFMA launch per direction (f32)" if (mode == "train" and learner.eval_qmix_net.fused_available(next(learner.eval_qmix_net.parameters())))
+             "mixer": ("one MFMA launch per direction (%s)" % ("bf16 operands" if learner.eval_qmix_net.bf16_hyper else "f32") if (mode == "train" and learner.eval_qmix_net.fused_available(next(learner.eval_qmix_net.parameters())))
                        else ("library GEMMs (%s) + tail kernel" % args.mixer_dtype)) if mode == "train" else None,
              "rollout": ("fused: agent-episode launch + many-step env launch per episode batch" +
                          (", replayed as one graph" if use_graphs else "")) if fused_rollout else

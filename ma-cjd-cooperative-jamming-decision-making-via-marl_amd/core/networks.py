@@ -284,12 +284,13 @@ class QMixer(nn.Module):
             raw = tuple(r.float() for r in raw)
         return raw
 
-    # the whole mixer as one MFMA chain per direction (ops.mixer_fused, csrc/macjd_mixer.hip); off -> LayerNorm + library
-    # GEMMs + the tail kernel (also the path of sizes the fused kernel does not cover and of the bf16 option)
+    # the whole mixer as one MFMA chain per direction (ops.mixer_fused, csrc/macjd_mixer.hip; the bf16 option runs its
+    # bf16-operand kernels); off -> LayerNorm + library GEMMs (under autocast for the bf16 option) + the tail kernel (also
+    # the path of sizes the fused kernel does not cover)
     fused = True   # class-level switch (tests set it): the one-launch mixer where the size is covered
 
     def fused_available(self, t) -> bool:
-        return (self.fused and t.is_cuda and not self.bf16_hyper and not torch.is_autocast_enabled()
+        return (self.fused and t.is_cuda and not torch.is_autocast_enabled()
                 and ops.mixer_fused_supported(self.n_agents, self.state_dim, self.hyper_hidden_dim, self.embed_dim))
 
     def _first_layer_cat(self):
@@ -309,8 +310,9 @@ class QMixer(nn.Module):
         l2 = (self.hyper_w_1[2].weight, self.hyper_w_1[2].bias, self.hyper_w_final[2].weight, self.hyper_w_final[2].bias,
               self.V[2].weight, self.V[2].bias)
         if torch.is_grad_enabled() and (q.requires_grad or ln.weight.requires_grad or l2[0].requires_grad):
-            return ops.mixer_fused(q, s, ln.weight, ln.bias, ln.eps, w_cat_b[0], w_cat_b[1], *l2, self.first_layer_params())
-        params = ops._mixerf_params(ln.weight, ln.bias, ln.eps, w_cat_b[0], w_cat_b[1], *l2)
+            return ops.mixer_fused(q, s, ln.weight, ln.bias, ln.eps, w_cat_b[0], w_cat_b[1], *l2, self.first_layer_params(),
+                                   bf16=self.bf16_hyper)
+        params = ops._mixerf_params(ln.weight, ln.bias, ln.eps, w_cat_b[0], w_cat_b[1], *l2, bf16=self.bf16_hyper)
         return ops.mixer_fused_forward(q, s, params, save=False)[0]
 
     def forward_paired_with_next_fused(self, agent_qs, states, td=None):
@@ -324,7 +326,7 @@ class QMixer(nn.Module):
         ln, w_cat_b = self.state_norm, self._first_layer_cat()
         params = ops._mixerf_params(ln.weight, ln.bias, ln.eps, w_cat_b[0], w_cat_b[1], self.hyper_w_1[2].weight,
                                     self.hyper_w_1[2].bias, self.hyper_w_final[2].weight, self.hyper_w_final[2].bias,
-                                    self.V[2].weight, self.V[2].bias)
+                                    self.V[2].weight, self.V[2].bias, bf16=self.bf16_hyper)
         if td is not None:
             y, placeholder = ops.pair_mixer_train_with_next_fused(q, s, params, **td)
             return y.view(agent_qs.size(0), -1, 1), placeholder

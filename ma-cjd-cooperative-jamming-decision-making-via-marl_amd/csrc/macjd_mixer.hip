@@ -33,6 +33,7 @@ namespace macjd {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4_u __attribute__((ext_vector_type(4), aligned(4)));   // weight rows are only 4-byte aligned (S = 46)
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 #ifndef MACJD_MX_ABLATE
 #define MACJD_MX_ABLATE 0   // timing experiments only (results wrong when non-zero): 1 no fragment loads, 2 no phase-1
@@ -53,20 +54,57 @@ __device__ __forceinline__ float mx_sum16(float x) {   // sum over the 16 lanes 
     return x;
 }
 
+// Operand type (template parameter BF of every body / kernel below; macjd_mixerf_io.operand_dtype).  BF = false: exact
+// f32, v_mfma_f32_16x16x4_f32.  BF = true: the same fragments, held as f32 (weights are the f32 parameters, activations
+// the f32 LDS images) and rounded to bf16 (v_cvt_pk_bf16_f32, round to nearest even) right before each
+// v_mfma_f32_16x16x32_bf16, which sums 32 k per instruction in f32.  Only the k each lane holds in a quad changes:
+// k of element jj of quad Q (16 k) for lane group g.  f32: k = 16 Q + 4 g + jj feeds MFMA jj of the quad (the permuted
+// assignment above).  bf16 (mx_kq + jj): quads pair up into 32-k steps, whose lane group g holds k = 32 P + 8 g + (0..7)
+// (A[row lane & 15][k], B[k][col lane & 15]): quad 2P + h holds k = 32 P + 8 g + 4 h + jj.  An odd last quad (S <= 48
+// at J = 3) is a half step: k = 16 Q + 4 g + jj in elements 0..3, zeros in 4..7 — no padding of the LDS rows or loads.
+// (The f32 index expressions below are spelled out as before, behind `BF ? ... :`, so that the f32 instantiations
+// compile to the same code as before the operand type existed.)
+template <int NQ>
+__device__ __forceinline__ constexpr int mx_kq(int Q, int g) {
+    return ((NQ & 1) && Q == NQ - 1) ? 16 * Q + 4 * g : 32 * (Q >> 1) + 8 * g + 4 * (Q & 1);
+}
+__device__ __forceinline__ bf16x8 mx_pack_bf16(const f32x4& lo, const f32x4& hi) {
+    return bf16x8{(__bf16)lo[0], (__bf16)lo[1], (__bf16)lo[2], (__bf16)lo[3],
+                  (__bf16)hi[0], (__bf16)hi[1], (__bf16)hi[2], (__bf16)hi[3]};
+}
+// A operand of 32-k step P from an f32 LDS row (row = base + (lane & 15) * pitch; pitches and bases are multiples of 8
+// floats, so both halves are ds_read_b128)
+template <int NQ>
+__device__ __forceinline__ bf16x8 mx_a_bf16(const float* row, int P, int g) {
+    const f32x4 lo = *reinterpret_cast<const f32x4*>(row + mx_kq<NQ>(2 * P, g));
+    const f32x4 hi = (2 * P + 1 < NQ) ? *reinterpret_cast<const f32x4*>(row + mx_kq<NQ>(2 * P + 1, g))
+                                      : f32x4{0.f, 0.f, 0.f, 0.f};
+    return mx_pack_bf16(lo, hi);
+}
+// B operand of 32-k step P from a lane's f32 fragments
+template <int NQ>
+__device__ __forceinline__ bf16x8 mx_b_bf16(const f32x4 (&B)[NQ], int P) {
+    return mx_pack_bf16(B[2 * P], (2 * P + 1 < NQ) ? B[2 * P + 1] : f32x4{0.f, 0.f, 0.f, 0.f});
+}
+__device__ __forceinline__ f32x4 mx_mfma_bf16(const bf16x8& a, const bf16x8& b, const f32x4& c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
+
 // B fragments (all quads) of one 16-column tile whose weight row is `row` of a row-major [*, K] matrix.  No branch
 // around any load: a divergent `if` with a load inside makes hipcc drain the memory counter (s_waitcnt vmcnt(0)) at
 // every join, which serialised the ~50 fragment loads of a wave one L2 latency after the other (16 us per launch
 // instead of ~5).  RAGGED (K not a multiple of 16, e.g. S = 46): the last quad is four dword loads from clamped
-// addresses, zeroed past the row by selects.
-template <int NQ, bool RAGGED>
+// addresses, zeroed past the row by selects (bf16 with NQ even: the last two quads, which share the last 32-k step).
+template <int NQ, bool RAGGED, bool BF = false>
 __device__ __forceinline__ void mx_load_frags(f32x4 (&dst)[NQ], const float* __restrict__ W, int K, int row, int g) {
+    constexpr int NRAG = (BF && NQ % 2 == 0) ? 2 : 1;
     const float* p = W + (int64_t)row * K;
 #pragma unroll
     for (int Q = 0; Q < NQ; ++Q) {
-        const int k0 = 16 * Q + 4 * g;
+        const int k0 = BF ? mx_kq<NQ>(Q, g) : 16 * Q + 4 * g;
         if (MX_ABL & 1) {
             dst[Q] = f32x4{(float)row, (float)g, 1.0f, 0.5f};
-        } else if (!RAGGED || Q < NQ - 1) {   // compile-time
+        } else if (!RAGGED || Q < NQ - NRAG) {   // compile-time
             dst[Q] = *reinterpret_cast<const f32x4_u*>(p + k0);
         } else {
 #pragma unroll
@@ -81,12 +119,25 @@ __device__ __forceinline__ void mx_load_frags(f32x4 (&dst)[NQ], const float* __r
 
 // Second layers + tail for this wave's embed block, shared by the forward kernel and the backward's recomputation:
 // acc2[j] = tile (j, eb) of w1_raw WITHOUT its bias, accf = tile eb of wf_raw without its bias.
-template <int J>
+template <int J, bool BF>
 __device__ __forceinline__ void mx_second_layers(const float* __restrict__ Hs, const f32x4 (&B2)[J][MX_KQ2],
                                                  const f32x4 (&Bf)[MX_KQ2], f32x4 (&acc2)[J], f32x4& accf, int li, int g) {
 #pragma unroll
     for (int j = 0; j < J; ++j) acc2[j] = f32x4{0.f, 0.f, 0.f, 0.f};
     accf = f32x4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (BF) {
+        const float* a1p = Hs + li * MX_LDH;
+        const float* afp = a1p + MX_HH;
+#pragma unroll
+        for (int P = 0; P < ((MX_ABL & 4) ? 0 : MX_KQ2 / 2); ++P) {
+            const bf16x8 a1 = mx_a_bf16<MX_KQ2>(a1p, P, g);
+            const bf16x8 af = mx_a_bf16<MX_KQ2>(afp, P, g);
+#pragma unroll
+            for (int j = 0; j < J; ++j) acc2[j] = mx_mfma_bf16(a1, mx_b_bf16<MX_KQ2>(B2[j], P), acc2[j]);
+            accf = mx_mfma_bf16(af, mx_b_bf16<MX_KQ2>(Bf, P), accf);
+        }
+        return;
+    }
     const float* a1p = Hs + li * MX_LDH + 4 * g;            // h_w1: columns [0, Hh)
     const float* afp = a1p + MX_HH;                         // h_wf: columns [Hh, 2 Hh)
 #pragma unroll
@@ -138,7 +189,7 @@ struct MixerKeep {
 
 // m0 = first row of the tile, wave = this wave's index among the body's four (the training kernel runs two bodies side
 // by side in one eight-wave workgroup).  KEEP: hand the tiles / vectors above to the caller.
-template <int J, int SQ, bool SAVE, bool LATE2 = false, bool KEEP = false>
+template <int J, int SQ, bool SAVE, bool LATE2 = false, bool KEEP = false, bool BF = false>
 __device__ __forceinline__ void mixer_fused_forward_body(const macjd_mixerf_io& io, const int64_t m0, const int wave,
                                                          MixerFwdLds<SQ>& L, MixerKeep<J>* keep = nullptr) {
     constexpr int LDA = 16 * SQ + 8;
@@ -176,11 +227,11 @@ __device__ __forceinline__ void mixer_fused_forward_body(const macjd_mixerf_io& 
     const float bV2 = io.bV2[0];
     f32x4 B1[T1W][SQ], B2[J][MX_KQ2], Bf[MX_KQ2];
 #pragma unroll
-    for (int i = 0; i < T1W; ++i) mx_load_frags<SQ, true>(B1[i], io.W1, S, 16 * (T1W * wave + i) + li, g);
+    for (int i = 0; i < T1W; ++i) mx_load_frags<SQ, true, BF>(B1[i], io.W1, S, 16 * (T1W * wave + i) + li, g);
     auto load_second = [&]() {
 #pragma unroll
-        for (int j = 0; j < J; ++j) mx_load_frags<MX_KQ2, false>(B2[j], io.W2, MX_HH, j * MX_EM + 16 * wave + li, g);
-        mx_load_frags<MX_KQ2, false>(Bf, io.Wf2, MX_HH, 16 * wave + li, g);
+        for (int j = 0; j < J; ++j) mx_load_frags<MX_KQ2, false, BF>(B2[j], io.W2, MX_HH, j * MX_EM + 16 * wave + li, g);
+        mx_load_frags<MX_KQ2, false, BF>(Bf, io.Wf2, MX_HH, 16 * wave + li, g);
     };
     if (!LATE2) load_second();
     // this lane's rows of q (rows 4g..4g+3 of the tile), for the tail
@@ -231,14 +282,23 @@ __device__ __forceinline__ void mixer_fused_forward_body(const macjd_mixerf_io& 
         f32x4 acc[T1W];
 #pragma unroll
         for (int i = 0; i < T1W; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const float* ap = As + li * LDA + 4 * g;
+        if constexpr (BF) {
 #pragma unroll
-        for (int Q = 0; Q < ((MX_ABL & 2) ? 0 : SQ); ++Q) {
-            const f32x4 a = *reinterpret_cast<const f32x4*>(ap + 16 * Q);
+            for (int P = 0; P < ((MX_ABL & 2) ? 0 : (SQ + 1) / 2); ++P) {
+                const bf16x8 a = mx_a_bf16<SQ>(As + li * LDA, P, g);
 #pragma unroll
-            for (int jj = 0; jj < 4; ++jj)
+                for (int i = 0; i < T1W; ++i) acc[i] = mx_mfma_bf16(a, mx_b_bf16<SQ>(B1[i], P), acc[i]);
+            }
+        } else {
+            const float* ap = As + li * LDA + 4 * g;
 #pragma unroll
-                for (int i = 0; i < T1W; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[jj], B1[i][Q][jj], acc[i], 0, 0, 0);
+            for (int Q = 0; Q < ((MX_ABL & 2) ? 0 : SQ); ++Q) {
+                const f32x4 a = *reinterpret_cast<const f32x4*>(ap + 16 * Q);
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+                    for (int i = 0; i < T1W; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[jj], B1[i][Q][jj], acc[i], 0, 0, 0);
+            }
         }
         if (LATE2) load_second();
 #pragma unroll
@@ -258,7 +318,7 @@ __device__ __forceinline__ void mixer_fused_forward_body(const macjd_mixerf_io& 
 
     // ---- phase 2: second layers for embed block `wave`, tail (networks.py:301-310) ----
     f32x4 acc2[J], accf;
-    mx_second_layers<J>(Hs, B2, Bf, acc2, accf, li, g);
+    mx_second_layers<J, BF>(Hs, B2, Bf, acc2, accf, li, g);
     const int e = 16 * wave + li;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -292,20 +352,23 @@ __device__ __forceinline__ void mixer_fused_forward_body(const macjd_mixerf_io& 
     }
 }
 
-template <int J, int SQ, bool SAVE>
+// (bf16 at J = 6: the bf16 copies of the operands push the fragments-up-front plan past the 512 registers — 20 B / lane
+// of scratch — so the second layers' fragments are requested behind the first layer, LATE2)
+template <int J, int SQ, bool SAVE, bool BF>
 __global__ void __launch_bounds__(256) mixer_fused_forward_kernel(const macjd_mixerf_io io) {
     __shared__ MixerFwdLds<SQ> L;
-    mixer_fused_forward_body<J, SQ, SAVE>(io, (int64_t)blockIdx.x * 16, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), L);
+    mixer_fused_forward_body<J, SQ, SAVE, BF && J == 6, false, BF>(io, (int64_t)blockIdx.x * 16, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), L);
 }
 
 // blockIdx.y = 0: the mixer whose activations are saved for a backward (io_a), 1: the plain one (io_b)
-template <int J, int SQ>
+template <int J, int SQ, bool BF>
 __global__ void __launch_bounds__(256, (J <= 3) ? 2 : 1) mixer_fused_forward_pair_kernel(const macjd_mixerf_io io_a, const macjd_mixerf_io io_b) {
     __shared__ MixerFwdLds<SQ> L;
     const int64_t m0 = (int64_t)blockIdx.x * 16;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (blockIdx.y == 0) mixer_fused_forward_body<J, SQ, true, (J <= 3)>(io_a, m0, wave, L);
-    else mixer_fused_forward_body<J, SQ, false, (J <= 3)>(io_b, m0, wave, L);
+    constexpr bool LATE2 = (J <= 3) || (BF && J == 6);   // (bf16 at J = 6: see mixer_fused_forward_kernel)
+    if (blockIdx.y == 0) mixer_fused_forward_body<J, SQ, true, LATE2, false, BF>(io_a, m0, wave, L);
+    else mixer_fused_forward_body<J, SQ, false, LATE2, false, BF>(io_b, m0, wave, L);
 }
 
 // Backward (see the header): recompute the second layers from `act`, tail gradients, transposed second layers.
@@ -314,7 +377,7 @@ __global__ void __launch_bounds__(256, (J <= 3) ? 2 : 1) mixer_fused_forward_pai
 // otherwise — td_loss_kernel's own expression, with scale = 2 / *tot_m from a launch that summed the batch's mask earlier
 // (macjd_td_mask_sum: it needs the gathered batch only, so it runs long before).  Five loads per row, no reduction: the
 // loss launch leaves the update's serial chain (its logged sums are computed off the chain by macjd_td_loss).
-template <int J, bool TD = false>
+template <int J, bool TD, bool BF>
 __global__ void __launch_bounds__(256) mixer_fused_backward_kernel(const macjd_mixerf_io io, const macjd_tdloss_io td,
                                                                     const float* __restrict__ tot_m) {
     constexpr int LDG = J * MX_EM + 8;      // pitch of g_w1raw in LDS (= 8 mod 16)
@@ -338,8 +401,8 @@ __global__ void __launch_bounds__(256) mixer_fused_backward_kernel(const macjd_m
     // ---- weight fragments, requested up front: forward orientation for the recomputation ...
     f32x4 B2[J][MX_KQ2], Bf[MX_KQ2];
 #pragma unroll
-    for (int j = 0; j < J; ++j) mx_load_frags<MX_KQ2, false>(B2[j], io.W2, MX_HH, j * MX_EM + 16 * wave + li, g);
-    mx_load_frags<MX_KQ2, false>(Bf, io.Wf2, MX_HH, 16 * wave + li, g);
+    for (int j = 0; j < J; ++j) mx_load_frags<MX_KQ2, false, BF>(B2[j], io.W2, MX_HH, j * MX_EM + 16 * wave + li, g);
+    mx_load_frags<MX_KQ2, false, BF>(Bf, io.Wf2, MX_HH, 16 * wave + li, g);
     // ... and transposed for the input gradients of the second layers: this wave's output columns are the hidden units
     // n = 16 (2 wave + tt) + li; B[k][n] = W2[k][n] with k = 16 Q + 4 g + jj the row (a w1_raw column): four strided
     // dwords per quad, each a coalesced 64-byte row piece over li
@@ -354,11 +417,11 @@ __global__ void __launch_bounds__(256) mixer_fused_backward_kernel(const macjd_m
 #pragma unroll
             for (int Q = 0; Q < KQ1; ++Q)
 #pragma unroll
-                for (int jj = 0; jj < 4; ++jj) D1[tt][Q][jj] = io.W2[(int64_t)(16 * Q + 4 * g + jj) * MX_HH + n];
+                for (int jj = 0; jj < 4; ++jj) D1[tt][Q][jj] = io.W2[(int64_t)(BF ? mx_kq<KQ1>(Q, g) + jj : 16 * Q + 4 * g + jj) * MX_HH + n];
 #pragma unroll
             for (int Q = 0; Q < KQF; ++Q)
 #pragma unroll
-                for (int jj = 0; jj < 4; ++jj) Df[tt][Q][jj] = io.Wf2[(int64_t)(16 * Q + 4 * g + jj) * MX_HH + n];
+                for (int jj = 0; jj < 4; ++jj) Df[tt][Q][jj] = io.Wf2[(int64_t)(BF ? mx_kq<KQF>(Q, g) + jj : 16 * Q + 4 * g + jj) * MX_HH + n];
         }
     };
     if (EARLY_D) load_transposed();
@@ -406,7 +469,7 @@ __global__ void __launch_bounds__(256) mixer_fused_backward_kernel(const macjd_m
 
     // ---- recompute w1_raw / wf_raw tiles of embed block `wave` and the tail, then its gradients ----
     f32x4 acc2[J], accf;
-    mx_second_layers<J>(Hs, B2, Bf, acc2, accf, li, g);
+    mx_second_layers<J, BF>(Hs, B2, Bf, acc2, accf, li, g);
     const int e = 16 * wave + li;
     const float v_raw = (wave == 0) ? mx_v_raw(Hs, wv, bV2, li, g) : 0.0f;
 #pragma unroll
@@ -460,23 +523,38 @@ __global__ void __launch_bounds__(256) mixer_fused_backward_kernel(const macjd_m
         f32x4 a1[2], af[2];
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt) { a1[tt] = f32x4{0.f, 0.f, 0.f, 0.f}; af[tt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-        const float* gp = G1 + li * LDG + 4 * g;
-        const float* fp = Gf + li * LDF + 4 * g;
+        if constexpr (BF) {
 #pragma unroll
-        for (int Q = 0; Q < KQ1; ++Q) {
-            const f32x4 a = *reinterpret_cast<const f32x4*>(gp + 16 * Q);
+            for (int P = 0; P < KQ1 / 2; ++P) {
+                const bf16x8 a = mx_a_bf16<KQ1>(G1 + li * LDG, P, g);
 #pragma unroll
-            for (int jj = 0; jj < 4; ++jj)
+                for (int tt = 0; tt < 2; ++tt) a1[tt] = mx_mfma_bf16(a, mx_b_bf16<KQ1>(D1[tt], P), a1[tt]);
+            }
 #pragma unroll
-                for (int tt = 0; tt < 2; ++tt) a1[tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[jj], D1[tt][Q][jj], a1[tt], 0, 0, 0);
-        }
+            for (int P = 0; P < KQF / 2; ++P) {
+                const bf16x8 a = mx_a_bf16<KQF>(Gf + li * LDF, P, g);
 #pragma unroll
-        for (int Q = 0; Q < KQF; ++Q) {
-            const f32x4 a = *reinterpret_cast<const f32x4*>(fp + 16 * Q);
+                for (int tt = 0; tt < 2; ++tt) af[tt] = mx_mfma_bf16(a, mx_b_bf16<KQF>(Df[tt], P), af[tt]);
+            }
+        } else {
+            const float* gp = G1 + li * LDG + 4 * g;
+            const float* fp = Gf + li * LDF + 4 * g;
 #pragma unroll
-            for (int jj = 0; jj < 4; ++jj)
+            for (int Q = 0; Q < KQ1; ++Q) {
+                const f32x4 a = *reinterpret_cast<const f32x4*>(gp + 16 * Q);
 #pragma unroll
-                for (int tt = 0; tt < 2; ++tt) af[tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[jj], Df[tt][Q][jj], af[tt], 0, 0, 0);
+                for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+                    for (int tt = 0; tt < 2; ++tt) a1[tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[jj], D1[tt][Q][jj], a1[tt], 0, 0, 0);
+            }
+#pragma unroll
+            for (int Q = 0; Q < KQF; ++Q) {
+                const f32x4 a = *reinterpret_cast<const f32x4*>(fp + 16 * Q);
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+                    for (int tt = 0; tt < 2; ++tt) af[tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[jj], Df[tt][Q][jj], af[tt], 0, 0, 0);
+            }
         }
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt) {
@@ -524,7 +602,7 @@ struct MixerTrainLds {
     float ys[16], tqs[16];   // eval Q_tot of row m0 + i, target Q_tot of row m0 + 1 + i
 };
 
-template <int J>
+template <int J, bool BF>
 __global__ void __launch_bounds__(512) mixer_fused_train_kernel(const macjd_mixerf_io io, const macjd_mixerf_io tio,
                                                                  const macjd_tdloss_io td, const float* __restrict__ tot_m) {
     constexpr int LDG = J * MX_EM + 8;
@@ -561,11 +639,11 @@ __global__ void __launch_bounds__(512) mixer_fused_train_kernel(const macjd_mixe
     MixerKeep<J> K;
     f32x4 D1[KQ1], Df[KQF];
     if (eval_half) {
-        mixer_fused_forward_body<J, J, true, true, true>(io, m0, wave, L.ev, &K);
+        mixer_fused_forward_body<J, J, true, true, true, BF>(io, m0, wave, L.ev, &K);
         if (wave == 0 && g == 0) L.ys[li] = K.y;
     } else {
         MixerKeep<J> Kt;
-        mixer_fused_forward_body<J, J, false, true, true>(tio, m0 + 1, wave, L.tg, &Kt);
+        mixer_fused_forward_body<J, J, false, true, true, BF>(tio, m0 + 1, wave, L.tg, &Kt);
         if (wave == 0 && g == 0) L.tqs[li] = Kt.y;
     }
     // transposed second-layer fragments of this wave's gout1 column tile n = 16 wave8 + li (B[k][n] = W2[k][n], k = 16 Q +
@@ -575,11 +653,11 @@ __global__ void __launch_bounds__(512) mixer_fused_train_kernel(const macjd_mixe
 #pragma unroll
         for (int Q = 0; Q < KQ1; ++Q)
 #pragma unroll
-            for (int jj = 0; jj < 4; ++jj) D1[Q][jj] = io.W2[(int64_t)(16 * Q + 4 * g + jj) * MX_HH + n];
+            for (int jj = 0; jj < 4; ++jj) D1[Q][jj] = io.W2[(int64_t)(BF ? mx_kq<KQ1>(Q, g) + jj : 16 * Q + 4 * g + jj) * MX_HH + n];
 #pragma unroll
         for (int Q = 0; Q < KQF; ++Q)
 #pragma unroll
-            for (int jj = 0; jj < 4; ++jj) Df[Q][jj] = io.Wf2[(int64_t)(16 * Q + 4 * g + jj) * MX_HH + n];
+            for (int jj = 0; jj < 4; ++jj) Df[Q][jj] = io.Wf2[(int64_t)(BF ? mx_kq<KQF>(Q, g) + jj : 16 * Q + 4 * g + jj) * MX_HH + n];
     }
     float wvo[2];
 #pragma unroll
@@ -645,19 +723,26 @@ __global__ void __launch_bounds__(512) mixer_fused_train_kernel(const macjd_mixe
     // input gradients of the second layers, masked by the first layer's ReLU: column tile n of [0, Hh) and of [Hh, 2 Hh)
     {
         f32x4 a1 = f32x4{0.f, 0.f, 0.f, 0.f}, af = f32x4{0.f, 0.f, 0.f, 0.f};
-        const float* gp = L.G1 + li * LDG + 4 * g;
-        const float* fp = L.Gf + li * LDF + 4 * g;
+        if constexpr (BF) {
 #pragma unroll
-        for (int Q = 0; Q < KQ1; ++Q) {
-            const f32x4 a = *reinterpret_cast<const f32x4*>(gp + 16 * Q);
+            for (int P = 0; P < KQ1 / 2; ++P) a1 = mx_mfma_bf16(mx_a_bf16<KQ1>(L.G1 + li * LDG, P, g), mx_b_bf16<KQ1>(D1, P), a1);
 #pragma unroll
-            for (int jj = 0; jj < 4; ++jj) a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[jj], D1[Q][jj], a1, 0, 0, 0);
-        }
+            for (int P = 0; P < KQF / 2; ++P) af = mx_mfma_bf16(mx_a_bf16<KQF>(L.Gf + li * LDF, P, g), mx_b_bf16<KQF>(Df, P), af);
+        } else {
+            const float* gp = L.G1 + li * LDG + 4 * g;
+            const float* fp = L.Gf + li * LDF + 4 * g;
 #pragma unroll
-        for (int Q = 0; Q < KQF; ++Q) {
-            const f32x4 a = *reinterpret_cast<const f32x4*>(fp + 16 * Q);
+            for (int Q = 0; Q < KQ1; ++Q) {
+                const f32x4 a = *reinterpret_cast<const f32x4*>(gp + 16 * Q);
 #pragma unroll
-            for (int jj = 0; jj < 4; ++jj) af = __builtin_amdgcn_mfma_f32_16x16x4f32(a[jj], Df[Q][jj], af, 0, 0, 0);
+                for (int jj = 0; jj < 4; ++jj) a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[jj], D1[Q][jj], a1, 0, 0, 0);
+            }
+#pragma unroll
+            for (int Q = 0; Q < KQF; ++Q) {
+                const f32x4 a = *reinterpret_cast<const f32x4*>(fp + 16 * Q);
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) af = __builtin_amdgcn_mfma_f32_16x16x4f32(a[jj], Df[Q][jj], af, 0, 0, 0);
+            }
         }
         const int n = 16 * wave8 + li;
 #pragma unroll
@@ -687,17 +772,26 @@ __global__ void __launch_bounds__(512) mixer_fused_train_kernel(const macjd_mixe
 // fragments are loaded one pass ahead: the first layer two column tiles at a time, the J tiles of w1_raw PJ agents at
 // a time.  The tail's fmaf chain over the agents runs in agent order across the passes, i.e. it is the chain of
 // mixer_tail_kernel / the narrow kernels.
-template <int PJ>
+template <int PJ, bool BF>
 __device__ __forceinline__ void mx_load_pass(f32x4 (&dst)[PJ][MX_KQ2], const float* __restrict__ W2, int j0, int wave, int li, int g) {
 #pragma unroll
-    for (int jj = 0; jj < PJ; ++jj) mx_load_frags<MX_KQ2, false>(dst[jj], W2, MX_HH, (j0 + jj) * MX_EM + 16 * wave + li, g);
+    for (int jj = 0; jj < PJ; ++jj) mx_load_frags<MX_KQ2, false, BF>(dst[jj], W2, MX_HH, (j0 + jj) * MX_EM + 16 * wave + li, g);
 }
 
-template <int PJ>
+template <int PJ, bool BF>
 __device__ __forceinline__ void mx_pass_tiles(const float* __restrict__ Hs, const f32x4 (&B2)[PJ][MX_KQ2], f32x4 (&acc2)[PJ],
                                               int li, int g) {
 #pragma unroll
     for (int j = 0; j < PJ; ++j) acc2[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (BF) {
+#pragma unroll
+        for (int P = 0; P < MX_KQ2 / 2; ++P) {
+            const bf16x8 a1 = mx_a_bf16<MX_KQ2>(Hs + li * MX_LDH, P, g);
+#pragma unroll
+            for (int j = 0; j < PJ; ++j) acc2[j] = mx_mfma_bf16(a1, mx_b_bf16<MX_KQ2>(B2[j], P), acc2[j]);
+        }
+        return;
+    }
     const float* a1p = Hs + li * MX_LDH + 4 * g;            // h_w1: columns [0, Hh)
 #pragma unroll
     for (int Q = 0; Q < MX_KQ2; ++Q) {
@@ -709,8 +803,14 @@ __device__ __forceinline__ void mx_pass_tiles(const float* __restrict__ Hs, cons
     }
 }
 
+template <bool BF>
 __device__ __forceinline__ void mx_wf_tile(const float* __restrict__ Hs, const f32x4 (&Bf)[MX_KQ2], f32x4& accf, int li, int g) {
     accf = f32x4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (BF) {
+#pragma unroll
+        for (int P = 0; P < MX_KQ2 / 2; ++P) accf = mx_mfma_bf16(mx_a_bf16<MX_KQ2>(Hs + li * MX_LDH + MX_HH, P, g), mx_b_bf16<MX_KQ2>(Bf, P), accf);
+        return;
+    }
     const float* afp = Hs + li * MX_LDH + 4 * g + MX_HH;    // h_wf: columns [Hh, 2 Hh)
 #pragma unroll
     for (int Q = 0; Q < MX_KQ2; ++Q) {
@@ -720,7 +820,7 @@ __device__ __forceinline__ void mx_wf_tile(const float* __restrict__ Hs, const f
     }
 }
 
-template <int J, int SQ, bool SAVE, int PJ>
+template <int J, int SQ, bool SAVE, int PJ, bool BF>
 __device__ __forceinline__ void mixer_fused_forward_wide_body(const macjd_mixerf_io& io, const int blk, MixerFwdLds<SQ>& L) {
     static_assert(J % PJ == 0, "whole passes");
     constexpr int LDA = 16 * SQ + 8;
@@ -759,9 +859,9 @@ __device__ __forceinline__ void mixer_fused_forward_wide_body(const macjd_mixerf
     // first-layer fragments of passes 0 and 1 (the third pass re-uses the first buffer)
     f32x4 B1a[P1W][SQ], B1b[P1W][SQ];
 #pragma unroll
-    for (int i = 0; i < P1W; ++i) mx_load_frags<SQ, true>(B1a[i], io.W1, S, 16 * (T1W * wave + i) + li, g);
+    for (int i = 0; i < P1W; ++i) mx_load_frags<SQ, true, BF>(B1a[i], io.W1, S, 16 * (T1W * wave + i) + li, g);
 #pragma unroll
-    for (int i = 0; i < P1W; ++i) mx_load_frags<SQ, true>(B1b[i], io.W1, S, 16 * (T1W * wave + P1W + i) + li, g);
+    for (int i = 0; i < P1W; ++i) mx_load_frags<SQ, true, BF>(B1b[i], io.W1, S, 16 * (T1W * wave + P1W + i) + li, g);
     float qv[4][J];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -809,14 +909,23 @@ __device__ __forceinline__ void mixer_fused_forward_wide_body(const macjd_mixerf
         f32x4 acc[P1W];
 #pragma unroll
         for (int i = 0; i < P1W; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const float* ap = As + li * LDA + 4 * g;
+        if constexpr (BF) {
 #pragma unroll
-        for (int Q = 0; Q < SQ; ++Q) {
-            const f32x4 a = *reinterpret_cast<const f32x4*>(ap + 16 * Q);
+            for (int P = 0; P < (SQ + 1) / 2; ++P) {
+                const bf16x8 a = mx_a_bf16<SQ>(As + li * LDA, P, g);
 #pragma unroll
-            for (int jj = 0; jj < 4; ++jj)
+                for (int i = 0; i < P1W; ++i) acc[i] = mx_mfma_bf16(a, mx_b_bf16<SQ>(B1[i], P), acc[i]);
+            }
+        } else {
+            const float* ap = As + li * LDA + 4 * g;
 #pragma unroll
-                for (int i = 0; i < P1W; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[jj], B1[i][Q][jj], acc[i], 0, 0, 0);
+            for (int Q = 0; Q < SQ; ++Q) {
+                const f32x4 a = *reinterpret_cast<const f32x4*>(ap + 16 * Q);
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+                    for (int i = 0; i < P1W; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[jj], B1[i][Q][jj], acc[i], 0, 0, 0);
+            }
         }
 #pragma unroll
         for (int i = 0; i < P1W; ++i) {
@@ -834,11 +943,11 @@ __device__ __forceinline__ void mixer_fused_forward_wide_body(const macjd_mixerf
     };
     first_layer_pass(B1a, 0);
 #pragma unroll
-    for (int i = 0; i < P1W; ++i) mx_load_frags<SQ, true>(B1a[i], io.W1, S, 16 * (T1W * wave + 2 * P1W + i) + li, g);
+    for (int i = 0; i < P1W; ++i) mx_load_frags<SQ, true, BF>(B1a[i], io.W1, S, 16 * (T1W * wave + 2 * P1W + i) + li, g);
     // second-layer fragments of the first agent pass and of w_final: in flight under the rest of phase 1
     f32x4 B2a[PJ][MX_KQ2], B2b[PJ][MX_KQ2], Bf[MX_KQ2];
-    mx_load_pass<PJ>(B2a, io.W2, 0, wave, li, g);
-    mx_load_frags<MX_KQ2, false>(Bf, io.Wf2, MX_HH, 16 * wave + li, g);
+    mx_load_pass<PJ, BF>(B2a, io.W2, 0, wave, li, g);
+    mx_load_frags<MX_KQ2, false, BF>(Bf, io.Wf2, MX_HH, 16 * wave + li, g);
     first_layer_pass(B1b, 1);
     first_layer_pass(B1a, 2);
     __syncthreads();
@@ -853,12 +962,12 @@ __device__ __forceinline__ void mixer_fused_forward_wide_body(const macjd_mixerf
     for (int p = 0; p < NP; ++p) {
         f32x4 acc2[PJ];
         if (p + 1 < NP) {
-            if (p & 1) mx_load_pass<PJ>(B2a, io.W2, (p + 1) * PJ, wave, li, g);
-            else mx_load_pass<PJ>(B2b, io.W2, (p + 1) * PJ, wave, li, g);
+            if (p & 1) mx_load_pass<PJ, BF>(B2a, io.W2, (p + 1) * PJ, wave, li, g);
+            else mx_load_pass<PJ, BF>(B2b, io.W2, (p + 1) * PJ, wave, li, g);
         }
-        if (p & 1) mx_pass_tiles<PJ>(Hs, B2b, acc2, li, g);
-        else mx_pass_tiles<PJ>(Hs, B2a, acc2, li, g);
-        if (p == 0) mx_wf_tile(Hs, Bf, accf, li, g);
+        if (p & 1) mx_pass_tiles<PJ, BF>(Hs, B2b, acc2, li, g);
+        else mx_pass_tiles<PJ, BF>(Hs, B2a, acc2, li, g);
+        if (p == 0) mx_wf_tile<BF>(Hs, Bf, accf, li, g);
 #pragma unroll
         for (int jj = 0; jj < PJ; ++jj) {
             const int j = p * PJ + jj;
@@ -881,20 +990,20 @@ __device__ __forceinline__ void mixer_fused_forward_wide_body(const macjd_mixerf
     }
 }
 
-template <int J, int SQ, bool SAVE, int PJ>
+template <int J, int SQ, bool SAVE, int PJ, bool BF>
 __global__ void __launch_bounds__(256) mixer_fused_forward_wide_kernel(const macjd_mixerf_io io) {
     __shared__ MixerFwdLds<SQ> L;
-    mixer_fused_forward_wide_body<J, SQ, SAVE, PJ>(io, blockIdx.x, L);
+    mixer_fused_forward_wide_body<J, SQ, SAVE, PJ, BF>(io, blockIdx.x, L);
 }
 
-template <int J, int SQ, int PJ>
+template <int J, int SQ, int PJ, bool BF>
 __global__ void __launch_bounds__(256) mixer_fused_forward_wide_pair_kernel(const macjd_mixerf_io io_a, const macjd_mixerf_io io_b) {
     __shared__ MixerFwdLds<SQ> L;
-    if (blockIdx.y == 0) mixer_fused_forward_wide_body<J, SQ, true, PJ>(io_a, blockIdx.x, L);
-    else mixer_fused_forward_wide_body<J, SQ, false, PJ>(io_b, blockIdx.x, L);
+    if (blockIdx.y == 0) mixer_fused_forward_wide_body<J, SQ, true, PJ, BF>(io_a, blockIdx.x, L);
+    else mixer_fused_forward_wide_body<J, SQ, false, PJ, BF>(io_b, blockIdx.x, L);
 }
 
-template <int J, int PJ, bool TD = false>
+template <int J, int PJ, bool TD, bool BF>
 __global__ void __launch_bounds__(256) mixer_fused_backward_wide_kernel(const macjd_mixerf_io io, const macjd_tdloss_io td,
                                                                          const float* __restrict__ tot_m) {
     static_assert(J % PJ == 0, "whole passes");
@@ -918,8 +1027,8 @@ __global__ void __launch_bounds__(256) mixer_fused_backward_wide_kernel(const ma
     const int64_t m0 = (int64_t)blockIdx.x * 16;
 
     f32x4 B2a[PJ][MX_KQ2], B2b[PJ][MX_KQ2], Bf[MX_KQ2];
-    mx_load_pass<PJ>(B2a, io.W2, 0, wave, li, g);
-    mx_load_frags<MX_KQ2, false>(Bf, io.Wf2, MX_HH, 16 * wave + li, g);
+    mx_load_pass<PJ, BF>(B2a, io.W2, 0, wave, li, g);
+    mx_load_frags<MX_KQ2, false, BF>(Bf, io.Wf2, MX_HH, 16 * wave + li, g);
     float b2e[J], wv[16], wvo[4];
 #pragma unroll
     for (int j = 0; j < J; ++j) b2e[j] = io.b2[j * MX_EM + 16 * wave + li];
@@ -974,12 +1083,12 @@ __global__ void __launch_bounds__(256) mixer_fused_backward_wide_kernel(const ma
     for (int p = 0; p < NP; ++p) {
         f32x4 acc2[PJ];
         if (p + 1 < NP) {
-            if (p & 1) mx_load_pass<PJ>(B2a, io.W2, (p + 1) * PJ, wave, li, g);
-            else mx_load_pass<PJ>(B2b, io.W2, (p + 1) * PJ, wave, li, g);
+            if (p & 1) mx_load_pass<PJ, BF>(B2a, io.W2, (p + 1) * PJ, wave, li, g);
+            else mx_load_pass<PJ, BF>(B2b, io.W2, (p + 1) * PJ, wave, li, g);
         }
-        if (p & 1) mx_pass_tiles<PJ>(Hs, B2b, acc2, li, g);
-        else mx_pass_tiles<PJ>(Hs, B2a, acc2, li, g);
-        if (p == 0) mx_wf_tile(Hs, Bf, accf, li, g);
+        if (p & 1) mx_pass_tiles<PJ, BF>(Hs, B2b, acc2, li, g);
+        else mx_pass_tiles<PJ, BF>(Hs, B2a, acc2, li, g);
+        if (p == 0) mx_wf_tile<BF>(Hs, Bf, accf, li, g);
 #pragma unroll
         for (int jj = 0; jj < PJ; ++jj) {
             const int j = p * PJ + jj;
@@ -1028,7 +1137,7 @@ __global__ void __launch_bounds__(256) mixer_fused_backward_wide_kernel(const ma
 #pragma unroll
             for (int Q = 0; Q < KQP; ++Q)
 #pragma unroll
-                for (int jj = 0; jj < 4; ++jj) D1[tt][Q][jj] = io.W2[(int64_t)(p * PJ * MX_EM + 16 * Q + 4 * g + jj) * MX_HH + n];
+                for (int jj = 0; jj < 4; ++jj) D1[tt][Q][jj] = io.W2[(int64_t)(BF ? p * PJ * MX_EM + mx_kq<KQP>(Q, g) + jj : p * PJ * MX_EM + 16 * Q + 4 * g + jj) * MX_HH + n];
         }
         if (p > 0) __syncthreads();          // the previous pass's readers of G1 are done
 #pragma unroll
@@ -1053,14 +1162,23 @@ __global__ void __launch_bounds__(256) mixer_fused_backward_wide_kernel(const ma
             }
         }
         __syncthreads();
-        const float* gp = G1 + li * LDG + 4 * g;
+        if constexpr (BF) {
 #pragma unroll
-        for (int Q = 0; Q < KQP; ++Q) {
-            const f32x4 a = *reinterpret_cast<const f32x4*>(gp + 16 * Q);
+            for (int P = 0; P < KQP / 2; ++P) {
+                const bf16x8 a = mx_a_bf16<KQP>(G1 + li * LDG, P, g);
 #pragma unroll
-            for (int jj = 0; jj < 4; ++jj)
+                for (int tt = 0; tt < 2; ++tt) a1[tt] = mx_mfma_bf16(a, mx_b_bf16<KQP>(D1[tt], P), a1[tt]);
+            }
+        } else {
+            const float* gp = G1 + li * LDG + 4 * g;
 #pragma unroll
-                for (int tt = 0; tt < 2; ++tt) a1[tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[jj], D1[tt][Q][jj], a1[tt], 0, 0, 0);
+            for (int Q = 0; Q < KQP; ++Q) {
+                const f32x4 a = *reinterpret_cast<const f32x4*>(gp + 16 * Q);
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+                    for (int tt = 0; tt < 2; ++tt) a1[tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[jj], D1[tt][Q][jj], a1[tt], 0, 0, 0);
+            }
         }
     }
     // dL/dq: the four embed blocks' partial sums in fixed order (gq_part complete: barrier inside the last pass)
@@ -1078,16 +1196,25 @@ __global__ void __launch_bounds__(256) mixer_fused_backward_wide_kernel(const ma
 #pragma unroll
             for (int Q = 0; Q < KQF; ++Q)
 #pragma unroll
-                for (int jj = 0; jj < 4; ++jj) Df[tt][Q][jj] = io.Wf2[(int64_t)(16 * Q + 4 * g + jj) * MX_HH + n];
+                for (int jj = 0; jj < 4; ++jj) Df[tt][Q][jj] = io.Wf2[(int64_t)(BF ? mx_kq<KQF>(Q, g) + jj : 16 * Q + 4 * g + jj) * MX_HH + n];
         }
-        const float* fp = Gf + li * LDF + 4 * g;
+        if constexpr (BF) {
 #pragma unroll
-        for (int Q = 0; Q < KQF; ++Q) {
-            const f32x4 a = *reinterpret_cast<const f32x4*>(fp + 16 * Q);
+            for (int P = 0; P < KQF / 2; ++P) {
+                const bf16x8 a = mx_a_bf16<KQF>(Gf + li * LDF, P, g);
 #pragma unroll
-            for (int jj = 0; jj < 4; ++jj)
+                for (int tt = 0; tt < 2; ++tt) af[tt] = mx_mfma_bf16(a, mx_b_bf16<KQF>(Df[tt], P), af[tt]);
+            }
+        } else {
+            const float* fp = Gf + li * LDF + 4 * g;
 #pragma unroll
-                for (int tt = 0; tt < 2; ++tt) af[tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[jj], Df[tt][Q][jj], af[tt], 0, 0, 0);
+            for (int Q = 0; Q < KQF; ++Q) {
+                const f32x4 a = *reinterpret_cast<const f32x4*>(fp + 16 * Q);
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+                    for (int tt = 0; tt < 2; ++tt) af[tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[jj], Df[tt][Q][jj], af[tt], 0, 0, 0);
+            }
         }
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt) {
@@ -1114,6 +1241,8 @@ __global__ void __launch_bounds__(256) mixer_fused_backward_wide_kernel(const ma
 
 static int mixerf_check(const macjd_mixerf_io* io, bool backward, bool gy_from_td = false) {
     if (!io) return set_err(MACJD_EINVAL, "%s", "macjd_mixer_fused: NULL io");
+    if (io->operand_dtype != 0 && io->operand_dtype != 1)
+        return set_err(MACJD_EINVAL, "%s", "macjd_mixer_fused: operand_dtype must be 0 (f32) or 1 (bf16)");
     if (!macjd_mixer_fused_supported(io->J, io->S, io->Hh, io->Em))
         return set_err(MACJD_EUNSUPPORTED, "%s", "macjd_mixer_fused: unsupported J / S / Hh / Em (see include/macjd_nets.h)");
     if (io->M < 0 || !io->q || !io->W2 || !io->b2 || !io->Wf2 || !io->bf2 || !io->wV2 || !io->bV2)
@@ -1131,6 +1260,46 @@ static int mixerf_check(const macjd_mixerf_io* io, bool backward, bool gy_from_t
     return MACJD_OK;
 }
 
+// launches of one operand type (the entry points below have checked the arguments)
+template <bool BF>
+static void mixerf_launch_forward(const macjd_mixerf_io* io, dim3 grid, dim3 block, hipStream_t s) {
+#define MACJD_MXF(J_, SQ_)                                                                                          \
+    do {                                                                                                            \
+        if (io->save) hipLaunchKernelGGL((mixer_fused_forward_kernel<J_, SQ_, true, BF>), grid, block, 0, s, *io);  \
+        else hipLaunchKernelGGL((mixer_fused_forward_kernel<J_, SQ_, false, BF>), grid, block, 0, s, *io);          \
+    } while (0)
+    if (io->J == 2) MACJD_MXF(2, 2);
+    else if (io->J == 3) MACJD_MXF(3, 3);
+    else if (io->J == 6) MACJD_MXF(6, 6);
+    else if (io->save) hipLaunchKernelGGL((mixer_fused_forward_wide_kernel<12, 12, true, 4, BF>), grid, block, 0, s, *io);
+    else hipLaunchKernelGGL((mixer_fused_forward_wide_kernel<12, 12, false, 4, BF>), grid, block, 0, s, *io);
+#undef MACJD_MXF
+}
+
+template <bool BF>
+static void mixerf_launch_pair(const macjd_mixerf_io* saved, const macjd_mixerf_io* plain, dim3 grid, dim3 block, hipStream_t s) {
+    if (saved->J == 2) hipLaunchKernelGGL((mixer_fused_forward_pair_kernel<2, 2, BF>), grid, block, 0, s, *saved, *plain);
+    else if (saved->J == 3) hipLaunchKernelGGL((mixer_fused_forward_pair_kernel<3, 3, BF>), grid, block, 0, s, *saved, *plain);
+    else if (saved->J == 6) hipLaunchKernelGGL((mixer_fused_forward_pair_kernel<6, 6, BF>), grid, block, 0, s, *saved, *plain);
+    else hipLaunchKernelGGL((mixer_fused_forward_wide_pair_kernel<12, 12, 4, BF>), grid, block, 0, s, *saved, *plain);
+}
+
+template <bool TD, bool BF>
+static void mixerf_launch_backward(const macjd_mixerf_io* io, const macjd_tdloss_io& td, const float* tot_m, dim3 grid, dim3 block,
+                                   hipStream_t s) {
+    if (io->J == 2) hipLaunchKernelGGL((mixer_fused_backward_kernel<2, TD, BF>), grid, block, 0, s, *io, td, tot_m);
+    else if (io->J == 3) hipLaunchKernelGGL((mixer_fused_backward_kernel<3, TD, BF>), grid, block, 0, s, *io, td, tot_m);
+    else if (io->J == 6) hipLaunchKernelGGL((mixer_fused_backward_kernel<6, TD, BF>), grid, block, 0, s, *io, td, tot_m);
+    else hipLaunchKernelGGL((mixer_fused_backward_wide_kernel<12, 4, TD, BF>), grid, block, 0, s, *io, td, tot_m);
+}
+
+template <bool BF>
+static void mixerf_launch_train(const macjd_mixerf_io* eval, const macjd_mixerf_io* target, const macjd_tdloss_io* td,
+                                const float* tot_m, dim3 grid, dim3 block, hipStream_t s) {
+    if (eval->J == 2) hipLaunchKernelGGL((mixer_fused_train_kernel<2, BF>), grid, block, 0, s, *eval, *target, *td, tot_m);
+    else hipLaunchKernelGGL((mixer_fused_train_kernel<3, BF>), grid, block, 0, s, *eval, *target, *td, tot_m);
+}
+
 }  // namespace macjd
 
 extern "C" int macjd_mixer_fused_supported(int32_t J, int32_t S, int32_t Hh, int32_t Em) {
@@ -1145,17 +1314,8 @@ extern "C" int macjd_mixer_fused_forward(const macjd_mixerf_io* io, void* hip_st
     if (io->M == 0) return MACJD_OK;
     const dim3 grid((unsigned)((io->M + 15) / 16)), block(256);
     hipStream_t s = (hipStream_t)hip_stream;
-#define MACJD_MXF(J_, SQ_)                                                                                     \
-    do {                                                                                                       \
-        if (io->save) hipLaunchKernelGGL((mixer_fused_forward_kernel<J_, SQ_, true>), grid, block, 0, s, *io);  \
-        else hipLaunchKernelGGL((mixer_fused_forward_kernel<J_, SQ_, false>), grid, block, 0, s, *io);          \
-    } while (0)
-    if (io->J == 2) MACJD_MXF(2, 2);
-    else if (io->J == 3) MACJD_MXF(3, 3);
-    else if (io->J == 6) MACJD_MXF(6, 6);
-    else if (io->save) hipLaunchKernelGGL((mixer_fused_forward_wide_kernel<12, 12, true, 4>), grid, block, 0, s, *io);
-    else hipLaunchKernelGGL((mixer_fused_forward_wide_kernel<12, 12, false, 4>), grid, block, 0, s, *io);
-#undef MACJD_MXF
+    if (io->operand_dtype) mixerf_launch_forward<true>(io, grid, block, s);
+    else mixerf_launch_forward<false>(io, grid, block, s);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_mixer_fused_forward: %s", hipGetErrorString(err));
     return MACJD_OK;
@@ -1170,13 +1330,13 @@ extern "C" int macjd_mixer_fused_forward_pair(const macjd_mixerf_io* saved, cons
     if (!saved->save || plain->save) return set_err(MACJD_EINVAL, "%s", "macjd_mixer_fused_forward_pair: the first mixer saves, the second does not");
     if (saved->J != plain->J || saved->S != plain->S || saved->M != plain->M)
         return set_err(MACJD_EINVAL, "%s", "macjd_mixer_fused_forward_pair: the two mixers differ in J / S / M");
+    if (saved->operand_dtype != plain->operand_dtype)
+        return set_err(MACJD_EINVAL, "%s", "macjd_mixer_fused_forward_pair: the two mixers differ in operand_dtype");
     if (saved->M == 0) return MACJD_OK;
     const dim3 grid((unsigned)((saved->M + 15) / 16), 2), block(256);
     hipStream_t s = (hipStream_t)hip_stream;
-    if (saved->J == 2) hipLaunchKernelGGL((mixer_fused_forward_pair_kernel<2, 2>), grid, block, 0, s, *saved, *plain);
-    else if (saved->J == 3) hipLaunchKernelGGL((mixer_fused_forward_pair_kernel<3, 3>), grid, block, 0, s, *saved, *plain);
-    else if (saved->J == 6) hipLaunchKernelGGL((mixer_fused_forward_pair_kernel<6, 6>), grid, block, 0, s, *saved, *plain);
-    else hipLaunchKernelGGL((mixer_fused_forward_wide_pair_kernel<12, 12, 4>), grid, block, 0, s, *saved, *plain);
+    if (saved->operand_dtype) mixerf_launch_pair<true>(saved, plain, grid, block, s);
+    else mixerf_launch_pair<false>(saved, plain, grid, block, s);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_mixer_fused_forward_pair: %s", hipGetErrorString(err));
     return MACJD_OK;
@@ -1190,10 +1350,8 @@ extern "C" int macjd_mixer_fused_backward(const macjd_mixerf_io* io, void* hip_s
     const dim3 grid((unsigned)((io->M + 15) / 16)), block(256);
     hipStream_t s = (hipStream_t)hip_stream;
     const macjd_tdloss_io none{};
-    if (io->J == 2) hipLaunchKernelGGL((mixer_fused_backward_kernel<2>), grid, block, 0, s, *io, none, nullptr);
-    else if (io->J == 3) hipLaunchKernelGGL((mixer_fused_backward_kernel<3>), grid, block, 0, s, *io, none, nullptr);
-    else if (io->J == 6) hipLaunchKernelGGL((mixer_fused_backward_kernel<6>), grid, block, 0, s, *io, none, nullptr);
-    else hipLaunchKernelGGL((mixer_fused_backward_wide_kernel<12, 4>), grid, block, 0, s, *io, none, nullptr);
+    if (io->operand_dtype) mixerf_launch_backward<false, true>(io, none, nullptr, grid, block, s);
+    else mixerf_launch_backward<false, false>(io, none, nullptr, grid, block, s);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_mixer_fused_backward: %s", hipGetErrorString(err));
     return MACJD_OK;
@@ -1212,10 +1370,8 @@ extern "C" int macjd_mixer_fused_backward_td(const macjd_mixerf_io* io, const ma
     // td->stats != NULL: one workgroup more, which computes the loss's logged sums (stats[0..2]) beside the others
     const dim3 grid((unsigned)((io->M + 15) / 16) + (td->stats ? 1u : 0u)), block(256);
     hipStream_t s = (hipStream_t)hip_stream;
-    if (io->J == 2) hipLaunchKernelGGL((mixer_fused_backward_kernel<2, true>), grid, block, 0, s, *io, *td, tot_m);
-    else if (io->J == 3) hipLaunchKernelGGL((mixer_fused_backward_kernel<3, true>), grid, block, 0, s, *io, *td, tot_m);
-    else if (io->J == 6) hipLaunchKernelGGL((mixer_fused_backward_kernel<6, true>), grid, block, 0, s, *io, *td, tot_m);
-    else hipLaunchKernelGGL((mixer_fused_backward_wide_kernel<12, 4, true>), grid, block, 0, s, *io, *td, tot_m);
+    if (io->operand_dtype) mixerf_launch_backward<true, true>(io, *td, tot_m, grid, block, s);
+    else mixerf_launch_backward<true, false>(io, *td, tot_m, grid, block, s);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_mixer_fused_backward_td: %s", hipGetErrorString(err));
     return MACJD_OK;
@@ -1233,6 +1389,8 @@ extern "C" int macjd_mixer_fused_train(const macjd_mixerf_io* eval, const macjd_
     if (!eval->save || target->save) return set_err(MACJD_EINVAL, "%s", "macjd_mixer_fused_train: the eval mixer saves, the target mixer does not");
     if (eval->J != target->J || eval->S != target->S || eval->M != target->M)
         return set_err(MACJD_EINVAL, "%s", "macjd_mixer_fused_train: the two mixers differ in J / S / M");
+    if (eval->operand_dtype != target->operand_dtype)
+        return set_err(MACJD_EINVAL, "%s", "macjd_mixer_fused_train: the two mixers differ in operand_dtype");
     if (eval->J != 2 && eval->J != 3) return set_err(MACJD_EINVAL, "%s", "macjd_mixer_fused_train: J must be 2 or 3");
     if (!td || !tot_m || td->B < 1 || td->Tm1 < 1 || !td->y || !td->tq || !td->reward || !td->terminated || !td->filled)
         return set_err(MACJD_EINVAL, "%s", "macjd_mixer_fused_train: bad TD-loss argument");
@@ -1244,8 +1402,8 @@ extern "C" int macjd_mixer_fused_train(const macjd_mixerf_io* eval, const macjd_
     if (eval->M == 0) return MACJD_OK;
     const dim3 grid((unsigned)((eval->M + 15) / 16)), block(512);
     hipStream_t s = (hipStream_t)hip_stream;
-    if (eval->J == 2) hipLaunchKernelGGL((mixer_fused_train_kernel<2>), grid, block, 0, s, *eval, *target, *td, tot_m);
-    else hipLaunchKernelGGL((mixer_fused_train_kernel<3>), grid, block, 0, s, *eval, *target, *td, tot_m);
+    if (eval->operand_dtype) mixerf_launch_train<true>(eval, target, td, tot_m, grid, block, s);
+    else mixerf_launch_train<false>(eval, target, td, tot_m, grid, block, s);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_mixer_fused_train: %s", hipGetErrorString(err));
     return MACJD_OK;

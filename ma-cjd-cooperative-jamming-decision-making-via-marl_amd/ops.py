@@ -567,10 +567,12 @@ def mixer_fused_supported(J: int, S: int, Hh: int, Em: int) -> bool:
 
 
 def _mixerf_io(q, s, p):
-    """p = dict(ln_w, ln_b, eps, W1, b1, W2, b2, Wf2, bf2, wV2, bV2) of contiguous float32 device tensors."""
+    """p = dict(ln_w, ln_b, eps, W1, b1, W2, b2, Wf2, bf2, wV2, bV2) of contiguous float32 device tensors, and "bf16":
+    the products take bf16 operands (macjd_mixerf_io.operand_dtype, include/macjd_nets.h)."""
     io = _native.MixerFusedIO()
     io.M, io.J, io.S, io.Hh, io.Em = q.shape[0], q.shape[1], p["W1"].shape[1], p["W2"].shape[1], p["Wf2"].shape[0]
     io.ln_eps = float(p["eps"])
+    io.operand_dtype = 1 if p.get("bf16") else 0
     io.q = q.data_ptr()
     if s is not None:
         io.s, io.s_ld = s.data_ptr(), s.stride(0)
@@ -579,10 +581,11 @@ def _mixerf_io(q, s, p):
     return io
 
 
-def _mixerf_params(ln_w, ln_b, eps, w_cat, b_cat, W2, b2, Wf2, bf2, wV2, bV2):
+def _mixerf_params(ln_w, ln_b, eps, w_cat, b_cat, W2, b2, Wf2, bf2, wV2, bV2, bf16=False):
+    """The fused mixer's arguments; ``bf16``: the kernels' products take bf16 operands (f32 accumulation)."""
     c = lambda t: t.detach() if (t.dtype == torch.float32 and t.is_contiguous()) else t.detach().float().contiguous()
     return {"ln_w": c(ln_w), "ln_b": c(ln_b), "eps": eps, "W1": c(w_cat), "b1": c(b_cat), "W2": c(W2), "b2": c(b2),
-            "Wf2": c(Wf2), "bf2": c(bf2), "wV2": c(wV2).reshape(-1), "bV2": c(bV2).reshape(-1)}
+            "Wf2": c(Wf2), "bf2": c(bf2), "wV2": c(wV2).reshape(-1), "bV2": c(bV2).reshape(-1), "bf16": bool(bf16)}
 
 
 def mixer_fused_forward(q, s, params, save=False):
@@ -619,11 +622,11 @@ class _FusedMixer(torch.autograd.Function):
     q [M,J] (differentiable), s [M,S] (no gradient), the LayerNorm parameters, the merged first layer (w_cat / b_cat:
     views of the flat parameter vector or a concatenation; ``first`` = the eight underlying parameters, passed so that
     autograd routes their gradients: backward returns row blocks of ONE weight-gradient product), the three second
-    layers."""
+    layers; ``bf16``: bf16 operands in the kernels' products (include/macjd_nets.h)."""
 
     @staticmethod
-    def forward(ctx, q, s, ln_w, ln_b, eps, w_cat, b_cat, W2, b2, Wf2, bf2, wV2, bV2, *first):
-        params = _mixerf_params(ln_w, ln_b, eps, w_cat, b_cat, W2, b2, Wf2, bf2, wV2, bV2)
+    def forward(ctx, q, s, ln_w, ln_b, eps, w_cat, b_cat, W2, b2, Wf2, bf2, wV2, bV2, bf16, *first):
+        params = _mixerf_params(ln_w, ln_b, eps, w_cat, b_cat, W2, b2, Wf2, bf2, wV2, bV2, bf16=bf16)
         global _PAIRED_TRAIN
         train, _PAIRED_TRAIN = _PAIRED_TRAIN, None
         ctx.train = None
@@ -632,7 +635,7 @@ class _FusedMixer(torch.autograd.Function):
         else:
             y, qc, (sn, xhat, act) = mixer_fused_forward(q, s, params, save=True)
         ctx.save_for_backward(qc, sn, xhat, act, w_cat, W2, Wf2, wV2, ln_w, ln_b, b2, bf2, bV2)
-        ctx.params = {k: v for k, v in params.items() if k in ("eps",)}
+        ctx.params = {k: v for k, v in params.items() if k in ("eps", "bf16")}
         ctx.sizes = [p.shape[0] for p in first[:len(first) // 2]]
         ctx.keys = {"b_cat": grad_key(b_cat), "ln_w": grad_key(ln_w), "ln_b": grad_key(ln_b), "b2": grad_key(b2),
                     "bf2": grad_key(bf2), "bV2": grad_key(bV2)}
@@ -656,7 +659,8 @@ class _FusedMixer(torch.autograd.Function):
         g_w1 = torch.empty((M, J * Em), dtype=torch.float32, device=dev)
         g_wf = torch.empty((M, Em), dtype=torch.float32, device=dev)
         g_v = torch.empty((M, 1), dtype=torch.float32, device=dev)
-        params = _mixerf_params(ln_w, ln_b, ctx.params["eps"], w_cat, gout1[0], W2, b2, Wf2, bf2, wV2, bV2)   # b1 unused here
+        params = _mixerf_params(ln_w, ln_b, ctx.params["eps"], w_cat, gout1[0], W2, b2, Wf2, bf2, wV2, bV2,
+                                bf16=ctx.params["bf16"])   # b1 unused here
         io = _mixerf_io(q, None, params)
         io.act, io.gy, io.gq, io.gout1 = act.data_ptr(), gy.data_ptr(), gq.data_ptr(), gout1.data_ptr()
         io.g_w1raw, io.g_wfraw, io.g_v = g_w1.data_ptr(), g_wf.data_ptr(), g_v.data_ptr()
@@ -706,7 +710,7 @@ class _FusedMixer(torch.autograd.Function):
         else:
             post()
         first = tuple(gW1.split(ctx.sizes, 0)) + tuple(gb1.split(ctx.sizes, 0))
-        return (gq, None, dgamma, dbeta, None, None, None, gW2, gb2, gWf, gbf, gWv, gbv) + first
+        return (gq, None, dgamma, dbeta, None, None, None, gW2, gb2, gWf, gbf, gWv, gbv, None) + first
 
 
 def _mixer_train(q, s, params, train):
@@ -740,9 +744,9 @@ def _mixer_train(q, s, params, train):
     return y, q, (sn, xhat, act), (placeholder, (gq, gout1, g_w1, g_wf, g_v))
 
 
-def mixer_fused(q, s, ln_w, ln_b, eps, w_cat, b_cat, W2, b2, Wf2, bf2, wV2, bV2, first_params):
-    """Differentiable fused mixer (see _FusedMixer); y [M, 1]."""
-    return _FusedMixer.apply(q, s, ln_w, ln_b, eps, w_cat, b_cat, W2, b2, Wf2, bf2, wV2, bV2, *first_params)
+def mixer_fused(q, s, ln_w, ln_b, eps, w_cat, b_cat, W2, b2, Wf2, bf2, wV2, bV2, first_params, bf16=False):
+    """Differentiable fused mixer (see _FusedMixer); y [M, 1].  ``bf16``: the bf16-operand kernels."""
+    return _FusedMixer.apply(q, s, ln_w, ln_b, eps, w_cat, b_cat, W2, b2, Wf2, bf2, wV2, bV2, bool(bf16), *first_params)
 
 
 def enable_gemm_tuning(results_file: Optional[str] = None, max_tuning_ms: int = 30) -> bool:
