@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MACJD_ABI_VERSION 4
+#define MACJD_ABI_VERSION 5
 #define MACJD_PE_ROWS(R, J) (6 * (R) + 3 * (J) + (J) * (R))
 
 #define MACJD_OK          0
@@ -158,6 +158,45 @@ typedef struct macjd_step_io {
                             (runners/episode_runner.py:88-90,141-143) without a separate launch */
 } macjd_step_io;
 
+/*
+ * Scanning radars (opt-in, sim-config `environment_params.radar_scan`): every radar's beam has an azimuth theta_a that
+ * the step advances, and the target / a jammer outside the main lobe is seen with the side-lobe gain.  Host-derived
+ * float64 tables per radar r (dt = step_seconds, rho = 10^(sidelobe_db / 10), wrap(x) = x - 360 floor(x / 360)):
+ *   half_beam = theta_m / 2, sweep = 360 dt / t_s, sweep_mod = fmod(sweep, 360), full = (sweep + 2 half_beam >= 360),
+ *   az0 = wrap(theta_a), bear_tgt = wrap(deg(atan2(ty - ry, tx - rx))), bear_jam[j*R + r] likewise for jammer j,
+ *   GaPs_side = GaPs rho^2 (two-way), gr_side = gr rho, snr_no / pd_no of GaPs_side by the host expressions of the
+ *   main tables.  Per step, with a = theta_a[e,r] and s = track[e,r] at its start, an object at bearing b is in the
+ *   main lobe iff  full || off <= w + 2 half_beam,  w = s ? 0 : sweep,  off = (b - a) + half_beam wrapped once into
+ *   [0, 360) by +-360 (plain IEEE float64, no division: host and device agree bit for bit).  The target path takes the
+ *   main or the _side (GaPs, snr_no, pd_no); a jammer acting on radar r takes gr or gr_side by its own bearing.  The
+ *   beam then moves: detected -> a' = bear_tgt; TRACK before -> a' = a; else a' = a + sweep_mod, minus 360 if >= 360.
+ *   Everything else is macjd_env_step's arithmetic, RNG slots and Philox keying.  The outcome now depends on the past
+ *   through theta_a and track: macjd_env_step_many does not apply.
+ */
+typedef struct macjd_scan_desc {
+    int32_t n_radars, n_jammers;   /* must equal the scenario's */
+    const double* half_beam;       /* [R] */
+    const double* sweep;           /* [R] */
+    const double* sweep_mod;       /* [R] */
+    const uint8_t* full;           /* [R] 0 / 1 */
+    const double* az0;             /* [R] wrap(theta_a)                                                   */
+    const double* bear_tgt;        /* [R] wrap(...): [0, 360], 360 only from a tiny negative angle's rounding */
+    const double* bear_jam;        /* [J*R] j-major, likewise                                             */
+    const double* GaPs_side;       /* [R] */
+    const double* snr_no;          /* [R] main-lobe SNR without jamming (= macjd_scenario_desc.radar_snr_no) */
+    const double* snr_no_side;     /* [R] */
+    const double* pd_no_side;      /* [R] */
+    const double* gr_side;         /* [R] */
+} macjd_scan_desc;
+
+/* Per-call state of a scanning step / reset.  Device pointers. */
+typedef struct macjd_scan_io {
+    double* theta_a;  int64_t a_se, a_sx;   /* [E,R] beam azimuth in degrees, read-modify-write */
+    float*  state;    int64_t st_se;        /* optional [E,S] state rows: column st_col0 + r * st_col_step gets  */
+    int32_t st_col0, st_col_step;           /* (float)theta_a[e,r] after the step (reset: (float)az0[r])          */
+    float*  snr_no;   int64_t sn_se, sn_sx; /* optional [E,R] per-step SNR without jamming (main or side lobe)     */
+} macjd_scan_io;
+
 /* library / device */
 int         macjd_abi_version(void);
 const char* macjd_last_error(void);
@@ -189,6 +228,16 @@ int macjd_env_reset(const macjd_scenario* s, int64_t n_envs, uint8_t* track, int
 
 /* replaces ElectromagneticEnvironment.step (environment.py:221-477) */
 int macjd_env_step(const macjd_scenario* s, const macjd_step_io* io, void* hip_stream);
+
+/* copies the scanning tables into the handle (host call, synchronous; not for the hot path) */
+int macjd_scenario_set_scan(macjd_scenario* s, const macjd_scan_desc* d);
+/* macjd_env_step with scanning beams (see macjd_scan_desc); needs macjd_scenario_set_scan first.  Always the one-lane-
+   per-env kernel; per-env scenario tables (pe_tables) are refused. */
+int macjd_env_step_scan(const macjd_scenario* s, const macjd_step_io* io, const macjd_scan_io* scan, void* hip_stream);
+/* beam part of a reset, issued next to macjd_env_reset with the same mask: theta_a[e,:] = az0 (and the state
+   columns = (float)az0) for envs with mask != 0 (all when mask == NULL) */
+int macjd_env_reset_scan(const macjd_scenario* s, int64_t n_envs, const macjd_scan_io* scan, const uint8_t* mask,
+                         void* hip_stream);
 
 /* T consecutive steps of all E environments in ONE launch, given the actions of all T steps (time-major: step t of
    env e at offset t * t_stride + e * se + k * sx of T / P32; outputs reward / terminated / r_dpj likewise at

@@ -14,7 +14,7 @@ LIB_NAME = "libmacjd_hip.so"
 # MACJD_LIB points at another build of the same sources (kernel A/B runs); the default is the in-tree library
 LIB_PATH = os.environ.get("MACJD_LIB") or os.path.join(_PKG_DIR, LIB_NAME)
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 STEP_ARITH_F64 = 1
 STEP_LANE_KERNEL = 2
 STEP_SLOT_KERNEL = 4
@@ -30,6 +30,7 @@ EXPORTS = [
     "macjd_agent_episode_supported", "macjd_agent_episode", "macjd_env_step_many", "macjd_env_step_many_timed",
     "macjd_qhead_double_q_supported", "macjd_qhead_double_q", "macjd_qhead_taken_supported", "macjd_qhead_taken",
     "macjd_qheads_pair", "macjd_mixer_fused_forward_pair", "macjd_mixer_fused_train",
+    "macjd_scenario_set_scan", "macjd_env_step_scan", "macjd_env_reset_scan",
 ]
 
 
@@ -56,6 +57,26 @@ class StepIO(ctypes.Structure):
         ("pe_tables", ctypes.c_void_p), ("pe_flags", ctypes.c_void_p), ("pe_stride", ctypes.c_int64),
         ("pe_tile", ctypes.c_int32), ("reserved_pe", ctypes.c_int32),
         ("r_dpj_sum", ctypes.c_void_p),
+    ]
+
+
+class ScanDesc(ctypes.Structure):
+    """ctypes mirror of ``macjd_scan_desc`` (include/macjd.h)."""
+    _fields_ = [
+        ("n_radars", ctypes.c_int32), ("n_jammers", ctypes.c_int32),
+        ("half_beam", ctypes.c_void_p), ("sweep", ctypes.c_void_p), ("sweep_mod", ctypes.c_void_p),
+        ("full", ctypes.c_void_p), ("az0", ctypes.c_void_p), ("bear_tgt", ctypes.c_void_p), ("bear_jam", ctypes.c_void_p),
+        ("GaPs_side", ctypes.c_void_p), ("snr_no", ctypes.c_void_p), ("snr_no_side", ctypes.c_void_p),
+        ("pd_no_side", ctypes.c_void_p), ("gr_side", ctypes.c_void_p),
+    ]
+
+
+class ScanIO(ctypes.Structure):
+    """ctypes mirror of ``macjd_scan_io`` (include/macjd.h)."""
+    _fields_ = [
+        ("theta_a", ctypes.c_void_p), ("a_se", ctypes.c_int64), ("a_sx", ctypes.c_int64),
+        ("state", ctypes.c_void_p), ("st_se", ctypes.c_int64), ("st_col0", ctypes.c_int32), ("st_col_step", ctypes.c_int32),
+        ("snr_no", ctypes.c_void_p), ("sn_se", ctypes.c_int64), ("sn_sx", ctypes.c_int64),
     ]
 
 
@@ -318,6 +339,12 @@ def load() -> ctypes.CDLL:
     lib.macjd_env_reset.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     lib.macjd_env_step.restype = ctypes.c_int
+    lib.macjd_scenario_set_scan.restype = ctypes.c_int
+    lib.macjd_scenario_set_scan.argtypes = [ctypes.c_void_p, ctypes.POINTER(ScanDesc)]
+    lib.macjd_env_step_scan.restype = ctypes.c_int
+    lib.macjd_env_step_scan.argtypes = [ctypes.c_void_p, ctypes.POINTER(StepIO), ctypes.POINTER(ScanIO), ctypes.c_void_p]
+    lib.macjd_env_reset_scan.restype = ctypes.c_int
+    lib.macjd_env_reset_scan.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ScanIO), ctypes.c_void_p, ctypes.c_void_p]
     lib.macjd_env_step.argtypes = [ctypes.c_void_p, ctypes.POINTER(StepIO), ctypes.c_void_p]
     lib.macjd_env_step_timed.restype = ctypes.c_int
     lib.macjd_env_step_timed.argtypes = [ctypes.c_void_p, ctypes.POINTER(StepIO), ctypes.c_int, ctypes.c_void_p,
@@ -425,6 +452,10 @@ class ScenarioHandle:
         del keep
         self._h = h
         self._lib = lib
+        if getattr(scenario, "scanning", False):
+            sdesc, skeep = scenario.c_scan_desc()
+            check(lib.macjd_scenario_set_scan(h, ctypes.byref(sdesc)), "macjd_scenario_set_scan")
+            del skeep
 
     @property
     def ptr(self):

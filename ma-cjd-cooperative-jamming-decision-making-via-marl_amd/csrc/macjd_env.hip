@@ -25,6 +25,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <stddef.h>
 #include <string.h>
 #include <type_traits>
 
@@ -54,6 +55,12 @@ struct DevTables {
                                                    // it does not divide; the float32-rounded value where the division is
                                                    // float32) and its refined reciprocal
     uint8_t rflags[MAXJ * MAXR]; // flags | JR_RECORDABLE (denom >= 0) | JR_LIVE (denom > 1e-18)
+    // ---- scanning beams (macjd_scenario_set_scan; include/macjd.h, macjd_scan_desc), read by the SCAN variants only ----
+    int32_t scanning, scan_regular;   // tables set; side-lobe tables also pass the REGULAR range checks
+    double half[MAXR], h2[MAXR], sweep[MAXR], swm[MAXR], az0[MAXR], bt[MAXR];   // h2 = 2 half (exact)
+    double bj[MAXJ * MAXR];           // packed [j*R + r]
+    double GaPs_side[MAXR], pd_no_side[MAXR], gr_side[MAXR], snr_no[MAXR], snr_no_side[MAXR];
+    uint8_t full[MAXR];
 };
 constexpr uint8_t JR_RECORDABLE = 0x40, JR_LIVE = 0x80;
 
@@ -180,6 +187,15 @@ __device__ __forceinline__ float det_prob32(float snr, const Pd32Consts& k) {
     return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(y));
 }
 
+// Main-lobe test of a scanning beam (include/macjd.h, macjd_scan_desc): azimuth a, half beam h, lim = w + 2h; plain IEEE
+// float64 in the specified order (the TU is built with -ffp-contract=off), so the host restatement agrees bit for bit.
+__device__ __forceinline__ bool in_main_lobe(double beta, double a, double h, double lim, bool full) {
+    double off = (beta - a) + h;
+    if (off < 0.0) off += 360.0;
+    if (off >= 360.0) off -= 360.0;
+    return full || off <= lim;
+}
+
 // Uniform of (env e, slot) for the step that starts at `step_before` (include/macjd.h, macjd_step_io.u): supplied by the
 // caller, or word (slot & 3) of the env's Philox block (slot >> 2).  This on-demand form generates a whole block per
 // call; the kernels below generate each block they need ONCE per env-step and pick words out of it.
@@ -236,6 +252,19 @@ struct FastStepIO {
     static constexpr double* prj64 = nullptr;
 };
 
+// Argument block of a SCAN launch: the step's own block plus the beam state (include/macjd.h, macjd_scan_io).  A separate
+// type, so the non-scanning instantiations keep their argument layout and code.
+template <class Base>
+struct ScanStepIO : Base {
+    double* theta_a;
+    int64_t a_se, a_sx;
+    float* state;
+    int64_t st_se;
+    int32_t st_col0, st_col_step;
+    float* snr_no;
+    int64_t sn_se, sn_sx;
+};
+
 // PE = per-env scenario tables (io.pe_tables, SoA [row][env]): every table read becomes a load from this lane's
 // column of the SoA (row index static for the per-jammer / per-radar loops, data-dependent for the reads gathered by
 // the chosen target radar); the shared-table variant stages the gathered tables in LDS instead.
@@ -252,10 +281,14 @@ struct FastStepIO {
 // the guards that a regular scenario can never trigger (non-positive or tiny noise power, SNR < 0, the probability
 // formula's saturation selects) are not evaluated.  Same results bit for bit (tests: lane kernel vs (env x slot) kernel,
 // which keeps IEEE division and every guard, and both vs the oracle); 1285 -> ~1050 VALU instructions per env-step at 3j/4r.
-template <int JT, int RT, bool PE, bool FAST, class IO, bool REG = false, bool PD32 = false>
+// SCAN = scanning beams (include/macjd.h, macjd_scan_desc; IO = ScanStepIO<...>): the env's azimuths live in registers for
+// the step, the per-radar main-lobe test of the target selects the main or side-lobe (GaPs, pd_no), a jammer's test on
+// its chosen radar selects gr or gr_side; the rest of the step is unchanged.  Shared tables only, single-step launches.
+template <int JT, int RT, bool PE, bool FAST, class IO, bool REG = false, bool PD32 = false, bool SCAN = false>
 __global__ void __launch_bounds__(256) env_step_kernel(const DevTables* __restrict__ tb, const IO io) {
     static_assert(!REG || (FAST && !PE && JT && RT), "REG: production variant on shared tables, compiled sizes");
     static_assert(!PD32 || REG, "PD32: float32 detection-probability filter of the regular production variant");
+    static_assert(!SCAN || !PE, "SCAN: shared scenario tables only");
     constexpr int NJ = JT ? JT : MAXJ;
     constexpr int NR = RT ? RT : MAXR;
     const int J = JT ? JT : tb->J;
@@ -277,6 +310,20 @@ __global__ void __launch_bounds__(256) env_step_kernel(const DevTables* __restri
     __shared__ double s_supp[SCAT ? NR + 1 : 1][ACC_W], s_prod[SCAT ? NR + 1 : 1][ACC_W];
     __shared__ double s_D[PE ? 1 : NR], s_Pn[PE ? 1 : NR], s_gr[PE ? 1 : NR];
     __shared__ uint8_t s_flags[PE ? 1 : NJ * NR];
+    // SCAN: tables gathered by a jammer's chosen radar
+    __shared__ double s_half[SCAN ? NR : 1], s_h2[SCAN ? NR : 1], s_sweep[SCAN ? NR : 1], s_grs[SCAN ? NR : 1];
+    __shared__ double s_bj[SCAN ? NJ * NR : 1];
+    __shared__ uint8_t s_full[SCAN ? NR : 1];
+    if constexpr (SCAN) {
+        for (int i = threadIdx.x; i < J * R; i += blockDim.x) s_bj[i] = tb->bj[i];
+        for (int i = threadIdx.x; i < R; i += blockDim.x) {
+            s_half[i] = tb->half[i];
+            s_h2[i] = tb->h2[i];
+            s_sweep[i] = tb->sweep[i];
+            s_grs[i] = tb->gr_side[i];
+            s_full[i] = tb->full[i];
+        }
+    }
     if (!PE) {
         for (int i = threadIdx.x; i < J * R; i += blockDim.x) {
             s_denom[i] = REG ? tb->dsel[i] : tb->denom[i];
@@ -400,6 +447,45 @@ __global__ void __launch_bounds__(256) env_step_kernel(const DevTables* __restri
             return HOIST ? gv_fl[j] : PE ? pf[(int64_t)(j * R + t) * ps] : s_flags[j * R + t];
         };
 
+        // ---- SCAN: beam azimuths and FSM states at the start of the step, main-lobe test of the target per radar ----
+        // (compiled sizes keep the azimuths in registers; generic sizes read them again from the env's row)
+        constexpr int NS = (SCAN && PRE) ? NR : 1;
+        double az[NS];
+        uint32_t s_bits = 0, in_t = 0;   // bit r: radar r was TRACKing / sees the target in its main lobe
+        if constexpr (SCAN) {
+#pragma unroll
+            for (int r = 0; r < NR; ++r) {
+                if (!RT && r >= R) break;
+                const double a = at(io.theta_a, e, io.a_se, r, io.a_sx);
+                const bool s = at(io.track, e, io.k_se, r, io.k_sx) != 0;
+                if (PRE) az[PRE ? r : 0] = a;
+                s_bits |= s ? (1u << r) : 0u;
+                const double lim = (s ? 0.0 : tb->sweep[r]) + tb->h2[r];
+                in_t |= in_main_lobe(tb->bt[r], a, tb->half[r], lim, tb->full[r] != 0) ? (1u << r) : 0u;
+            }
+        }
+        // receive gain of jammer j's action on radar t: main or side lobe by the jammer's bearing (SCAN)
+        auto scan_gr = [&](int j, int t) -> double {
+            if constexpr (SCAN) {
+                // the chosen radar's azimuth from the env's row (cache-hot: loaded above); a select chain over az[] is
+                // turned into a dynamically indexed private array by hipcc (scratch)
+                const double a_t = at(io.theta_a, e, io.a_se, t, io.a_sx);
+                const double lim = (((s_bits >> t) & 1u) ? 0.0 : s_sweep[t]) + s_h2[t];
+                return in_main_lobe(s_bj[j * R + t], a_t, s_half[t], lim, s_full[t] != 0) ? s_gr[t] : s_grs[t];
+            } else {
+                return 0.0;
+            }
+        };
+        // target-path tables of radar r: main or side lobe (SCAN)
+        auto r_GaPs = [&](int r) -> double {
+            if constexpr (SCAN) return ((in_t >> r) & 1u) ? tb->GaPs[r] : tb->GaPs_side[r];
+            else return t_GaPs(r);
+        };
+        auto r_pdno = [&](int r) -> double {
+            if constexpr (SCAN) return ((in_t >> r) & 1u) ? tb->pd_no[r] : tb->pd_no_side[r];
+            else return t_pdno(r);
+        };
+
         // The step runs as straight-line passes over the (compile-time unrolled) jammers and radars: (1) decode, power,
         // received power, suppression sums; (2) SNR per radar; (3) ALL R + J detection probabilities side by side
         // (det_prob_batch); (4) the deception draws in jammer order; (5) detection draws, FSM, reward terms in radar
@@ -464,7 +550,7 @@ __global__ void __launch_bounds__(256) env_step_kernel(const DevTables* __restri
                 // `denom` is the divisor as the reference uses it here (1.0 where it does not divide)
                 const uint8_t fl = g_flags(j, target);
                 const bool live = recorded && (fl & JR_LIVE);
-                const float num = (actual_f * (float)t_gj(j)) * (float)g_gr(j, target);
+                const float num = (actual_f * (float)t_gj(j)) * (float)(SCAN ? scan_gr(j, target) : g_gr(j, target));
                 const double q64 = div_by_refined((double)num, denom, s_rsel[j * R + target]);
                 const double q = (fl & MACJD_JR_WEAK_DENOM) ? (double)(float)q64 : q64;
                 prj = (live && q > 0.0) ? q : 0.0;  // Python max(0.0, x)
@@ -472,7 +558,7 @@ __global__ void __launch_bounds__(256) env_step_kernel(const DevTables* __restri
                 // branch-free: the quotient is evaluated on a harmless divisor where the reference does not divide
                 const bool live = recorded && denom > 1e-18;
                 const double dsafe = live ? denom : 1.0;
-                const double grj = g_gr(j, target);
+                const double grj = SCAN ? scan_gr(j, target) : g_gr(j, target);
                 double q;
                 if (arith32) {
                     const float num = (actual_f * (float)t_gj(j)) * (float)grj;
@@ -482,7 +568,7 @@ __global__ void __launch_bounds__(256) env_step_kernel(const DevTables* __restri
                 }
                 prj = (live && q > 0.0) ? q : 0.0;  // Python max(0.0, x)
             } else if (recorded && denom > 1e-18) {
-                const double grj = g_gr(j, target);
+                const double grj = SCAN ? scan_gr(j, target) : g_gr(j, target);
                 if (arith32) {
                     const float num = (actual_f * (float)t_gj(j)) * (float)grj;
                     prj = (g_flags(j, target) & MACJD_JR_WEAK_DENOM) ? (double)(num / (float)denom)
@@ -542,18 +628,18 @@ __global__ void __launch_bounds__(256) env_step_kernel(const DevTables* __restri
             const double Pn = t_Pn(r);
             const double den = t_D(r) * (SCAT ? s_supp[r][col] : supp[r]) + Pn;   // :331
             if (PD32) {                                                      // float32 quotient (see det_prob32)
-                snr32r[PD32 ? r : 0] = (float)t_GaPs(r) * __builtin_amdgcn_rcpf((float)den);
+                snr32r[PD32 ? r : 0] = (float)r_GaPs(r) * __builtin_amdgcn_rcpf((float)den);
                 snr_w[r] = 0.0;   // (not formed; the outputs below take the float32 value)
             } else if (REG) {                                                // den >= Pn > 1e-18
-                snr_w[r] = div_by_refined(t_GaPs(r), den, rcp_refined(den));
+                snr_w[r] = div_by_refined(r_GaPs(r), den, rcp_refined(den));
                 snr_all[r] = snr_w[r];
             } else if (PRE) {
                 const bool live = den > 1e-18;
-                const double q = t_GaPs(r) / (live ? den : 1.0);
+                const double q = r_GaPs(r) / (live ? den : 1.0);
                 snr_w[r] = live ? q : 0.0;                                   // :332
                 snr_all[r] = snr_w[r];
             } else {
-                snr_w[r] = (den > 1e-18) ? t_GaPs(r) / den : 0.0;            // :332
+                snr_w[r] = (den > 1e-18) ? r_GaPs(r) / den : 0.0;            // :332
             }
         }
         // PD32: all R + J compares u <= pd decided here — by the float32 value where the two sides are further apart than
@@ -599,7 +685,8 @@ __global__ void __launch_bounds__(256) env_step_kernel(const DevTables* __restri
                     }
                     if (i < NR) {   // a radar: the exact SNR from the suppression sum (still in this lane's LDS column)
                         const double den_i = tb->D[i] * s_supp[SCAT ? i : 0][col] + tb->Pn[i];
-                        snr_i = div_by_refined(tb->GaPs[i], den_i, rcp_refined(den_i));
+                        const double gaps_i = SCAN ? (((in_t >> i) & 1u) ? tb->GaPs[i] : tb->GaPs_side[i]) : tb->GaPs[i];
+                        snr_i = div_by_refined(gaps_i, den_i, rcp_refined(den_i));
                     }
                     double p;
                     det_prob_batch_regular<1>(&snr_i, &p, pdk);
@@ -662,7 +749,7 @@ __global__ void __launch_bounds__(256) env_step_kernel(const DevTables* __restri
             const bool tracking = detected;
             track_bits |= tracking ? (1u << r) : 0u;
             r_d += tracking ? t_rdpen(r) : 0.0;                             // :359-366 (post-update state)
-            const double red = t_pdno(r) - pd;                               // :396-398
+            const double red = r_pdno(r) - pd;                               // :396-398
             r_j += ((supp_mask & (1u << r)) && red > 0.0) ? red : 0.0;
             r_j_dec += (hit_mask & (1u << r)) ? 1.0 - (SCAT ? s_prod[r][col] : prod[r]) : 0.0;   // :438-451
             pd_r[r] = pd;
@@ -678,6 +765,16 @@ __global__ void __launch_bounds__(256) env_step_kernel(const DevTables* __restri
             if (io.snr_with) at(io.snr_with, e, io.sw_se, r, io.sw_sx) = (float)snr_rep;
             if (!FAST && io.pd64) io.pd64[e * R + r] = pd_r[r];
             if (!FAST && io.snr64) io.snr64[e * R + r] = snr_rep;
+            if constexpr (SCAN) {   // beam advance (include/macjd.h, macjd_scan_desc)
+                const bool in = (in_t >> r) & 1u;
+                if (io.snr_no) at(io.snr_no, e, io.sn_se, r, io.sn_sx) = (float)(in ? tb->snr_no[r] : tb->snr_no_side[r]);
+                const double a = PRE ? az[PRE ? r : 0] : at(io.theta_a, e, io.a_se, r, io.a_sx);
+                double x = a + tb->swm[r];
+                x = (x >= 360.0) ? x - 360.0 : x;
+                const double a1 = ((track_bits >> r) & 1u) ? tb->bt[r] : (((s_bits >> r) & 1u) ? a : x);
+                at(io.theta_a, e, io.a_se, r, io.a_sx) = a1;
+                if (io.state) at(io.state, e, io.st_se, io.st_col0 + r * io.st_col_step, 1) = (float)a1;
+            }
         }
         r_j += r_j_dec;                          // :454
         const double reward = r_d + r_p + r_j;  // :457
@@ -949,6 +1046,21 @@ __global__ void env_reset_kernel(int64_t n_envs, int R, uint8_t* track, int64_t 
     }
 }
 
+// beam part of a reset (macjd_env_reset_scan): azimuths back to az0, state columns to (float)az0
+__global__ void env_reset_scan_kernel(const DevTables* __restrict__ tb, int64_t n_envs, int R, double* theta_a, int64_t a_se,
+                                      int64_t a_sx, float* state, int64_t st_se, int32_t st_col0, int32_t st_col_step,
+                                      const uint8_t* mask) {
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n_envs;
+         e += (int64_t)gridDim.x * blockDim.x) {
+        if (mask && !mask[e]) continue;
+        for (int r = 0; r < R; ++r) {
+            const double a0 = tb->az0[r];
+            theta_a[e * a_se + (int64_t)r * a_sx] = a0;
+            if (state) state[e * st_se + st_col0 + (int64_t)r * st_col_step] = (float)a0;
+        }
+    }
+}
+
 // second half of macjd_env_step_many: the step counters advance by T, the per-episode reward-component sums get the T
 // steps' (r_d, r_p, r_j) added in step order (deterministic).  One thread per (env, component): for a given step the
 // 3 E values are contiguous, so every load of a wave is one coalesced row piece (one thread per env walking its three
@@ -1128,6 +1240,8 @@ static int validate_io(const macjd_scenario* s, const macjd_step_io* io) {
     return MACJD_OK;
 }
 
+static int launch_step_scan(const macjd_scenario* s, const macjd_step_io* io, const macjd_scan_io* scan, hipStream_t stream);
+
 static int launch_step(const macjd_scenario* s, const macjd_step_io* io, hipStream_t stream, int32_t many_T = 0,
                        int64_t t_stride = 0) {
     const int64_t E = io->n_envs * (many_T > 0 ? many_T : 1);   // work items of the launch
@@ -1223,6 +1337,137 @@ static int launch_step(const macjd_scenario* s, const macjd_step_io* io, hipStre
     }
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_env_step launch: %s", hipGetErrorString(err));
+    return MACJD_OK;
+}
+
+// SCAN launches: always the lane kernel, shared tables, single step (include/macjd.h, macjd_env_step_scan)
+static int launch_step_scan(const macjd_scenario* s, const macjd_step_io* io, const macjd_scan_io* sc, hipStream_t stream) {
+    const int64_t E = io->n_envs;
+    const int J = s->host.J, R = s->host.R;
+    const int block = (E >= (1 << 16)) ? 256 : 64;
+    int64_t grid = (E + block - 1) / block;
+    const dim3 gf((unsigned)grid), b(block);
+    const int64_t cap = (block == 256) ? 256 * 8 : 256 * 16;
+    if (grid > cap) grid = cap;
+    const dim3 g((unsigned)grid);
+    auto span_ok = [&](int64_t se, int64_t sx, int items, int64_t elem, int64_t extra = 0) {
+        return se >= 0 && sx >= 0 && extra >= 0 && ((E - 1) * se + (int64_t)(items - 1) * sx + extra + 1) * elem < (int64_t)1 << 32;
+    };
+    const bool st_ok = !sc->state || (sc->st_col0 >= 0 && sc->st_col_step >= 0 &&
+                                      span_ok(sc->st_se, 1, 1, 4, (int64_t)sc->st_col0 + (int64_t)(R - 1) * sc->st_col_step));
+    const bool fast = !io->u && io->P32 && !(io->flags & MACJD_STEP_ARITH_F64) && !io->out64 && !io->pd64 && !io->snr64 &&
+                      !io->prj64 && grid <= 0x7fffffff && span_ok(io->T_se, io->T_sx, J, 4) && span_ok(io->P_se, io->P_sx, J, 4) &&
+                      span_ok(io->k_se, io->k_sx, R, 1) && (E * 3 + 3) * 4 < ((int64_t)1 << 32) &&
+                      (!io->pd || span_ok(io->pd_se, io->pd_sx, R, 4)) && (!io->snr_with || span_ok(io->sw_se, io->sw_sx, R, 4)) &&
+                      span_ok(sc->a_se, sc->a_sx, R, 8) && st_ok && (!sc->snr_no || span_ok(sc->sn_se, sc->sn_sx, R, 4));
+    auto fill_scan = [&](auto& x) {
+        x.theta_a = sc->theta_a; x.a_se = sc->a_se; x.a_sx = sc->a_sx;
+        x.state = sc->state; x.st_se = sc->st_se; x.st_col0 = sc->st_col0; x.st_col_step = sc->st_col_step;
+        x.snr_no = sc->snr_no; x.sn_se = sc->sn_se; x.sn_sx = sc->sn_sx;
+    };
+    using FastScan = macjd::ScanStepIO<macjd::FastStepIO>;
+    using FullScan = macjd::ScanStepIO<macjd_step_io>;
+    FastScan f{};
+    FullScan w{};
+    static_cast<macjd_step_io&>(w) = *io;
+    fill_scan(w);
+    if (fast) {
+        f.n_envs = io->n_envs; f.env_offset = io->env_offset; f.seed = io->seed;
+        f.T = io->T; f.P32 = io->P32; f.episode = io->episode; f.track = io->track; f.step = io->step;
+        f.reward = io->reward; f.r_dpj = io->r_dpj; f.terminated = io->terminated; f.pd = io->pd;
+        f.snr_with = io->snr_with; f.r_dpj_sum = io->r_dpj_sum;
+        f.T_se = (int32_t)io->T_se; f.T_sx = (int32_t)io->T_sx; f.P_se = (int32_t)io->P_se; f.P_sx = (int32_t)io->P_sx;
+        f.k_se = (int32_t)io->k_se; f.k_sx = (int32_t)io->k_sx; f.pd_se = (int32_t)io->pd_se; f.pd_sx = (int32_t)io->pd_sx;
+        f.sw_se = (int32_t)io->sw_se; f.sw_sx = (int32_t)io->sw_sx;
+        f.many_T = 0; f.t_stride = 0;
+        fill_scan(f);
+    }
+    const bool reg = s->host.regular && s->host.scan_regular && macjd::env_options().regular;
+    const bool pd32 = macjd::env_options().pd32;
+#define MACJD_LAUNCH_SCAN(JT, RT)                                                                                          \
+    do {                                                                                                                   \
+        if (fast && reg && pd32)                                                                                           \
+            hipLaunchKernelGGL((macjd::env_step_kernel<JT, RT, false, true, FastScan, true, true, true>), gf, b, 0, stream, s->dev, f); \
+        else if (fast && reg)                                                                                              \
+            hipLaunchKernelGGL((macjd::env_step_kernel<JT, RT, false, true, FastScan, true, false, true>), gf, b, 0, stream, s->dev, f); \
+        else if (fast)                                                                                                     \
+            hipLaunchKernelGGL((macjd::env_step_kernel<JT, RT, false, true, FastScan, false, false, true>), gf, b, 0, stream, s->dev, f); \
+        else                                                                                                               \
+            hipLaunchKernelGGL((macjd::env_step_kernel<JT, RT, false, false, FullScan, false, false, true>), g, b, 0, stream, s->dev, w); \
+    } while (0)
+    if (J == 3 && R == 4) MACJD_LAUNCH_SCAN(3, 4);
+    else if (J == 6 && R == 8) MACJD_LAUNCH_SCAN(6, 8);
+    else if (J == 12 && R == 16) MACJD_LAUNCH_SCAN(12, 16);
+    else if (J == 2 && R == 2) MACJD_LAUNCH_SCAN(2, 2);
+    else hipLaunchKernelGGL((macjd::env_step_kernel<0, 0, false, false, FullScan, false, false, true>), g, b, 0, stream, s->dev, w);
+#undef MACJD_LAUNCH_SCAN
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_env_step_scan launch: %s", hipGetErrorString(err));
+    return MACJD_OK;
+}
+
+static int validate_scan(const macjd_scenario* s, const macjd_scan_io* sc, const char* what) {
+    if (!sc || !sc->theta_a) return set_err(MACJD_EINVAL, "%s: NULL scan io / theta_a", what);
+    if (!s->host.scanning) return set_err(MACJD_EINVAL, "%s: the scenario has no scanning tables (macjd_scenario_set_scan)", what);
+    if (sc->a_se == 0 && sc->a_sx == 0) return set_err(MACJD_EINVAL, "%s: theta_a strides are zero", what);
+    if (sc->state && (sc->st_col0 < 0 || sc->st_col_step < 0)) return set_err(MACJD_EINVAL, "%s: bad state columns", what);
+    if (sc->snr_no && sc->sn_se == 0 && sc->sn_sx == 0) return set_err(MACJD_EINVAL, "%s: snr_no strides are zero", what);
+    return MACJD_OK;
+}
+
+int macjd_scenario_set_scan(macjd_scenario* s, const macjd_scan_desc* d) {
+    if (!s || !d) return set_err(MACJD_EINVAL, "%s", "macjd_scenario_set_scan: NULL argument");
+    DevTables& t = s->host;
+    const int R = t.R, J = t.J;
+    if (d->n_radars != R || d->n_jammers != J)
+        return set_err(MACJD_EINVAL, "%s", "macjd_scenario_set_scan: n_radars / n_jammers differ from the scenario's");
+    if (!d->half_beam || !d->sweep || !d->sweep_mod || !d->full || !d->az0 || !d->bear_tgt || !d->bear_jam || !d->GaPs_side ||
+        !d->snr_no || !d->snr_no_side || !d->pd_no_side || !d->gr_side)
+        return set_err(MACJD_EINVAL, "%s", "macjd_scenario_set_scan: NULL table pointer");
+    for (int r = 0; r < R; ++r) {
+        t.half[r] = d->half_beam[r]; t.h2[r] = 2.0 * d->half_beam[r]; t.sweep[r] = d->sweep[r]; t.swm[r] = d->sweep_mod[r];
+        t.full[r] = d->full[r] ? 1 : 0; t.az0[r] = d->az0[r]; t.bt[r] = d->bear_tgt[r];
+        t.GaPs_side[r] = d->GaPs_side[r]; t.snr_no[r] = d->snr_no[r]; t.snr_no_side[r] = d->snr_no_side[r];
+        t.pd_no_side[r] = d->pd_no_side[r]; t.gr_side[r] = d->gr_side[r];
+    }
+    for (int i = 0; i < J * R; ++i) t.bj[i] = d->bear_jam[i];
+    // the short-division (REG) variant also needs the side-lobe values inside its range (see macjd_scenario_create)
+    // (gr_side <= gr: the float32-numerator bound of the main tables holds)
+    bool ok = true;
+    for (int r = 0; r < R; ++r)
+        ok = ok && (t.GaPs_side[r] >= 1e-30 && t.GaPs_side[r] <= 1e30) && t.gr_side[r] <= t.gr[r] &&
+             (t.gr_side[r] == 0.0 || (t.gr_side[r] >= 1e-30 && t.gr_side[r] <= 1e30));
+    t.scan_regular = ok ? 1 : 0;
+    t.scanning = 1;
+    const size_t off = offsetof(DevTables, scanning);
+    hipError_t err = hipMemcpy(reinterpret_cast<char*>(s->dev) + off, reinterpret_cast<const char*>(&t) + off,
+                               sizeof(DevTables) - off, hipMemcpyHostToDevice);
+    if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_scenario_set_scan: %s", hipGetErrorString(err));
+    return MACJD_OK;
+}
+
+int macjd_env_step_scan(const macjd_scenario* s, const macjd_step_io* io, const macjd_scan_io* scan, void* hip_stream) {
+    int rc = validate_io(s, io);
+    if (rc != MACJD_OK) return rc;
+    rc = validate_scan(s, scan, "macjd_env_step_scan");
+    if (rc != MACJD_OK) return rc;
+    if (io->pe_tables) return set_err(MACJD_EUNSUPPORTED, "%s", "macjd_env_step_scan: per-env scenario tables are not supported");
+    if (io->n_envs == 0) return MACJD_OK;
+    return launch_step_scan(s, io, scan, (hipStream_t)hip_stream);
+}
+
+int macjd_env_reset_scan(const macjd_scenario* s, int64_t n_envs, const macjd_scan_io* scan, const uint8_t* mask, void* hip_stream) {
+    if (!s || n_envs < 0) return set_err(MACJD_EINVAL, "%s", "macjd_env_reset_scan: bad argument");
+    int rc = validate_scan(s, scan, "macjd_env_reset_scan");
+    if (rc != MACJD_OK) return rc;
+    if (n_envs == 0) return MACJD_OK;
+    int64_t grid = (n_envs + 255) / 256;
+    if (grid > 4096) grid = 4096;
+    hipLaunchKernelGGL(macjd::env_reset_scan_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)hip_stream, s->dev, n_envs,
+                       s->host.R, scan->theta_a, scan->a_se, scan->a_sx, scan->state, scan->st_se, scan->st_col0,
+                       scan->st_col_step, mask);
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_env_reset_scan launch: %s", hipGetErrorString(err));
     return MACJD_OK;
 }
 

@@ -68,6 +68,44 @@ def detection_probability(snr, consts=None):
     return 1 / (1 + np.exp(-B))
 
 
+def wrap_degrees(x):
+    """x - 360 floor(x / 360) in float64: an angle in [0, 360) (include/macjd.h, macjd_scan_desc)."""
+    x = np.float64(x)
+    return np.float64(x - 360.0 * np.floor(x / 360.0))
+
+
+def bearing_degrees(frm, to):
+    """wrap(degrees(atan2(to_y - from_y, to_x - from_x))) in float64."""
+    f = np.asarray(frm, dtype=np.float64).reshape(-1)
+    t = np.asarray(to, dtype=np.float64).reshape(-1)
+    return wrap_degrees(np.degrees(np.arctan2(t[1] - f[1], t[0] - f[0])))
+
+
+def parse_radar_scan(env_params: dict, source: str = "<dict>") -> Optional[Dict[str, float]]:
+    """``environment_params.radar_scan`` -> {'step_seconds', 'sidelobe_db'} or None (absent / null: static beams)."""
+    rs = env_params.get("radar_scan")
+    if rs is None:
+        return None
+    if not isinstance(rs, dict):
+        raise ValueError(f"{source}: environment_params.radar_scan must be a mapping or null")
+    unknown = set(rs) - {"step_seconds", "sidelobe_db"}
+    if unknown:
+        raise ValueError(f"{source}: unknown radar_scan key(s) {sorted(unknown)}")
+    out = {}
+    for key in ("step_seconds", "sidelobe_db"):
+        if key not in rs:
+            raise ValueError(f"{source}: radar_scan is missing '{key}'")
+        v = rs[key]
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not np.isfinite(v):
+            raise ValueError(f"{source}: radar_scan.{key} must be a finite number, got {v!r}")
+        out[key] = float(v)
+    if not out["step_seconds"] > 0.0:
+        raise ValueError(f"{source}: radar_scan.step_seconds must be > 0, got {out['step_seconds']}")
+    if not out["sidelobe_db"] <= 0.0:
+        raise ValueError(f"{source}: radar_scan.sidelobe_db must be <= 0, got {out['sidelobe_db']}")
+    return out
+
+
 class _Desc(ctypes.Structure):
     """ctypes mirror of ``macjd_scenario_desc`` (include/macjd.h)."""
     _fields_ = [
@@ -101,6 +139,26 @@ class Scenario:
     tables: Dict[str, np.ndarray] = field(default_factory=dict)
     pd_consts: tuple = (0.0, 0.0, 0.0)
     source: str = "<dict>"
+    radar_scan: Optional[Dict[str, float]] = None   # environment_params.radar_scan; None = static beams
+    scan_tables: Dict[str, np.ndarray] = field(default_factory=dict)
+
+    @property
+    def scanning(self) -> bool:
+        """The beams scan (environment_params.radar_scan given): theta_a changes every step, the observation is dynamic."""
+        return self.radar_scan is not None
+
+    @property
+    def theta_a_col0(self) -> int:
+        """Column of radar 0's theta_a in the state vector (see :meth:`state_vector`)."""
+        return 3 + self.max_radar_types
+
+    @property
+    def theta_a_col_step(self) -> int:
+        return self.radar_feature_dim
+
+    @property
+    def theta_a_columns(self) -> List[int]:
+        return [self.theta_a_col0 + r * self.theta_a_col_step for r in range(self.num_radars)]
 
     # ---- derived dims (environment.py:91-101) ----
     @property
@@ -144,6 +202,7 @@ class Scenario:
         env_params = sim_config.get("environment_params", {}) or {}  # :67-73
         max_radar_types = env_params.get("max_radar_types", 4)
         reward_params = env_params.get("rewards", {}) or {}
+        radar_scan = parse_radar_scan(env_params, source)
         rd_min = reward_params.get("rd_min", -1.2)
         rd_max = reward_params.get("rd_max", -0.8)
         rp_min = reward_params.get("rp_min", -0.1)
@@ -185,6 +244,15 @@ class Scenario:
             except ValueError as e:
                 print(f"Error initializing radar {i}: Invalid value - {e}")
                 raise
+            if radar_scan is not None:
+                tm, ts = params["theta_m"], params["t_s"]
+                if isinstance(tm, bool) or not isinstance(tm, (int, float)) or not (0.0 < tm <= 360.0):
+                    raise ValueError(f"Radar config {i}: theta_m must lie in (0, 360] when radar_scan is on, got {tm!r}")
+                if isinstance(ts, bool) or not isinstance(ts, (int, float)) or not (ts > 0.0) or not np.isfinite(ts):
+                    raise ValueError(f"Radar config {i}: t_s must be > 0 when radar_scan is on, got {ts!r}")
+                ta = params["theta_a"]
+                if isinstance(ta, bool) or not isinstance(ta, (int, float)) or not np.isfinite(ta):
+                    raise ValueError(f"Radar config {i}: theta_a must be a finite number when radar_scan is on, got {ta!r}")
             r = dict(params)
             r["threat_level"] = params.get("threat_level", 1.0)
             radars.append(r)
@@ -211,8 +279,10 @@ class Scenario:
         sc = cls(num_radars=num_radars, num_jammers=num_jammers, episode_limit=int(episode_limit),
                  max_radar_types=max_radar_types, rd_min=rd_min, rd_max=rd_max, rp_min=rp_min, rp_max=rp_max,
                  radars=radars, jammers=jammers, target_position=target_position, target_rcs=target_rcs,
-                 source=source)
+                 source=source, radar_scan=radar_scan)
         sc._compile()
+        if radar_scan is not None:
+            sc._compile_scan()
         return sc
 
     # ---- static tables ----
@@ -283,6 +353,59 @@ class Scenario:
             "jr_denom": np.ascontiguousarray(denom.reshape(-1)),
             "jr_flags": np.ascontiguousarray(flags.reshape(-1)),
         }
+
+    # ---- scanning-beam tables (include/macjd.h, macjd_scan_desc) ----
+    def _compile_scan(self) -> None:
+        R, J = self.num_radars, self.num_jammers
+        dt = self.radar_scan["step_seconds"]
+        rho = 10 ** (self.radar_scan["sidelobe_db"] / 10)
+        t = self.tables
+        half = np.zeros(R); sweep = np.zeros(R); swm = np.zeros(R); full = np.zeros(R, dtype=np.uint8)
+        az0 = np.zeros(R); bt = np.zeros(R); bj = np.zeros((J, R))
+        GaPs_side = np.zeros(R); snr_no_side = np.zeros(R); pd_no_side = np.zeros(R); gr_side = np.zeros(R)
+        for r, p in enumerate(self.radars):
+            half[r] = float(p["theta_m"]) / 2
+            sweep[r] = 360.0 * dt / float(p["t_s"])
+            swm[r] = np.fmod(sweep[r], 360.0)
+            full[r] = 1 if sweep[r] + 2 * half[r] >= 360.0 else 0
+            az0[r] = wrap_degrees(float(p["theta_a"]))
+            bt[r] = bearing_degrees(p["position"], self.target_position)
+            for j, q in enumerate(self.jammers):
+                bj[j, r] = bearing_degrees(p["position"], q["position"])
+            # side lobe: received jamming one-way (gr rho), the target's echo two-way (GaPs rho^2); the no-jamming SNR
+            # and Pd from GaPs_side through the same host expressions as the main tables (_compile)
+            gr_side[r] = t["radar_gr"][r] * rho
+            ga_ps = t["radar_GaPs"][r] * (rho * rho)
+            pn_watts = t["radar_Pn"][r]
+            s_no = ga_ps / pn_watts if pn_watts > 1e-18 else 0.0
+            s_no = max(0.0, s_no)
+            GaPs_side[r] = ga_ps
+            snr_no_side[r] = s_no
+            pd_no_side[r] = detection_probability(s_no, self.pd_consts)
+        self.scan_tables = {
+            "half_beam": half, "sweep": sweep, "sweep_mod": swm, "full": full, "az0": az0, "bear_tgt": bt,
+            "bear_jam": np.ascontiguousarray(bj.reshape(-1)), "GaPs_side": GaPs_side, "snr_no_side": snr_no_side,
+            "pd_no_side": pd_no_side, "gr_side": gr_side, "rho": np.float64(rho),
+        }
+
+    def c_scan_desc(self):
+        """Returns (``_native.ScanDesc`` instance, keepalive list).  Pointers reference ``self.scan_tables`` arrays."""
+        from ._native import ScanDesc
+        st = self.scan_tables
+        d = ScanDesc()
+        d.n_radars, d.n_jammers = self.num_radars, self.num_jammers
+        keep = []
+        for name, src in (("half_beam", st["half_beam"]), ("sweep", st["sweep"]), ("sweep_mod", st["sweep_mod"]),
+                          ("az0", st["az0"]), ("bear_tgt", st["bear_tgt"]), ("bear_jam", st["bear_jam"]),
+                          ("GaPs_side", st["GaPs_side"]), ("snr_no", self.tables["radar_snr_no"]),
+                          ("snr_no_side", st["snr_no_side"]), ("pd_no_side", st["pd_no_side"]), ("gr_side", st["gr_side"])):
+            a = np.ascontiguousarray(src, dtype=np.float64)
+            keep.append(a)
+            setattr(d, name, a.ctypes.data)
+        f = np.ascontiguousarray(st["full"], dtype=np.uint8)
+        keep.append(f)
+        d.full = f.ctypes.data
+        return d, keep
 
     # ---- observation pieces (static; environment.py:479-565) ----
     def state_vector(self) -> np.ndarray:
@@ -371,6 +494,9 @@ class ScenarioBatch:
             if not same:
                 raise ValueError(f"ScenarioBatch: scenario {i} differs from scenario 0 in shape / episode limit / "
                                  f"r_p bounds / Pd constants (these are shared by the whole batch)")
+        if any(sc.scanning for sc in scenarios):
+            raise ValueError("ScenarioBatch: scanning radars (environment_params.radar_scan) are not supported with per-env "
+                             "scenario batches")
         self.scenarios = list(scenarios)
         self.base = s0
         self.n_envs = len(scenarios)

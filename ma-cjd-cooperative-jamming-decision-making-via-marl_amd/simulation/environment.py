@@ -80,6 +80,10 @@ class BatchedElectromagneticEnvironment:
                 raise ValueError(f"batch_envs ({batch_envs}) != scenarios in the batch ({scenario_batch.n_envs})")
         self.scenario = scenario if scenario is not None else Scenario.from_yaml(sim_config_path, config)
         sc = self.scenario
+        if sc.scanning and scenario_batch is not None:
+            raise ValueError("scanning radars (environment_params.radar_scan) are not supported with per-env scenario batches")
+        # scanning beams (environment_params.radar_scan): theta_a moves every step, so the observation does too
+        self.observation_is_static = not sc.scanning
         self.num_jammers, self.num_radars = sc.num_jammers, sc.num_radars
         self.episode_limit = sc.episode_limit
         self.state_dim = self.obs_dim = self.agent_obs_dim = sc.state_dim
@@ -129,6 +133,24 @@ class BatchedElectromagneticEnvironment:
             self._pe_flags = torch.from_numpy(fl).to(dev)        # u8  [J*R, E] or [n_tiles, J*R, w]
             self._state_vecs = torch.from_numpy(scenario_batch.state_vectors).to(dev)   # f32 [E, S]
             self._snr_no = torch.from_numpy(scenario_batch.snr_no).to(dev)          # f64 [E, R]
+        self._theta_a = self._state_dyn = self._snr_no_step = None
+        self._scan_io = None
+        if sc.scanning:
+            # beam azimuths f64 [R, E] (radar-major like track), the per-env state rows f32 [E, S] whose theta_a columns the
+            # kernel rewrites every step (get_state / get_obs are views of it: one address for captured graphs), and the
+            # per-step SNR without jamming (main or side lobe) f32 [R, E]
+            az0 = torch.from_numpy(sc.scan_tables["az0"]).to(dev)
+            self._theta_a = az0.view(R, 1).repeat(1, E).contiguous()
+            st = torch.from_numpy(sc.state_vector()).to(dev)
+            st[sc.theta_a_columns] = az0.to(torch.float32)
+            self._state_dyn = st.view(1, -1).repeat(E, 1).contiguous()
+            self._snr_no_step = torch.from_numpy(sc.tables["radar_snr_no"]).to(dev).to(torch.float32).view(R, 1).repeat(1, E)
+            self._snr_no_step = self._snr_no_step.contiguous()
+            si = self._scan_io = _native.ScanIO()
+            si.theta_a, si.a_se, si.a_sx = self._theta_a.data_ptr(), 1, E
+            si.state, si.st_se = self._state_dyn.data_ptr(), self._state_dyn.stride(0)
+            si.st_col0, si.st_col_step = sc.theta_a_col0, sc.theta_a_col_step
+            si.snr_no, si.sn_se, si.sn_sx = self._snr_no_step.data_ptr(), 1, E
         self._io = _native.StepIO()
         self.kernel_flags = 0  # A/B hook: _native.STEP_LANE_KERNEL / STEP_SLOT_KERNEL force one kernel variant
         if verbose:
@@ -136,13 +158,18 @@ class BatchedElectromagneticEnvironment:
 
     # ---- reference-shaped getters, broadcast views (never materialised per env) ----
     def get_state(self) -> torch.Tensor:
-        """f32 [E, S] expanded view of the static state vector (environment.py:479-510)."""
+        """f32 [E, S] expanded view of the static state vector (environment.py:479-510); with scanning beams the per-env
+        state rows, whose theta_a columns every step / reset rewrites in place."""
+        if self._state_dyn is not None:
+            return self._state_dyn
         if self._state_vecs is not None:
             return self._state_vecs
         return self._state_vec.unsqueeze(0).expand(self.batch_envs, -1)
 
     def get_obs(self) -> torch.Tensor:
         """f32 [E, J, S] expanded view: every agent observes the global state (environment.py:512-522)."""
+        if self._state_dyn is not None:
+            return self._state_dyn.unsqueeze(1).expand(-1, self.num_jammers, -1)
         if self._state_vecs is not None:
             return self._state_vecs.unsqueeze(1).expand(-1, self.num_jammers, -1)
         return self._state_vec.view(1, 1, -1).expand(self.batch_envs, self.num_jammers, -1)
@@ -158,6 +185,13 @@ class BatchedElectromagneticEnvironment:
     def track(self) -> torch.Tensor:
         """uint8 [E, R] view, 1 = TRACK."""
         return self._track.t()
+
+    @property
+    def beam_azimuth(self) -> torch.Tensor:
+        """f64 [E, R] view of the beam azimuths in degrees (scanning beams only)."""
+        if self._theta_a is None:
+            raise AttributeError("beam_azimuth: the scenario's beams do not scan (no environment_params.radar_scan)")
+        return self._theta_a.t()
 
     @property
     def step_count(self) -> torch.Tensor:
@@ -181,6 +215,10 @@ class BatchedElectromagneticEnvironment:
                                                     1, self.batch_envs, self._step.data_ptr(), mptr,
                                                     self._episode.data_ptr(), stream),
                           "macjd_env_reset")
+            if self._scan_io is not None:
+                _native.check(self._lib.macjd_env_reset_scan(self._handle.ptr, self.batch_envs, ctypes.byref(self._scan_io),
+                                                             mptr, stream), "macjd_env_reset_scan")
+        self._keep_mask = mask
         return self.get_state()
 
     # ---- the hot call ----
@@ -266,7 +304,11 @@ class BatchedElectromagneticEnvironment:
                            rdpj_sum)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         with torch.cuda.device(self.device):
-            _native.check(self._lib.macjd_env_step(self._handle.ptr, ctypes.byref(io), stream), "macjd_env_step")
+            if self._scan_io is not None:
+                _native.check(self._lib.macjd_env_step_scan(self._handle.ptr, ctypes.byref(io), ctypes.byref(self._scan_io),
+                                                            stream), "macjd_env_step_scan")
+            else:
+                _native.check(self._lib.macjd_env_step(self._handle.ptr, ctypes.byref(io), stream), "macjd_env_step")
         rew = self._reward if out_reward is None else out_reward
         ter = self._terminated if out_terminated is None else out_terminated
         info = {"r_d": self._r_dpj[:, 0], "r_p": self._r_dpj[:, 1], "r_j": self._r_dpj[:, 2],
@@ -274,7 +316,7 @@ class BatchedElectromagneticEnvironment:
         if want_info:
             info["radar_pds"] = self._pd.t()
             info["snr_with_jamming"] = self._snr.t()
-            info["snr_no_jamming"] = self._snr_no
+            info["snr_no_jamming"] = self._snr_no if self._snr_no_step is None else self._snr_no_step.t()
         return rew, (ter.view(torch.bool) if ter.dtype == torch.uint8 else ter), info
 
     def step_many(self, actions_T: torch.Tensor, actions_P: torch.Tensor, out_reward: torch.Tensor,
@@ -285,6 +327,7 @@ class BatchedElectromagneticEnvironment:
         all contiguous.  Legal because a step's outcome depends on the env's past only through the step counter (the
         FSM's next state equals `detected`, core/radar.py:102-117) — see include/macjd.h, macjd_env_step_many; meant for
         actions that do not depend on the env's outputs (static observation).  Philox uniforms, no pd / snr outputs."""
+        self._refuse_scanning("step_many")
         E, J = self.batch_envs, self.num_jammers
         n = actions_T.shape[0]
         for name, t, dt in (("actions_T", actions_T, torch.int32), ("actions_P", actions_P, torch.float32),
@@ -309,6 +352,7 @@ class BatchedElectromagneticEnvironment:
     def time_step_many_kernel(self, actions_T, actions_P, out_reward, out_terminated, out_rdpj, iters: int) -> float:
         """bench.py helper: average milliseconds per launch of the many-step kernel (n x E work items), ``iters``
         launches replayed from a HIP graph and bracketed by HIP events on the replay stream (macjd_env_step_many_timed)."""
+        self._refuse_scanning("time_step_many_kernel")
         E, J = self.batch_envs, self.num_jammers
         n = actions_T.shape[0]
         io = self._fill_io(actions_T[0].view(E, J), actions_P[0].view(E, J), None, False, out_reward.view(-1)[:E],
@@ -326,6 +370,7 @@ class BatchedElectromagneticEnvironment:
                          uniforms: Optional[torch.Tensor] = None, want_info: bool = True) -> float:
         """bench.py helper: average milliseconds per env_step launch over ``iters`` back-to-back
         launches, measured with HIP events recorded on the launch stream (macjd_env_step_timed)."""
+        self._refuse_scanning("time_step_kernel")
         io = self._fill_io(actions_T, actions_P, uniforms, False, None, None, want_info, None)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         ms = ctypes.c_float(0.0)
@@ -333,6 +378,12 @@ class BatchedElectromagneticEnvironment:
             _native.check(self._lib.macjd_env_step_timed(self._handle.ptr, ctypes.byref(io), int(iters), stream,
                                                          ctypes.byref(ms)), "macjd_env_step_timed")
         return float(ms.value)
+
+    def _refuse_scanning(self, what: str) -> None:
+        # macjd_env_step_many rests on "a step's outcome depends on the past only through the step counter" (include/
+        # macjd.h), which the beam azimuth breaks; the timing helper runs the non-scanning launch
+        if self._scan_io is not None:
+            raise RuntimeError(f"{what}: not available with scanning radars (environment_params.radar_scan)")
 
     @property
     def scenario_regular(self) -> bool:
@@ -364,7 +415,7 @@ class ElectromagneticEnvironment:
         self.protected_target_config = {"position": sc.target_position, "rcs": sc.target_rcs}
         self._step_count = 0
         self._last_actions = np.zeros((self.num_jammers, 2))
-        self._state = sc.state_vector()
+        self._state = sc.state_vector() if not sc.scanning else self._batched.get_state()[0].cpu().numpy().copy()
         dev = self._batched.device
         R, J = self.num_radars, self.num_jammers
         self._diag = {"out64": torch.zeros((1, 4), dtype=torch.float64, device=dev),
@@ -384,6 +435,8 @@ class ElectromagneticEnvironment:
 
     def reset(self) -> np.ndarray:
         self._batched.reset()
+        if self._batched._scan_io is not None:
+            self._state = self._batched.get_state()[0].cpu().numpy().copy()
         self._step_count = 0
         self._last_actions.fill(0)
         return self.get_state()
@@ -451,14 +504,24 @@ class ElectromagneticEnvironment:
                 "is_tracking": bool(tracking[r]),
                 "locked_target": self.protected_target_config if tracking[r] else None,
             })
+        if b._scan_io is not None:
+            # the kernel reports which lobe's no-jamming SNR applied (float32); hand out that table's float64 value
+            snr32 = b._snr_no_step.t().cpu().numpy()[0]
+            main = sc.tables["radar_snr_no"]
+            snr_no = np.where(main.astype(np.float32) == snr32, main, sc.scan_tables["snr_no_side"]).astype(np.float64)
+            self._state = b.get_state()[0].cpu().numpy().copy()
+        else:
+            snr_no = sc.tables["radar_snr_no"].copy()
         info = {
             "radar_pds": pd,
             "radar_states": radar_states,
-            "snr_no_jamming": sc.tables["radar_snr_no"].copy(),
+            "snr_no_jamming": snr_no,
             "snr_with_jamming": snr,
             "r_d": out[1], "r_p": out[2], "r_j": out[3],
             "jammer_actions": jammer_actions,
         }
+        if b._scan_io is not None:
+            info["radar_beam_azimuth"] = b.beam_azimuth.cpu().numpy()[0].copy()
         return self.get_obs(), np.float64(out[0]), terminated, info
 
     def get_state(self) -> np.ndarray:

@@ -1,0 +1,85 @@
+"""Lane-kernel env step with and without scanning beams (environment_params.radar_scan), timed with HIP events.
+
+For each size (3j/4r, 12j/16r ring scenarios; E = 4096 and 2^20) both environments take the one-lane-per-env kernel
+(the scanning path's only kernel) in its production configuration (Philox uniforms, float32 actions, no info outputs),
+`iters` steps are captured as one graph and replayed; the figure is the replay's event-timed milliseconds per step.
+The scanning scenario is the same ring with 0.25 s steps, -30 dB side lobes and the shipped 2.0 / 1.8 degree beams.
+
+    python scripts/probe_scan_env.py [--iters 200] [--reps 5]
+
+Prints one JSON line per (size, E) with the median of `reps` replays of each and their ratio."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import macjd_amd  # noqa: E402,F401
+from macjd_amd import _native  # noqa: E402
+from macjd_amd.scenario import Scenario, ring_scenario_dict  # noqa: E402
+from macjd_amd.simulation.environment import BatchedElectromagneticEnvironment  # noqa: E402
+
+
+def timed(env, T, P, iters, reps):
+    out_r = torch.zeros(env.batch_envs, device="cuda")
+    out_t = torch.zeros(env.batch_envs, dtype=torch.uint8, device="cuda")
+    env.reset()
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        for _ in range(3):   # warm-up (and the lazy library options) outside the capture
+            env.step(T, P, out_reward=out_r, out_terminated=out_t, want_info=False)
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(iters):
+            env.step(T, P, out_reward=out_r, out_terminated=out_t, want_info=False)
+    g.replay()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        g.replay()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b) / iters)
+    del g
+    return statistics.median(ms)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--reps", type=int, default=5)
+    a = ap.parse_args()
+    for J, R in ((3, 4), (12, 16)):
+        d0 = ring_scenario_dict(J, R)
+        ds = dict(d0)
+        ds["environment_params"] = dict(d0["environment_params"], radar_scan={"step_seconds": 0.25, "sidelobe_db": -30.0})
+        sc0, scs = Scenario.from_dict(d0), Scenario.from_dict(ds)
+        for E in (4096, 1 << 20):
+            rng = np.random.default_rng(0)
+            T = torch.from_numpy(rng.integers(0, 2 * R + 1, size=(J, E)).astype(np.int32)).cuda().t()   # agent-major
+            P = torch.from_numpy(rng.random((J, E), dtype=np.float32)).cuda().t()
+            res = {}
+            for tag, sc in (("static", sc0), ("scan", scs)):
+                env = BatchedElectromagneticEnvironment(scenario=sc, batch_envs=E, device="cuda", seed=1)
+                env.kernel_flags = _native.STEP_LANE_KERNEL
+                res[tag] = timed(env, T, P, a.iters if E < (1 << 20) else max(20, a.iters // 10), a.reps)
+                env.close()
+                del env
+                torch.cuda.empty_cache()
+            print(json.dumps({"J": J, "R": R, "E": E, "static_ms": round(res["static"], 5), "scan_ms": round(res["scan"], 5),
+                              "ratio": round(res["scan"] / res["static"], 3)}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
