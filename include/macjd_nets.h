@@ -19,6 +19,8 @@
 
 #include <stdint.h>
 
+#include "macjd.h"   /* macjd_scenario, macjd_scan_io (macjd_agent_env_episode_scan) */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -559,6 +561,66 @@ typedef struct macjd_agent_episode_io {
 
 int macjd_agent_episode_supported(int32_t J, int32_t H, int32_t A);
 int macjd_agent_episode(const macjd_agent_episode_io* io, void* hip_stream);
+
+/*
+ * Closed-loop episode launch for scanning radars (macjd_scan_desc): agent AND environment of a whole episode batch in
+ * ONE launch.  With scanning beams the observation's theta_a columns change every step and depend, through the FSM, on
+ * what the agents did, so macjd_agent_episode + macjd_env_step_many do not apply; environments are still independent of
+ * each other, so the workgroup that owns 16 environments runs, for t = 0 .. T-1 and without leaving the kernel:
+ *   observation-only work once per ENV (every agent sees the same state vector): x = ReLU(fc1 obs + b),
+ *     gi = W_ih x + b_ih, actor P = sigma(L3 ReLU(L2 ReLU(L1 obs))); the first layers as (static columns, once per launch)
+ *     + sum_r W[:, col_r] theta_a[r] — a different summation order than the GEMM, ~1e-7 relative;
+ *   the agent step of macjd_agent_episode (same gate / Q-head expressions, same Philox draw (row, *counter_base + t + 1));
+ *   the scanning env step of macjd_env_step_scan on the chosen actions (general all-float64 form, same Philox stream:
+ *     counter = (global env, episode, step, slot / 4), key = env_seed): reward[t], terminated[t], r_dpj sums;
+ *   (float) theta_a -> the theta_a columns of state[t + 1] / obs[t + 1, :, j, :] and the next agent step.
+ * The kernel writes ONLY the theta_a columns (scan.st_col0 + r * scan.st_col_step) of the staging rows t < T; their
+ * static columns are the caller's.  At exit theta_a, track, step, the theta_a columns of the env's state rows
+ * (scan.state), scan.snr_no (last step's lobe), rdpj_sum and h_final hold what T single steps would have left.
+ * Needs macjd_scenario_set_scan; shared scenario tables only (pe_tables must be NULL).
+ * Supported: H = 64, actor_hidden = 128, (J, R, A) in {(3, 4, 9), (2, 2, 5)}; MACJD_EUNSUPPORTED otherwise.
+ */
+typedef struct macjd_agent_env_episode_scan_io {
+    int64_t n_envs;            /* E */
+    int64_t env_offset;        /* global index of env 0 (keys the env's Philox stream) */
+    int32_t T, J, R, H, A, S;  /* steps, agents, radars, rnn_hidden_dim, n_actions, state / observation width */
+    int32_t actor_hidden, greedy_only;
+    /* agent */
+    const float* h0;                                  /* [E*J, H] initial hidden state or NULL = zeros */
+    const float* fc1_w; const float* fc1_b;           /* fc1 [H, S], [H] */
+    const float* w_ih;  const float* b_ih;            /* rnn.weight_ih [3H, H], rnn.bias_ih [3H] */
+    const float* w_hh;  const float* b_hh;            /* rnn.weight_hh [3H, H], rnn.bias_hh [3H] */
+    const float* a1_w;  const float* a1_b;            /* actor.0 [128, S] */
+    const float* a2_w;  const float* a2_b;            /* actor.2 [128, 128] */
+    const float* a3_w;  const float* a3_b;            /* actor.4 [A, 128] */
+    const float* W1;    int64_t w1_ld;                /* fc2_q_head.0.weight [H, H+A+1] */
+    const float* b1;    const float* w2; const float* b2;
+    const void* avail;  int32_t avail_elem_size, reserved;   /* optional mask (static), int32 / int64 elements */
+    int64_t av_se, av_sj, av_sa;
+    const float* eps;          /* [T] exploration probability of every step (device memory) */
+    uint64_t seed;             /* exploration draws */
+    const uint64_t* counter_base;
+    /* environment */
+    uint64_t env_seed;         /* macjd_step_io.seed */
+    const int32_t* episode;    /* [E] episode index, optional (NULL = 0) */
+    uint8_t* track;     int64_t k_se, k_sx;           /* [E, R] read-modify-write */
+    int32_t* step;                                    /* [E] read-modify-write */
+    macjd_scan_io scan;        /* theta_a, the env's state rows and their theta_a columns, snr_no */
+    const double* pe_tables;   /* must be NULL */
+    /* outputs, time-major staging rows of the batched runner */
+    float*   hidden;    /* [T(+1), E, J, H] row t = post-update h_t */
+    int32_t* T_out;     /* [T, E, J] */
+    float*   P_out;     /* [T, E, J] */
+    float*   h_final;   /* [E*J, H] optional */
+    float*   st_state;  /* [T(+1), E, S]: theta_a columns of rows t < T */
+    float*   st_obs;    /* [T(+1), E, J, S]: likewise */
+    float*   reward;    /* [T, E] */
+    uint8_t* terminated;/* [T, E] */
+    float*   rdpj_sum;  /* [E, 3] optional: the T steps' (r_d, r_p, r_j) are added in step order */
+} macjd_agent_env_episode_scan_io;
+
+int macjd_agent_env_episode_scan_supported(int32_t J, int32_t R, int32_t H, int32_t A);
+int macjd_agent_env_episode_scan(const macjd_scenario* scenario, const macjd_agent_env_episode_scan_io* io, void* hip_stream);
 
 /*
  * Double-DQN target values straight from the unrolled hidden states (reference core/qmix.py:138-147): for every row n

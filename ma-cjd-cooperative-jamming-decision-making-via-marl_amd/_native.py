@@ -31,6 +31,7 @@ EXPORTS = [
     "macjd_qhead_double_q_supported", "macjd_qhead_double_q", "macjd_qhead_taken_supported", "macjd_qhead_taken",
     "macjd_qheads_pair", "macjd_mixer_fused_forward_pair", "macjd_mixer_fused_train",
     "macjd_scenario_set_scan", "macjd_env_step_scan", "macjd_env_reset_scan",
+    "macjd_agent_env_episode_scan_supported", "macjd_agent_env_episode_scan",
 ]
 
 
@@ -156,6 +157,29 @@ class AgentEpisodeIO(ctypes.Structure):
         ("av_se", ctypes.c_int64), ("av_sj", ctypes.c_int64), ("av_sa", ctypes.c_int64),
         ("eps", ctypes.c_void_p), ("seed", ctypes.c_uint64), ("counter_base", ctypes.c_void_p),
         ("hidden", ctypes.c_void_p), ("T_out", ctypes.c_void_p), ("P_out", ctypes.c_void_p), ("h_final", ctypes.c_void_p),
+    ]
+
+
+class AgentEnvEpisodeScanIO(ctypes.Structure):
+    """ctypes mirror of ``macjd_agent_env_episode_scan_io`` (include/macjd_nets.h)."""
+    _fields_ = [
+        ("n_envs", ctypes.c_int64), ("env_offset", ctypes.c_int64),
+        ("T", ctypes.c_int32), ("J", ctypes.c_int32), ("R", ctypes.c_int32), ("H", ctypes.c_int32), ("A", ctypes.c_int32),
+        ("S", ctypes.c_int32), ("actor_hidden", ctypes.c_int32), ("greedy_only", ctypes.c_int32),
+        ("h0", ctypes.c_void_p), ("fc1_w", ctypes.c_void_p), ("fc1_b", ctypes.c_void_p),
+        ("w_ih", ctypes.c_void_p), ("b_ih", ctypes.c_void_p), ("w_hh", ctypes.c_void_p), ("b_hh", ctypes.c_void_p),
+        ("a1_w", ctypes.c_void_p), ("a1_b", ctypes.c_void_p), ("a2_w", ctypes.c_void_p), ("a2_b", ctypes.c_void_p),
+        ("a3_w", ctypes.c_void_p), ("a3_b", ctypes.c_void_p),
+        ("W1", ctypes.c_void_p), ("w1_ld", ctypes.c_int64), ("b1", ctypes.c_void_p), ("w2", ctypes.c_void_p), ("b2", ctypes.c_void_p),
+        ("avail", ctypes.c_void_p), ("avail_elem_size", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("av_se", ctypes.c_int64), ("av_sj", ctypes.c_int64), ("av_sa", ctypes.c_int64),
+        ("eps", ctypes.c_void_p), ("seed", ctypes.c_uint64), ("counter_base", ctypes.c_void_p),
+        ("env_seed", ctypes.c_uint64), ("episode", ctypes.c_void_p),
+        ("track", ctypes.c_void_p), ("k_se", ctypes.c_int64), ("k_sx", ctypes.c_int64), ("step", ctypes.c_void_p),
+        ("scan", ScanIO), ("pe_tables", ctypes.c_void_p),
+        ("hidden", ctypes.c_void_p), ("T_out", ctypes.c_void_p), ("P_out", ctypes.c_void_p), ("h_final", ctypes.c_void_p),
+        ("st_state", ctypes.c_void_p), ("st_obs", ctypes.c_void_p), ("reward", ctypes.c_void_p), ("terminated", ctypes.c_void_p),
+        ("rdpj_sum", ctypes.c_void_p),
     ]
 
 
@@ -364,6 +388,10 @@ def load() -> ctypes.CDLL:
     lib.macjd_agent_episode_supported.argtypes = [ctypes.c_int32] * 3
     lib.macjd_agent_episode.restype = ctypes.c_int
     lib.macjd_agent_episode.argtypes = [ctypes.POINTER(AgentEpisodeIO), ctypes.c_void_p]
+    lib.macjd_agent_env_episode_scan_supported.restype = ctypes.c_int
+    lib.macjd_agent_env_episode_scan_supported.argtypes = [ctypes.c_int32] * 4
+    lib.macjd_agent_env_episode_scan.restype = ctypes.c_int
+    lib.macjd_agent_env_episode_scan.argtypes = [ctypes.c_void_p, ctypes.POINTER(AgentEnvEpisodeScanIO), ctypes.c_void_p]
     lib.macjd_env_step_many.restype = ctypes.c_int
     lib.macjd_env_step_many.argtypes = [ctypes.c_void_p, ctypes.POINTER(StepIO), ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p]
     lib.macjd_env_step_many_timed.restype = ctypes.c_int

@@ -676,3 +676,6 @@ extern "C" int macjd_agent_episode(const macjd_agent_episode_io* io, void* hip_s
     if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_agent_episode: %s", hipGetErrorString(err));
     return MACJD_OK;
 }
+
+// closed-loop episode launch for scanning radars: agent and env in one kernel (macjd_agent_env_episode_scan)
+#include "macjd_episode_scan.h"

@@ -346,6 +346,90 @@ def agent_episode(gi, P_all, h0, w_hh, b_hh, W1, b1, w2, b2, n_envs: int, n_agen
         _native.check(lib.macjd_agent_episode(ctypes.byref(io), _stream(gi)), "macjd_agent_episode")
 
 
+def agent_env_episode_scan_supported(J: int, R: int, H: int, A: int) -> bool:
+    return bool(_native.load().macjd_agent_env_episode_scan_supported(int(J), int(R), int(H), int(A)))
+
+
+def agent_env_episode_scan(agent, env_args: dict, n_envs: int, n_agents: int, T: int, avail, eps_sched, greedy_only: bool,
+                           seed: int, counter_base, stage: dict, rdpj_sum=None, h0=None, h_final=None):
+    """Closed-loop episode launch for scanning radars (csrc/macjd_episode_scan.h; include/macjd_nets.h,
+    macjd_agent_env_episode_scan_io): all T steps of agent AND environment of an episode batch in ONE launch.  ``agent`` is
+    the stock RNNAgent on the device, ``env_args`` what ``BatchedElectromagneticEnvironment.episode_scan_args()`` hands
+    over, ``stage`` the runner's time-major staging tensors (state, obs, hidden_state, actions_discrete,
+    actions_continuous, reward, terminated; the static columns of state / obs rows are the caller's).  ``eps_sched`` float32
+    [>= T] and ``counter_base`` int64 / uint64 [1] live on the device."""
+    lib = _native.load()
+    io = _native.AgentEnvEpisodeScanIO()
+    keep = []
+
+    def f32(t):
+        t = t.detach()
+        t = t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
+        keep.append(t)
+        return t
+
+    H, A, S = agent.rnn_hidden_dim, agent.n_actions, agent.input_shape
+    io.n_envs, io.env_offset = int(n_envs), int(env_args["env_offset"])
+    io.T, io.J, io.R, io.H, io.A, io.S = int(T), int(n_agents), int(env_args["n_radars"]), int(H), int(A), int(S)
+    io.actor_hidden, io.greedy_only = int(agent.actor_hidden_dim), 1 if greedy_only else 0
+    if h0 is not None:
+        io.h0 = f32(h0).data_ptr()
+    a, l1, l2 = agent.actor, agent.fc2_q_head[0], agent.fc2_q_head[2]
+    for name, t_ in (("fc1_w", agent.fc1.weight), ("fc1_b", agent.fc1.bias), ("w_ih", agent.rnn.weight_ih),
+                     ("b_ih", agent.rnn.bias_ih), ("w_hh", agent.rnn.weight_hh), ("b_hh", agent.rnn.bias_hh),
+                     ("a1_w", a[0].weight), ("a1_b", a[0].bias), ("a2_w", a[2].weight), ("a2_b", a[2].bias),
+                     ("a3_w", a[4].weight), ("a3_b", a[4].bias), ("b1", l1.bias), ("w2", l2.weight.reshape(-1)),
+                     ("b2", l2.bias.reshape(-1))):
+        setattr(io, name, f32(t_).data_ptr())
+    W1 = l1.weight.detach()
+    W1 = W1 if (W1.dtype == torch.float32 and W1.stride(-1) == 1) else W1.float().contiguous()
+    keep.append(W1)
+    io.W1, io.w1_ld = W1.data_ptr(), W1.stride(0)
+    dev = W1.device
+    if avail is not None:
+        if avail.dtype not in (torch.int32, torch.int64):
+            avail = avail.to(torch.int32)
+        keep.append(avail)
+        io.avail, io.avail_elem_size = avail.data_ptr(), avail.element_size()
+        io.av_se, io.av_sj, io.av_sa = avail.stride(0), avail.stride(1), avail.stride(2)
+    if eps_sched is not None:
+        assert eps_sched.dtype == torch.float32 and eps_sched.numel() >= T and eps_sched.is_contiguous()
+        io.eps = eps_sched.data_ptr()
+    io.seed = int(seed) & (2 ** 64 - 1)
+    if counter_base is not None:
+        assert counter_base.dtype in (torch.int64, torch.uint64) and counter_base.numel() >= 1
+        io.counter_base = counter_base.data_ptr()
+    io.env_seed = int(env_args["seed"]) & (2 ** 64 - 1)
+    io.episode = env_args["episode"].data_ptr()
+    track, step = env_args["track"], env_args["step"]           # uint8 [R, E] radar-major, int32 [E]
+    io.track, io.k_se, io.k_sx = track.data_ptr(), track.stride(1), track.stride(0)
+    io.step = step.data_ptr()
+    ctypes.memmove(ctypes.addressof(io) + _native.AgentEnvEpisodeScanIO.scan.offset, ctypes.addressof(env_args["scan_io"]),
+                   ctypes.sizeof(_native.ScanIO))
+    io.pe_tables = env_args.get("pe_tables")
+    E, J = int(n_envs), int(n_agents)
+    sizes = {"state": (T * E * S, torch.float32), "obs": (T * E * J * S, torch.float32),
+             "hidden_state": (T * E * J * H, torch.float32), "actions_discrete": (T * E * J, torch.int32),
+             "actions_continuous": (T * E * J, torch.float32), "reward": (T * E, torch.float32), "terminated": (T * E, None)}
+    for k, (n, dt) in sizes.items():
+        t_ = stage[k]
+        assert t_.is_contiguous() and t_.device == dev and t_.numel() >= n and (dt is None or t_.dtype == dt), k
+    assert stage["terminated"].dtype in (torch.bool, torch.uint8)
+    assert stage["state"].shape[-1] == S and stage["obs"].shape[-1] == S
+    io.hidden, io.T_out, io.P_out = stage["hidden_state"].data_ptr(), stage["actions_discrete"].data_ptr(), stage["actions_continuous"].data_ptr()
+    io.st_state, io.st_obs = stage["state"].data_ptr(), stage["obs"].data_ptr()
+    io.reward, io.terminated = stage["reward"].data_ptr(), stage["terminated"].data_ptr()
+    if rdpj_sum is not None:
+        assert rdpj_sum.is_contiguous() and rdpj_sum.dtype == torch.float32 and rdpj_sum.numel() == 3 * E
+        io.rdpj_sum = rdpj_sum.data_ptr()
+    if h_final is not None:
+        assert h_final.is_contiguous() and h_final.dtype == torch.float32 and h_final.numel() == E * J * H
+        io.h_final = h_final.data_ptr()
+    with torch.cuda.device(dev):
+        _native.check(lib.macjd_agent_env_episode_scan(env_args["handle"], ctypes.byref(io), _stream(W1)),
+                      "macjd_agent_env_episode_scan")
+
+
 def gru_sequence_reference(gi: torch.Tensor, w_hh: torch.Tensor, b_hh: torch.Tensor,
                            h0: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Step-by-step GRU recurrence with stock torch ops (host tensors / numerics tests).

@@ -19,6 +19,7 @@ for normal operation.
     MACJD_MIXER_TRAIN         1 | 0      paired update at 2 / 3 agents: both mixers, the loss gradient and the mixer backward
                                          as one launch / the mixer pair + the backward launch
     MACJD_GRAPHED_ALLREDUCE   0 | 1      with ranks: RCCL all-reduce captured inside the update graph
+    MACJD_CLOSED_LOOP_ROLLOUT 0 | 1      scanning radars: step-by-step rollout / agent and env of an episode batch in one launch
 """
 from __future__ import annotations
 
@@ -28,6 +29,7 @@ _DEFAULTS = {
     "UPDATE_STREAMS": "2", "UPDATES_PER_GRAPH": "1", "PIPELINED_GROUP": "1", "SHARED_BODY": "1",
     "LEARNER_STATIC_OBS": "1", "ACTOR_IN_SCAN": "1", "DEVICE_SAMPLER": "1", "LN_IN_SQNORM": "1", "WGRAD_OUTER": "1",
     "QHEAD_TAKEN": "1", "PAIRED_HEADS": "1", "MIXER_TRAIN": "1", "GRAPHED_ALLREDUCE": "0",
+    "CLOSED_LOOP_ROLLOUT": "0",
 }
 _values = None
 

@@ -23,6 +23,27 @@ import torch
 
 _ENV_SERIAL = itertools.count(1)   # static-content tags of the replay slots (BatchedEpisodeRunner.end_episodes)
 
+
+class _OptionSwitch:
+    """Class attribute that reads a MACJD_* switch of options.py until the attribute is set on the class or an instance
+    (tests and A/B scripts set it), so ``options.reload()`` reaches runners that exist already."""
+
+    def __init__(self, option):
+        self.option = option
+
+    def __set_name__(self, owner, name):
+        self.slot = "_switch_" + name
+
+    def __get__(self, obj, owner=None):
+        if obj is not None and self.slot in obj.__dict__:
+            return obj.__dict__[self.slot]
+        from .. import options
+        return options.get(self.option) == "1"
+
+    def __set__(self, obj, value):
+        obj.__dict__[self.slot] = bool(value)
+
+
 class EpisodeBatch:
     """Per-episode staging arrays (episode_runner.py:184-277)."""
 
@@ -323,6 +344,9 @@ class BatchedEpisodeRunner:
         if device_schedule and self.fused_rollout_available():
             self._fused_launches(T)     # whole-episode launches (static observation): the same rows as the loop below
             return
+        if device_schedule and self.closed_loop_rollout and self.closed_loop_available():
+            self._closed_loop_launch(T)   # scanning radars: agent and env of the whole batch in one launch
+            return
         for t in range(T):
             if device_schedule:
                 self.mac.device_schedule = (self._eps_sched[t:t + 1], self._ctr_base, t + 1)
@@ -433,6 +457,58 @@ class BatchedEpisodeRunner:
         env.step_many(st["actions_discrete"][:n], st["actions_continuous"][:n], st["reward"][:n], st["terminated"][:n],
                       self._rdpj_steps[:n], rdpj_sum=self._rdpj_sum)
 
+    # ---- scanning radars: agent and env of a whole episode batch as ONE closed-loop launch ----
+    closed_loop_rollout = _OptionSwitch("CLOSED_LOOP_ROLLOUT")   # default off (MACJD_CLOSED_LOOP_ROLLOUT=1 turns it on)
+
+    def closed_loop_available(self) -> bool:
+        """The env's beams scan (dynamic observation, shared scenario tables), the MAC is the stock RNNAgent on a HIP
+        device, and the closed-loop episode kernel covers the sizes (``ops.agent_env_episode_scan_supported``)."""
+        env = self.env
+        if self.device.type != "cuda" or not hasattr(env, "episode_scan_args") or not getattr(env.scenario, "scanning", False):
+            return False
+        if getattr(env, "scenario_batch", None) is not None or getattr(env, "kernel_flags", 0) != 0:
+            return False
+        agent = getattr(self.mac, "agent", None)
+        if agent is None or not hasattr(agent, "fc2_q_head") or not next(agent.parameters()).is_cuda:
+            return False
+        from .. import ops
+        return (getattr(agent, "actor_hidden_dim", 0) == 128 and agent.input_shape == env.state_dim and env.state_dim <= 48
+                and ops.agent_env_episode_scan_supported(self.n_agents, env.num_radars, agent.rnn_hidden_dim, agent.n_actions))
+
+    def rollout_closed_loop(self, test_mode=False, n_steps=None):
+        """One episode batch (or its first ``n_steps`` steps) of a scanning scenario in ONE launch
+        (``ops.agent_env_episode_scan``): per step the observation-only work once per env, the agent step of
+        ``rollout_fused``, the scanning env step on the chosen actions and the next observation, for 16 envs per workgroup
+        without leaving the kernel.  Same staging rows, exploration draws and Monte-Carlo streams as the step-by-step
+        path; hidden states / Q-values / powers differ from it by the summation order of the matrix products (~1e-7) and
+        rewards by the all-float64 env form (<= (R + J) 6e-7), which can flip a choice only on a near-tie."""
+        if not self.closed_loop_available():
+            raise RuntimeError("rollout_closed_loop: not available for this environment / agent (closed_loop_available())")
+        T = self.episode_limit
+        n = T if n_steps is None else int(n_steps)
+        if not 1 <= n <= T:
+            raise ValueError(f"rollout_closed_loop: n_steps must be in 1..{T}, got {n_steps}")
+        if getattr(self, "_eps_sched", None) is None:
+            self._eps_sched = torch.zeros(T, dtype=torch.float32, device=self.device)
+            self._ctr_base = torch.zeros(1, dtype=torch.int64, device=self.device)
+        if not test_mode and n in (getattr(self, "_graphs", None) or {}):
+            return self.rollout_graphed(n)
+        self._upload_eps_schedule(self._eps_schedule(n, test_mode))
+        self.begin_episodes()
+        self._ctr_base.fill_(self._ep * (T + 1))
+        self._closed_loop_launch(n, test_mode=test_mode)
+        self.t_env += n
+
+    def _closed_loop_launch(self, n, test_mode=False):
+        """The launch of ``rollout_closed_loop`` (behind ``begin_episodes``).  The kernel writes only the theta_a columns
+        of the state / obs staging rows; their static columns and the availability rows never change and are filled once."""
+        from .. import ops
+        if not self._static_filled:
+            self._fill_static()
+        ops.agent_env_episode_scan(self.mac.agent, self.env.episode_scan_args(), self.batch_envs, self.n_agents, n, self._avail,
+                                   self._eps_sched, bool(test_mode), self.mac.select_seed, self._ctr_base, self.stage,
+                                   rdpj_sum=self._rdpj_sum, h_final=self.mac.hidden_states)
+
     def run(self, test_mode=False, store=True, sync_stats=True):
         """One batch of E episodes.  Returns the reference's ``run_info`` keys as means over the E
         episodes (one host sync at the very end; pass ``sync_stats=False`` to get 0-dim tensors)."""
@@ -440,6 +516,8 @@ class BatchedEpisodeRunner:
         T, E, J = self.episode_limit, self.batch_envs, self.n_agents
         if self.fused_rollout_available():
             self.rollout_fused(test_mode=test_mode)
+        elif self.closed_loop_rollout and self.closed_loop_available():
+            self.rollout_closed_loop(test_mode=test_mode)
         elif getattr(self, "_graph", None) is not None and not test_mode:
             self.rollout_graphed()
         else:

@@ -379,6 +379,18 @@ class BatchedElectromagneticEnvironment:
                                                          ctypes.byref(ms)), "macjd_env_step_timed")
         return float(ms.value)
 
+    def episode_scan_args(self) -> Dict[str, Any]:
+        """What the closed-loop episode launch (``ops.agent_env_episode_scan``) needs from a scanning environment: the
+        scenario handle, the beam / state-row block, the FSM bits, step counters and episode indices it reads and leaves
+        as T single steps would, and the Monte-Carlo stream's seed and env offset."""
+        if self._scan_io is None:
+            raise RuntimeError("episode_scan_args: the scenario's beams do not scan (no environment_params.radar_scan)")
+        if self._pe_tables is not None:
+            raise RuntimeError("episode_scan_args: per-env scenario tables are not supported with scanning radars")
+        return {"handle": self._handle.ptr, "scan_io": self._scan_io, "track": self._track, "step": self._step,
+                "episode": self._episode, "seed": self.seed, "env_offset": self.env_offset, "n_radars": self.num_radars,
+                "pe_tables": None}
+
     def _refuse_scanning(self, what: str) -> None:
         # macjd_env_step_many rests on "a step's outcome depends on the past only through the step counter" (include/
         # macjd.h), which the beam azimuth breaks; the timing helper runs the non-scanning launch
