@@ -533,9 +533,14 @@ int macjd_mixer_fused_train(const macjd_mixerf_io* eval, const macjd_mixerf_io* 
  * environments are independent.  Exact float32 (v_mfma_f32_16x16x4_f32); gate and Q-head expressions and the Philox
  * exploration draws are those of macjd_gru_gates / macjd_qhead_select (same (row, counter) keying), so the episode equals
  * the step-by-step rollout up to the summation order of the two matrix products.
- * Supported: H = 64, A in {5, 9, 17, 33}, any J >= 1 (J in {2, 3, 6} with A <= 17: one row tile per agent as described; every
- * other size: four tiles of 16 consecutive rows n = env * J + agent per workgroup — the arithmetic per row is the same);
- * MACJD_EUNSUPPORTED otherwise.
+ * Supported:
+ *   H = 64:  A in {5, 9, 17, 33}, any J >= 1 (J in {2, 3, 6} with A <= 17: one row tile per agent as described; every
+ *            other size: four tiles of 16 consecutive rows n = env * J + agent per workgroup — the arithmetic per row is
+ *            the same);
+ *   H = 128: (J, A) in {2, 3} x {5, 9}, one row tile per agent only (eight waves, wave w = units [16w, 16w+16); the
+ *            Q-head's h-columns are read from LDS instead of registers; same arithmetic per row).  No four-tile form and
+ *            no A in {17, 33} at this size (they did not compile without scratch memory);
+ *   MACJD_EUNSUPPORTED otherwise.  w_hh must be 16-byte aligned with contiguous rows of H floats.
  */
 typedef struct macjd_agent_episode_io {
     int64_t n_envs;            /* E */
@@ -628,7 +633,8 @@ int macjd_agent_env_episode_scan(const macjd_scenario* scenario, const macjd_age
  *   out[n] = Q_target(h_t[n], a*, P_t[n,a*])
  * in ONE launch: both Q-head base products W1[:, :H] h + b1 on the matrix cores (exact f32), both all-action Q-heads,
  * arg-max and gather.  Replaces two library GEMMs + two macjd_qhead_select launches behind the learner's scan.
- * h_e / h_t [n, H] (the same tensor when the agent body is shared), P_e / P_t [n, A].  Supported: H = 64, A in {5, 9, 17}.
+ * h_e / h_t [n, H] (the same tensor when the agent body is shared), P_e / P_t [n, A].
+ * Supported: H = 64 with A in {5, 9, 17, 33}; H = 128 with A in {5, 9, 17}; MACJD_EUNSUPPORTED otherwise.
  */
 typedef struct macjd_doubleq_io {
     int64_t n_rows;
@@ -648,7 +654,8 @@ int macjd_qhead_double_q_supported(int32_t H, int32_t A);
 int macjd_qhead_double_q(const macjd_doubleq_io* io, void* hip_stream);
 /* macjd_qhead_taken and macjd_qhead_double_q of one learner update (reference core/qmix.py:138-147 and :161-184: both read
  * the same unrolled hidden states, neither reads the other's result) as ONE grid; same A in both.  Results equal the two
- * single launches bit for bit. */
+ * single launches bit for bit.  H = 64 only (macjd_qhead_taken exists at H = 64 only): MACJD_EUNSUPPORTED at H = 128, where
+ * the caller launches macjd_qhead_double_q on its own. */
 int macjd_qheads_pair(const macjd_qtaken_io* taken, const macjd_doubleq_io* dq, void* hip_stream);
 
 #ifdef __cplusplus

@@ -40,6 +40,8 @@ namespace macjd {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4_u __attribute__((ext_vector_type(4), aligned(4)));
 
+// hidden size of the kernels below that exist at H = 64 only (taken-action Q-head, closed-loop scan launch); the episode
+// and Double-DQN kernels take H as a template parameter and derive their own pitch / quad count from it
 constexpr int EP_H = 64;
 constexpr int EP_LD = EP_H + 8;   // LDS pitch (= 8 mod 16 floats: conflict-free ds_read_b128 fragments)
 constexpr int EP_KQ = EP_H / 16;  // quads of a K = 64 product
@@ -47,12 +49,30 @@ constexpr int EP_KQ = EP_H / 16;  // quads of a K = 64 product
 // FLAT (wide scenarios, e.g. 12 jammers): nothing above depends on WHICH agent a row belongs to — the networks are shared
 // and every output is indexed by the flattened row n = env * n_agents + agent — so the workgroup simply owns J = 4 tiles
 // of 16 consecutive rows n (64 rows: 36 KB of LDS instead of 110 KB for 12 agent tiles); same arithmetic per row.
-template <int J, int A, bool FLAT = false>
-__global__ void __launch_bounds__(256) agent_episode_kernel(const macjd_agent_episode_io io) {
-    static_assert(J <= 8, "one wave per agent tile in the Q-head phase, two passes above 4");
+//
+// H = 128 (template parameter EP_H; EP_LD / EP_KQ / the wave count follow from it): the same mapping with EIGHT waves, two
+// per SIMD — wave w still owns units [16w, 16w+16) of all three gates, now 3 x 8 W_hh fragments = 96 VGPRs.  Two waves per
+// SIMD leave 256 registers per lane; with gi (12 J), the accumulators (12 J) and h (4 J) at J = 3 the 32 registers of the
+// Q-head's h-column fragments do not fit beside them, so W1[:, :H] lives in LDS (H x EP_LD floats, same pitch: the B
+// fragments are conflict-free ds_read_b128 like the A fragments) and is read once per step.  The Q-head phase keeps
+// wave = agent tile, lane = (row, quarter of the units) = 32 units per lane: the waves without a tile do not wait there
+// (no barrier closes a step) but run ahead into the next step's gh products, so the matrix pipe works on step t + 1
+// while waves 0 .. J-1 evaluate the heads of step t on the vector pipe.
+template <int EP_H, int J, int A, bool FLAT = false>
+__global__ void __launch_bounds__(EP_H * 4) agent_episode_kernel(const macjd_agent_episode_io io) {
+    static_assert(EP_H == 64 || EP_H == 128, "hidden size");
+    constexpr int EP_LD = EP_H + 8;    // LDS pitch (= 8 mod 16 floats: conflict-free ds_read_b128 fragments)
+    constexpr int EP_KQ = EP_H / 16;   // quads of a K = H product
+    constexpr int NW = EP_H / 16;      // waves: one per 16 hidden units
+    constexpr int NT = 64 * NW;        // threads
+    constexpr int UQ = EP_H / 4;       // Q-head phase: units per lane
+    constexpr bool BQ_LDS = EP_H > 64; // the Q-head's h-column fragments: registers / LDS
+    constexpr bool H_REG = EP_H == 64; // the lane's own h values between steps: registers / re-read from the LDS tile
+    static_assert(J <= 2 * NW, "one wave per agent tile in the Q-head phase, two passes above the wave count");
     __shared__ __attribute__((aligned(16))) float Hl[2][J][16 * EP_LD];   // h_{t-1} / h_t, ping-pong
     __shared__ __attribute__((aligned(16))) float Bl[J][16 * EP_LD];      // Q-head base of the current step
     __shared__ float Wq[(A + 2) * EP_H];   // Q-head: action columns W1[u][H + a] at [a][u], power column at [A][u], w2 at [A+1][u]
+    __shared__ __attribute__((aligned(16))) float Wh[BQ_LDS ? EP_H * EP_LD : 4];   // BQ_LDS: W1[u][:H] at [u][:]
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int li = lane & 15, g = lane >> 4;
@@ -76,22 +96,29 @@ __global__ void __launch_bounds__(256) agent_episode_kernel(const macjd_agent_ep
 
     // ---- episode constants into registers / LDS -------------------------------------------------------------
     // weight fragments (B operands): rows gate * 64 + 16 wave + li of W_hh, row 16 wave + li of W1's h-columns
-    f32x4 Bh[3][EP_KQ], Bq[EP_KQ];
+    f32x4 Bh[3][EP_KQ], Bq[BQ_LDS ? 1 : EP_KQ];
 #pragma unroll
     for (int c = 0; c < 3; ++c)
 #pragma unroll
         for (int Q = 0; Q < EP_KQ; ++Q)
             Bh[c][Q] = *reinterpret_cast<const f32x4*>(io.w_hh + (int64_t)(c * EP_H + 16 * wave + li) * EP_H + 16 * Q + 4 * g);
+    if constexpr (BQ_LDS) {
+        for (int idx = threadIdx.x; idx < EP_H * (EP_H / 4); idx += NT) {
+            const int uu = idx / (EP_H / 4), c4 = idx - uu * (EP_H / 4);
+            *reinterpret_cast<f32x4*>(&Wh[uu * EP_LD + 4 * c4]) = *reinterpret_cast<const f32x4_u*>(io.W1 + (int64_t)uu * io.w1_ld + 4 * c4);
+        }
+    } else {
 #pragma unroll
-    for (int Q = 0; Q < EP_KQ; ++Q)
-        Bq[Q] = *reinterpret_cast<const f32x4_u*>(io.W1 + (int64_t)(16 * wave + li) * io.w1_ld + 16 * Q + 4 * g);
+        for (int Q = 0; Q < EP_KQ; ++Q)
+            Bq[Q] = *reinterpret_cast<const f32x4_u*>(io.W1 + (int64_t)(16 * wave + li) * io.w1_ld + 16 * Q + 4 * g);
+    }
     const int u = 16 * wave + li;          // this lane's hidden unit (gates) / Q-head unit (base) in the C layout
     float bhh[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) bhh[c] = io.b_hh[c * EP_H + u];
     const float b1u = io.b1[u];
     // C layout of a 16 x 16 tile: lane holds rows 4g + r (r = 0..3) of column li.  gi of (tile j, row 4g + r), unit u:
-    float giv[J][4][3], hreg[J][4];
+    float giv[J][4][3], hreg[H_REG ? J : 1][4];
 #pragma unroll
     for (int j = 0; j < J; ++j)
 #pragma unroll
@@ -100,22 +127,23 @@ __global__ void __launch_bounds__(256) agent_episode_kernel(const macjd_agent_ep
             const int64_t n = row_of(j, 4 * g + r, live);           // clamped: rows past the end are computed, never stored
 #pragma unroll
             for (int c = 0; c < 3; ++c) giv[j][r][c] = io.gi[n * io.gi_ld + c * EP_H + u];
-            hreg[j][r] = io.h0 ? io.h0[n * EP_H + u] : 0.0f;
-            Hl[0][j][(4 * g + r) * EP_LD + u] = hreg[j][r];
+            const float hinit = io.h0 ? io.h0[n * EP_H + u] : 0.0f;
+            if constexpr (H_REG) hreg[j][r] = hinit;
+            Hl[0][j][(4 * g + r) * EP_LD + u] = hinit;
         }
-    for (int idx = threadIdx.x; idx < (A + 2) * EP_H; idx += 256) {
+    for (int idx = threadIdx.x; idx < (A + 2) * EP_H; idx += NT) {
         const int a = idx / EP_H, uu = idx - a * EP_H;
         Wq[idx] = (a <= A) ? io.W1[(int64_t)uu * io.w1_ld + EP_H + a] : io.w2[uu];
     }
     const float b2 = io.b2[0];
-    // Q-head phase roles: wave = agent tile (waves >= J idle there; J > 4: a second pass), lane = (row qr, quarter qq)
+    // Q-head phase roles: wave = agent tile (waves >= J idle there; J > NW: a second pass), lane = (row qr, quarter qq)
     const int qr = lane & 15, qq = lane >> 4;
-    float pv[(J + 3) / 4][A];         // the row's actor output P[a] (static within the episode)
-    uint64_t avail_bits[(J + 3) / 4];
-    int n_avail[(J + 3) / 4];
+    float pv[(J + NW - 1) / NW][A];         // the row's actor output P[a] (static within the episode)
+    uint64_t avail_bits[(J + NW - 1) / NW];
+    int n_avail[(J + NW - 1) / NW];
 #pragma unroll
-    for (int pass = 0; pass < (J + 3) / 4; ++pass) {
-        const int j = wave + 4 * pass;
+    for (int pass = 0; pass < (J + NW - 1) / NW; ++pass) {
+        const int j = wave + NW * pass;
         bool live_q;
         const int64_t n = row_of(j < J ? j : 0, qr, live_q);
         const int64_t ec = n / NA, jc = n - ec * NA;      // (env, agent) of the row, for the availability mask
@@ -166,9 +194,12 @@ __global__ void __launch_bounds__(256) agent_episode_kernel(const macjd_agent_ep
                 const float rg = 1.0f / (1.0f + expf(-(giv[j][r][0] + hr)));
                 const float zg = 1.0f / (1.0f + expf(-(giv[j][r][1] + hz)));
                 const float nn = 1.0f - 2.0f / (expf(2.0f * (giv[j][r][2] + rg * hn)) + 1.0f);
-                const float hnew = (hreg[j][r] - nn) * zg + nn;
-                hreg[j][r] = hnew;
                 const int row = 4 * g + r;
+                float hold;
+                if constexpr (H_REG) hold = hreg[j][r];
+                else hold = Hl[cur][j][row * EP_LD + u];   // written by this very lane one step ago
+                const float hnew = (hold - nn) * zg + nn;
+                if constexpr (H_REG) hreg[j][r] = hnew;
                 Hl[nxt][j][row * EP_LD + u] = hnew;
                 bool live;
                 const int64_t n = row_of(j, row, live);
@@ -185,10 +216,13 @@ __global__ void __launch_bounds__(256) agent_episode_kernel(const macjd_agent_ep
                 f32x4 a[J];
 #pragma unroll
                 for (int j = 0; j < J; ++j) a[j] = *reinterpret_cast<const f32x4*>(&Hl[nxt][j][li * EP_LD + 16 * Q + 4 * g]);
+                f32x4 bq;
+                if constexpr (BQ_LDS) bq = *reinterpret_cast<const f32x4*>(&Wh[u * EP_LD + 16 * Q + 4 * g]);
+                else bq = Bq[Q];
 #pragma unroll
                 for (int jj = 0; jj < 4; ++jj)
 #pragma unroll
-                    for (int j = 0; j < J; ++j) ab[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j][jj], Bq[Q][jj], ab[j], 0, 0, 0);
+                    for (int j = 0; j < J; ++j) ab[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j][jj], bq[jj], ab[j], 0, 0, 0);
             }
 #pragma unroll
             for (int j = 0; j < J; ++j)
@@ -199,19 +233,22 @@ __global__ void __launch_bounds__(256) agent_episode_kernel(const macjd_agent_ep
         // ---- (4) all-action Q-head + (5) selection: wave = agent tile ----
         const float epsilon = io.greedy_only ? 0.0f : io.eps[t];
 #pragma unroll
-        for (int pass = 0; pass < (J + 3) / 4; ++pass) {
-            const int j = wave + 4 * pass;   // wave-uniform
+        for (int pass = 0; pass < (J + NW - 1) / NW; ++pass) {
+            const int j = wave + NW * pass;   // wave-uniform
             if (j < J) {
                 float q[A];
 #pragma unroll
                 for (int a = 0; a < A; ++a) q[a] = 0.0f;
-                const float* brow = &Bl[j][qr * EP_LD + 16 * qq];
-#pragma unroll
-                for (int k4 = 0; k4 < 4; ++k4) {
+                const float* brow = &Bl[j][qr * EP_LD + UQ * qq];
+                // (H = 128: groups of four units one after the other — unrolled, the 32 x (A + 2) LDS reads move in front
+                // of the arithmetic and the registers run out)
+                constexpr int K4_UNROLL = EP_H > 64 ? 1 : 4;
+#pragma unroll K4_UNROLL
+                for (int k4 = 0; k4 < UQ / 4; ++k4) {
                     const f32x4 b4 = *reinterpret_cast<const f32x4*>(brow + 4 * k4);
 #pragma unroll
                     for (int kk = 0; kk < 4; ++kk) {
-                        const int uu = 16 * qq + 4 * k4 + kk;
+                        const int uu = UQ * qq + 4 * k4 + kk;
                         const float wp = Wq[A * EP_H + uu], w2u = Wq[(A + 1) * EP_H + uu];
 #pragma unroll
                         for (int a = 0; a < A; ++a) {
@@ -276,7 +313,7 @@ __global__ void __launch_bounds__(256) agent_episode_kernel(const macjd_agent_ep
             for (int r = 0; r < 4; ++r) {
                 bool live;
                 const int64_t n = row_of(j, 4 * g + r, live);
-                if (live) io.h_final[n * EP_H + u] = hreg[j][r];
+                if (live) io.h_final[n * EP_H + u] = H_REG ? hreg[H_REG ? j : 0][r] : Hl[T & 1][j][(4 * g + r) * EP_LD + u];
             }
     }
 }
@@ -287,8 +324,12 @@ __global__ void __launch_bounds__(256) agent_episode_kernel(const macjd_agent_ep
 // the heads for all actions — wave w: head (w & 1) (0 = eval, 1 = target), action half (w >> 1), lane = (row, quarter of
 // the 64 units) as in agent_episode_kernel — and the first arg-max of the eval head (its two halves meet through LDS)
 // picks the target head's value.  (Round 2 used two of the four waves for the all-action phase: 156 us at A = 33.)
-template <int A>
+// H = 128 (template parameter EP_H): still four waves; wave w computes the TWO column tiles [32w, 32w+16), [32w+16, 32w+32)
+// of both bases over K = 128 (2 x 2 x 8 fragments = 128 VGPRs of the 512 a one-wave-per-SIMD workgroup may use), and a
+// lane of the all-action phase covers a quarter of 128 units.
+template <int EP_H, int A>
 struct DoubleQLds {
+    static constexpr int EP_LD = EP_H + 8;
     alignas(16) float Hs[2][16 * EP_LD];    // h rows of the eval / target unroll
     alignas(16) float Bs[2][16 * EP_LD];    // base of the eval / target head
     float Wq[2][(A + 2) * EP_H];
@@ -298,8 +339,11 @@ struct DoubleQLds {
 
 // (the body is a device function of (arguments, workgroup index, LDS) so that macjd_qheads_pair can run it beside the
 // taken-action Q-head in ONE launch)
-template <int A>
-__device__ __forceinline__ void qhead_double_q_body(const macjd_doubleq_io& io, const int blk, DoubleQLds<A>& L) {
+template <int EP_H, int A>
+__device__ __forceinline__ void qhead_double_q_body(const macjd_doubleq_io& io, const int blk, DoubleQLds<EP_H, A>& L) {
+    constexpr int EP_LD = EP_H + 8, EP_KQ = EP_H / 16;
+    constexpr int NTL = EP_H / 64;                                       // 16-column base tiles per wave
+    constexpr int UQ = EP_H / 4;                                         // all-action phase: units per lane
     constexpr int AH = (A + 1) / 2;                                      // actions per half (the second half may hold one less)
     auto& Hs = L.Hs;
     auto& Bs = L.Bs;
@@ -312,14 +356,19 @@ __device__ __forceinline__ void qhead_double_q_body(const macjd_doubleq_io& io, 
     const int64_t n0 = (int64_t)blk * 16;
     const bool same_h = (io.h_e == io.h_t) && (io.he_ld == io.ht_ld);
     // weight fragments + this lane's bias of both heads
-    f32x4 Be[EP_KQ], Bt[EP_KQ];
+    f32x4 Be[NTL][EP_KQ], Bt[NTL][EP_KQ];
+    const int u0 = 16 * NTL * wave + li;                                 // this lane's unit of tile 0 (tile i: u0 + 16 i)
+    float b1e[NTL], b1t[NTL];
 #pragma unroll
-    for (int Q = 0; Q < EP_KQ; ++Q) {
-        Be[Q] = *reinterpret_cast<const f32x4_u*>(io.W1_e + (int64_t)(16 * wave + li) * io.w1e_ld + 16 * Q + 4 * g);
-        Bt[Q] = *reinterpret_cast<const f32x4_u*>(io.W1_t + (int64_t)(16 * wave + li) * io.w1t_ld + 16 * Q + 4 * g);
+    for (int i = 0; i < NTL; ++i) {
+#pragma unroll
+        for (int Q = 0; Q < EP_KQ; ++Q) {
+            Be[i][Q] = *reinterpret_cast<const f32x4_u*>(io.W1_e + (int64_t)(u0 + 16 * i) * io.w1e_ld + 16 * Q + 4 * g);
+            Bt[i][Q] = *reinterpret_cast<const f32x4_u*>(io.W1_t + (int64_t)(u0 + 16 * i) * io.w1t_ld + 16 * Q + 4 * g);
+        }
+        b1e[i] = io.b1_e[u0 + 16 * i];
+        b1t[i] = io.b1_t[u0 + 16 * i];
     }
-    const int u = 16 * wave + li;
-    const float b1e = io.b1_e[u], b1t = io.b1_t[u];
     // all-action roles: head = wave & 1, actions [a0, a0 + na); lane = (row qr, quarter qq)
     const int head = wave & 1, a0 = (wave >> 1) * AH, na = (wave >> 1) ? A - AH : AH;
     const int qr = lane & 15, qq = lane >> 4;
@@ -352,7 +401,9 @@ __device__ __forceinline__ void qhead_double_q_body(const macjd_doubleq_io& io, 
     }
     __syncthreads();
     {
-        f32x4 ae = f32x4{0.f, 0.f, 0.f, 0.f}, at = f32x4{0.f, 0.f, 0.f, 0.f};
+        f32x4 ae[NTL], at[NTL];
+#pragma unroll
+        for (int i = 0; i < NTL; ++i) ae[i] = at[i] = f32x4{0.f, 0.f, 0.f, 0.f};
         const float* he = &Hs[0][li * EP_LD + 4 * g];
         const float* ht = &Hs[same_h ? 0 : 1][li * EP_LD + 4 * g];
 #pragma unroll
@@ -360,16 +411,20 @@ __device__ __forceinline__ void qhead_double_q_body(const macjd_doubleq_io& io, 
             const f32x4 xe = *reinterpret_cast<const f32x4*>(he + 16 * Q);
             const f32x4 xt = *reinterpret_cast<const f32x4*>(ht + 16 * Q);
 #pragma unroll
-            for (int jj = 0; jj < 4; ++jj) {
-                ae = __builtin_amdgcn_mfma_f32_16x16x4f32(xe[jj], Be[Q][jj], ae, 0, 0, 0);
-                at = __builtin_amdgcn_mfma_f32_16x16x4f32(xt[jj], Bt[Q][jj], at, 0, 0, 0);
-            }
+            for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+                for (int i = 0; i < NTL; ++i) {
+                    ae[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(xe[jj], Be[i][Q][jj], ae[i], 0, 0, 0);
+                    at[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(xt[jj], Bt[i][Q][jj], at[i], 0, 0, 0);
+                }
         }
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            Bs[0][(4 * g + r) * EP_LD + u] = ae[r] + b1e;
-            Bs[1][(4 * g + r) * EP_LD + u] = at[r] + b1t;
-        }
+        for (int i = 0; i < NTL; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                Bs[0][(4 * g + r) * EP_LD + u0 + 16 * i] = ae[i][r] + b1e[i];
+                Bs[1][(4 * g + r) * EP_LD + u0 + 16 * i] = at[i][r] + b1t[i];
+            }
     }
     __syncthreads();
     float q[AH];
@@ -377,17 +432,17 @@ __device__ __forceinline__ void qhead_double_q_body(const macjd_doubleq_io& io, 
         const float* wq = Wq[head];
 #pragma unroll
         for (int a = 0; a < AH; ++a) q[a] = 0.0f;
-        const float* brow = &Bs[head][qr * EP_LD + 16 * qq];
+        const float* brow = &Bs[head][qr * EP_LD + UQ * qq];
         // (33 actions: fully unrolled, the compiler hoists all 16 x 19 LDS reads of the lane's units in front of the
         // arithmetic — 256 VGPRs + spills, one workgroup per CU, 118 us for 38 784 rows; unit groups of four one after
         // the other keep ~80 values live)
-        constexpr int K4_UNROLL = A > 17 ? 1 : 4;
+        constexpr int K4_UNROLL = (A > 17 || EP_H > 64) ? 1 : 4;
 #pragma unroll K4_UNROLL
-        for (int k4 = 0; k4 < 4; ++k4) {
+        for (int k4 = 0; k4 < UQ / 4; ++k4) {
             const f32x4 b4 = *reinterpret_cast<const f32x4*>(brow + 4 * k4);
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk) {
-                const int uu = 16 * qq + 4 * k4 + kk;
+                const int uu = UQ * qq + 4 * k4 + kk;
                 const float wp = wq[A * EP_H + uu], w2u = wq[(A + 1) * EP_H + uu];
 #pragma unroll
                 for (int a = 0; a < AH; ++a) {
@@ -426,10 +481,10 @@ __device__ __forceinline__ void qhead_double_q_body(const macjd_doubleq_io& io, 
     }
 }
 
-template <int A>
+template <int EP_H, int A>
 __global__ void __launch_bounds__(256) qhead_double_q_kernel(const macjd_doubleq_io io) {
-    __shared__ DoubleQLds<A> L;
-    qhead_double_q_body<A>(io, blockIdx.x, L);
+    __shared__ DoubleQLds<EP_H, A> L;
+    qhead_double_q_body<EP_H, A>(io, blockIdx.x, L);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -537,11 +592,11 @@ template <int A>
 __global__ void __launch_bounds__(256) qheads_pair_kernel(const macjd_qtaken_io tio, const macjd_doubleq_io dio, const int n_taken) {
     __shared__ union PairLds {
         QtakenLds t;
-        DoubleQLds<A> d;
+        DoubleQLds<EP_H, A> d;
         __device__ PairLds() {}
     } L;
     if ((int)blockIdx.x < n_taken) qhead_taken_body(tio, blockIdx.x, L.t);
-    else qhead_double_q_body<A>(dio, (int)blockIdx.x - n_taken, L.d);
+    else qhead_double_q_body<EP_H, A>(dio, (int)blockIdx.x - n_taken, L.d);
 }
 
 }  // namespace macjd
@@ -575,7 +630,8 @@ extern "C" int macjd_qhead_taken(const macjd_qtaken_io* io, void* hip_stream) {
 }
 
 extern "C" int macjd_qhead_double_q_supported(int32_t H, int32_t A) {
-    return (H == macjd::EP_H) && (A == 5 || A == 9 || A == 17 || A == 33);
+    if (H == 128) return (A == 5 || A == 9 || A == 17) ? 1 : 0;
+    return (H == 64) && (A == 5 || A == 9 || A == 17 || A == 33);
 }
 
 static int doubleq_check(const macjd_doubleq_io* io) {
@@ -598,6 +654,7 @@ extern "C" int macjd_qheads_pair(const macjd_qtaken_io* taken, const macjd_doubl
     if (rc != MACJD_OK) return rc;
     rc = doubleq_check(dq);
     if (rc != MACJD_OK) return rc;
+    if (dq->H != EP_H) return set_err(MACJD_EUNSUPPORTED, "%s", "macjd_qheads_pair: unsupported H");
     if (taken->A != dq->A) return set_err(MACJD_EINVAL, "%s", "macjd_qheads_pair: the two heads differ in A");
     const int64_t nt = (taken->n_rows + 16 * QT_TILES - 1) / (16 * QT_TILES), nd = (dq->n_rows + 15) / 16;
     if (nt + nd == 0) return MACJD_OK;
@@ -620,18 +677,24 @@ extern "C" int macjd_qhead_double_q(const macjd_doubleq_io* io, void* hip_stream
     if (io->n_rows == 0) return MACJD_OK;
     const dim3 grid((unsigned)((io->n_rows + 15) / 16)), block(256);
     hipStream_t s = (hipStream_t)hip_stream;
-    if (io->A == 5) hipLaunchKernelGGL((qhead_double_q_kernel<5>), grid, block, 0, s, *io);
-    else if (io->A == 9) hipLaunchKernelGGL((qhead_double_q_kernel<9>), grid, block, 0, s, *io);
-    else if (io->A == 17) hipLaunchKernelGGL((qhead_double_q_kernel<17>), grid, block, 0, s, *io);
-    else hipLaunchKernelGGL((qhead_double_q_kernel<33>), grid, block, 0, s, *io);
+    if (io->H == 128) {
+        if (io->A == 5) hipLaunchKernelGGL((qhead_double_q_kernel<128, 5>), grid, block, 0, s, *io);
+        else if (io->A == 9) hipLaunchKernelGGL((qhead_double_q_kernel<128, 9>), grid, block, 0, s, *io);
+        else hipLaunchKernelGGL((qhead_double_q_kernel<128, 17>), grid, block, 0, s, *io);
+    } else if (io->A == 5) hipLaunchKernelGGL((qhead_double_q_kernel<64, 5>), grid, block, 0, s, *io);
+    else if (io->A == 9) hipLaunchKernelGGL((qhead_double_q_kernel<64, 9>), grid, block, 0, s, *io);
+    else if (io->A == 17) hipLaunchKernelGGL((qhead_double_q_kernel<64, 17>), grid, block, 0, s, *io);
+    else hipLaunchKernelGGL((qhead_double_q_kernel<64, 33>), grid, block, 0, s, *io);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_qhead_double_q: %s", hipGetErrorString(err));
     return MACJD_OK;
 }
 
 extern "C" int macjd_agent_episode_supported(int32_t J, int32_t H, int32_t A) {
-    // J in {2, 3, 6}: one row tile per agent; any other agent count: four tiles of consecutive rows (FLAT)
-    return (H == macjd::EP_H) && J >= 1 && (A == 5 || A == 9 || A == 17 || A == 33);
+    // H = 64: J in {2, 3, 6}: one row tile per agent; any other agent count: four tiles of consecutive rows (FLAT)
+    // H = 128: the per-agent-tile form only
+    if (H == 128) return ((J == 2 || J == 3) && (A == 5 || A == 9)) ? 1 : 0;
+    return (H == 64) && J >= 1 && (A == 5 || A == 9 || A == 17 || A == 33);
 }
 
 extern "C" int macjd_agent_episode(const macjd_agent_episode_io* io, void* hip_stream) {
@@ -648,13 +711,31 @@ extern "C" int macjd_agent_episode(const macjd_agent_episode_io* io, void* hip_s
         return set_err(MACJD_EINVAL, "%s", "macjd_agent_episode: avail_elem_size must be 4 or 8");
     if (((uintptr_t)io->w_hh) & 15) return set_err(MACJD_EINVAL, "%s", "macjd_agent_episode: w_hh must be 16-byte aligned");
     if (io->n_envs == 0) return MACJD_OK;
+    if (io->H == 128) {   // eight waves; rows of w_hh are 128 floats, so the 16-byte check above covers every fragment
+        const int64_t wgs128 = (io->n_envs + 15) / 16;
+        if (wgs128 > 0x7fffffff) return set_err(MACJD_EINVAL, "%s", "macjd_agent_episode: too many rows for one launch");
+        const dim3 grid128((unsigned)wgs128), block128(512);
+        hipStream_t s128 = (hipStream_t)hip_stream;
+#define MACJD_EP128(J_, A_) hipLaunchKernelGGL((agent_episode_kernel<128, J_, A_>), grid128, block128, 0, s128, *io)
+        if (io->J == 2) {
+            if (io->A == 5) MACJD_EP128(2, 5);
+            else MACJD_EP128(2, 9);
+        } else {
+            if (io->A == 5) MACJD_EP128(3, 5);
+            else MACJD_EP128(3, 9);
+        }
+#undef MACJD_EP128
+        const hipError_t err128 = hipGetLastError();
+        if (err128 != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_agent_episode: %s", hipGetErrorString(err128));
+        return MACJD_OK;
+    }
     const bool flat = !(io->J == 2 || io->J == 3 || io->J == 6) || io->A == 33;
     const int64_t wgs = flat ? (io->n_envs * io->J + 63) / 64 : (io->n_envs + 15) / 16;
     if (wgs > 0x7fffffff) return set_err(MACJD_EINVAL, "%s", "macjd_agent_episode: too many rows for one launch");
     const dim3 grid((unsigned)wgs), block(256);
     hipStream_t s = (hipStream_t)hip_stream;
-#define MACJD_EP(J_, A_) hipLaunchKernelGGL((agent_episode_kernel<J_, A_>), grid, block, 0, s, *io)
-#define MACJD_EP_FLAT(A_) hipLaunchKernelGGL((agent_episode_kernel<4, A_, true>), grid, block, 0, s, *io)
+#define MACJD_EP(J_, A_) hipLaunchKernelGGL((agent_episode_kernel<64, J_, A_>), grid, block, 0, s, *io)
+#define MACJD_EP_FLAT(A_) hipLaunchKernelGGL((agent_episode_kernel<64, 4, A_, true>), grid, block, 0, s, *io)
 #define MACJD_EP_J(J_)                     \
     do {                                   \
         if (io->A == 5) MACJD_EP(J_, 5);   \

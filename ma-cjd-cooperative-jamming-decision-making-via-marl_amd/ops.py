@@ -92,7 +92,11 @@ def qhead_double_q(base_eval, P_eval, head_eval, base_tgt, P_tgt, head_tgt, H: i
 
 
 def qhead_double_q_fused_supported(h, H: int, A: int) -> bool:
-    return h.is_cuda and bool(_native.load().macjd_qhead_double_q_supported(int(H), int(A)))
+    """The one-launch Double-DQN form exists at this size (include/macjd_nets.h) and is switched on: MACJD_QHEAD_DOUBLE_Q not
+    0, and at H = 128 — where it measured slower than the two-launch form inside the update — MACJD_QHEAD_DOUBLE_Q_H128=1."""
+    if not (h.is_cuda and options.on("QHEAD_DOUBLE_Q")) or (int(H) == 128 and options.get("QHEAD_DOUBLE_Q_H128") != "1"):
+        return False
+    return bool(_native.load().macjd_qhead_double_q_supported(int(H), int(A)))
 
 
 def qhead_double_q_from_h(h_eval, P_eval, head_eval, h_tgt, P_tgt, head_tgt, H: int, A: int, want_argmax: bool = False,

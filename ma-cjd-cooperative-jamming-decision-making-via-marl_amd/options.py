@@ -14,6 +14,10 @@ for normal operation.
     MACJD_LN_IN_SQNORM        1 | 0      LayerNorm-parameter gradients inside the optimiser's first launch
     MACJD_WGRAD_OUTER         1 | 0      Q-head ReLU-backward operand formed inside the weight-gradient launch
     MACJD_QHEAD_TAKEN         1 | 0      taken-action Q-head as one launch / input rows + GEMM + row-dot
+    MACJD_QHEAD_DOUBLE_Q      1 | 0      Double-DQN target values as one launch from the hidden states / library GEMM bases +
+                                         two Q-head launches
+    MACJD_QHEAD_DOUBLE_Q_H128 0 | 1      the same choice at rnn_hidden_dim 128, where the one-launch form measured slower inside
+                                         the update: two-launch form / one launch (needs MACJD_QHEAD_DOUBLE_Q != 0)
     MACJD_PAIRED_HEADS        1 | 0      pipelined update: both Q-head launches as one grid and both mixers as one grid on
                                          the chain's stream / target branch on the side stream beside the eval head
     MACJD_MIXER_TRAIN         1 | 0      paired update at 2 / 3 agents: both mixers, the loss gradient and the mixer backward
@@ -28,7 +32,7 @@ import os
 _DEFAULTS = {
     "UPDATE_STREAMS": "2", "UPDATES_PER_GRAPH": "1", "PIPELINED_GROUP": "1", "SHARED_BODY": "1",
     "LEARNER_STATIC_OBS": "1", "ACTOR_IN_SCAN": "1", "DEVICE_SAMPLER": "1", "LN_IN_SQNORM": "1", "WGRAD_OUTER": "1",
-    "QHEAD_TAKEN": "1", "PAIRED_HEADS": "1", "MIXER_TRAIN": "1", "GRAPHED_ALLREDUCE": "0",
+    "QHEAD_TAKEN": "1", "QHEAD_DOUBLE_Q": "1", "QHEAD_DOUBLE_Q_H128": "0", "PAIRED_HEADS": "1", "MIXER_TRAIN": "1", "GRAPHED_ALLREDUCE": "0",
     "CLOSED_LOOP_ROLLOUT": "0",
 }
 _values = None

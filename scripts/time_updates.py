@@ -2,7 +2,7 @@
 """Microseconds per learner update of the benchmark configuration WITHOUT a profiler attached (rocprofv3 inflates exactly
 the cross-queue hand-overs one is usually trying to judge): groups of 20 updates replayed as one graph, wall clock over
 n updates, several repetitions.  Environment switches (MACJD_*) select the variant:
-    [UPG=updates per graph] [JAMMERS= RADARS=] python scripts/time_updates.py [n_updates] [repetitions]"""
+    [UPG=updates per graph] [JAMMERS= RADARS= HIDDEN=] python scripts/time_updates.py [n_updates] [repetitions]"""
 import contextlib
 import io
 import os
@@ -28,7 +28,7 @@ dev = torch.device("cuda", 0)
 sc = Scenario.from_dict(ring_scenario_dict(J, R))
 E = int(os.environ.get("BATCH_ENVS", 4096))
 env = BatchedElectromagneticEnvironment(scenario=sc, batch_envs=E, device=dev, seed=1)
-args = bench_rollout.make_args(sc, 64, dev, batch_envs=E, mixer_dtype=os.environ.get("MIXER_DTYPE", "fp32"))
+args = bench_rollout.make_args(sc, int(os.environ.get("HIDDEN", 64)), dev, batch_envs=E, mixer_dtype=os.environ.get("MIXER_DTYPE", "fp32"))
 torch.manual_seed(42)
 with contextlib.redirect_stdout(io.StringIO()):
     mac = BasicMAC(args.obs_shape, args)
@@ -44,5 +44,5 @@ for _ in range(reps):
     learner.train_from_buffer_many(n)
     torch.cuda.synchronize()
     out.append((time.perf_counter() - t0) / n * 1e6)
-tag = " ".join(f"{k}={v}" for k, v in sorted(os.environ.items()) if k.startswith("MACJD_") or k in ("UPG", "JAMMERS", "RADARS"))
+tag = " ".join(f"{k}={v}" for k, v in sorted(os.environ.items()) if k.startswith("MACJD_") or k in ("UPG", "JAMMERS", "RADARS", "HIDDEN"))
 print(f"us/update [{tag or 'defaults'}]: " + " ".join(f"{x:.1f}" for x in out) + f"   min {min(out):.1f}")
