@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MACJD_ABI_VERSION 5
+#define MACJD_ABI_VERSION 6
 #define MACJD_PE_ROWS(R, J) (6 * (R) + 3 * (J) + (J) * (R))
 
 #define MACJD_OK          0
@@ -39,6 +39,7 @@ extern "C" {
 
 #define MACJD_MAX_RADARS  32
 #define MACJD_MAX_JAMMERS 32
+#define MACJD_MAX_PATTERN_LEVELS 6
 
 /* jr_flags bits */
 #define MACJD_JR_WEAK_DENOM 1u /* denominator was a Python float (d^2 <= 1e-9 branch of
@@ -189,6 +190,32 @@ typedef struct macjd_scan_desc {
     const double* gr_side;         /* [R] */
 } macjd_scan_desc;
 
+/*
+ * Stepped antenna pattern of a scanning radar (opt-in, sim-config `radar_scan.pattern`): between the main lobe and the
+ * far side lobe lie L = 1..MACJD_MAX_PATTERN_LEVELS levels, each `level_width` half beam widths wide, with their own
+ * one-way gains.  With off, lim = w + 2 half_beam, full as in macjd_scan_desc, an object's level at radar r is
+ *   0 (main)            if  full || off <= lim;  otherwise, with
+ *   lead = off - lim,  trail = 360.0 - off,  x = lead < trail ? lead : trail   (distance to the nearer edge of the covered
+ *   sector),  q = x * inv_width[r],   inv_width[r] = 1.0 / (level_width * half_beam[r])  (host, float64),
+ *   k = (q >= (double)L) ? L + 1 : 1 + (int)q.
+ * Plain IEEE float64 in this order, no division and no transcendental on the device: host and device agree bit for bit.
+ * Levels 1..L have the one-way gain rho_k = 10^(gain_db[k-1] / 10); their tables come from the host expressions of the
+ * side-lobe tables (gr_k = gr rho_k, GaPs_k = GaPs rho_k^2, snr_no_k / pd_no_k of GaPs_k); level L + 1 is the side lobe of
+ * macjd_scan_desc.  The target path of radar r takes the level-k (GaPs, snr_no, pd_no); a jammer acting on radar r takes
+ * gr_k by its own bearing.  Beam advance, RNG slots, Philox keying and everything else are unchanged; without pattern
+ * tables (L = 0) the model is macjd_scan_desc's.  Host pointers; the level tables are level-major: level k (1..L) of
+ * radar r at [(k - 1) * R + r].
+ */
+typedef struct macjd_scan_pattern_desc {
+    int32_t n_radars;              /* must equal the scenario's */
+    int32_t n_levels;              /* L, 1..MACJD_MAX_PATTERN_LEVELS */
+    const double* inv_width;       /* [R] finite, > 0 */
+    const double* GaPs_lvl;        /* [L*R] */
+    const double* snr_no_lvl;      /* [L*R] */
+    const double* pd_no_lvl;       /* [L*R] */
+    const double* gr_lvl;          /* [L*R] */
+} macjd_scan_pattern_desc;
+
 /* Per-call state of a scanning step / reset.  Device pointers. */
 typedef struct macjd_scan_io {
     double* theta_a;  int64_t a_se, a_sx;   /* [E,R] beam azimuth in degrees, read-modify-write */
@@ -231,6 +258,10 @@ int macjd_env_step(const macjd_scenario* s, const macjd_step_io* io, void* hip_s
 
 /* copies the scanning tables into the handle (host call, synchronous; not for the hot path) */
 int macjd_scenario_set_scan(macjd_scenario* s, const macjd_scan_desc* d);
+/* adds the stepped antenna pattern's level tables to a scanning handle (host call, synchronous; after
+   macjd_scenario_set_scan, which drops an earlier pattern).  macjd_env_step_scan and macjd_agent_env_episode_scan then
+   launch their pattern variants: no other call changes. */
+int macjd_scenario_set_scan_pattern(macjd_scenario* s, const macjd_scan_pattern_desc* d);
 /* macjd_env_step with scanning beams (see macjd_scan_desc); needs macjd_scenario_set_scan first.  Always the one-lane-
    per-env kernel; per-env scenario tables (pe_tables) are refused. */
 int macjd_env_step_scan(const macjd_scenario* s, const macjd_step_io* io, const macjd_scan_io* scan, void* hip_stream);

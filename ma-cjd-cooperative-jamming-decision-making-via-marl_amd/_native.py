@@ -14,7 +14,7 @@ LIB_NAME = "libmacjd_hip.so"
 # MACJD_LIB points at another build of the same sources (kernel A/B runs); the default is the in-tree library
 LIB_PATH = os.environ.get("MACJD_LIB") or os.path.join(_PKG_DIR, LIB_NAME)
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 STEP_ARITH_F64 = 1
 STEP_LANE_KERNEL = 2
 STEP_SLOT_KERNEL = 4
@@ -32,6 +32,7 @@ EXPORTS = [
     "macjd_qheads_pair", "macjd_mixer_fused_forward_pair", "macjd_mixer_fused_train",
     "macjd_scenario_set_scan", "macjd_env_step_scan", "macjd_env_reset_scan",
     "macjd_agent_env_episode_scan_supported", "macjd_agent_env_episode_scan",
+    "macjd_scenario_set_scan_pattern",
 ]
 
 
@@ -69,6 +70,15 @@ class ScanDesc(ctypes.Structure):
         ("full", ctypes.c_void_p), ("az0", ctypes.c_void_p), ("bear_tgt", ctypes.c_void_p), ("bear_jam", ctypes.c_void_p),
         ("GaPs_side", ctypes.c_void_p), ("snr_no", ctypes.c_void_p), ("snr_no_side", ctypes.c_void_p),
         ("pd_no_side", ctypes.c_void_p), ("gr_side", ctypes.c_void_p),
+    ]
+
+
+class ScanPatternDesc(ctypes.Structure):
+    """ctypes mirror of ``macjd_scan_pattern_desc`` (include/macjd.h)."""
+    _fields_ = [
+        ("n_radars", ctypes.c_int32), ("n_levels", ctypes.c_int32),
+        ("inv_width", ctypes.c_void_p), ("GaPs_lvl", ctypes.c_void_p), ("snr_no_lvl", ctypes.c_void_p),
+        ("pd_no_lvl", ctypes.c_void_p), ("gr_lvl", ctypes.c_void_p),
     ]
 
 
@@ -365,6 +375,8 @@ def load() -> ctypes.CDLL:
     lib.macjd_env_step.restype = ctypes.c_int
     lib.macjd_scenario_set_scan.restype = ctypes.c_int
     lib.macjd_scenario_set_scan.argtypes = [ctypes.c_void_p, ctypes.POINTER(ScanDesc)]
+    lib.macjd_scenario_set_scan_pattern.restype = ctypes.c_int
+    lib.macjd_scenario_set_scan_pattern.argtypes = [ctypes.c_void_p, ctypes.POINTER(ScanPatternDesc)]
     lib.macjd_env_step_scan.restype = ctypes.c_int
     lib.macjd_env_step_scan.argtypes = [ctypes.c_void_p, ctypes.POINTER(StepIO), ctypes.POINTER(ScanIO), ctypes.c_void_p]
     lib.macjd_env_reset_scan.restype = ctypes.c_int
@@ -484,6 +496,10 @@ class ScenarioHandle:
             sdesc, skeep = scenario.c_scan_desc()
             check(lib.macjd_scenario_set_scan(h, ctypes.byref(sdesc)), "macjd_scenario_set_scan")
             del skeep
+            if getattr(scenario, "scan_pattern_levels", 0):
+                pdesc, pkeep = scenario.c_scan_pattern_desc()
+                check(lib.macjd_scenario_set_scan_pattern(h, ctypes.byref(pdesc)), "macjd_scenario_set_scan_pattern")
+                del pkeep
 
     @property
     def ptr(self):

@@ -142,6 +142,34 @@ struct ScanStepIO : Base {
     int64_t sn_se, sn_sx;
 };
 
+// Argument block of a SCAN launch under a stepped antenna pattern (include/macjd.h, macjd_scan_pattern_desc): the same
+// members; the type itself is the compile-time switch (io_has_pattern), so env_step_kernel keeps its template parameter
+// list and every other instantiation its name, argument layout and code.
+template <class Base>
+struct ScanPatStepIO : ScanStepIO<Base> {
+    static constexpr bool scan_pattern = true;
+};
+template <class T, class = void>
+struct io_has_pattern : std::false_type {};
+template <class T>
+struct io_has_pattern<T, std::void_t<decltype(T::scan_pattern)>> : std::true_type {};
+// Per-lane pattern state of an env-step: the number of levels and the target's level at each radar, four bits per radar
+// in 64-bit words (word r >> 4; shifts only, so the per-lane index of the PD32 re-evaluation loop — compiled sizes,
+// R <= 16, one word — is no private-array index).  Empty without a pattern: those instantiations carry nothing.
+template <bool PAT, int NR>
+struct PatLanes {
+    static constexpr int L = 0;
+    __device__ __forceinline__ void set(int, int) {}
+    __device__ __forceinline__ int lv(int) const { return 0; }
+};
+template <int NR>
+struct PatLanes<true, NR> {
+    int L;
+    uint64_t w[(NR + 15) / 16];
+    __device__ __forceinline__ void set(int r, int k) { w[NR > 16 ? (r >> 4) : 0] |= (uint64_t)k << ((r & 15) * 4); }
+    __device__ __forceinline__ int lv(int r) const { return (int)((w[NR > 16 ? (r >> 4) : 0] >> ((r & 15) * 4)) & 15u); }
+};
+
 // PE = per-env scenario tables (io.pe_tables, SoA [row][env]): every table read becomes a load from this lane's
 // column of the SoA (row index static for the per-jammer / per-radar loops, data-dependent for the reads gathered by
 // the chosen target radar); the shared-table variant stages the gathered tables in LDS instead.
@@ -161,11 +189,15 @@ struct ScanStepIO : Base {
 // SCAN = scanning beams (include/macjd.h, macjd_scan_desc; IO = ScanStepIO<...>): the env's azimuths live in registers for
 // the step, the per-radar main-lobe test of the target selects the main or side-lobe (GaPs, pd_no), a jammer's test on
 // its chosen radar selects gr or gr_side; the rest of the step is unchanged.  Shared tables only, single-step launches.
+// PAT (IO = ScanPatStepIO<...>) = SCAN under a stepped antenna pattern: the two-way selects become a level 0..L + 1 per
+// object (beam_level) that indexes the [L + 2, R] level tables staged in LDS; the target's R levels of an env are packed
+// four bits each into 64-bit words (shifts by compile-time amounts, never a register array indexed per lane).
 template <int JT, int RT, bool PE, bool FAST, class IO, bool REG = false, bool PD32 = false, bool SCAN = false>
 __global__ void __launch_bounds__(256) env_step_kernel(const DevTables* __restrict__ tb, const IO io) {
     static_assert(!REG || (FAST && !PE && JT && RT), "REG: production variant on shared tables, compiled sizes");
     static_assert(!PD32 || REG, "PD32: float32 detection-probability filter of the regular production variant");
     static_assert(!SCAN || !PE, "SCAN: shared scenario tables only");
+    constexpr bool PAT = SCAN && io_has_pattern<IO>::value;
     constexpr int NJ = JT ? JT : MAXJ;
     constexpr int NR = RT ? RT : MAXR;
     const int J = JT ? JT : tb->J;
@@ -191,6 +223,19 @@ __global__ void __launch_bounds__(256) env_step_kernel(const DevTables* __restri
     __shared__ double s_half[SCAN ? NR : 1], s_h2[SCAN ? NR : 1], s_sweep[SCAN ? NR : 1], s_grs[SCAN ? NR : 1];
     __shared__ double s_bj[SCAN ? NJ * NR : 1];
     __shared__ uint8_t s_full[SCAN ? NR : 1];
+    // PAT: level tables [L + 2, R] (row 0 main, 1..L the pattern's levels, L + 1 side lobe), indexed by the per-lane level
+    __shared__ double s_lgr[PAT ? MAXLV * NR : 1], s_lGaPs[PAT ? MAXLV * NR : 1], s_lpdno[PAT ? MAXLV * NR : 1];
+    __shared__ double s_lsnrno[PAT ? MAXLV * NR : 1], s_invw[PAT ? NR : 1];
+    if constexpr (PAT) {
+        const int pat_L = tb->pat_levels;
+        for (int i = threadIdx.x; i < (pat_L + 2) * R; i += blockDim.x) {
+            s_lgr[i] = tb->lv_gr[i];
+            s_lGaPs[i] = tb->lv_GaPs[i];
+            s_lpdno[i] = tb->lv_pd_no[i];
+            s_lsnrno[i] = tb->lv_snr_no[i];
+        }
+        for (int i = threadIdx.x; i < R; i += blockDim.x) s_invw[i] = tb->pat_inv_width[i];
+    }
     if constexpr (SCAN) {
         for (int i = threadIdx.x; i < J * R; i += blockDim.x) s_bj[i] = tb->bj[i];
         for (int i = threadIdx.x; i < R; i += blockDim.x) {
@@ -329,6 +374,12 @@ __global__ void __launch_bounds__(256) env_step_kernel(const DevTables* __restri
         constexpr int NS = (SCAN && PRE) ? NR : 1;
         double az[NS];
         uint32_t s_bits = 0, in_t = 0;   // bit r: radar r was TRACKing / sees the target in its main lobe
+        PatLanes<PAT, NR> pl;
+        if constexpr (PAT) {
+            pl.L = tb->pat_levels;
+#pragma unroll
+            for (int i = 0; i < (NR + 15) / 16; ++i) pl.w[i] = 0;
+        }
         if constexpr (SCAN) {
 #pragma unroll
             for (int r = 0; r < NR; ++r) {
@@ -338,7 +389,13 @@ __global__ void __launch_bounds__(256) env_step_kernel(const DevTables* __restri
                 if (PRE) az[PRE ? r : 0] = a;
                 s_bits |= s ? (1u << r) : 0u;
                 const double lim = (s ? 0.0 : tb->sweep[r]) + tb->h2[r];
-                in_t |= in_main_lobe(tb->bt[r], a, tb->half[r], lim, tb->full[r] != 0) ? (1u << r) : 0u;
+                if constexpr (PAT) {
+                    const int k = beam_level(tb->bt[r], a, tb->half[r], lim, tb->full[r] != 0, tb->pat_inv_width[r], pl.L);
+                    pl.set(r, k);
+                    in_t |= (k == 0) ? (1u << r) : 0u;
+                } else {
+                    in_t |= in_main_lobe(tb->bt[r], a, tb->half[r], lim, tb->full[r] != 0) ? (1u << r) : 0u;
+                }
             }
         }
         // receive gain of jammer j's action on radar t: main or side lobe by the jammer's bearing (SCAN)
@@ -348,6 +405,8 @@ __global__ void __launch_bounds__(256) env_step_kernel(const DevTables* __restri
                 // turned into a dynamically indexed private array by hipcc (scratch)
                 const double a_t = at(io.theta_a, e, io.a_se, t, io.a_sx);
                 const double lim = (((s_bits >> t) & 1u) ? 0.0 : s_sweep[t]) + s_h2[t];
+                if constexpr (PAT)
+                    return s_lgr[beam_level(s_bj[j * R + t], a_t, s_half[t], lim, s_full[t] != 0, s_invw[t], pl.L) * R + t];
                 return in_main_lobe(s_bj[j * R + t], a_t, s_half[t], lim, s_full[t] != 0) ? s_gr[t] : s_grs[t];
             } else {
                 return 0.0;
@@ -355,11 +414,13 @@ __global__ void __launch_bounds__(256) env_step_kernel(const DevTables* __restri
         };
         // target-path tables of radar r: main or side lobe (SCAN)
         auto r_GaPs = [&](int r) -> double {
-            if constexpr (SCAN) return ((in_t >> r) & 1u) ? tb->GaPs[r] : tb->GaPs_side[r];
+            if constexpr (PAT) return s_lGaPs[pl.lv(r) * R + r];
+            else if constexpr (SCAN) return ((in_t >> r) & 1u) ? tb->GaPs[r] : tb->GaPs_side[r];
             else return t_GaPs(r);
         };
         auto r_pdno = [&](int r) -> double {
-            if constexpr (SCAN) return ((in_t >> r) & 1u) ? tb->pd_no[r] : tb->pd_no_side[r];
+            if constexpr (PAT) return s_lpdno[pl.lv(r) * R + r];
+            else if constexpr (SCAN) return ((in_t >> r) & 1u) ? tb->pd_no[r] : tb->pd_no_side[r];
             else return t_pdno(r);
         };
 
@@ -562,7 +623,8 @@ __global__ void __launch_bounds__(256) env_step_kernel(const DevTables* __restri
                     }
                     if (i < NR) {   // a radar: the exact SNR from the suppression sum (still in this lane's LDS column)
                         const double den_i = tb->D[i] * s_supp[SCAT ? i : 0][col] + tb->Pn[i];
-                        const double gaps_i = SCAN ? (((in_t >> i) & 1u) ? tb->GaPs[i] : tb->GaPs_side[i]) : tb->GaPs[i];
+                        const double gaps_i = PAT ? s_lGaPs[pl.lv(i) * R + i]
+                                                  : SCAN ? (((in_t >> i) & 1u) ? tb->GaPs[i] : tb->GaPs_side[i]) : tb->GaPs[i];
                         snr_i = div_by_refined(gaps_i, den_i, rcp_refined(den_i));
                     }
                     double p;
@@ -644,7 +706,11 @@ __global__ void __launch_bounds__(256) env_step_kernel(const DevTables* __restri
             if (!FAST && io.snr64) io.snr64[e * R + r] = snr_rep;
             if constexpr (SCAN) {   // beam advance (include/macjd.h, macjd_scan_desc)
                 const bool in = (in_t >> r) & 1u;
-                if (io.snr_no) at(io.snr_no, e, io.sn_se, r, io.sn_sx) = (float)(in ? tb->snr_no[r] : tb->snr_no_side[r]);
+                if constexpr (PAT) {
+                    if (io.snr_no) at(io.snr_no, e, io.sn_se, r, io.sn_sx) = (float)s_lsnrno[pl.lv(r) * R + r];
+                } else {
+                    if (io.snr_no) at(io.snr_no, e, io.sn_se, r, io.sn_sx) = (float)(in ? tb->snr_no[r] : tb->snr_no_side[r]);
+                }
                 const double a = PRE ? az[PRE ? r : 0] : at(io.theta_a, e, io.a_se, r, io.a_sx);
                 double x = a + tb->swm[r];
                 x = (x >= 360.0) ? x - 360.0 : x;
@@ -1255,6 +1321,35 @@ static int launch_step_scan(const macjd_scenario* s, const macjd_step_io* io, co
     }
     const bool reg = s->host.regular && s->host.scan_regular && macjd::env_options().regular;
     const bool pd32 = macjd::env_options().pd32;
+    if (s->host.pat_levels > 0) {
+        // stepped antenna pattern: the production variant (fast + REG + PD32) or the general all-float64 one, which
+        // serves every other switch combination (same integers; rewards within the PD32 bound of each other)
+        using PatFast = macjd::ScanPatStepIO<macjd::FastStepIO>;
+        using PatFull = macjd::ScanPatStepIO<macjd_step_io>;
+        PatFast pf{};
+        PatFull pw{};
+        static_cast<FastScan&>(pf) = f;
+        static_cast<FullScan&>(pw) = w;
+#define MACJD_LAUNCH_PAT(JT, RT)                                                                                           \
+    do {                                                                                                                   \
+        if (fast && reg && pd32)                                                                                           \
+            hipLaunchKernelGGL((macjd::env_step_kernel<JT, RT, false, true, PatFast, true, true, true>), gf, b, 0, stream, s->dev, pf); \
+        else                                                                                                               \
+            hipLaunchKernelGGL((macjd::env_step_kernel<JT, RT, false, false, PatFull, false, false, true>), g, b, 0, stream, s->dev, pw); \
+    } while (0)
+        if (J == 3 && R == 4) MACJD_LAUNCH_PAT(3, 4);
+        else if (J == 6 && R == 8) MACJD_LAUNCH_PAT(6, 8);
+        else if (J == 2 && R == 2) MACJD_LAUNCH_PAT(2, 2);
+        else if (J == 12 && R == 16 && fast && reg && pd32)
+            hipLaunchKernelGGL((macjd::env_step_kernel<12, 16, false, true, PatFast, true, true, true>), gf, b, 0, stream, s->dev, pf);
+        // generic sizes, and 12j/16r outside the production configuration: its compiled general form needs all 512
+        // registers and 8 more (12 B of scratch per lane); the generic-size kernel computes the same bits without any
+        else hipLaunchKernelGGL((macjd::env_step_kernel<0, 0, false, false, PatFull, false, false, true>), g, b, 0, stream, s->dev, pw);
+#undef MACJD_LAUNCH_PAT
+        hipError_t perr = hipGetLastError();
+        if (perr != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_env_step_scan launch: %s", hipGetErrorString(perr));
+        return MACJD_OK;
+    }
 #define MACJD_LAUNCH_SCAN(JT, RT)                                                                                          \
     do {                                                                                                                   \
         if (fast && reg && pd32)                                                                                           \
@@ -1310,10 +1405,51 @@ int macjd_scenario_set_scan(macjd_scenario* s, const macjd_scan_desc* d) {
              (t.gr_side[r] == 0.0 || (t.gr_side[r] >= 1e-30 && t.gr_side[r] <= 1e30));
     t.scan_regular = ok ? 1 : 0;
     t.scanning = 1;
+    t.pat_levels = 0;   // new scan tables: an earlier pattern's level 0 / L + 1 rows no longer match them
     const size_t off = offsetof(DevTables, scanning);
     hipError_t err = hipMemcpy(reinterpret_cast<char*>(s->dev) + off, reinterpret_cast<const char*>(&t) + off,
                                sizeof(DevTables) - off, hipMemcpyHostToDevice);
     if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_scenario_set_scan: %s", hipGetErrorString(err));
+    return MACJD_OK;
+}
+
+int macjd_scenario_set_scan_pattern(macjd_scenario* s, const macjd_scan_pattern_desc* d) {
+    const char* me = "macjd_scenario_set_scan_pattern";
+    if (!s || !d) return set_err(MACJD_EINVAL, "%s: NULL argument", me);
+    DevTables& t = s->host;
+    const int R = t.R, L = d->n_levels;
+    if (!t.scanning) return set_err(MACJD_EINVAL, "%s: the scenario has no scanning tables (macjd_scenario_set_scan comes first)", me);
+    if (d->n_radars != R) return set_err(MACJD_EINVAL, "%s: n_radars differs from the scenario's", me);
+    if (L < 1 || L > MACJD_MAX_PATTERN_LEVELS) return set_err(MACJD_EINVAL, "%s: n_levels outside 1..MACJD_MAX_PATTERN_LEVELS", me);
+    if (!d->inv_width || !d->GaPs_lvl || !d->snr_no_lvl || !d->pd_no_lvl || !d->gr_lvl)
+        return set_err(MACJD_EINVAL, "%s: NULL table pointer", me);
+    for (int r = 0; r < R; ++r)
+        if (!(d->inv_width[r] > 0.0 && d->inv_width[r] <= 1e3))   // 1 / (level_width half_beam) with the product >= 1e-3
+            return set_err(MACJD_EINVAL, "%s: inv_width must lie in (0, 1e3]", me);
+    // rows 0 and L + 1 from the handle's main / side-lobe tables, rows 1..L from the caller
+    bool ok = true;
+    for (int r = 0; r < R; ++r) {
+        t.pat_inv_width[r] = d->inv_width[r];
+        t.lv_GaPs[r] = t.GaPs[r]; t.lv_pd_no[r] = t.pd_no[r]; t.lv_snr_no[r] = t.snr_no[r]; t.lv_gr[r] = t.gr[r];
+        const int z = (L + 1) * R + r;
+        t.lv_GaPs[z] = t.GaPs_side[r]; t.lv_pd_no[z] = t.pd_no_side[r]; t.lv_snr_no[z] = t.snr_no_side[r]; t.lv_gr[z] = t.gr_side[r];
+        for (int k = 1; k <= L; ++k) {
+            const int i = k * R + r, c = (k - 1) * R + r;
+            t.lv_GaPs[i] = d->GaPs_lvl[c]; t.lv_pd_no[i] = d->pd_no_lvl[c]; t.lv_snr_no[i] = d->snr_no_lvl[c]; t.lv_gr[i] = d->gr_lvl[c];
+            // the short-division (REG) variant needs every level's values inside its range (see macjd_scenario_set_scan)
+            ok = ok && (t.lv_GaPs[i] >= 1e-30 && t.lv_GaPs[i] <= 1e30) && t.lv_gr[i] <= t.gr[r] &&
+                 (t.lv_gr[i] == 0.0 || (t.lv_gr[i] >= 1e-30 && t.lv_gr[i] <= 1e30));
+        }
+    }
+    t.scan_regular = (t.scan_regular && ok) ? 1 : 0;
+    t.pat_levels = L;
+    const size_t off = offsetof(DevTables, scanning);
+    hipError_t err = hipMemcpy(reinterpret_cast<char*>(s->dev) + off, reinterpret_cast<const char*>(&t) + off,
+                               sizeof(DevTables) - off, hipMemcpyHostToDevice);
+    if (err != hipSuccess) {
+        t.pat_levels = 0;
+        return set_err(MACJD_EDEVICE, "macjd_scenario_set_scan_pattern: %s", hipGetErrorString(err));
+    }
     return MACJD_OK;
 }
 

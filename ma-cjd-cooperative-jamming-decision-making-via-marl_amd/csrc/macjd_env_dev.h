@@ -13,6 +13,7 @@ namespace macjd {
 
 constexpr int MAXR = MACJD_MAX_RADARS;
 constexpr int MAXJ = MACJD_MAX_JAMMERS;
+constexpr int MAXLV = MACJD_MAX_PATTERN_LEVELS + 2;   // main, the pattern's levels, side lobe
 
 // Device-resident scenario tables (one per scenario handle).
 struct DevTables {
@@ -37,6 +38,12 @@ struct DevTables {
     double bj[MAXJ * MAXR];           // packed [j*R + r]
     double GaPs_side[MAXR], pd_no_side[MAXR], gr_side[MAXR], snr_no[MAXR], snr_no_side[MAXR];
     uint8_t full[MAXR];
+    // ---- stepped antenna pattern (macjd_scenario_set_scan_pattern; include/macjd.h, macjd_scan_pattern_desc), read by the
+    // pattern variants only.  Level tables [L + 2, R] packed [k * R + r]: level 0 = the main tables, 1..L the pattern's,
+    // L + 1 the side lobe's, so a kernel stages (L + 2) R consecutive values and indexes them by the per-lane level ----
+    int32_t pat_levels, pad3;         // L, 0 = no pattern
+    double pat_inv_width[MAXR];
+    double lv_GaPs[MAXLV * MAXR], lv_pd_no[MAXLV * MAXR], lv_snr_no[MAXLV * MAXR], lv_gr[MAXLV * MAXR];
 };
 constexpr uint8_t JR_RECORDABLE = 0x40, JR_LIVE = 0x80;
 
@@ -123,6 +130,23 @@ __device__ __forceinline__ bool in_main_lobe(double beta, double a, double h, do
     if (off < 0.0) off += 360.0;
     if (off >= 360.0) off -= 360.0;
     return full || off <= lim;
+}
+
+// Level of an object under a stepped antenna pattern (include/macjd.h, macjd_scan_pattern_desc): 0 = main lobe (the very
+// test of in_main_lobe), 1..L by the distance x to the nearer edge of the covered sector in units of 1 / inv_w, L + 1 beyond
+// the last level.  Plain IEEE float64 in the specified order, no division; the conversion acts on min(q, L) (q >= 0 outside
+// the main lobe, < 3.6e5 by the host's validation), so q >= L gives 1 + L and no lane converts an out-of-range value.
+__device__ __forceinline__ int beam_level(double beta, double a, double h, double lim, bool full, double inv_w, int L) {
+    double off = (beta - a) + h;
+    if (off < 0.0) off += 360.0;
+    if (off >= 360.0) off -= 360.0;
+    const double lead = off - lim, trail = 360.0 - off;
+    const double x = lead < trail ? lead : trail;
+    const double q = x * inv_w;
+    const double Ld = (double)L;
+    const double qc = (q >= Ld) ? Ld : ((q > 0.0) ? q : 0.0);
+    const int k = 1 + (int)qc;
+    return (full || off <= lim) ? 0 : k;
 }
 
 // Word w (0..3, possibly different per lane) of a block, as shifts on 64-bit pairs.  NOT b.v[w] and not a chain of

@@ -25,6 +25,7 @@ DEFAULT_SIM_CONFIG_PATH = "config/simulation_config.yaml"  # environment.py:11
 
 MAX_RADARS = 32   # MACJD_MAX_RADARS
 MAX_JAMMERS = 32  # MACJD_MAX_JAMMERS
+MAX_PATTERN_LEVELS = 6  # MACJD_MAX_PATTERN_LEVELS
 
 _REQUIRED_RADAR_PARAMS = [  # environment.py:136-140
     "pt", "gt", "gr", "wavelength", "rcs", "loss", "latm", "pn",
@@ -82,13 +83,14 @@ def bearing_degrees(frm, to):
 
 
 def parse_radar_scan(env_params: dict, source: str = "<dict>") -> Optional[Dict[str, float]]:
-    """``environment_params.radar_scan`` -> {'step_seconds', 'sidelobe_db'} or None (absent / null: static beams)."""
+    """``environment_params.radar_scan`` -> {'step_seconds', 'sidelobe_db'} or None (absent / null: static beams); with the
+    optional stepped antenna pattern also 'pattern': {'level_width': float, 'gain_db': [float] * L}."""
     rs = env_params.get("radar_scan")
     if rs is None:
         return None
     if not isinstance(rs, dict):
         raise ValueError(f"{source}: environment_params.radar_scan must be a mapping or null")
-    unknown = set(rs) - {"step_seconds", "sidelobe_db"}
+    unknown = set(rs) - {"step_seconds", "sidelobe_db", "pattern"}
     if unknown:
         raise ValueError(f"{source}: unknown radar_scan key(s) {sorted(unknown)}")
     out = {}
@@ -103,7 +105,30 @@ def parse_radar_scan(env_params: dict, source: str = "<dict>") -> Optional[Dict[
         raise ValueError(f"{source}: radar_scan.step_seconds must be > 0, got {out['step_seconds']}")
     if not out["sidelobe_db"] <= 0.0:
         raise ValueError(f"{source}: radar_scan.sidelobe_db must be <= 0, got {out['sidelobe_db']}")
+    if "pattern" in rs:
+        out["pattern"] = _parse_scan_pattern(rs["pattern"], source)
     return out
+
+
+def _parse_scan_pattern(pat, source: str) -> Dict[str, Any]:
+    """``radar_scan.pattern`` (include/macjd.h, macjd_scan_pattern_desc): exactly ``level_width`` (finite, > 0, in half beam
+    widths) and ``gain_db`` (1..MAX_PATTERN_LEVELS finite one-way gains <= 0)."""
+    def number(v):
+        return not isinstance(v, bool) and isinstance(v, (int, float)) and bool(np.isfinite(v))
+    if not isinstance(pat, dict):
+        raise ValueError(f"{source}: radar_scan.pattern must be a mapping")
+    if set(pat) != {"level_width", "gain_db"}:
+        raise ValueError(f"{source}: radar_scan.pattern must have exactly the keys 'level_width' and 'gain_db', "
+                         f"got {sorted(map(str, pat))}")
+    lw, gains = pat["level_width"], pat["gain_db"]
+    if not number(lw) or not lw > 0.0:
+        raise ValueError(f"{source}: radar_scan.pattern.level_width must be a finite number > 0, got {lw!r}")
+    if not isinstance(gains, (list, tuple)) or not 1 <= len(gains) <= MAX_PATTERN_LEVELS:
+        raise ValueError(f"{source}: radar_scan.pattern.gain_db must be a list of 1..{MAX_PATTERN_LEVELS} numbers, got {gains!r}")
+    for g in gains:
+        if not number(g) or not g <= 0.0:
+            raise ValueError(f"{source}: radar_scan.pattern.gain_db entries must be finite numbers <= 0, got {g!r}")
+    return {"level_width": float(lw), "gain_db": [float(g) for g in gains]}
 
 
 class _Desc(ctypes.Structure):
@@ -139,7 +164,7 @@ class Scenario:
     tables: Dict[str, np.ndarray] = field(default_factory=dict)
     pd_consts: tuple = (0.0, 0.0, 0.0)
     source: str = "<dict>"
-    radar_scan: Optional[Dict[str, float]] = None   # environment_params.radar_scan; None = static beams
+    radar_scan: Optional[Dict[str, Any]] = None     # environment_params.radar_scan; None = static beams
     scan_tables: Dict[str, np.ndarray] = field(default_factory=dict)
 
     @property
@@ -253,6 +278,10 @@ class Scenario:
                 ta = params["theta_a"]
                 if isinstance(ta, bool) or not isinstance(ta, (int, float)) or not np.isfinite(ta):
                     raise ValueError(f"Radar config {i}: theta_a must be a finite number when radar_scan is on, got {ta!r}")
+                if "pattern" in radar_scan and not radar_scan["pattern"]["level_width"] * (float(tm) / 2) >= 1e-3:
+                    # keeps q = x / (level_width half_beam) below 3.6e5 (x < 360): far inside the int32 conversion's range
+                    raise ValueError(f"Radar config {i}: radar_scan.pattern.level_width * theta_m / 2 must be >= 1e-3, "
+                                     f"got {radar_scan['pattern']['level_width']} * {tm} / 2")
             r = dict(params)
             r["threat_level"] = params.get("threat_level", 1.0)
             radars.append(r)
@@ -387,6 +416,50 @@ class Scenario:
             "bear_jam": np.ascontiguousarray(bj.reshape(-1)), "GaPs_side": GaPs_side, "snr_no_side": snr_no_side,
             "pd_no_side": pd_no_side, "gr_side": gr_side, "rho": np.float64(rho),
         }
+        pat = self.radar_scan.get("pattern")
+        if pat is not None:
+            # stepped antenna pattern (include/macjd.h, macjd_scan_pattern_desc): per level k = 1..L the side-lobe
+            # expressions above with rho_k in place of rho
+            L = len(pat["gain_db"])
+            inv_width = np.zeros(R); pat_rho = np.zeros(L)
+            pat_GaPs = np.zeros((L, R)); pat_gr = np.zeros((L, R)); pat_snr_no = np.zeros((L, R)); pat_pd_no = np.zeros((L, R))
+            for r in range(R):
+                inv_width[r] = 1.0 / (pat["level_width"] * half[r])
+            for k, g_db in enumerate(pat["gain_db"]):
+                rho_k = 10 ** (g_db / 10)
+                pat_rho[k] = rho_k
+                for r in range(R):
+                    pat_gr[k, r] = t["radar_gr"][r] * rho_k
+                    ga_ps = t["radar_GaPs"][r] * (rho_k * rho_k)
+                    pn_watts = t["radar_Pn"][r]
+                    s_no = ga_ps / pn_watts if pn_watts > 1e-18 else 0.0
+                    s_no = max(0.0, s_no)
+                    pat_GaPs[k, r] = ga_ps
+                    pat_snr_no[k, r] = s_no
+                    pat_pd_no[k, r] = detection_probability(s_no, self.pd_consts)
+            self.scan_tables.update({"pat_inv_width": inv_width, "pat_rho": pat_rho, "pat_GaPs": pat_GaPs, "pat_gr": pat_gr,
+                                     "pat_snr_no": pat_snr_no, "pat_pd_no": pat_pd_no})
+
+    @property
+    def scan_pattern_levels(self) -> int:
+        """L of the stepped antenna pattern (``radar_scan.pattern.gain_db``), 0 without one."""
+        return len(self.radar_scan["pattern"]["gain_db"]) if self.radar_scan and "pattern" in self.radar_scan else 0
+
+    def c_scan_pattern_desc(self):
+        """Returns (``_native.ScanPatternDesc`` instance, keepalive list) for a scenario with ``radar_scan.pattern``."""
+        from ._native import ScanPatternDesc
+        if not self.scan_pattern_levels:
+            raise ValueError("c_scan_pattern_desc: the scenario has no radar_scan.pattern")
+        st = self.scan_tables
+        d = ScanPatternDesc()
+        d.n_radars, d.n_levels = self.num_radars, self.scan_pattern_levels
+        keep = []
+        for name, key in (("inv_width", "pat_inv_width"), ("GaPs_lvl", "pat_GaPs"), ("snr_no_lvl", "pat_snr_no"),
+                          ("pd_no_lvl", "pat_pd_no"), ("gr_lvl", "pat_gr")):
+            a = np.ascontiguousarray(st[key], dtype=np.float64).reshape(-1)
+            keep.append(a)
+            setattr(d, name, a.ctypes.data)
+        return d, keep
 
     def c_scan_desc(self):
         """Returns (``_native.ScanDesc`` instance, keepalive list).  Pointers reference ``self.scan_tables`` arrays."""

@@ -521,6 +521,10 @@ class ElectromagneticEnvironment:
             snr32 = b._snr_no_step.t().cpu().numpy()[0]
             main = sc.tables["radar_snr_no"]
             snr_no = np.where(main.astype(np.float32) == snr32, main, sc.scan_tables["snr_no_side"]).astype(np.float64)
+            if sc.scan_pattern_levels:
+                # stepped pattern: the matching level's value (equal gains give equal values: any of them will do)
+                for lvl in sc.scan_tables["pat_snr_no"][::-1]:
+                    snr_no = np.where((lvl.astype(np.float32) == snr32) & (main.astype(np.float32) != snr32), lvl, snr_no)
             self._state = b.get_state()[0].cpu().numpy().copy()
         else:
             snr_no = sc.tables["radar_snr_no"].copy()

@@ -5,7 +5,7 @@
 
 Kernels are matched by name.  When `before.s` is from a tree without the SCAN template parameter (the last template
 argument of env_step_kernel), the instantiations of `after.s` with that argument false are matched to the kernel of the
-same name in `before.s` without it.  Each body is normalised (symbol names, basic-block / temporary label numbers) and hashed together with
+same name in `before.s` without it.  Each body is normalised (symbol names, basic-block / temporary / long-branch label numbers) and hashed together with
 its kernel descriptor (.amdhsa_kernel: registers, LDS, scratch); instruction count, VGPRs and scratch bytes are printed
 next to the hashes.  Exits non-zero when any existing kernel differs."""
 import hashlib
@@ -23,6 +23,7 @@ def kernels(path):
 def digest(body, desc):
     b = re.sub(r"\.?LBB\d+_|BB\d+_", "BB_", body)
     b = re.sub(r"\.Ltmp\d+", ".Ltmp", b)
+    b = re.sub(r"\.Lpost_getpc\d+", ".Lpost_getpc", b)   # long-branch labels: numbered per module, like the blocks
     b = re.sub(r"_Z\S+", "SYM", b)
     b = re.sub(r"[ \t]*;[^\n]*", "", b)   # assembler comments (their padding follows the label numbers)
     return hashlib.sha256((b + "\n--\n" + desc).encode()).hexdigest()[:16]

@@ -7,12 +7,21 @@ The scanning scenario is the same ring with 0.25 s steps, -30 dB side lobes and 
 
     python scripts/probe_scan_env.py [--iters 200] [--reps 5]
 
-Prints one JSON line per (size, E) with the median of `reps` replays of each and their ratio."""
+Prints one JSON line per (size, E) with the median of `reps` replays of each and their ratio.
+
+    python scripts/probe_scan_env.py --pattern [--out profiles/r09_scan_pattern_env_probe.jsonl]
+
+compares two-level scanning with the stepped antenna pattern (radar_scan.pattern) instead: the shipped
+config/scenario_3j4r_scan_pattern.yaml with and without its pattern block (same beams), 3j/4r at E = 4096 and 2^20, default
+kernel choice, one process per run, the two alternating three times; every run appends one JSON line to --out."""
 import argparse
+import copy
 import json
 import os
 import statistics
+import subprocess
 import sys
+import time
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
@@ -55,11 +64,53 @@ def timed(env, T, P, iters, reps):
     return statistics.median(ms)
 
 
+PATTERN_OUT = os.path.join(REPO, "profiles", "r09_scan_pattern_env_probe.jsonl")
+
+
+def pattern_run(tag, E, iters, reps, out):
+    """One (two-level | pattern, E) measurement in this process."""
+    import yaml
+    path = os.path.join(REPO, "ma-cjd-cooperative-jamming-decision-making-via-marl_amd", "config", "scenario_3j4r_scan_pattern.yaml")
+    d = yaml.safe_load(open(path))
+    if tag == "scan":
+        d = copy.deepcopy(d)
+        del d["environment_params"]["radar_scan"]["pattern"]
+    sc = Scenario.from_dict(d)
+    J, R = sc.num_jammers, sc.num_radars
+    rng = np.random.default_rng(0)
+    T = torch.from_numpy(rng.integers(0, 2 * R + 1, size=(J, E)).astype(np.int32)).cuda().t()   # agent-major
+    P = torch.from_numpy(rng.random((J, E), dtype=np.float32)).cuda().t()
+    env = BatchedElectromagneticEnvironment(scenario=sc, batch_envs=E, device="cuda", seed=1)
+    n = iters if E < (1 << 20) else max(20, iters // 10)
+    ms = timed(env, T, P, n, reps)
+    line = {"probe": "scan_pattern_env", "variant": tag, "levels": sc.scan_pattern_levels, "J": J, "R": R, "E": E, "iters": n,
+            "reps": reps, "ms_per_step_median": round(ms, 6), "device": torch.cuda.get_device_name(0),
+            "time": time.strftime("%Y-%m-%dT%H:%M:%S")}
+    env.close()
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "a") as f:
+        f.write(json.dumps(line) + "\n")
+    print(json.dumps(line), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--pattern", action="store_true", help="two-level scanning vs the stepped pattern, one process per run")
+    ap.add_argument("--one", nargs=2, metavar=("VARIANT", "E"), help="(internal) one run of --pattern in this process")
+    ap.add_argument("--alternations", type=int, default=3)
+    ap.add_argument("--out", default=PATTERN_OUT)
     a = ap.parse_args()
+    if a.one:
+        return pattern_run(a.one[0], int(a.one[1]), a.iters, a.reps, a.out)
+    if a.pattern:
+        for E in (4096, 1 << 20):
+            for _ in range(a.alternations):
+                for tag in ("scan", "pattern"):   # a failing run ends the sequence: nothing more is started on the device
+                    subprocess.run([sys.executable, os.path.abspath(__file__), "--one", tag, str(E), "--iters", str(a.iters),
+                                    "--reps", str(a.reps), "--out", a.out], check=True, timeout=300)
+        return
     for J, R in ((3, 4), (12, 16)):
         d0 = ring_scenario_dict(J, R)
         ds = dict(d0)

@@ -5,6 +5,10 @@
 
     python scripts/probe_scan_rollout.py                 # alternates step / closed three times, one process per run
     python scripts/probe_scan_rollout.py --mode closed   # one run in this process
+    python scripts/probe_scan_rollout.py --compare-pattern   # closed-loop launch: two-level scanning / stepped antenna
+                                                             # pattern (config/scenario_3j4r_scan_pattern.yaml without and
+                                                             # with its pattern block), alternating, one process per run;
+                                                             # lines go to profiles/r09_scan_pattern_rollout_probe.jsonl
 
 Every run appends one JSON line to profiles/r07_scan_rollout_probe.jsonl: ms per episode batch as the mean over
 ``--reps`` replays after ``--warmup`` replays, and the fastest / slowest single replay.  No profiler is attached."""
@@ -17,16 +21,24 @@ import time
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(REPO, "profiles", "r07_scan_rollout_probe.jsonl")
+PATTERN_OUT = os.path.join(REPO, "profiles", "r09_scan_pattern_rollout_probe.jsonl")
 
 
-def one_run(mode, E, reps, warmup, out):
+def one_run(mode, E, reps, warmup, out, scenario="shipped"):
     sys.path.insert(0, REPO)
     sys.path.insert(0, os.path.join(REPO, "tests"))
     import torch
     import macjd_amd  # noqa: F401
     from macjd_amd.scenario import Scenario
     from test_scan_gpu import PKG, _runner
-    sc = Scenario.from_yaml(os.path.join(PKG, "config", "scenario_3j4r_scan.yaml"))
+    if scenario == "shipped":
+        sc = Scenario.from_yaml(os.path.join(PKG, "config", "scenario_3j4r_scan.yaml"))
+    else:   # "pattern" / "two_level": the pattern scenario with / without its pattern block (same beams)
+        import yaml
+        d = yaml.safe_load(open(os.path.join(PKG, "config", "scenario_3j4r_scan_pattern.yaml")))
+        if scenario == "two_level":
+            del d["environment_params"]["radar_scan"]["pattern"]
+        sc = Scenario.from_dict(d)
     r, _, _ = _runner(sc, E)
     r.closed_loop_rollout = mode == "closed"
     assert r.closed_loop_available() and not r.fused_rollout_available()
@@ -41,7 +53,7 @@ def one_run(mode, E, reps, warmup, out):
         b.record()
     torch.cuda.synchronize()
     ms = [a.elapsed_time(b) for a, b in ev]
-    line = {"probe": "scan_rollout", "mode": mode, "E": E, "T": sc.episode_limit, "reps": reps, "warmup": warmup,
+    line = {"probe": "scan_rollout", "mode": mode, "scenario": scenario, "levels": sc.scan_pattern_levels, "E": E, "T": sc.episode_limit, "reps": reps, "warmup": warmup,
             "ms_per_batch_mean": sum(ms) / len(ms), "ms_per_batch_min": min(ms), "ms_per_batch_max": max(ms),
             "device": torch.cuda.get_device_name(0), "time": time.strftime("%Y-%m-%dT%H:%M:%S")}
     r.release_graphs()
@@ -58,10 +70,19 @@ def main():
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--out", default=OUT)
+    ap.add_argument("--out")
+    ap.add_argument("--scenario", choices=["shipped", "two_level", "pattern"], default="shipped")
+    ap.add_argument("--compare-pattern", action="store_true")
     a = ap.parse_args()
+    a.out = a.out or (PATTERN_OUT if a.compare_pattern or a.scenario != "shipped" else OUT)
     if a.mode:
-        return one_run(a.mode, a.envs, a.reps, a.warmup, a.out)
+        return one_run(a.mode, a.envs, a.reps, a.warmup, a.out, a.scenario)
+    if a.compare_pattern:
+        for _ in range(a.alternations):
+            for scenario in ("two_level", "pattern"):   # a failing run ends the sequence
+                subprocess.run([sys.executable, os.path.abspath(__file__), "--mode", "closed", "--scenario", scenario, "--envs",
+                                str(a.envs), "--reps", str(a.reps), "--warmup", str(a.warmup), "--out", a.out], check=True, timeout=300)
+        return
     for _ in range(a.alternations):
         for mode in ("step", "closed"):     # a failing run ends the sequence: nothing more is started on the device
             subprocess.run([sys.executable, os.path.abspath(__file__), "--mode", mode, "--envs", str(a.envs), "--reps", str(a.reps),
