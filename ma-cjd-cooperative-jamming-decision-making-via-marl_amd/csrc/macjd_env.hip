@@ -142,17 +142,6 @@ struct ScanStepIO : Base {
     int64_t sn_se, sn_sx;
 };
 
-// Argument block of a SCAN launch under a stepped antenna pattern (include/macjd.h, macjd_scan_pattern_desc): the same
-// members; the type itself is the compile-time switch (io_has_pattern), so env_step_kernel keeps its template parameter
-// list and every other instantiation its name, argument layout and code.
-template <class Base>
-struct ScanPatStepIO : ScanStepIO<Base> {
-    static constexpr bool scan_pattern = true;
-};
-template <class T, class = void>
-struct io_has_pattern : std::false_type {};
-template <class T>
-struct io_has_pattern<T, std::void_t<decltype(T::scan_pattern)>> : std::true_type {};
 // Per-lane pattern state of an env-step: the number of levels and the target's level at each radar, four bits per radar
 // in 64-bit words (word r >> 4; shifts only, so the per-lane index of the PD32 re-evaluation loop — compiled sizes,
 // R <= 16, one word — is no private-array index).  Empty without a pattern: those instantiations carry nothing.
@@ -189,15 +178,17 @@ struct PatLanes<true, NR> {
 // SCAN = scanning beams (include/macjd.h, macjd_scan_desc; IO = ScanStepIO<...>): the env's azimuths live in registers for
 // the step, the per-radar main-lobe test of the target selects the main or side-lobe (GaPs, pd_no), a jammer's test on
 // its chosen radar selects gr or gr_side; the rest of the step is unchanged.  Shared tables only, single-step launches.
-// PAT (IO = ScanPatStepIO<...>) = SCAN under a stepped antenna pattern: the two-way selects become a level 0..L + 1 per
-// object (beam_level) that indexes the [L + 2, R] level tables staged in LDS; the target's R levels of an env are packed
-// four bits each into 64-bit words (shifts by compile-time amounts, never a register array indexed per lane).
-template <int JT, int RT, bool PE, bool FAST, class IO, bool REG = false, bool PD32 = false, bool SCAN = false>
+// PAT = SCAN under a stepped antenna pattern (include/macjd.h, macjd_scan_pattern_desc; the same ScanStepIO<...> block):
+// the two-way selects become a level 0..L + 1 per object (beam_level) that indexes the [L + 2, R] level tables staged in
+// LDS; the target's R levels of an env are packed four bits each into 64-bit words (shifts by compile-time amounts, never
+// a register array indexed per lane).  (PAT was first switched by the type of the argument block, so that the kernel
+// kept its template parameter list; the parameter changes only the kernels' names, profiles/r10_env_isa_check.txt.)
+template <int JT, int RT, bool PE, bool FAST, class IO, bool REG = false, bool PD32 = false, bool SCAN = false, bool PAT = false>
 __global__ void __launch_bounds__(256) env_step_kernel(const DevTables* __restrict__ tb, const IO io) {
     static_assert(!REG || (FAST && !PE && JT && RT), "REG: production variant on shared tables, compiled sizes");
     static_assert(!PD32 || REG, "PD32: float32 detection-probability filter of the regular production variant");
     static_assert(!SCAN || !PE, "SCAN: shared scenario tables only");
-    constexpr bool PAT = SCAN && io_has_pattern<IO>::value;
+    static_assert(!PAT || SCAN, "PAT: stepped antenna pattern of the scanning beams");
     constexpr int NJ = JT ? JT : MAXJ;
     constexpr int NR = RT ? RT : MAXR;
     const int J = JT ? JT : tb->J;
@@ -1054,6 +1045,76 @@ __global__ void scenario_derive_kernel(DevTables* t) {
 using macjd::DevTables;
 using macjd::set_err;
 
+// ---- host side of the env_step_kernel launches: each rule once (templates: outside the extern "C" block) ----
+
+// Geometry of a lane-kernel launch (one lane per work item).  Small batches: one wave per workgroup spreads the envs
+// over more CUs (latency-bound regime); from 2^16 items: 256-lane workgroups, tables staged once per workgroup.
+// `blocks` gives every item a lane of its own (production variants: no grid-stride loop), `strided` is the capped grid
+// of the general variants' grid-stride loop.
+struct LaneGrid { int block; int64_t blocks; unsigned strided; };
+static LaneGrid lane_grid(int64_t items) {
+    const int block = (items >= (1 << 16)) ? 256 : 64;
+    const int64_t blocks = (items + block - 1) / block, cap = (block == 256) ? 256 * 8 : 256 * 16;
+    return {block, blocks, (unsigned)(blocks > cap ? cap : blocks)};
+}
+
+// Every byte offset of a strided per-env array ([n_envs] x items elements of `elem` bytes, + extra elements) below 2^32
+static bool span_ok(int64_t n_envs, int64_t se, int64_t sx, int items, int64_t elem, int64_t extra = 0) {
+    return se >= 0 && sx >= 0 && extra >= 0 && ((n_envs - 1) * se + (int64_t)(items - 1) * sx + extra + 1) * elem < (int64_t)1 << 32;
+}
+
+// Production configuration (FAST): Philox uniforms, float32 actions / power arithmetic, no float64 diagnostics, strides
+// that fit int32 and every byte offset of the launch below 2^32 (the production variants form them in 32 bits).  A SCAN
+// launch adds the spans of its own arrays.
+static bool production_io(const macjd_step_io* io, int J, int R, int64_t blocks, int32_t many_T, int64_t t_stride) {
+    const int64_t En = io->n_envs, E = En * (many_T > 0 ? many_T : 1);
+    const int64_t act_extra = many_T > 0 ? (int64_t)(many_T - 1) * t_stride : 0;
+    return !io->u && io->P32 && !(io->flags & MACJD_STEP_ARITH_F64) && !io->out64 && !io->pd64 && !io->snr64 && !io->prj64 &&
+           blocks <= 0x7fffffff && span_ok(En, io->T_se, io->T_sx, J, 4, act_extra) &&
+           span_ok(En, io->P_se, io->P_sx, J, 4, act_extra) && span_ok(En, io->k_se, io->k_sx, R, 1) &&
+           (E * 3 + 3) * 4 < ((int64_t)1 << 32) && t_stride <= INT32_MAX && (!io->pd || span_ok(En, io->pd_se, io->pd_sx, R, 4)) &&
+           (!io->snr_with || span_ok(En, io->sw_se, io->sw_sx, R, 4));
+}
+
+// The production variants' argument block from the caller's (per-env tables: launch_step adds them)
+static void fill_fast(macjd::FastStepIO& f, const macjd_step_io* io, int32_t many_T, int64_t t_stride) {
+    f.n_envs = io->n_envs; f.env_offset = io->env_offset; f.seed = io->seed;   // (n_envs: real envs, not work items)
+    f.T = io->T; f.P32 = io->P32; f.episode = io->episode; f.track = io->track; f.step = io->step;
+    f.reward = io->reward; f.r_dpj = io->r_dpj; f.terminated = io->terminated; f.pd = io->pd;
+    f.snr_with = io->snr_with; f.r_dpj_sum = io->r_dpj_sum;
+    f.T_se = (int32_t)io->T_se; f.T_sx = (int32_t)io->T_sx; f.P_se = (int32_t)io->P_se; f.P_sx = (int32_t)io->P_sx;
+    f.k_se = (int32_t)io->k_se; f.k_sx = (int32_t)io->k_sx; f.pd_se = (int32_t)io->pd_se; f.pd_sx = (int32_t)io->pd_sx;
+    f.sw_se = (int32_t)io->sw_se; f.sw_sx = (int32_t)io->sw_sx;
+    f.many_T = many_T; f.t_stride = (int32_t)t_stride;
+}
+
+template <int JT, int RT, bool PE, bool FAST, bool REG = false, bool PD32 = false, bool SCAN = false, bool PAT = false, class IO>
+static void launch_lanes(dim3 grid, dim3 block, hipStream_t stream, const macjd_scenario* s, const IO& io) {
+    hipLaunchKernelGGL((macjd::env_step_kernel<JT, RT, PE, FAST, IO, REG, PD32, SCAN, PAT>), grid, block, 0, stream, s->dev, io);
+}
+
+// The compiled (J, R) sizes of env_step_kernel; every other size runs the generic <0, 0> kernel.  fn(JT, RT) takes the
+// size as two std::integral_constants and picks the variant.
+template <int N>
+using CompiledDim = std::integral_constant<int, N>;
+template <class F>
+static int with_compiled_size(int J, int R, F&& fn) {
+    if (J == 3 && R == 4) return fn(CompiledDim<3>{}, CompiledDim<4>{});
+    if (J == 6 && R == 8) return fn(CompiledDim<6>{}, CompiledDim<8>{});
+    if (J == 12 && R == 16) return fn(CompiledDim<12>{}, CompiledDim<16>{});
+    if (J == 2 && R == 2) return fn(CompiledDim<2>{}, CompiledDim<2>{});
+    return fn(CompiledDim<0>{}, CompiledDim<0>{});
+}
+
+// Error check after a launch of entry point `who`
+static int launch_status(const char* who) {
+    const hipError_t err = hipGetLastError();
+    if (err == hipSuccess) return MACJD_OK;
+    char msg[256];
+    snprintf(msg, sizeof(msg), "%s launch: %s", who, hipGetErrorString(err));
+    return set_err(MACJD_EDEVICE, "%s", msg);
+}
+
 extern "C" {
 
 int macjd_abi_version(void) { return MACJD_ABI_VERSION; }
@@ -1067,6 +1128,10 @@ int macjd_device_count(void) {
     if (err != hipSuccess) return set_err(MACJD_EDEVICE, "hipGetDeviceCount: %s", hipGetErrorString(err));
     return n;
 }
+
+// REGULAR range of a table value (see macjd_scenario_create); a gain may also be zero
+static bool reg_mag(double v) { return v >= 1e-30 && v <= 1e30; }
+static bool reg_gain(double v) { return v == 0.0 || reg_mag(v); }
 
 int macjd_scenario_create(const macjd_scenario_desc* d, macjd_scenario** out) {
     if (!d || !out) return set_err(MACJD_EINVAL, "macjd_scenario_create: NULL argument");
@@ -1096,18 +1161,16 @@ int macjd_scenario_create(const macjd_scenario_desc* d, macjd_scenario** out) {
     // give quotients and residuals within 1e-220 .. 1e100), the float32 numerator cannot overflow, the noise power is
     // positive (SNR denominators >= Pn > 1e-18, SNRs >= +0), and the probability formula's argument stays above -700.
     {
-        auto mag = [](double v) { return v >= 1e-30 && v <= 1e30; };
         bool ok = t.pd_denB >= 1e-9 && t.pd_denB <= 1e30 && fabs(t.pd_A) <= 1e30 && fabs(t.pd_c1) <= 1e30 &&
                   (10.0 * t.pd_c1 - t.pd_A) / t.pd_denB >= -700.0;
         double gr_max = 0.0, pg_max = 0.0;
         for (int r = 0; r < R && ok; ++r) {
-            ok = mag(t.GaPs[r]) && t.Pn[r] > 1e-18 && t.Pn[r] <= 1e30 && (t.D[r] == 0.0 || mag(t.D[r])) &&
-                 (t.gr[r] == 0.0 || mag(t.gr[r]));
+            ok = reg_mag(t.GaPs[r]) && t.Pn[r] > 1e-18 && t.Pn[r] <= 1e30 && reg_gain(t.D[r]) && reg_gain(t.gr[r]);
             gr_max = t.gr[r] > gr_max ? t.gr[r] : gr_max;
         }
         for (int j = 0; j < J && ok; ++j) {
             const double range = t.pmax[j] - t.pmin[j], pm = fabs(t.pmin[j]) > fabs(t.pmax[j]) ? fabs(t.pmin[j]) : fabs(t.pmax[j]);
-            ok = pm <= 1e30 && (t.gj[j] == 0.0 || mag(t.gj[j])) && (range <= 1e-6 || mag(range));
+            ok = pm <= 1e30 && reg_gain(t.gj[j]) && (range <= 1e-6 || reg_mag(range));
             pg_max = pm * t.gj[j] > pg_max ? pm * t.gj[j] : pg_max;
         }
         for (int i = 0; i < J * R && ok; ++i) ok = !(t.denom[i] > 1e-18) || t.denom[i] <= 1e30;
@@ -1158,9 +1221,7 @@ int macjd_env_reset(const macjd_scenario* s, int64_t n_envs, uint8_t* track, int
     if (grid > 4096) grid = 4096;
     hipLaunchKernelGGL(macjd::env_reset_kernel, dim3((unsigned)grid), dim3(block), 0, (hipStream_t)hip_stream, n_envs,
                        s->host.R, track, k_se, k_sx, step, mask, episode);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_env_reset launch: %s", hipGetErrorString(err));
-    return MACJD_OK;
+    return launch_status("macjd_env_reset");
 }
 
 static int validate_io(const macjd_scenario* s, const macjd_step_io* io) {
@@ -1176,8 +1237,6 @@ static int validate_io(const macjd_scenario* s, const macjd_step_io* io) {
         return set_err(MACJD_EINVAL, "macjd_env_step: per-env tables need pe_flags and pe_stride >= n_envs (or pe_tile > 0)");
     return MACJD_OK;
 }
-
-static int launch_step_scan(const macjd_scenario* s, const macjd_step_io* io, const macjd_scan_io* scan, hipStream_t stream);
 
 static int launch_step(const macjd_scenario* s, const macjd_step_io* io, hipStream_t stream, int32_t many_T = 0,
                        int64_t t_stride = 0) {
@@ -1201,175 +1260,91 @@ static int launch_step(const macjd_scenario* s, const macjd_step_io* io, hipStre
         else if (J == 12) MACJD_SLOTS(12, 16, 4, 8);
         else MACJD_SLOTS(2, 2, 2, 2);
 #undef MACJD_SLOTS
-    } else {
-        // generic sizes (and the A/B hook): one lane per env
-        // small batches: one wave per workgroup spreads the envs over more CUs (latency-bound regime);
-        // large batches: 256-lane workgroups, grid-stride, tables staged once per workgroup.
-        const int block = (E >= (1 << 16)) ? 256 : 64;
-        int64_t grid = (E + block - 1) / block;
-        // production variants: one env per lane, no grid-stride loop; many-step launches: grid = (envs / block, steps)
-        if (many_T > 65535) return set_err(MACJD_EINVAL, "%s", "macjd_env_step_many: at most 65535 steps per launch");
-        const dim3 gf((unsigned)(many_T > 0 ? (io->n_envs + block - 1) / block : grid), (unsigned)(many_T > 0 ? many_T : 1)), b(block);
-        const int64_t cap = (block == 256) ? 256 * 8 : 256 * 16;
-        if (grid > cap) grid = cap;
-        const dim3 g((unsigned)grid);
-        // production configuration (Philox uniforms, float32 actions / power arithmetic, no float64 diagnostics,
-        // strides that fit int32)
-        // ... and every byte offset of the launch below 2^32 (the production variant forms them in 32 bits)
-        const int64_t En = io->n_envs;
-        auto span_ok = [&](int64_t se, int64_t sx, int items, int64_t elem, int64_t extra = 0) {
-            return se >= 0 && sx >= 0 && extra >= 0 &&
-                   ((En - 1) * se + (int64_t)(items - 1) * sx + extra + 1) * elem < (int64_t)1 << 32;
-        };
-        const int64_t act_extra = many_T > 0 ? (int64_t)(many_T - 1) * t_stride : 0;
-        const bool fast = !io->u && io->P32 && !(io->flags & MACJD_STEP_ARITH_F64) && !io->out64 && !io->pd64 &&
-                          !io->snr64 && !io->prj64 && (E + block - 1) / block <= 0x7fffffff &&
-                          span_ok(io->T_se, io->T_sx, J, 4, act_extra) && span_ok(io->P_se, io->P_sx, J, 4, act_extra) &&
-                          span_ok(io->k_se, io->k_sx, R, 1) && (E * 3 + 3) * 4 < ((int64_t)1 << 32) && t_stride <= INT32_MAX &&
-                          (!io->pd || span_ok(io->pd_se, io->pd_sx, R, 4)) &&
-                          (!io->snr_with || span_ok(io->sw_se, io->sw_sx, R, 4));
-        macjd::FastStepIO f{};
-        if (fast) {
-            f.n_envs = io->n_envs; f.env_offset = io->env_offset; f.seed = io->seed;   // (n_envs: real envs, not work items)
-            f.T = io->T; f.P32 = io->P32; f.episode = io->episode; f.track = io->track; f.step = io->step;
-            f.reward = io->reward; f.r_dpj = io->r_dpj; f.terminated = io->terminated; f.pd = io->pd;
-            f.snr_with = io->snr_with; f.r_dpj_sum = io->r_dpj_sum; f.pe_tables = io->pe_tables;
-            f.pe_flags = io->pe_flags; f.pe_stride = io->pe_stride; f.pe_tile = io->pe_tile;
-            f.T_se = (int32_t)io->T_se; f.T_sx = (int32_t)io->T_sx; f.P_se = (int32_t)io->P_se; f.P_sx = (int32_t)io->P_sx;
-            f.k_se = (int32_t)io->k_se; f.k_sx = (int32_t)io->k_sx; f.pd_se = (int32_t)io->pd_se; f.pd_sx = (int32_t)io->pd_sx;
-            f.sw_se = (int32_t)io->sw_se; f.sw_sx = (int32_t)io->sw_sx;
-            f.many_T = many_T; f.t_stride = (int32_t)t_stride;
-        } else if (many_T > 0) {
-            return set_err(MACJD_EUNSUPPORTED, "%s", "macjd_env_step_many: production configuration only (Philox uniforms, "
-                           "float32 actions, no float64 diagnostics, offsets below 2^32 bytes)");
-        }
-        const bool no_reg = !macjd::env_options().regular;   // MACJD_ENV_REGULAR=0: keep IEEE divisions + all guards
-        const bool pd32 = macjd::env_options().pd32;          // MACJD_ENV_PD32=0: all-float64 detection probabilities
-#define MACJD_LAUNCH(JT, RT)                                                                                          \
-    do {                                                                                                              \
-        if (per_env && fast)                                                                                          \
-            hipLaunchKernelGGL((macjd::env_step_kernel<JT, RT, true, true, macjd::FastStepIO>), gf, b, 0, stream, s->dev, f);      \
-        else if (per_env)                                                                                             \
-            hipLaunchKernelGGL((macjd::env_step_kernel<JT, RT, true, false, macjd_step_io>), g, b, 0, stream, s->dev, *io);        \
-        else if (fast && s->host.regular && !no_reg && pd32)                                                          \
-            hipLaunchKernelGGL((macjd::env_step_kernel<JT, RT, false, true, macjd::FastStepIO, true, true>), gf, b, 0, stream, s->dev, f); \
-        else if (fast && s->host.regular && !no_reg)                                                                  \
-            hipLaunchKernelGGL((macjd::env_step_kernel<JT, RT, false, true, macjd::FastStepIO, true>), gf, b, 0, stream, s->dev, f); \
-        else if (fast)                                                                                                \
-            hipLaunchKernelGGL((macjd::env_step_kernel<JT, RT, false, true, macjd::FastStepIO>), gf, b, 0, stream, s->dev, f);     \
-        else                                                                                                          \
-            hipLaunchKernelGGL((macjd::env_step_kernel<JT, RT, false, false, macjd_step_io>), g, b, 0, stream, s->dev, *io);       \
-    } while (0)
-        if (J == 3 && R == 4) MACJD_LAUNCH(3, 4);
-        else if (J == 6 && R == 8) MACJD_LAUNCH(6, 8);
-        else if (J == 12 && R == 16) MACJD_LAUNCH(12, 16);
-        else if (J == 2 && R == 2) MACJD_LAUNCH(2, 2);
-        else if (many_T > 0) {
-            return set_err(MACJD_EUNSUPPORTED, "%s", "macjd_env_step_many: scenario size without a compiled production variant");
-        } else {   // generic sizes: one (non-FAST) variant per table mode
-            if (per_env) hipLaunchKernelGGL((macjd::env_step_kernel<0, 0, true, false, macjd_step_io>), g, b, 0, stream, s->dev, *io);
-            else hipLaunchKernelGGL((macjd::env_step_kernel<0, 0, false, false, macjd_step_io>), g, b, 0, stream, s->dev, *io);
-        }
-#undef MACJD_LAUNCH
+        return launch_status("macjd_env_step");
     }
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_env_step launch: %s", hipGetErrorString(err));
-    return MACJD_OK;
+    // generic sizes (and the A/B hook): one lane per env
+    if (many_T > 65535) return set_err(MACJD_EINVAL, "%s", "macjd_env_step_many: at most 65535 steps per launch");
+    const LaneGrid lg = lane_grid(E);
+    // many-step launches: grid = (envs / block, steps)
+    const dim3 gf((unsigned)(many_T > 0 ? (io->n_envs + lg.block - 1) / lg.block : lg.blocks), (unsigned)(many_T > 0 ? many_T : 1));
+    const dim3 g(lg.strided), b(lg.block);
+    const bool fast = production_io(io, J, R, lg.blocks, many_T, t_stride);
+    macjd::FastStepIO f{};
+    if (fast) {
+        fill_fast(f, io, many_T, t_stride);
+        f.pe_tables = io->pe_tables; f.pe_flags = io->pe_flags; f.pe_stride = io->pe_stride; f.pe_tile = io->pe_tile;
+    } else if (many_T > 0) {
+        return set_err(MACJD_EUNSUPPORTED, "%s", "macjd_env_step_many: production configuration only (Philox uniforms, "
+                       "float32 actions, no float64 diagnostics, offsets below 2^32 bytes)");
+    }
+    const bool reg = s->host.regular && macjd::env_options().regular;   // MACJD_ENV_REGULAR=0: keep IEEE divisions + all guards
+    const bool pd32 = macjd::env_options().pd32;                         // MACJD_ENV_PD32=0: all-float64 detection probabilities
+    // launch_lanes<JT, RT, PE, FAST, REG, PD32> (SCAN = PAT = false)
+    const int rc = with_compiled_size(J, R, [&](auto jt, auto rt) -> int {
+        constexpr int JT = decltype(jt)::value, RT = decltype(rt)::value;
+        if constexpr (JT == 0) {   // generic sizes: one (non-FAST) variant per table mode
+            if (many_T > 0)
+                return set_err(MACJD_EUNSUPPORTED, "%s", "macjd_env_step_many: scenario size without a compiled production variant");
+            if (per_env) launch_lanes<0, 0, true, false>(g, b, stream, s, *io);
+            else launch_lanes<0, 0, false, false>(g, b, stream, s, *io);
+        } else if (per_env && fast) launch_lanes<JT, RT, true, true>(gf, b, stream, s, f);
+        else if (per_env) launch_lanes<JT, RT, true, false>(g, b, stream, s, *io);
+        else if (fast && reg && pd32) launch_lanes<JT, RT, false, true, true, true>(gf, b, stream, s, f);
+        else if (fast && reg) launch_lanes<JT, RT, false, true, true>(gf, b, stream, s, f);
+        else if (fast) launch_lanes<JT, RT, false, true>(gf, b, stream, s, f);
+        else launch_lanes<JT, RT, false, false>(g, b, stream, s, *io);
+        return MACJD_OK;
+    });
+    return rc != MACJD_OK ? rc : launch_status("macjd_env_step");
 }
 
 // SCAN launches: always the lane kernel, shared tables, single step (include/macjd.h, macjd_env_step_scan)
 static int launch_step_scan(const macjd_scenario* s, const macjd_step_io* io, const macjd_scan_io* sc, hipStream_t stream) {
     const int64_t E = io->n_envs;
     const int J = s->host.J, R = s->host.R;
-    const int block = (E >= (1 << 16)) ? 256 : 64;
-    int64_t grid = (E + block - 1) / block;
-    const dim3 gf((unsigned)grid), b(block);
-    const int64_t cap = (block == 256) ? 256 * 8 : 256 * 16;
-    if (grid > cap) grid = cap;
-    const dim3 g((unsigned)grid);
-    auto span_ok = [&](int64_t se, int64_t sx, int items, int64_t elem, int64_t extra = 0) {
-        return se >= 0 && sx >= 0 && extra >= 0 && ((E - 1) * se + (int64_t)(items - 1) * sx + extra + 1) * elem < (int64_t)1 << 32;
-    };
+    const LaneGrid lg = lane_grid(E);
+    const dim3 gf((unsigned)lg.blocks), g(lg.strided), b(lg.block);
     const bool st_ok = !sc->state || (sc->st_col0 >= 0 && sc->st_col_step >= 0 &&
-                                      span_ok(sc->st_se, 1, 1, 4, (int64_t)sc->st_col0 + (int64_t)(R - 1) * sc->st_col_step));
-    const bool fast = !io->u && io->P32 && !(io->flags & MACJD_STEP_ARITH_F64) && !io->out64 && !io->pd64 && !io->snr64 &&
-                      !io->prj64 && grid <= 0x7fffffff && span_ok(io->T_se, io->T_sx, J, 4) && span_ok(io->P_se, io->P_sx, J, 4) &&
-                      span_ok(io->k_se, io->k_sx, R, 1) && (E * 3 + 3) * 4 < ((int64_t)1 << 32) &&
-                      (!io->pd || span_ok(io->pd_se, io->pd_sx, R, 4)) && (!io->snr_with || span_ok(io->sw_se, io->sw_sx, R, 4)) &&
-                      span_ok(sc->a_se, sc->a_sx, R, 8) && st_ok && (!sc->snr_no || span_ok(sc->sn_se, sc->sn_sx, R, 4));
+                                      span_ok(E, sc->st_se, 1, 1, 4, (int64_t)sc->st_col0 + (int64_t)(R - 1) * sc->st_col_step));
+    const bool fast = production_io(io, J, R, lg.blocks, 0, 0) && span_ok(E, sc->a_se, sc->a_sx, R, 8) && st_ok &&
+                      (!sc->snr_no || span_ok(E, sc->sn_se, sc->sn_sx, R, 4));
     auto fill_scan = [&](auto& x) {
         x.theta_a = sc->theta_a; x.a_se = sc->a_se; x.a_sx = sc->a_sx;
         x.state = sc->state; x.st_se = sc->st_se; x.st_col0 = sc->st_col0; x.st_col_step = sc->st_col_step;
         x.snr_no = sc->snr_no; x.sn_se = sc->sn_se; x.sn_sx = sc->sn_sx;
     };
-    using FastScan = macjd::ScanStepIO<macjd::FastStepIO>;
-    using FullScan = macjd::ScanStepIO<macjd_step_io>;
-    FastScan f{};
-    FullScan w{};
+    macjd::ScanStepIO<macjd::FastStepIO> f{};
+    macjd::ScanStepIO<macjd_step_io> w{};
     static_cast<macjd_step_io&>(w) = *io;
     fill_scan(w);
     if (fast) {
-        f.n_envs = io->n_envs; f.env_offset = io->env_offset; f.seed = io->seed;
-        f.T = io->T; f.P32 = io->P32; f.episode = io->episode; f.track = io->track; f.step = io->step;
-        f.reward = io->reward; f.r_dpj = io->r_dpj; f.terminated = io->terminated; f.pd = io->pd;
-        f.snr_with = io->snr_with; f.r_dpj_sum = io->r_dpj_sum;
-        f.T_se = (int32_t)io->T_se; f.T_sx = (int32_t)io->T_sx; f.P_se = (int32_t)io->P_se; f.P_sx = (int32_t)io->P_sx;
-        f.k_se = (int32_t)io->k_se; f.k_sx = (int32_t)io->k_sx; f.pd_se = (int32_t)io->pd_se; f.pd_sx = (int32_t)io->pd_sx;
-        f.sw_se = (int32_t)io->sw_se; f.sw_sx = (int32_t)io->sw_sx;
-        f.many_T = 0; f.t_stride = 0;
+        fill_fast(f, io, 0, 0);
         fill_scan(f);
     }
     const bool reg = s->host.regular && s->host.scan_regular && macjd::env_options().regular;
     const bool pd32 = macjd::env_options().pd32;
-    if (s->host.pat_levels > 0) {
-        // stepped antenna pattern: the production variant (fast + REG + PD32) or the general all-float64 one, which
-        // serves every other switch combination (same integers; rewards within the PD32 bound of each other)
-        using PatFast = macjd::ScanPatStepIO<macjd::FastStepIO>;
-        using PatFull = macjd::ScanPatStepIO<macjd_step_io>;
-        PatFast pf{};
-        PatFull pw{};
-        static_cast<FastScan&>(pf) = f;
-        static_cast<FullScan&>(pw) = w;
-#define MACJD_LAUNCH_PAT(JT, RT)                                                                                           \
-    do {                                                                                                                   \
-        if (fast && reg && pd32)                                                                                           \
-            hipLaunchKernelGGL((macjd::env_step_kernel<JT, RT, false, true, PatFast, true, true, true>), gf, b, 0, stream, s->dev, pf); \
-        else                                                                                                               \
-            hipLaunchKernelGGL((macjd::env_step_kernel<JT, RT, false, false, PatFull, false, false, true>), g, b, 0, stream, s->dev, pw); \
-    } while (0)
-        if (J == 3 && R == 4) MACJD_LAUNCH_PAT(3, 4);
-        else if (J == 6 && R == 8) MACJD_LAUNCH_PAT(6, 8);
-        else if (J == 2 && R == 2) MACJD_LAUNCH_PAT(2, 2);
-        else if (J == 12 && R == 16 && fast && reg && pd32)
-            hipLaunchKernelGGL((macjd::env_step_kernel<12, 16, false, true, PatFast, true, true, true>), gf, b, 0, stream, s->dev, pf);
-        // generic sizes, and 12j/16r outside the production configuration: its compiled general form needs all 512
-        // registers and 8 more (12 B of scratch per lane); the generic-size kernel computes the same bits without any
-        else hipLaunchKernelGGL((macjd::env_step_kernel<0, 0, false, false, PatFull, false, false, true>), g, b, 0, stream, s->dev, pw);
-#undef MACJD_LAUNCH_PAT
-        hipError_t perr = hipGetLastError();
-        if (perr != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_env_step_scan launch: %s", hipGetErrorString(perr));
+    const bool pat = s->host.pat_levels > 0;   // stepped antenna pattern (macjd_scenario_set_scan_pattern)
+    // launch_lanes<JT, RT, PE = false, FAST, REG, PD32, SCAN = true, PAT>
+    with_compiled_size(J, R, [&](auto jt, auto rt) -> int {
+        constexpr int JT = decltype(jt)::value, RT = decltype(rt)::value;
+        if constexpr (JT == 0) {   // generic sizes: the general variant
+            if (pat) launch_lanes<0, 0, false, false, false, false, true, true>(g, b, stream, s, w);
+            else launch_lanes<0, 0, false, false, false, false, true>(g, b, stream, s, w);
+        } else if (pat) {
+            // the production variant (fast + REG + PD32) or the general all-float64 one, which serves every other switch
+            // combination (same integers; rewards within the PD32 bound of each other)
+            if (fast && reg && pd32) launch_lanes<JT, RT, false, true, true, true, true, true>(gf, b, stream, s, f);
+            // 12j/16r outside the production configuration: its compiled general form needs all 512 registers and 8 more
+            // (12 B of scratch per lane); the generic-size kernel computes the same bits without any
+            else if constexpr (JT == 12) launch_lanes<0, 0, false, false, false, false, true, true>(g, b, stream, s, w);
+            else launch_lanes<JT, RT, false, false, false, false, true, true>(g, b, stream, s, w);
+        } else if (fast && reg && pd32) launch_lanes<JT, RT, false, true, true, true, true>(gf, b, stream, s, f);
+        else if (fast && reg) launch_lanes<JT, RT, false, true, true, false, true>(gf, b, stream, s, f);
+        else if (fast) launch_lanes<JT, RT, false, true, false, false, true>(gf, b, stream, s, f);
+        else launch_lanes<JT, RT, false, false, false, false, true>(g, b, stream, s, w);
         return MACJD_OK;
-    }
-#define MACJD_LAUNCH_SCAN(JT, RT)                                                                                          \
-    do {                                                                                                                   \
-        if (fast && reg && pd32)                                                                                           \
-            hipLaunchKernelGGL((macjd::env_step_kernel<JT, RT, false, true, FastScan, true, true, true>), gf, b, 0, stream, s->dev, f); \
-        else if (fast && reg)                                                                                              \
-            hipLaunchKernelGGL((macjd::env_step_kernel<JT, RT, false, true, FastScan, true, false, true>), gf, b, 0, stream, s->dev, f); \
-        else if (fast)                                                                                                     \
-            hipLaunchKernelGGL((macjd::env_step_kernel<JT, RT, false, true, FastScan, false, false, true>), gf, b, 0, stream, s->dev, f); \
-        else                                                                                                               \
-            hipLaunchKernelGGL((macjd::env_step_kernel<JT, RT, false, false, FullScan, false, false, true>), g, b, 0, stream, s->dev, w); \
-    } while (0)
-    if (J == 3 && R == 4) MACJD_LAUNCH_SCAN(3, 4);
-    else if (J == 6 && R == 8) MACJD_LAUNCH_SCAN(6, 8);
-    else if (J == 12 && R == 16) MACJD_LAUNCH_SCAN(12, 16);
-    else if (J == 2 && R == 2) MACJD_LAUNCH_SCAN(2, 2);
-    else hipLaunchKernelGGL((macjd::env_step_kernel<0, 0, false, false, FullScan, false, false, true>), g, b, 0, stream, s->dev, w);
-#undef MACJD_LAUNCH_SCAN
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_env_step_scan launch: %s", hipGetErrorString(err));
-    return MACJD_OK;
+    });
+    return launch_status("macjd_env_step_scan");
 }
 
 static int validate_scan(const macjd_scenario* s, const macjd_scan_io* sc, const char* what) {
@@ -1379,6 +1354,13 @@ static int validate_scan(const macjd_scenario* s, const macjd_scan_io* sc, const
     if (sc->state && (sc->st_col0 < 0 || sc->st_col_step < 0)) return set_err(MACJD_EINVAL, "%s: bad state columns", what);
     if (sc->snr_no && sc->sn_se == 0 && sc->sn_sx == 0) return set_err(MACJD_EINVAL, "%s: snr_no strides are zero", what);
     return MACJD_OK;
+}
+
+// The scanning tail of the tables (everything from DevTables.scanning on) to the device
+static hipError_t upload_scan_tables(macjd_scenario* s) {
+    const size_t off = offsetof(DevTables, scanning);
+    return hipMemcpy(reinterpret_cast<char*>(s->dev) + off, reinterpret_cast<const char*>(&s->host) + off,
+                     sizeof(DevTables) - off, hipMemcpyHostToDevice);
 }
 
 int macjd_scenario_set_scan(macjd_scenario* s, const macjd_scan_desc* d) {
@@ -1401,14 +1383,11 @@ int macjd_scenario_set_scan(macjd_scenario* s, const macjd_scan_desc* d) {
     // (gr_side <= gr: the float32-numerator bound of the main tables holds)
     bool ok = true;
     for (int r = 0; r < R; ++r)
-        ok = ok && (t.GaPs_side[r] >= 1e-30 && t.GaPs_side[r] <= 1e30) && t.gr_side[r] <= t.gr[r] &&
-             (t.gr_side[r] == 0.0 || (t.gr_side[r] >= 1e-30 && t.gr_side[r] <= 1e30));
+        ok = ok && reg_mag(t.GaPs_side[r]) && t.gr_side[r] <= t.gr[r] && reg_gain(t.gr_side[r]);
     t.scan_regular = ok ? 1 : 0;
     t.scanning = 1;
     t.pat_levels = 0;   // new scan tables: an earlier pattern's level 0 / L + 1 rows no longer match them
-    const size_t off = offsetof(DevTables, scanning);
-    hipError_t err = hipMemcpy(reinterpret_cast<char*>(s->dev) + off, reinterpret_cast<const char*>(&t) + off,
-                               sizeof(DevTables) - off, hipMemcpyHostToDevice);
+    const hipError_t err = upload_scan_tables(s);
     if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_scenario_set_scan: %s", hipGetErrorString(err));
     return MACJD_OK;
 }
@@ -1437,15 +1416,12 @@ int macjd_scenario_set_scan_pattern(macjd_scenario* s, const macjd_scan_pattern_
             const int i = k * R + r, c = (k - 1) * R + r;
             t.lv_GaPs[i] = d->GaPs_lvl[c]; t.lv_pd_no[i] = d->pd_no_lvl[c]; t.lv_snr_no[i] = d->snr_no_lvl[c]; t.lv_gr[i] = d->gr_lvl[c];
             // the short-division (REG) variant needs every level's values inside its range (see macjd_scenario_set_scan)
-            ok = ok && (t.lv_GaPs[i] >= 1e-30 && t.lv_GaPs[i] <= 1e30) && t.lv_gr[i] <= t.gr[r] &&
-                 (t.lv_gr[i] == 0.0 || (t.lv_gr[i] >= 1e-30 && t.lv_gr[i] <= 1e30));
+            ok = ok && reg_mag(t.lv_GaPs[i]) && t.lv_gr[i] <= t.gr[r] && reg_gain(t.lv_gr[i]);
         }
     }
     t.scan_regular = (t.scan_regular && ok) ? 1 : 0;
     t.pat_levels = L;
-    const size_t off = offsetof(DevTables, scanning);
-    hipError_t err = hipMemcpy(reinterpret_cast<char*>(s->dev) + off, reinterpret_cast<const char*>(&t) + off,
-                               sizeof(DevTables) - off, hipMemcpyHostToDevice);
+    const hipError_t err = upload_scan_tables(s);
     if (err != hipSuccess) {
         t.pat_levels = 0;
         return set_err(MACJD_EDEVICE, "macjd_scenario_set_scan_pattern: %s", hipGetErrorString(err));
@@ -1473,9 +1449,7 @@ int macjd_env_reset_scan(const macjd_scenario* s, int64_t n_envs, const macjd_sc
     hipLaunchKernelGGL(macjd::env_reset_scan_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)hip_stream, s->dev, n_envs,
                        s->host.R, scan->theta_a, scan->a_se, scan->a_sx, scan->state, scan->st_se, scan->st_col0,
                        scan->st_col_step, mask);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_env_reset_scan launch: %s", hipGetErrorString(err));
-    return MACJD_OK;
+    return launch_status("macjd_env_reset_scan");
 }
 
 int macjd_env_step(const macjd_scenario* s, const macjd_step_io* io, void* hip_stream) {
@@ -1498,9 +1472,7 @@ int macjd_env_step_many(const macjd_scenario* s, const macjd_step_io* io, int32_
     if (grid > 4096) grid = 4096;
     hipLaunchKernelGGL(macjd::env_advance_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)hip_stream, io->n_envs,
                        n_steps, io->step, io->r_dpj, io->r_dpj_sum);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_env_step_many launch: %s", hipGetErrorString(err));
-    return MACJD_OK;
+    return launch_status("macjd_env_step_many");
 }
 
 static int env_step_timed_impl(const macjd_scenario* s, const macjd_step_io* io, int iters, void* hip_stream,

@@ -27,11 +27,12 @@
 //   Five barriers per step.  The env's tables are copied into LDS once per launch (uniform ds_read instead of ~100 SGPRs
 //   of loop-invariant scalars).
 //
-// Stepped antenna pattern (include/macjd.h, macjd_scan_pattern_desc): the kernel's text lives in
-// macjd_episode_scan_kernel.h and is compiled twice, as agent_env_episode_scan_kernel (PAT = false) and as
-// agent_env_episode_scan_pat_kernel (PAT = true), which is launched for a handle that carries pattern tables.  Its env
-// half takes a level per object from beam_level and reads the [L + 2, R] level tables (GaPs, pd_no, gr) from a second LDS
-// block; the target's levels of the last step are kept four bits per radar for the hand-over's snr_no.
+// Stepped antenna pattern (include/macjd.h, macjd_scan_pattern_desc): PAT, the kernel's last template parameter, selects
+// the variant that is launched for a handle that carries pattern tables.  Its env half takes a level per object from
+// beam_level and reads the [L + 2, R] level tables (GaPs, pd_no, gr) from a second LDS block; the target's levels of the
+// last step are kept four bits per radar for the hand-over's snr_no.  (The two variants were first compiled from one text
+// included twice under two names, so that the variant without a pattern kept its name; the parameter changes only the
+// name: both variants compile to the same code either way, profiles/r10_episode_isa_check.txt.)
 #pragma once
 
 #include "macjd_env_dev.h"
@@ -53,22 +54,603 @@ struct EpScanTab {   // LDS copy of what the env half reads from the scenario ha
     uint8_t flags[J * R], full[R];
 };
 
-}  // namespace macjd
+template <int J, int R, int A, int SQ, bool PAT>
+__global__ void __launch_bounds__(256) agent_env_episode_scan_kernel(const DevTables* __restrict__ tb,
+                                                                     const macjd_agent_env_episode_scan_io io) {
+    static_assert(J <= 4, "one wave per agent tile in the Q-head phase");
+    static_assert(!PAT || R <= 8, "PAT: the target's levels are packed four bits per radar into 32 bits");
+    static_assert(16 * A <= 256, "actor layer 3: one thread per (env, action)");
+    constexpr int OLD = 16 * SQ + 8;   // LDS pitch of the observation tile (S <= 16 SQ columns, zero-padded)
+    __shared__ __attribute__((aligned(16))) float Hl[2][J][16 * EP_LD];   // h_{t-1} / h_t, ping-pong
+    __shared__ __attribute__((aligned(16))) float Bl[J][16 * EP_LD];      // Q-head base of the current step
+    __shared__ float Wq[(A + 2) * EP_H];                                  // Q-head columns, as agent_episode_kernel
+    __shared__ __attribute__((aligned(16))) float Ol[16 * OLD];           // the 16 envs' observation rows
+    __shared__ __attribute__((aligned(16))) float Xl[16 * EP_LD];         // x = ReLU(fc1 obs)
+    __shared__ __attribute__((aligned(16))) float A1l[16 * ES_ALD], A2l[16 * ES_ALD];   // actor layers 1, 2
+    __shared__ __attribute__((aligned(16))) float W2l[ES_AH * ES_ALD];    // actor layer 2 weights [out][in], pitch ES_ALD
+    __shared__ __attribute__((aligned(16))) float W3l[A * ES_AH];         // actor layer 3 weights
+    __shared__ float Pl[16 * A];                                          // actor output P[row][a] of the current step
+    __shared__ float thf[R][16];                                          // (float) theta_a of the current observation
+    __shared__ double s_az[R][16];                                        // theta_a (gathered by a jammer's chosen radar)
+    __shared__ int Tl[J][16];                                             // chosen actions of the current step
+    __shared__ float Pcl[J][16];
+    __shared__ EpScanTab<J, R> tab;
+    // PAT: level tables [L + 2, R] packed [k * R + r] (row 0 main, 1..L the pattern's levels, L + 1 side lobe), 1 / width
+    constexpr int LVN = PAT ? MAXLV * R : 1;
+    __shared__ double lv_GaPs[LVN], lv_pd_no[LVN], lv_gr[LVN], lv_invw[PAT ? R : 1];
+    int pat_L = 0;
+    if constexpr (PAT) {
+        pat_L = tb->pat_levels;
+        if (threadIdx.x < (pat_L + 2) * R) {
+            lv_GaPs[threadIdx.x] = tb->lv_GaPs[threadIdx.x];
+            lv_pd_no[threadIdx.x] = tb->lv_pd_no[threadIdx.x];
+            lv_gr[threadIdx.x] = tb->lv_gr[threadIdx.x];
+        }
+        if (threadIdx.x < R) lv_invw[threadIdx.x] = tb->pat_inv_width[threadIdx.x];
+    }
 
-#define MACJD_EPSCAN_KERNEL agent_env_episode_scan_kernel
-#define MACJD_EPSCAN_PAT 0
-namespace macjd {
-#include "macjd_episode_scan_kernel.h"
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int li = lane & 15, g = lane >> 4;
+    const int64_t e0 = (int64_t)blockIdx.x * 16;
+    const int T = io.T, S = io.S;
+    const int64_t E = io.n_envs;
+    const int64_t N = E * J;
+    const int col0 = io.scan.st_col0, colstep = io.scan.st_col_step;
+    auto env_of = [&](int r, bool& live) -> int64_t {   // clamped: rows past the end are computed, never stored
+        const int64_t e = e0 + r;
+        live = e < E;
+        return live ? e : E - 1;
+    };
+
+    // ---- launch constants: weight fragments (B operands) ----
+    f32x4 Bh[3][EP_KQ], Bi[3][EP_KQ], Bq[EP_KQ];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int Q = 0; Q < EP_KQ; ++Q) {
+            const int64_t off = (int64_t)(c * EP_H + 16 * wave + li) * EP_H + 16 * Q + 4 * g;
+            Bh[c][Q] = *reinterpret_cast<const f32x4_u*>(io.w_hh + off);
+            Bi[c][Q] = *reinterpret_cast<const f32x4_u*>(io.w_ih + off);
+        }
+#pragma unroll
+    for (int Q = 0; Q < EP_KQ; ++Q)
+        Bq[Q] = *reinterpret_cast<const f32x4_u*>(io.W1 + (int64_t)(16 * wave + li) * io.w1_ld + 16 * Q + 4 * g);
+    // actor layer 2 (128 x 128) is staged in LDS once per launch: as resident fragments it is 64 more VGPRs per lane, which
+    // pushed the 3j/4r variant past 512 registers into scratch; read as B fragments it is 16 ds_read_b128 per wave and step
+    for (int idx = tid; idx < ES_AH * (ES_AH / 4); idx += 256) {
+        const int n = idx / (ES_AH / 4), k4 = idx - n * (ES_AH / 4);
+        *reinterpret_cast<f32x4*>(&W2l[n * ES_ALD + 4 * k4]) = *reinterpret_cast<const f32x4_u*>(io.a2_w + (int64_t)n * ES_AH + 4 * k4);
+    }
+    const int u = 16 * wave + li;          // this lane's hidden unit (gates) / Q-head unit (base) in the C layout
+    float bhh[3], bih[3], b2a[2];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        bhh[c] = io.b_hh[c * EP_H + u];
+        bih[c] = io.b_ih[c * EP_H + u];
+    }
+#pragma unroll
+    for (int tl = 0; tl < 2; ++tl) b2a[tl] = io.a2_b[16 * (2 * wave + tl) + li];
+    const float b1u = io.b1[u];
+    // ---- first layers (fc1, actor layer 1): B fragments over the S observation columns, zero beyond S; the same k order,
+    // zero padding and bias-after-sum as mlp_forward_kernel, so x and the actor's first layer are the step-by-step path's
+    // values bit for bit (theta_a reaches 360: a different summation order moves these sums by ~1e-5) ----
+    f32x4 Bx[SQ], Ba[2][SQ];
+    auto frag_s = [&](const float* w, int row, int Q) {
+        f32x4 v;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int c = 16 * Q + 4 * g + i;
+            const float x = w[(int64_t)row * S + (c < S ? c : S - 1)];   // clamped address + select: no load in a branch
+            v[i] = c < S ? x : 0.0f;
+        }
+        return v;
+    };
+#pragma unroll
+    for (int Q = 0; Q < SQ; ++Q) {
+        Bx[Q] = frag_s(io.fc1_w, 16 * wave + li, Q);
+#pragma unroll
+        for (int tl = 0; tl < 2; ++tl) Ba[tl][Q] = frag_s(io.a1_w, 16 * (2 * wave + tl) + li, Q);
+    }
+    const float bfx = io.fc1_b[u];
+    float bfa[2];
+#pragma unroll
+    for (int tl = 0; tl < 2; ++tl) bfa[tl] = io.a1_b[16 * (2 * wave + tl) + li];
+    for (int idx = tid; idx < 16 * 16 * SQ; idx += 256) {   // observation rows: the env's own state row, zero pad columns
+        const int row = idx / (16 * SQ), c = idx - row * (16 * SQ);
+        bool live;
+        const int64_t e = env_of(row, live);
+        const float x = io.scan.state[e * io.scan.st_se + (c < S ? c : S - 1)];
+        Ol[row * OLD + c] = c < S ? x : 0.0f;
+    }
+    // actor layer 3: thread -> (row = tid & 15, action = tid >> 4), clamped for the threads past 16 A
+    const int r3 = tid & 15, a3 = (tid >> 4) < A ? (tid >> 4) : A - 1;
+    const float b3 = io.a3_b[a3];
+    for (int idx = tid; idx < A * ES_AH; idx += 256) W3l[idx] = io.a3_w[idx];
+    for (int idx = tid; idx < (A + 2) * EP_H; idx += 256) {
+        const int a = idx / EP_H, uu = idx - a * EP_H;
+        Wq[idx] = (a <= A) ? io.W1[(int64_t)uu * io.w1_ld + EP_H + a] : io.w2[uu];
+    }
+    const float b2 = io.b2[0];
+    // env tables -> LDS
+    if (tid < R) {
+        const int r = tid;
+        tab.GaPs[r] = tb->GaPs[r]; tab.GaPs_side[r] = tb->GaPs_side[r]; tab.Pn[r] = tb->Pn[r]; tab.D[r] = tb->D[r];
+        tab.pd_no[r] = tb->pd_no[r]; tab.pd_no_side[r] = tb->pd_no_side[r]; tab.rd_pen[r] = tb->rd_pen[r];
+        tab.gr[r] = tb->gr[r]; tab.gr_side[r] = tb->gr_side[r]; tab.half[r] = tb->half[r]; tab.h2[r] = tb->h2[r];
+        tab.sweep[r] = tb->sweep[r]; tab.swm[r] = tb->swm[r]; tab.bt[r] = tb->bt[r]; tab.full[r] = tb->full[r];
+        tab.snr_no[r] = tb->snr_no[r]; tab.snr_no_side[r] = tb->snr_no_side[r];
+    }
+    if (tid < J) {
+        tab.pmin[tid] = tb->pmin[tid]; tab.pmax[tid] = tb->pmax[tid]; tab.gj[tid] = tb->gj[tid];
+    }
+    if (tid < J * R) {
+        tab.denom[tid] = tb->denom[tid]; tab.bj[tid] = tb->bj[tid]; tab.flags[tid] = tb->flags[tid];
+    }
+    if (tid == 0) {
+        tab.rp_min = tb->rp_min; tab.rp_max = tb->rp_max; tab.pd_A = tb->pd_A; tab.pd_c1 = tb->pd_c1;
+        tab.pd_denB = tb->pd_denB; tab.episode_limit = tb->episode_limit;
+    }
+    // ---- hidden state ----
+    float hreg[J][4];
+#pragma unroll
+    for (int j = 0; j < J; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            bool live;
+            const int64_t n = env_of(4 * g + r, live) * J + j;
+            hreg[j][r] = io.h0 ? io.h0[n * EP_H + u] : 0.0f;
+            Hl[0][j][(4 * g + r) * EP_LD + u] = hreg[j][r];
+        }
+    // Q-head phase roles: wave = agent tile (waves >= J idle there), lane = (row qr, quarter qq)
+    const int qr = lane & 15, qq = lane >> 4;
+    const int jq = wave < J ? wave : 0;
+    bool live_q;
+    const int64_t eq = env_of(qr, live_q);
+    const int64_t nq = eq * J + jq;
+    uint64_t avail_bits = 0;
+    int n_avail = 0;
+#pragma unroll
+    for (int a = 0; a < A; ++a) {
+        bool av = true;
+        if (io.avail) {
+            const int64_t off = eq * io.av_se + jq * io.av_sj + (int64_t)a * io.av_sa;
+            av = (io.avail_elem_size == 8) ? (((const int64_t*)io.avail)[off] != 0) : (((const int32_t*)io.avail)[off] != 0);
+        }
+        avail_bits |= av ? (1ull << a) : 0ull;
+        n_avail += av ? 1 : 0;
+    }
+    const uint64_t ctr_base = io.counter_base ? io.counter_base[0] : 0ull;
+    // ---- env state of lane (lane & 15)'s env (used by wave 0; the other waves carry copies) ----
+    const int er = lane & 15;
+    bool live_e;
+    const int64_t ee = env_of(er, live_e);
+    const bool env_lane = (wave == 0) && (lane < 16);
+    double az[R];
+    uint32_t s_bits = 0, in_t_last = 0;
+    uint32_t lv_last = 0;   // PAT: the target's level at radar r in the last step, bits [4r, 4r + 4)
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        az[r] = io.scan.theta_a[ee * io.scan.a_se + (int64_t)r * io.scan.a_sx];
+        s_bits |= (io.track[ee * io.k_se + (int64_t)r * io.k_sx] != 0) ? (1u << r) : 0u;
+    }
+    int32_t step_ctr = io.step[ee];
+    const uint32_t episode = io.episode ? (uint32_t)io.episode[ee] : 0u;
+    float rsum[3] = {0.0f, 0.0f, 0.0f};
+    if (io.rdpj_sum) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) rsum[k] = io.rdpj_sum[ee * 3 + k];
+    }
+    if (env_lane) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            thf[r][er] = (float)az[r];
+            s_az[r][er] = az[r];
+        }
+    }
+    __syncthreads();
+    const PdConsts pdk = pd_consts(tab.pd_A, tab.pd_c1, tab.pd_denB);
+
+    for (int t = 0; t < T; ++t) {
+        const int cur = t & 1, nxt = cur ^ 1;
+        // ---- (S1) this step's observation: theta_a columns of the staging rows; first layers ----
+        for (int i = tid; i < 16 * R * (J + 1); i += 256) {
+            const int row = i & 15, rest = i >> 4;
+            const int r = rest % R, jj = rest / R;      // jj == J: the state row
+            bool live;
+            const int64_t e = env_of(row, live);
+            const float v = thf[r][row];
+            const int c = col0 + r * colstep;
+            if (live) {
+                if (jj == J) io.st_state[((int64_t)t * E + e) * S + c] = v;
+                else io.st_obs[(((int64_t)t * E + e) * J + jj) * S + c] = v;
+            }
+        }
+        {
+            f32x4 ax = f32x4{0.f, 0.f, 0.f, 0.f}, aa[2];
+            aa[0] = f32x4{0.f, 0.f, 0.f, 0.f};
+            aa[1] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int Q = 0; Q < SQ; ++Q) {
+                const f32x4 a = *reinterpret_cast<const f32x4*>(&Ol[li * OLD + 16 * Q + 4 * g]);
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) {
+                    ax = __builtin_amdgcn_mfma_f32_16x16x4f32(a[jj], Bx[Q][jj], ax, 0, 0, 0);
+#pragma unroll
+                    for (int tl = 0; tl < 2; ++tl) aa[tl] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[jj], Ba[tl][Q][jj], aa[tl], 0, 0, 0);
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                Xl[(4 * g + r) * EP_LD + u] = fmaxf(ax[r] + bfx, 0.0f);
+#pragma unroll
+                for (int tl = 0; tl < 2; ++tl)
+                    A1l[(4 * g + r) * ES_ALD + 16 * (2 * wave + tl) + li] = fmaxf(aa[tl][r] + bfa[tl], 0.0f);
+            }
+        }
+        __syncthreads();
+        // ---- (S2) gi = W_ih x + b_ih (one tile, shared by the agents); actor layer 2; gh; gates ----
+        float giv[4][3];
+        {
+            f32x4 ai[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) ai[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int Q = 0; Q < EP_KQ; ++Q) {
+                const f32x4 a = *reinterpret_cast<const f32x4*>(&Xl[li * EP_LD + 16 * Q + 4 * g]);
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) ai[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[jj], Bi[c][Q][jj], ai[c], 0, 0, 0);
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) giv[r][c] = ai[c][r] + bih[c];
+        }
+        {
+            f32x4 a2[2];
+            a2[0] = f32x4{0.f, 0.f, 0.f, 0.f};
+            a2[1] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int Q = 0; Q < ES_AKQ; ++Q) {
+                const f32x4 a = *reinterpret_cast<const f32x4*>(&A1l[li * ES_ALD + 16 * Q + 4 * g]);
+                f32x4 b[2];
+#pragma unroll
+                for (int tl = 0; tl < 2; ++tl)
+                    b[tl] = *reinterpret_cast<const f32x4*>(&W2l[(16 * (2 * wave + tl) + li) * ES_ALD + 16 * Q + 4 * g]);
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+                    for (int tl = 0; tl < 2; ++tl) a2[tl] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[jj], b[tl][jj], a2[tl], 0, 0, 0);
+            }
+#pragma unroll
+            for (int tl = 0; tl < 2; ++tl)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    A2l[(4 * g + r) * ES_ALD + 16 * (2 * wave + tl) + li] = fmaxf(a2[tl][r] + b2a[tl], 0.0f);
+        }
+        f32x4 acc[J][3];
+#pragma unroll
+        for (int j = 0; j < J; ++j)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) acc[j][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int Q = 0; Q < EP_KQ; ++Q) {
+            f32x4 a[J];
+#pragma unroll
+            for (int j = 0; j < J; ++j) a[j] = *reinterpret_cast<const f32x4*>(&Hl[cur][j][li * EP_LD + 16 * Q + 4 * g]);
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+                for (int j = 0; j < J; ++j)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c)
+                        acc[j][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j][jj], Bh[c][Q][jj], acc[j][c], 0, 0, 0);
+        }
+        // gates (torch.nn.GRUCell, gate order r, z, n; expressions of gru_gates_kernel)
+#pragma unroll
+        for (int j = 0; j < J; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float hr = acc[j][0][r] + bhh[0], hz = acc[j][1][r] + bhh[1], hn = acc[j][2][r] + bhh[2];
+                const float rg = 1.0f / (1.0f + expf(-(giv[r][0] + hr)));
+                const float zg = 1.0f / (1.0f + expf(-(giv[r][1] + hz)));
+                const float nn = 1.0f - 2.0f / (expf(2.0f * (giv[r][2] + rg * hn)) + 1.0f);
+                const float hnew = (hreg[j][r] - nn) * zg + nn;
+                hreg[j][r] = hnew;
+                const int row = 4 * g + r;
+                Hl[nxt][j][row * EP_LD + u] = hnew;
+                bool live;
+                const int64_t n = env_of(row, live) * J + j;
+                if (live) io.hidden[((int64_t)t * N + n) * EP_H + u] = hnew;   // staging row t: post-update h_t
+            }
+        __syncthreads();
+        // ---- (S3) actor layer 3 + sigmoid -> P; Q-head base = W1[:, :H] h_t + b1 ----
+        {
+            float s = 0.0f;
+            const float* arow = &A2l[r3 * ES_ALD];
+            const float* wrow = &W3l[a3 * ES_AH];
+#pragma unroll 4
+            for (int k4 = 0; k4 < ES_AH / 4; ++k4) {
+                const f32x4 av = *reinterpret_cast<const f32x4*>(arow + 4 * k4);
+                const f32x4 wv = *reinterpret_cast<const f32x4*>(wrow + 4 * k4);
+#pragma unroll
+                for (int kk = 0; kk < 4; ++kk) s = fmaf(av[kk], wv[kk], s);
+            }
+            s += b3;
+            const float p = 1.0f / (1.0f + expf(-s));
+            if (tid < 16 * A) Pl[r3 * A + a3] = p;
+        }
+        {
+            f32x4 ab[J];
+#pragma unroll
+            for (int j = 0; j < J; ++j) ab[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int Q = 0; Q < EP_KQ; ++Q) {
+                f32x4 a[J];
+#pragma unroll
+                for (int j = 0; j < J; ++j) a[j] = *reinterpret_cast<const f32x4*>(&Hl[nxt][j][li * EP_LD + 16 * Q + 4 * g]);
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+                    for (int j = 0; j < J; ++j) ab[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j][jj], Bq[Q][jj], ab[j], 0, 0, 0);
+            }
+#pragma unroll
+            for (int j = 0; j < J; ++j)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) Bl[j][(4 * g + r) * EP_LD + u] = ab[j][r] + b1u;
+        }
+        __syncthreads();
+        // ---- (S4) all-action Q-head + selection: wave = agent tile ----
+        const float epsilon = io.greedy_only ? 0.0f : io.eps[t];
+        if (wave < J) {
+            const int j = wave;
+            float q[A], pv[A];
+#pragma unroll
+            for (int a = 0; a < A; ++a) {
+                q[a] = 0.0f;
+                pv[a] = Pl[qr * A + a];
+            }
+            const float* brow = &Bl[j][qr * EP_LD + 16 * qq];
+#pragma unroll
+            for (int k4 = 0; k4 < 4; ++k4) {
+                const f32x4 b4 = *reinterpret_cast<const f32x4*>(brow + 4 * k4);
+#pragma unroll
+                for (int kk = 0; kk < 4; ++kk) {
+                    const int uu = 16 * qq + 4 * k4 + kk;
+                    const float wp = Wq[A * EP_H + uu], w2u = Wq[(A + 1) * EP_H + uu];
+#pragma unroll
+                    for (int a = 0; a < A; ++a) {
+                        float v = b4[kk] + Wq[a * EP_H + uu];          // (W_h h + b1)[u] + W1[u, H + a]
+                        v = fmaf(pv[a], wp, v);                        // + W1[u, H + A] * P_a
+                        v = fmaxf(v, 0.0f);                            // ReLU
+                        q[a] = fmaf(v, w2u, q[a]);                     // second layer
+                    }
+                }
+            }
+#pragma unroll
+            for (int a = 0; a < A; ++a) {
+                q[a] += __shfl_xor(q[a], 16, 64);
+                q[a] += __shfl_xor(q[a], 32, 64);
+                q[a] += b2;
+            }
+            if (qq == 0) {
+                // mask, first arg-max, epsilon-greedy: as agent_episode_kernel / qhead_select_kernel
+                int best = 0;
+                float bestq = -INFINITY;
+#pragma unroll
+                for (int a = 0; a < A; ++a) {
+                    const float qa = ((avail_bits >> a) & 1ull) ? q[a] : -INFINITY;
+                    if (qa > bestq) { bestq = qa; best = a; }
+                }
+                int chosen = best;
+                if (epsilon > 0.0f) {
+                    const uint64_t counter = ctr_base + (uint64_t)(t + 1);
+                    const Philox4 rr = philox4x32_10((uint32_t)nq, (uint32_t)((uint64_t)nq >> 32), (uint32_t)counter,
+                                                     (uint32_t)(counter >> 32), (uint32_t)io.seed, (uint32_t)(io.seed >> 32));
+                    const float u_pick = (float)(rr.v[0] >> 8) * (1.0f / 16777216.0f);
+                    if (u_pick < epsilon) {
+                        const int pool = n_avail > 0 ? n_avail : A;
+                        int k = (int)(((uint64_t)rr.v[1] * (uint64_t)pool) >> 32);
+                        chosen = 0;
+#pragma unroll
+                        for (int a = 0; a < A; ++a) {
+                            const bool av = (n_avail > 0) ? ((avail_bits >> a) & 1ull) : true;
+                            if (av) { if (k == 0) chosen = a; --k; }
+                        }
+                    }
+                }
+                float pc = 0.0f;
+#pragma unroll
+                for (int a = 0; a < A; ++a) pc = (a == chosen) ? pv[a] : pc;
+                Tl[j][qr] = chosen;
+                Pcl[j][qr] = pc;
+                if (live_q) {
+                    const int64_t o = (int64_t)t * N + nq;
+                    io.T_out[o] = chosen;
+                    io.P_out[o] = pc;
+                }
+            }
+        }
+        __syncthreads();
+        // ---- (S5) scanning env step, one lane per env (wave 0; its lanes >= 16 repeat lanes 0..15 and store nothing) ----
+        if (wave == 0) {
+            constexpr int NP = R + J, NBLK = (NP + 3) / 4;
+            const uint32_t step_before = (uint32_t)step_ctr;
+            uint32_t rw[NBLK * 4];
+#pragma unroll
+            for (int b = 0; b < NBLK; ++b) {
+                const Philox4 blk = env_philox_block(io.env_seed, (uint64_t)(io.env_offset + ee), episode, step_before, (uint32_t)b);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) rw[b * 4 + i] = blk.v[i];
+            }
+            uint32_t in_t = 0;   // bit r: radar r sees the target in its main lobe (start-of-step azimuth and FSM state)
+            uint32_t lv_t = 0;   // PAT: the target's level at radar r, bits [4r, 4r + 4)
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const double lim = (((s_bits >> r) & 1u) ? 0.0 : tab.sweep[r]) + tab.h2[r];
+                if constexpr (PAT)
+                    lv_t |= (uint32_t)beam_level(tab.bt[r], az[r], tab.half[r], lim, tab.full[r] != 0, lv_invw[r], pat_L) << (4 * r);
+                else
+                    in_t |= in_main_lobe(tab.bt[r], az[r], tab.half[r], lim, tab.full[r] != 0) ? (1u << r) : 0u;
+            }
+            double supp[R], prod[R], snr_all[NP], pd_all[NP];
+#pragma unroll
+            for (int r = 0; r < R; ++r) { supp[r] = 0.0; prod[r] = 1.0; }
+            uint32_t supp_mask = 0, hit_mask = 0;
+            int dec_tgt[J];
+            double r_p = 0.0;
+#pragma unroll
+            for (int j = 0; j < J; ++j) {
+                // action decode, power scale, r_p term (environment.py:249-277)
+                const int32_t Tj = Tl[j][er];
+                const bool is_jamming = (Tj >= 1) && (Tj <= 2 * R);
+                const int target = is_jamming ? ((Tj + 1) / 2 - 1) : 0;
+                const int jtype = Tj % 2;
+                const double pmin = tab.pmin[j], pmax = tab.pmax[j];
+                const double power_range = pmax - pmin;
+                float Pc = Pcl[j][er];
+                Pc = Pc < 0.0f ? 0.0f : (Pc > 1.0f ? 1.0f : Pc);
+                const float actual_f = (float)pmin + Pc * (float)power_range;
+                const double actual_d = (double)actual_f;
+                const double norm = (power_range > 1e-6) ? (double)((actual_f - (float)pmin) / (float)power_range) : 0.0;
+                r_p += tab.rp_max + (tab.rp_min - tab.rp_max) * norm;
+                // received jamming power (environment.py:280-302), receive gain by the jammer's bearing
+                const double denom = tab.denom[j * R + target];
+                const uint8_t fl = tab.flags[j * R + target];
+                const bool recorded = is_jamming && (actual_d > 0.0) && (denom >= 0.0);
+                const bool live = recorded && denom > 1e-18;
+                const double dsafe = live ? denom : 1.0;
+                const double lim = (((s_bits >> target) & 1u) ? 0.0 : tab.sweep[target]) + tab.h2[target];
+                double grj;
+                if constexpr (PAT)
+                    grj = lv_gr[beam_level(tab.bj[j * R + target], s_az[target][er], tab.half[target], lim, tab.full[target] != 0,
+                                           lv_invw[target], pat_L) * R + target];
+                else
+                    grj = in_main_lobe(tab.bj[j * R + target], s_az[target][er], tab.half[target], lim, tab.full[target] != 0)
+                              ? tab.gr[target] : tab.gr_side[target];
+                const float num = (actual_f * (float)tab.gj[j]) * (float)grj;
+                const double q = (fl & MACJD_JR_WEAK_DENOM) ? (double)(num / (float)dsafe) : (double)num / dsafe;
+                const double prj = (live && q > 0.0) ? q : 0.0;
+                const bool is_sup = recorded && (jtype == 1);
+                const bool is_dec = recorded && (jtype == 0);
+                supp_mask |= is_sup ? (1u << target) : 0u;
+#pragma unroll
+                for (int r = 0; r < R; ++r) supp[r] = __builtin_fma(prj, (is_sup && target == r) ? 1.0 : 0.0, supp[r]);
+                dec_tgt[j] = is_dec ? target : -1;
+                // SNR of the false target (environment.py:410-422)
+                const double Pn_t = tab.Pn[target];
+                const bool live_f = is_dec && Pn_t > 1e-18;
+                const double snr_f = (tab.D[target] * prj) / (live_f ? Pn_t : 1.0);
+                snr_all[R + j] = (live_f && snr_f > 0.0) ? snr_f : 0.0;
+            }
+#pragma unroll
+            for (int r = 0; r < R; ++r) {   // SNR with jamming (environment.py:316-333)
+                const double den = tab.D[r] * supp[r] + tab.Pn[r];
+                const bool live = den > 1e-18;
+                double gaps;
+                if constexpr (PAT) gaps = lv_GaPs[(int)((lv_t >> (4 * r)) & 15u) * R + r];
+                else gaps = ((in_t >> r) & 1u) ? tab.GaPs[r] : tab.GaPs_side[r];
+                const double q = gaps / (live ? den : 1.0);
+                snr_all[r] = live ? q : 0.0;
+            }
+            det_prob_batch<NP>(snr_all, pd_all, pdk);
+            int n_dec = 0;
+#pragma unroll
+            for (int j = 0; j < J; ++j) {   // Monte-Carlo detection of the false targets in jammer order
+                const bool is_dec = dec_tgt[j] >= 0;
+                uint32_t w = rw[R];
+#pragma unroll
+                for (int k = 1; k < J; ++k) w = (n_dec == k) ? rw[R + k] : w;
+                const double uu = u32_mid(w);
+                n_dec += is_dec ? 1 : 0;
+                const double pd_f = pd_all[R + j];
+                const bool hit = is_dec && (uu <= pd_f);
+                const double safe = pd_f < 0.999999 ? pd_f : 0.999999;
+                hit_mask |= hit ? (1u << (dec_tgt[j] & 31)) : 0u;
+#pragma unroll
+                for (int r = 0; r < R; ++r) prod[r] = (hit && dec_tgt[j] == r) ? prod[r] * (1.0 - safe) : prod[r];
+            }
+            double r_d = 0.0, r_j = 0.0, r_j_dec = 0.0;
+            uint32_t track_bits = 0;
+#pragma unroll
+            for (int r = 0; r < R; ++r) {   // detections, FSM, reward terms, beam advance
+                const double pd = pd_all[r];
+                const bool detected = u32_mid(rw[r]) <= pd;
+                track_bits |= detected ? (1u << r) : 0u;
+                r_d += detected ? tab.rd_pen[r] : 0.0;
+                double pd_no_r;
+                if constexpr (PAT) pd_no_r = lv_pd_no[(int)((lv_t >> (4 * r)) & 15u) * R + r];
+                else pd_no_r = ((in_t >> r) & 1u) ? tab.pd_no[r] : tab.pd_no_side[r];
+                const double red = pd_no_r - pd;
+                r_j += ((supp_mask & (1u << r)) && red > 0.0) ? red : 0.0;
+                r_j_dec += (hit_mask & (1u << r)) ? 1.0 - prod[r] : 0.0;
+                double x = az[r] + tab.swm[r];
+                x = (x >= 360.0) ? x - 360.0 : x;
+                az[r] = detected ? tab.bt[r] : (((s_bits >> r) & 1u) ? az[r] : x);
+            }
+            r_j += r_j_dec;
+            const double reward = r_d + r_p + r_j;
+            s_bits = track_bits;
+            in_t_last = in_t;
+            lv_last = lv_t;
+            step_ctr += 1;
+            rsum[0] += (float)r_d;
+            rsum[1] += (float)r_p;
+            rsum[2] += (float)r_j;
+            if (lane < 16) {
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    thf[r][er] = (float)az[r];
+                    s_az[r][er] = az[r];
+                    Ol[er * OLD + col0 + r * colstep] = (float)az[r];
+                }
+                if (live_e) {
+                    io.reward[(int64_t)t * E + ee] = (float)reward;
+                    io.terminated[(int64_t)t * E + ee] = (step_ctr >= tab.episode_limit) ? 1 : 0;
+                }
+            }
+        }
+        __syncthreads();
+    }
+    // ---- hand-over: what a step-by-step rollout leaves in the environment and the controller ----
+    if (env_lane && live_e) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            io.scan.theta_a[ee * io.scan.a_se + (int64_t)r * io.scan.a_sx] = az[r];
+            io.track[ee * io.k_se + (int64_t)r * io.k_sx] = (s_bits >> r) & 1u;
+            io.scan.state[ee * io.scan.st_se + col0 + r * colstep] = (float)az[r];
+            if constexpr (PAT) {
+                if (io.scan.snr_no)
+                    io.scan.snr_no[ee * io.scan.sn_se + (int64_t)r * io.scan.sn_sx] =
+                        (float)tb->lv_snr_no[(int)((lv_last >> (4 * r)) & 15u) * R + r];
+            } else {
+                if (io.scan.snr_no)
+                    io.scan.snr_no[ee * io.scan.sn_se + (int64_t)r * io.scan.sn_sx] =
+                        (float)(((in_t_last >> r) & 1u) ? tab.snr_no[r] : tab.snr_no_side[r]);
+            }
+        }
+        io.step[ee] = step_ctr;
+        if (io.rdpj_sum) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) io.rdpj_sum[ee * 3 + k] = rsum[k];
+        }
+    }
+    if (io.h_final) {
+#pragma unroll
+        for (int j = 0; j < J; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                bool live;
+                const int64_t n = env_of(4 * g + r, live) * J + j;
+                if (live) io.h_final[n * EP_H + u] = hreg[j][r];
+            }
+    }
+}
+
 }  // namespace macjd
-#undef MACJD_EPSCAN_KERNEL
-#undef MACJD_EPSCAN_PAT
-#define MACJD_EPSCAN_KERNEL agent_env_episode_scan_pat_kernel
-#define MACJD_EPSCAN_PAT 1
-namespace macjd {
-#include "macjd_episode_scan_kernel.h"
-}  // namespace macjd
-#undef MACJD_EPSCAN_KERNEL
-#undef MACJD_EPSCAN_PAT
 
 extern "C" int macjd_agent_env_episode_scan_supported(int32_t J, int32_t R, int32_t H, int32_t A) {
     return (H == macjd::EP_H && ((J == 3 && R == 4 && A == 9) || (J == 2 && R == 2 && A == 5))) ? 1 : 0;
@@ -102,10 +684,10 @@ extern "C" int macjd_agent_env_episode_scan(const macjd_scenario* s, const macjd
     const dim3 grid((unsigned)wgs), block(256);
     hipStream_t st = (hipStream_t)hip_stream;
     if (s->host.pat_levels > 0) {   // stepped antenna pattern (macjd_scenario_set_scan_pattern)
-        if (io->J == 3) hipLaunchKernelGGL((agent_env_episode_scan_pat_kernel<3, 4, 9, 3>), grid, block, 0, st, s->dev, *io);
-        else hipLaunchKernelGGL((agent_env_episode_scan_pat_kernel<2, 2, 5, 3>), grid, block, 0, st, s->dev, *io);
-    } else if (io->J == 3) hipLaunchKernelGGL((agent_env_episode_scan_kernel<3, 4, 9, 3>), grid, block, 0, st, s->dev, *io);
-    else hipLaunchKernelGGL((agent_env_episode_scan_kernel<2, 2, 5, 3>), grid, block, 0, st, s->dev, *io);
+        if (io->J == 3) hipLaunchKernelGGL((agent_env_episode_scan_kernel<3, 4, 9, 3, true>), grid, block, 0, st, s->dev, *io);
+        else hipLaunchKernelGGL((agent_env_episode_scan_kernel<2, 2, 5, 3, true>), grid, block, 0, st, s->dev, *io);
+    } else if (io->J == 3) hipLaunchKernelGGL((agent_env_episode_scan_kernel<3, 4, 9, 3, false>), grid, block, 0, st, s->dev, *io);
+    else hipLaunchKernelGGL((agent_env_episode_scan_kernel<2, 2, 5, 3, false>), grid, block, 0, st, s->dev, *io);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_agent_env_episode_scan: %s", hipGetErrorString(err));
     return MACJD_OK;

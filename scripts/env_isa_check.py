@@ -1,13 +1,15 @@
-"""Compare the env-step kernels of two gfx950 assembly listings of csrc/macjd_env.hip.
+"""Compare the kernels of two gfx950 assembly listings of one source file (csrc/macjd_env.hip, csrc/macjd_episode.hip).
 
     hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -std=c++17 --cuda-device-only -S -o before.s macjd_env.hip
     python scripts/env_isa_check.py before.s after.s
 
-Kernels are matched by name.  When `before.s` is from a tree without the SCAN template parameter (the last template
-argument of env_step_kernel), the instantiations of `after.s` with that argument false are matched to the kernel of the
-same name in `before.s` without it.  Each body is normalised (symbol names, basic-block / temporary / long-branch label numbers) and hashed together with
+Each body is normalised (symbol names, basic-block / temporary / long-branch label numbers) and hashed together with
 its kernel descriptor (.amdhsa_kernel: registers, LDS, scratch); instruction count, VGPRs and scratch bytes are printed
-next to the hashes.  Exits non-zero when any existing kernel differs."""
+next to the hashes.  A kernel whose name is in both listings is matched by name.  The kernels whose names are in one
+listing only (a changed template parameter list changes the name) are paired by digest and reported as `same (renamed)`
+with both names; what is left over is `DIFF` (a kernel of `before.s` without a counterpart of its digest) or `new`.
+Exits non-zero when any kernel of `before.s` has no counterpart with the same digest, or the two listings differ in
+their number of kernels."""
 import hashlib
 import re
 import sys
@@ -17,7 +19,7 @@ def kernels(path):
     txt = open(path).read()
     body = {m.group(1): m.group(2) for m in re.finditer(r"^(_Z\S*macjd\S*):[^\n]*$(.*?)^\.Lfunc_end\d+:", txt, re.M | re.S)}
     desc = {m.group(1): m.group(2) for m in re.finditer(r"^\s*\.amdhsa_kernel (\S+)$(.*?)\.end_amdhsa_kernel", txt, re.M | re.S)}
-    return body, desc
+    return {n: (b, desc[n]) for n, b in body.items() if "desc" not in n}
 
 
 def digest(body, desc):
@@ -37,31 +39,34 @@ def stats(body, desc):
 
 
 def main(before, after):
-    bb, bd = kernels(before)
-    ab, ad = kernels(after)
-    bad = n_old = n_scan = 0
-    for name in sorted(ab):
-        if "desc" in name:
-            continue
-        # (a kernel of the same name in both listings is matched by name: both trees have the SCAN parameter)
-        m = None if name in bb else re.match(r"(_ZN5macjd15env_step_kernel.*)Lb([01])E(EEv.*)$", name)
-        if m and m.group(2) == "1":
-            n_scan += 1
-            print(f"scan  {stats(ab[name], ad[name])}  {name}")
-            continue
-        old = m.group(1) + m.group(3) if m else name
-        if old not in bb:
-            print(f"new   {stats(ab[name], ad[name])}  {name}")
-            continue
-        n_old += 1
-        h_old = digest(bb[old], bd[old])
-        h_new = digest(ab[name], ad[name])
-        same = h_old == h_new
-        bad += not same
-        s_old = stats(bb[old], bd[old])
-        print(f"{'same' if same else 'DIFF'}  {h_old}  {h_new}  {s_old} -> {stats(ab[name], ad[name])}  {old}")
-    print(f"{len(bb)} kernels before; {n_old} matched after ({bad} differ); {n_scan} SCAN instantiations added")
-    return 1 if bad or n_old != len(bb) else 0
+    bk, ak = kernels(before), kernels(after)
+    bad = 0
+    for name in sorted(set(bk) & set(ak)):
+        h_old, h_new = digest(*bk[name]), digest(*ak[name])
+        bad += h_old != h_new
+        print(f"{'same' if h_old == h_new else 'DIFF'}  {h_old}  {h_new}  {stats(*bk[name])} -> {stats(*ak[name])}  {name}")
+    # names on one side only: pair by digest
+    unpaired = {}
+    for name in sorted(set(ak) - set(bk)):
+        unpaired.setdefault(digest(*ak[name]), []).append(name)
+    n_renamed = 0
+    for old in sorted(set(bk) - set(ak)):
+        h = digest(*bk[old])
+        if unpaired.get(h):
+            new = unpaired[h].pop(0)
+            n_renamed += 1
+            print(f"same (renamed)  {h}  {h}  {stats(*bk[old])} -> {stats(*ak[new])}  {old} -> {new}")
+        else:
+            bad += 1
+            print(f"DIFF  {h}  {'-' * 16}  {stats(*bk[old])} -> (no kernel with this digest)  {old}")
+    n_new = 0
+    for h, names in sorted(unpaired.items()):
+        for name in names:
+            n_new += 1
+            print(f"new   {'-' * 16}  {h}  {stats(*ak[name])}  {name}")
+    print(f"{len(bk)} kernels before, {len(ak)} after; {len(bk) - bad} of before's have a counterpart of the same digest "
+          f"({n_renamed} renamed), {bad} do not; {n_new} new")
+    return 1 if bad or len(bk) != len(ak) else 0
 
 
 if __name__ == "__main__":

@@ -13,9 +13,13 @@ Prints one JSON line per (size, E) with the median of `reps` replays of each and
 
 compares two-level scanning with the stepped antenna pattern (radar_scan.pattern) instead: the shipped
 config/scenario_3j4r_scan_pattern.yaml with and without its pattern block (same beams), 3j/4r at E = 4096 and 2^20, default
-kernel choice, one process per run, the two alternating three times; every run appends one JSON line to --out."""
+kernel choice, one process per run, the two alternating three times; every run appends one JSON line to --out.
+
+    python scripts/probe_scan_env.py --eager static|scan|pattern [--E 4096] [--iters 2000] [--reps 5] [--label L] [--out FILE]
+
+times the host side of the launch path instead: `iters` eager env.step calls (no graph) on that scenario, wall clock per
+call up to the last call's return (enqueue) and up to the device's completion (total), median of `reps` repetitions."""
 import argparse
-import copy
 import json
 import os
 import statistics
@@ -67,41 +71,85 @@ def timed(env, T, P, iters, reps):
 PATTERN_OUT = os.path.join(REPO, "profiles", "r09_scan_pattern_env_probe.jsonl")
 
 
-def pattern_run(tag, E, iters, reps, out):
-    """One (two-level | pattern, E) measurement in this process."""
+def pattern_env(tag, E):
+    """The shipped pattern scenario as it is (pattern), without its pattern block (scan) or without scanning (static)."""
     import yaml
     path = os.path.join(REPO, "ma-cjd-cooperative-jamming-decision-making-via-marl_amd", "config", "scenario_3j4r_scan_pattern.yaml")
     d = yaml.safe_load(open(path))
     if tag == "scan":
-        d = copy.deepcopy(d)
         del d["environment_params"]["radar_scan"]["pattern"]
+    elif tag == "static":
+        del d["environment_params"]["radar_scan"]
     sc = Scenario.from_dict(d)
     J, R = sc.num_jammers, sc.num_radars
     rng = np.random.default_rng(0)
     T = torch.from_numpy(rng.integers(0, 2 * R + 1, size=(J, E)).astype(np.int32)).cuda().t()   # agent-major
     P = torch.from_numpy(rng.random((J, E), dtype=np.float32)).cuda().t()
-    env = BatchedElectromagneticEnvironment(scenario=sc, batch_envs=E, device="cuda", seed=1)
+    return sc, T, P, BatchedElectromagneticEnvironment(scenario=sc, batch_envs=E, device="cuda", seed=1)
+
+
+def emit(line, out):
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "a") as f:
+            f.write(json.dumps(line) + "\n")
+    print(json.dumps(line), flush=True)
+
+
+def eager_run(tag, E, iters, reps, out, label):
+    """Host cost of the launch path: eager env.step calls in this process."""
+    sc, T, P, env = pattern_env(tag, E)
+    out_r = torch.zeros(E, device="cuda")
+    out_t = torch.zeros(E, dtype=torch.uint8, device="cuda")
+    env.reset()
+    enq, tot = [], []
+    for rep in range(reps + 1):   # (the first repetition warms up)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(iters):
+            env.step(T, P, out_reward=out_r, out_terminated=out_t, want_info=False)
+        t1 = time.perf_counter()
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        if rep:
+            enq.append((t1 - t0) / iters * 1e6)
+            tot.append((t2 - t0) / iters * 1e6)
+    env.close()
+    emit({"probe": "scan_env_eager", "variant": tag, "label": label,
+          "E": E, "iters": iters, "reps": reps, "us_per_call_enqueue_median": round(statistics.median(enq), 3),
+          "us_per_call_total_median": round(statistics.median(tot), 3), "us_per_call_total_all": [round(x, 3) for x in tot],
+          "device": torch.cuda.get_device_name(0), "time": time.strftime("%Y-%m-%dT%H:%M:%S")}, out)
+
+
+def pattern_run(tag, E, iters, reps, out):
+    """One (two-level | pattern, E) measurement in this process."""
+    sc, T, P, env = pattern_env(tag, E)
+    J, R = sc.num_jammers, sc.num_radars
     n = iters if E < (1 << 20) else max(20, iters // 10)
     ms = timed(env, T, P, n, reps)
     line = {"probe": "scan_pattern_env", "variant": tag, "levels": sc.scan_pattern_levels, "J": J, "R": R, "E": E, "iters": n,
             "reps": reps, "ms_per_step_median": round(ms, 6), "device": torch.cuda.get_device_name(0),
             "time": time.strftime("%Y-%m-%dT%H:%M:%S")}
     env.close()
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    with open(out, "a") as f:
-        f.write(json.dumps(line) + "\n")
-    print(json.dumps(line), flush=True)
+    emit(line, out)
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--iters", type=int, default=None, help="default 200 (--eager: 2000)")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--pattern", action="store_true", help="two-level scanning vs the stepped pattern, one process per run")
     ap.add_argument("--one", nargs=2, metavar=("VARIANT", "E"), help="(internal) one run of --pattern in this process")
     ap.add_argument("--alternations", type=int, default=3)
-    ap.add_argument("--out", default=PATTERN_OUT)
+    ap.add_argument("--eager", choices=["static", "scan", "pattern"], help="host cost of eager env.step calls on that scenario")
+    ap.add_argument("--E", type=int, default=4096, help="batch size of --eager")
+    ap.add_argument("--label", default="", help="copied into the line of --eager (A/B runs: MACJD_LIB names the library)")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    a.iters = a.iters or (2000 if a.eager else 200)
+    if a.eager:
+        return eager_run(a.eager, a.E, a.iters, a.reps, a.out, a.label)
+    a.out = a.out or PATTERN_OUT
     if a.one:
         return pattern_run(a.one[0], int(a.one[1]), a.iters, a.reps, a.out)
     if a.pattern:

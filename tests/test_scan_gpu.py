@@ -193,15 +193,11 @@ def test_restatement_jammer_lobes_and_float32_actions(name):
         assert abs(d["bj"][1, 0] - d["bt"][0]) > 20.0
 
 
-@pytest.mark.parametrize("name", ["3j4r", "6j8r"])
-@pytest.mark.parametrize("pd32", ["1", "0"])
-def test_default_production_variants_vs_restatement(name, pd32, monkeypatch):
-    """Philox uniforms and float32 actions (the production variants): the restatement is driven with the same Philox
-    values (the oracle's generator); integer outputs bit-exact, rewards within 1e-5."""
+def _production_vs_model(name, monkeypatch, **options):
     sc = _sc(SCN[name])
     R, J, E = sc.num_radars, sc.num_jammers, 65
     lib = oracle_lib()
-    with _options(monkeypatch, MACJD_ENV_PD32=pd32):
+    with _options(monkeypatch, **options):
         env, m = _env(sc, E, seed=123), scan_model.ScanModel(sc, E)
         env.reset()
         rng = np.random.default_rng(3)
@@ -216,6 +212,20 @@ def test_default_production_variants_vs_restatement(name, pd32, monkeypatch):
             np.testing.assert_array_equal(term.cpu().numpy(), o["terminated"])
             assert env.beam_azimuth.cpu().numpy().tobytes() == o["theta_a"].tobytes()
             np.testing.assert_allclose(rew.cpu().numpy(), o["out"][:, 0], rtol=0, atol=1e-5)
+
+
+@pytest.mark.parametrize("name", ["3j4r", "6j8r"])
+@pytest.mark.parametrize("pd32", ["1", "0"])
+def test_default_production_variants_vs_restatement(name, pd32, monkeypatch):
+    """Philox uniforms and float32 actions (the production variants): the restatement is driven with the same Philox
+    values (the oracle's generator); integer outputs bit-exact, rewards within 1e-5."""
+    _production_vs_model(name, monkeypatch, MACJD_ENV_PD32=pd32)
+
+
+def test_ieee_division_production_variant_vs_restatement(monkeypatch):
+    """MACJD_ENV_REGULAR=0 under Philox uniforms and float32 actions: the production variant that keeps IEEE divisions and
+    every guard (the other tests of that switch supply uniforms, which selects the general variant); same bars."""
+    _production_vs_model("3j4r", monkeypatch, MACJD_ENV_REGULAR="0")
 
 
 # ---------------------------------------------------------------------------------------------------------------
