@@ -466,7 +466,9 @@ int macjd_gru_gates(const macjd_grugates_io* io, void* hip_stream);
  *
  * Supported: hyper_hidden_dim Hh = 128, mixing_embed_dim Em = 64 (the reference's sizes), n_agents J in {2, 3, 6, 12},
  * state_dim S <= 16 J (the shipped 2j/2r, 3j/4r, 6j/8r and 12j/16r scenarios; J = 12 runs both layers in passes); everything else returns
- * MACJD_EUNSUPPORTED and the caller keeps the unfused kernels.
+ * MACJD_EUNSUPPORTED and the caller keeps the unfused kernels.  Narrow states, S <= 16 (J - 1), run variants of the f32
+ * kernels that guard every first-layer weight load; with bf16 operands S <= 16 (J - 1) (even J: 16 (J - 2)) is
+ * unsupported (the entry points return MACJD_EUNSUPPORTED; macjd_mixer_fused_supported does not know the operand type).
  */
 typedef struct macjd_mixerf_io {
     int64_t M;                 /* rows */

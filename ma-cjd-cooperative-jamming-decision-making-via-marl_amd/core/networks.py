@@ -291,7 +291,8 @@ class QMixer(nn.Module):
 
     def fused_available(self, t) -> bool:
         return (self.fused and t.is_cuda and not torch.is_autocast_enabled()
-                and ops.mixer_fused_supported(self.n_agents, self.state_dim, self.hyper_hidden_dim, self.embed_dim))
+                and ops.mixer_fused_supported(self.n_agents, self.state_dim, self.hyper_hidden_dim, self.embed_dim,
+                                              bf16=self.bf16_hyper))
 
     def _first_layer_cat(self):
         """(W_cat [2Hh+2Em, S], b_cat) of the merged first layer: the flat-parameter views, the inference cache, or a

@@ -95,7 +95,11 @@ __device__ __forceinline__ f32x4 mx_mfma_bf16(const bf16x8& a, const bf16x8& b, 
 // every join, which serialised the ~50 fragment loads of a wave one L2 latency after the other (16 us per launch
 // instead of ~5).  RAGGED (K not a multiple of 16, e.g. S = 46): the last quad is four dword loads from clamped
 // addresses, zeroed past the row by selects (bf16 with NQ even: the last two quads, which share the last 32-k step).
-template <int NQ, bool RAGGED, bool BF = false>
+// RAGGED = 2 (narrow rows, K <= 16 (NQ - 1), no shipped size): the quads in front of the last reach past the row as well —
+// in the last rows past the matrix, where what they read meets zero activations but need not be finite — so EVERY quad
+// takes the clamped form.  A variant of its own (see mixerf_narrow), so that the kernels of the shipped sizes stay as
+// they are.
+template <int NQ, int RAGGED, bool BF = false>
 __device__ __forceinline__ void mx_load_frags(f32x4 (&dst)[NQ], const float* __restrict__ W, int K, int row, int g) {
     constexpr int NRAG = (BF && NQ % 2 == 0) ? 2 : 1;
     const float* p = W + (int64_t)row * K;
@@ -104,7 +108,7 @@ __device__ __forceinline__ void mx_load_frags(f32x4 (&dst)[NQ], const float* __r
         const int k0 = BF ? mx_kq<NQ>(Q, g) : 16 * Q + 4 * g;
         if (MX_ABL & 1) {
             dst[Q] = f32x4{(float)row, (float)g, 1.0f, 0.5f};
-        } else if (!RAGGED || Q < NQ - NRAG) {   // compile-time
+        } else if (RAGGED == 0 || (RAGGED == 1 && Q < NQ - NRAG)) {   // compile-time
             dst[Q] = *reinterpret_cast<const f32x4_u*>(p + k0);
         } else {
 #pragma unroll
@@ -189,7 +193,7 @@ struct MixerKeep {
 
 // m0 = first row of the tile, wave = this wave's index among the body's four (the training kernel runs two bodies side
 // by side in one eight-wave workgroup).  KEEP: hand the tiles / vectors above to the caller.
-template <int J, int SQ, bool SAVE, bool LATE2 = false, bool KEEP = false, bool BF = false>
+template <int J, int SQ, bool SAVE, bool LATE2 = false, bool KEEP = false, bool BF = false, bool NARROW = false>
 __device__ __forceinline__ void mixer_fused_forward_body(const macjd_mixerf_io& io, const int64_t m0, const int wave,
                                                          MixerFwdLds<SQ>& L, MixerKeep<J>* keep = nullptr) {
     constexpr int LDA = 16 * SQ + 8;
@@ -227,7 +231,7 @@ __device__ __forceinline__ void mixer_fused_forward_body(const macjd_mixerf_io& 
     const float bV2 = io.bV2[0];
     f32x4 B1[T1W][SQ], B2[J][MX_KQ2], Bf[MX_KQ2];
 #pragma unroll
-    for (int i = 0; i < T1W; ++i) mx_load_frags<SQ, true, BF>(B1[i], io.W1, S, 16 * (T1W * wave + i) + li, g);
+    for (int i = 0; i < T1W; ++i) mx_load_frags<SQ, NARROW ? 2 : 1, BF>(B1[i], io.W1, S, 16 * (T1W * wave + i) + li, g);
     auto load_second = [&]() {
 #pragma unroll
         for (int j = 0; j < J; ++j) mx_load_frags<MX_KQ2, false, BF>(B2[j], io.W2, MX_HH, j * MX_EM + 16 * wave + li, g);
@@ -354,21 +358,21 @@ __device__ __forceinline__ void mixer_fused_forward_body(const macjd_mixerf_io& 
 
 // (bf16 at J = 6: the bf16 copies of the operands push the fragments-up-front plan past the 512 registers — 20 B / lane
 // of scratch — so the second layers' fragments are requested behind the first layer, LATE2)
-template <int J, int SQ, bool SAVE, bool BF>
+template <int J, int SQ, bool SAVE, bool BF, bool NARROW>
 __global__ void __launch_bounds__(256) mixer_fused_forward_kernel(const macjd_mixerf_io io) {
     __shared__ MixerFwdLds<SQ> L;
-    mixer_fused_forward_body<J, SQ, SAVE, BF && J == 6, false, BF>(io, (int64_t)blockIdx.x * 16, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), L);
+    mixer_fused_forward_body<J, SQ, SAVE, BF && J == 6, false, BF, NARROW>(io, (int64_t)blockIdx.x * 16, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), L);
 }
 
 // blockIdx.y = 0: the mixer whose activations are saved for a backward (io_a), 1: the plain one (io_b)
-template <int J, int SQ, bool BF>
+template <int J, int SQ, bool BF, bool NARROW>
 __global__ void __launch_bounds__(256, (J <= 3) ? 2 : 1) mixer_fused_forward_pair_kernel(const macjd_mixerf_io io_a, const macjd_mixerf_io io_b) {
     __shared__ MixerFwdLds<SQ> L;
     const int64_t m0 = (int64_t)blockIdx.x * 16;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     constexpr bool LATE2 = (J <= 3) || (BF && J == 6);   // (bf16 at J = 6: see mixer_fused_forward_kernel)
-    if (blockIdx.y == 0) mixer_fused_forward_body<J, SQ, true, LATE2, false, BF>(io_a, m0, wave, L);
-    else mixer_fused_forward_body<J, SQ, false, LATE2, false, BF>(io_b, m0, wave, L);
+    if (blockIdx.y == 0) mixer_fused_forward_body<J, SQ, true, LATE2, false, BF, NARROW>(io_a, m0, wave, L);
+    else mixer_fused_forward_body<J, SQ, false, LATE2, false, BF, NARROW>(io_b, m0, wave, L);
 }
 
 // Backward (see the header): recompute the second layers from `act`, tail gradients, transposed second layers.
@@ -602,7 +606,7 @@ struct MixerTrainLds {
     float ys[16], tqs[16];   // eval Q_tot of row m0 + i, target Q_tot of row m0 + 1 + i
 };
 
-template <int J, bool BF>
+template <int J, bool BF, bool NARROW>
 __global__ void __launch_bounds__(512) mixer_fused_train_kernel(const macjd_mixerf_io io, const macjd_mixerf_io tio,
                                                                  const macjd_tdloss_io td, const float* __restrict__ tot_m) {
     constexpr int LDG = J * MX_EM + 8;
@@ -639,11 +643,11 @@ __global__ void __launch_bounds__(512) mixer_fused_train_kernel(const macjd_mixe
     MixerKeep<J> K;
     f32x4 D1[KQ1], Df[KQF];
     if (eval_half) {
-        mixer_fused_forward_body<J, J, true, true, true, BF>(io, m0, wave, L.ev, &K);
+        mixer_fused_forward_body<J, J, true, true, true, BF, NARROW>(io, m0, wave, L.ev, &K);
         if (wave == 0 && g == 0) L.ys[li] = K.y;
     } else {
         MixerKeep<J> Kt;
-        mixer_fused_forward_body<J, J, false, true, true, BF>(tio, m0 + 1, wave, L.tg, &Kt);
+        mixer_fused_forward_body<J, J, false, true, true, BF, NARROW>(tio, m0 + 1, wave, L.tg, &Kt);
         if (wave == 0 && g == 0) L.tqs[li] = Kt.y;
     }
     // transposed second-layer fragments of this wave's gout1 column tile n = 16 wave8 + li (B[k][n] = W2[k][n], k = 16 Q +
@@ -820,7 +824,7 @@ __device__ __forceinline__ void mx_wf_tile(const float* __restrict__ Hs, const f
     }
 }
 
-template <int J, int SQ, bool SAVE, int PJ, bool BF>
+template <int J, int SQ, bool SAVE, int PJ, bool BF, bool NARROW>
 __device__ __forceinline__ void mixer_fused_forward_wide_body(const macjd_mixerf_io& io, const int blk, MixerFwdLds<SQ>& L) {
     static_assert(J % PJ == 0, "whole passes");
     constexpr int LDA = 16 * SQ + 8;
@@ -859,9 +863,9 @@ __device__ __forceinline__ void mixer_fused_forward_wide_body(const macjd_mixerf
     // first-layer fragments of passes 0 and 1 (the third pass re-uses the first buffer)
     f32x4 B1a[P1W][SQ], B1b[P1W][SQ];
 #pragma unroll
-    for (int i = 0; i < P1W; ++i) mx_load_frags<SQ, true, BF>(B1a[i], io.W1, S, 16 * (T1W * wave + i) + li, g);
+    for (int i = 0; i < P1W; ++i) mx_load_frags<SQ, NARROW ? 2 : 1, BF>(B1a[i], io.W1, S, 16 * (T1W * wave + i) + li, g);
 #pragma unroll
-    for (int i = 0; i < P1W; ++i) mx_load_frags<SQ, true, BF>(B1b[i], io.W1, S, 16 * (T1W * wave + P1W + i) + li, g);
+    for (int i = 0; i < P1W; ++i) mx_load_frags<SQ, NARROW ? 2 : 1, BF>(B1b[i], io.W1, S, 16 * (T1W * wave + P1W + i) + li, g);
     float qv[4][J];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -943,7 +947,7 @@ __device__ __forceinline__ void mixer_fused_forward_wide_body(const macjd_mixerf
     };
     first_layer_pass(B1a, 0);
 #pragma unroll
-    for (int i = 0; i < P1W; ++i) mx_load_frags<SQ, true, BF>(B1a[i], io.W1, S, 16 * (T1W * wave + 2 * P1W + i) + li, g);
+    for (int i = 0; i < P1W; ++i) mx_load_frags<SQ, NARROW ? 2 : 1, BF>(B1a[i], io.W1, S, 16 * (T1W * wave + 2 * P1W + i) + li, g);
     // second-layer fragments of the first agent pass and of w_final: in flight under the rest of phase 1
     f32x4 B2a[PJ][MX_KQ2], B2b[PJ][MX_KQ2], Bf[MX_KQ2];
     mx_load_pass<PJ, BF>(B2a, io.W2, 0, wave, li, g);
@@ -990,17 +994,17 @@ __device__ __forceinline__ void mixer_fused_forward_wide_body(const macjd_mixerf
     }
 }
 
-template <int J, int SQ, bool SAVE, int PJ, bool BF>
+template <int J, int SQ, bool SAVE, int PJ, bool BF, bool NARROW>
 __global__ void __launch_bounds__(256) mixer_fused_forward_wide_kernel(const macjd_mixerf_io io) {
     __shared__ MixerFwdLds<SQ> L;
-    mixer_fused_forward_wide_body<J, SQ, SAVE, PJ, BF>(io, blockIdx.x, L);
+    mixer_fused_forward_wide_body<J, SQ, SAVE, PJ, BF, NARROW>(io, blockIdx.x, L);
 }
 
-template <int J, int SQ, int PJ, bool BF>
+template <int J, int SQ, int PJ, bool BF, bool NARROW>
 __global__ void __launch_bounds__(256) mixer_fused_forward_wide_pair_kernel(const macjd_mixerf_io io_a, const macjd_mixerf_io io_b) {
     __shared__ MixerFwdLds<SQ> L;
-    if (blockIdx.y == 0) mixer_fused_forward_wide_body<J, SQ, true, PJ, BF>(io_a, blockIdx.x, L);
-    else mixer_fused_forward_wide_body<J, SQ, false, PJ, BF>(io_b, blockIdx.x, L);
+    if (blockIdx.y == 0) mixer_fused_forward_wide_body<J, SQ, true, PJ, BF, NARROW>(io_a, blockIdx.x, L);
+    else mixer_fused_forward_wide_body<J, SQ, false, PJ, BF, NARROW>(io_b, blockIdx.x, L);
 }
 
 template <int J, int PJ, bool TD, bool BF>
@@ -1239,12 +1243,23 @@ __global__ void __launch_bounds__(256) mixer_fused_backward_wide_kernel(const ma
     }
 }
 
+// Narrow state rows: S so small that first-layer fragment quads in front of the last one reach past a row of W1
+// (mx_load_frags, RAGGED = 2).  No shipped scenario is (S = 24 / 46 / 92 / 184 at J = 2 / 3 / 6 / 12): those keep the kernels
+// that load whole quads there.
+static bool mixerf_narrow(const macjd_mixerf_io* io) {
+    const int nrag = (io->operand_dtype && io->J % 2 == 0) ? 2 : 1;   // NRAG of mx_load_frags
+    return io->S <= 16 * (io->J - nrag);
+}
+// (only the f32 operand type has NARROW instantiations: mixerf_check turns narrow rows away at bf16)
+
 static int mixerf_check(const macjd_mixerf_io* io, bool backward, bool gy_from_td = false) {
     if (!io) return set_err(MACJD_EINVAL, "%s", "macjd_mixer_fused: NULL io");
     if (io->operand_dtype != 0 && io->operand_dtype != 1)
         return set_err(MACJD_EINVAL, "%s", "macjd_mixer_fused: operand_dtype must be 0 (f32) or 1 (bf16)");
     if (!macjd_mixer_fused_supported(io->J, io->S, io->Hh, io->Em))
         return set_err(MACJD_EUNSUPPORTED, "%s", "macjd_mixer_fused: unsupported J / S / Hh / Em (see include/macjd_nets.h)");
+    if (io->operand_dtype == 1 && mixerf_narrow(io))
+        return set_err(MACJD_EUNSUPPORTED, "%s", "macjd_mixer_fused: bf16 operands need S > 16 (J - 1) (even J: 16 (J - 2)), see include/macjd_nets.h");
     if (io->M < 0 || !io->q || !io->W2 || !io->b2 || !io->Wf2 || !io->bf2 || !io->wV2 || !io->bV2)
         return set_err(MACJD_EINVAL, "%s", "macjd_mixer_fused: bad M / NULL input");
     if (!backward) {
@@ -1260,28 +1275,28 @@ static int mixerf_check(const macjd_mixerf_io* io, bool backward, bool gy_from_t
     return MACJD_OK;
 }
 
-// launches of one operand type (the entry points below have checked the arguments)
-template <bool BF>
+// launches of one operand type and row kind (the entry points below have checked the arguments)
+template <bool BF, bool NARROW>
 static void mixerf_launch_forward(const macjd_mixerf_io* io, dim3 grid, dim3 block, hipStream_t s) {
 #define MACJD_MXF(J_, SQ_)                                                                                          \
     do {                                                                                                            \
-        if (io->save) hipLaunchKernelGGL((mixer_fused_forward_kernel<J_, SQ_, true, BF>), grid, block, 0, s, *io);  \
-        else hipLaunchKernelGGL((mixer_fused_forward_kernel<J_, SQ_, false, BF>), grid, block, 0, s, *io);          \
+        if (io->save) hipLaunchKernelGGL((mixer_fused_forward_kernel<J_, SQ_, true, BF, NARROW>), grid, block, 0, s, *io);  \
+        else hipLaunchKernelGGL((mixer_fused_forward_kernel<J_, SQ_, false, BF, NARROW>), grid, block, 0, s, *io);          \
     } while (0)
     if (io->J == 2) MACJD_MXF(2, 2);
     else if (io->J == 3) MACJD_MXF(3, 3);
     else if (io->J == 6) MACJD_MXF(6, 6);
-    else if (io->save) hipLaunchKernelGGL((mixer_fused_forward_wide_kernel<12, 12, true, 4, BF>), grid, block, 0, s, *io);
-    else hipLaunchKernelGGL((mixer_fused_forward_wide_kernel<12, 12, false, 4, BF>), grid, block, 0, s, *io);
+    else if (io->save) hipLaunchKernelGGL((mixer_fused_forward_wide_kernel<12, 12, true, 4, BF, NARROW>), grid, block, 0, s, *io);
+    else hipLaunchKernelGGL((mixer_fused_forward_wide_kernel<12, 12, false, 4, BF, NARROW>), grid, block, 0, s, *io);
 #undef MACJD_MXF
 }
 
-template <bool BF>
+template <bool BF, bool NARROW>
 static void mixerf_launch_pair(const macjd_mixerf_io* saved, const macjd_mixerf_io* plain, dim3 grid, dim3 block, hipStream_t s) {
-    if (saved->J == 2) hipLaunchKernelGGL((mixer_fused_forward_pair_kernel<2, 2, BF>), grid, block, 0, s, *saved, *plain);
-    else if (saved->J == 3) hipLaunchKernelGGL((mixer_fused_forward_pair_kernel<3, 3, BF>), grid, block, 0, s, *saved, *plain);
-    else if (saved->J == 6) hipLaunchKernelGGL((mixer_fused_forward_pair_kernel<6, 6, BF>), grid, block, 0, s, *saved, *plain);
-    else hipLaunchKernelGGL((mixer_fused_forward_wide_pair_kernel<12, 12, 4, BF>), grid, block, 0, s, *saved, *plain);
+    if (saved->J == 2) hipLaunchKernelGGL((mixer_fused_forward_pair_kernel<2, 2, BF, NARROW>), grid, block, 0, s, *saved, *plain);
+    else if (saved->J == 3) hipLaunchKernelGGL((mixer_fused_forward_pair_kernel<3, 3, BF, NARROW>), grid, block, 0, s, *saved, *plain);
+    else if (saved->J == 6) hipLaunchKernelGGL((mixer_fused_forward_pair_kernel<6, 6, BF, NARROW>), grid, block, 0, s, *saved, *plain);
+    else hipLaunchKernelGGL((mixer_fused_forward_wide_pair_kernel<12, 12, 4, BF, NARROW>), grid, block, 0, s, *saved, *plain);
 }
 
 template <bool TD, bool BF>
@@ -1293,11 +1308,11 @@ static void mixerf_launch_backward(const macjd_mixerf_io* io, const macjd_tdloss
     else hipLaunchKernelGGL((mixer_fused_backward_wide_kernel<12, 4, TD, BF>), grid, block, 0, s, *io, td, tot_m);
 }
 
-template <bool BF>
+template <bool BF, bool NARROW>
 static void mixerf_launch_train(const macjd_mixerf_io* eval, const macjd_mixerf_io* target, const macjd_tdloss_io* td,
                                 const float* tot_m, dim3 grid, dim3 block, hipStream_t s) {
-    if (eval->J == 2) hipLaunchKernelGGL((mixer_fused_train_kernel<2, BF>), grid, block, 0, s, *eval, *target, *td, tot_m);
-    else hipLaunchKernelGGL((mixer_fused_train_kernel<3, BF>), grid, block, 0, s, *eval, *target, *td, tot_m);
+    if (eval->J == 2) hipLaunchKernelGGL((mixer_fused_train_kernel<2, BF, NARROW>), grid, block, 0, s, *eval, *target, *td, tot_m);
+    else hipLaunchKernelGGL((mixer_fused_train_kernel<3, BF, NARROW>), grid, block, 0, s, *eval, *target, *td, tot_m);
 }
 
 }  // namespace macjd
@@ -1314,8 +1329,9 @@ extern "C" int macjd_mixer_fused_forward(const macjd_mixerf_io* io, void* hip_st
     if (io->M == 0) return MACJD_OK;
     const dim3 grid((unsigned)((io->M + 15) / 16)), block(256);
     hipStream_t s = (hipStream_t)hip_stream;
-    if (io->operand_dtype) mixerf_launch_forward<true>(io, grid, block, s);
-    else mixerf_launch_forward<false>(io, grid, block, s);
+    const bool narrow = mixerf_narrow(io);
+    if (io->operand_dtype) mixerf_launch_forward<true, false>(io, grid, block, s);
+    else narrow ? mixerf_launch_forward<false, true>(io, grid, block, s) : mixerf_launch_forward<false, false>(io, grid, block, s);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_mixer_fused_forward: %s", hipGetErrorString(err));
     return MACJD_OK;
@@ -1335,8 +1351,9 @@ extern "C" int macjd_mixer_fused_forward_pair(const macjd_mixerf_io* saved, cons
     if (saved->M == 0) return MACJD_OK;
     const dim3 grid((unsigned)((saved->M + 15) / 16), 2), block(256);
     hipStream_t s = (hipStream_t)hip_stream;
-    if (saved->operand_dtype) mixerf_launch_pair<true>(saved, plain, grid, block, s);
-    else mixerf_launch_pair<false>(saved, plain, grid, block, s);
+    const bool narrow = mixerf_narrow(saved);
+    if (saved->operand_dtype) mixerf_launch_pair<true, false>(saved, plain, grid, block, s);
+    else narrow ? mixerf_launch_pair<false, true>(saved, plain, grid, block, s) : mixerf_launch_pair<false, false>(saved, plain, grid, block, s);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_mixer_fused_forward_pair: %s", hipGetErrorString(err));
     return MACJD_OK;
@@ -1402,8 +1419,9 @@ extern "C" int macjd_mixer_fused_train(const macjd_mixerf_io* eval, const macjd_
     if (eval->M == 0) return MACJD_OK;
     const dim3 grid((unsigned)((eval->M + 15) / 16)), block(512);
     hipStream_t s = (hipStream_t)hip_stream;
-    if (eval->operand_dtype) mixerf_launch_train<true>(eval, target, td, tot_m, grid, block, s);
-    else mixerf_launch_train<false>(eval, target, td, tot_m, grid, block, s);
+    const bool narrow = mixerf_narrow(eval);
+    if (eval->operand_dtype) mixerf_launch_train<true, false>(eval, target, td, tot_m, grid, block, s);
+    else narrow ? mixerf_launch_train<false, true>(eval, target, td, tot_m, grid, block, s) : mixerf_launch_train<false, false>(eval, target, td, tot_m, grid, block, s);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_mixer_fused_train: %s", hipGetErrorString(err));
     return MACJD_OK;

@@ -650,7 +650,10 @@ def mixer_tail(q, w1_raw, b1_raw, wf_raw, v_raw):
 
 # ---------------------------------------------------------------------------------------------
 # The whole mixer as one MFMA chain per direction (csrc/macjd_mixer.hip, include/macjd_nets.h: macjd_mixerf_io)
-def mixer_fused_supported(J: int, S: int, Hh: int, Em: int) -> bool:
+def mixer_fused_supported(J: int, S: int, Hh: int, Em: int, bf16: bool = False) -> bool:
+    """The fused mixer covers this size (``bf16``: with bf16 operands, which need S > 16 (J - 1), even J: 16 (J - 2))."""
+    if bf16 and S <= 16 * (J - (2 if J % 2 == 0 else 1)):
+        return False
     return bool(_native.load().macjd_mixer_fused_supported(int(J), int(S), int(Hh), int(Em)))
 
 
