@@ -518,6 +518,30 @@ int macjd_mixer_fused_backward_td(const macjd_mixerf_io* io, const macjd_tdloss_
    with td->gy = NULL after this launch).  J in {2, 3}; other J return MACJD_EINVAL. */
 int macjd_mixer_fused_train(const macjd_mixerf_io* eval, const macjd_mixerf_io* target, const macjd_tdloss_io* td,
                             const float* tot_m, void* hip_stream);
+/* macjd_mixer_fused_train for episodes whose STATE does not change in time: every row (b, t) of `eval->s` that the loss
+   reaches (t < Tm1) equals row (b, 0) — the caller's promise, not checked; rows t >= Tm1 get zero gradient, so what they
+   hold does not matter (a full-length episode's row T is zeros).  The hyper-networks read only the state, so the `inp` operand of
+   each of the mixer's five weight-gradient products (sn, xhat, three column blocks of act) repeats within an episode and
+   dW = sum_m g[m]^T x[m] = sum_tiles (sum of the tile's rows of g)^T x[tile], provided no 16-row tile straddles two
+   episodes.  Row mapping: T1 = td->gy_cols rows per episode, TPE = ceil(T1 / 16); workgroup b * TPE + k owns rows
+   t = 16 k .. 16 k + 15 of episode b; rows t >= T1 are dead (loads clamped, nothing stored, gradient operands exact zeros).
+   eval->y, target->y (rows >= 1) and eval->gq are written per row and equal macjd_mixer_fused_train bit for bit.  The
+   operands of the weight-gradient products are written compact, n_tiles = B * TPE rows: sn / xhat / act hold the tile's
+   row 0, the four *_sum buffers the sum over the tile's rows of what macjd_mixer_fused_train writes per row (fixed
+   summation order, no atomics: deterministic; order in csrc/macjd_mixer.hip).  K = n_tiles in macjd_linear_wgrad_many.
+   The per-row forms are NOT written: eval->sn / xhat / act / gout1 / g_w1raw / g_wfraw / g_v must be NULL (MACJD_EINVAL
+   otherwise, as for M != B * gy_cols, J not in {2, 3}, differing operand types and a NULL compact pointer). */
+typedef struct macjd_mixer_static_io {
+    int64_t n_tiles;           /* B * ceil(gy_cols / 16) */
+    float* sn; float* xhat;    /* [n_tiles, S] */
+    float* act;                /* [n_tiles, 2Hh+2Em], 16-byte aligned */
+    float* gout1_sum;          /* [n_tiles, 2Hh+2Em] */
+    float* g_w1raw_sum;        /* [n_tiles, J Em]    */
+    float* g_wfraw_sum;        /* [n_tiles, Em]      */
+    float* g_v_sum;            /* [n_tiles]          */
+} macjd_mixer_static_io;
+int macjd_mixer_fused_train_static(const macjd_mixerf_io* eval, const macjd_mixerf_io* target, const macjd_tdloss_io* td,
+                                   const float* tot_m, const macjd_mixer_static_io* st, void* hip_stream);
 
 /*
  * The agent side of a WHOLE episode batch in one launch: for t = 0 .. T-1 and every (env, agent) row

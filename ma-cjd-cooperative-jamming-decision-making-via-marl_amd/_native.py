@@ -29,7 +29,7 @@ EXPORTS = [
     "macjd_mixer_fused_supported", "macjd_mixer_fused_forward", "macjd_mixer_fused_backward", "macjd_mixer_fused_backward_td", "macjd_td_mask_sum",
     "macjd_agent_episode_supported", "macjd_agent_episode", "macjd_env_step_many", "macjd_env_step_many_timed",
     "macjd_qhead_double_q_supported", "macjd_qhead_double_q", "macjd_qhead_taken_supported", "macjd_qhead_taken",
-    "macjd_qheads_pair", "macjd_mixer_fused_forward_pair", "macjd_mixer_fused_train",
+    "macjd_qheads_pair", "macjd_mixer_fused_forward_pair", "macjd_mixer_fused_train", "macjd_mixer_fused_train_static",
     "macjd_scenario_set_scan", "macjd_env_step_scan", "macjd_env_reset_scan",
     "macjd_agent_env_episode_scan_supported", "macjd_agent_env_episode_scan",
     "macjd_scenario_set_scan_pattern",
@@ -152,6 +152,15 @@ class MixerFusedIO(ctypes.Structure):
         ("y", ctypes.c_void_p), ("sn", ctypes.c_void_p), ("xhat", ctypes.c_void_p), ("act", ctypes.c_void_p),
         ("gy", ctypes.c_void_p), ("gq", ctypes.c_void_p), ("gout1", ctypes.c_void_p), ("g_w1raw", ctypes.c_void_p),
         ("g_wfraw", ctypes.c_void_p), ("g_v", ctypes.c_void_p),
+    ]
+
+
+class MixerStaticIO(ctypes.Structure):
+    """ctypes mirror of ``macjd_mixer_static_io`` (include/macjd_nets.h)."""
+    _fields_ = [
+        ("n_tiles", ctypes.c_int64), ("sn", ctypes.c_void_p), ("xhat", ctypes.c_void_p), ("act", ctypes.c_void_p),
+        ("gout1_sum", ctypes.c_void_p), ("g_w1raw_sum", ctypes.c_void_p), ("g_wfraw_sum", ctypes.c_void_p),
+        ("g_v_sum", ctypes.c_void_p),
     ]
 
 
@@ -419,6 +428,9 @@ def load() -> ctypes.CDLL:
     lib.macjd_mixer_fused_train.restype = ctypes.c_int
     lib.macjd_mixer_fused_train.argtypes = [ctypes.POINTER(MixerFusedIO), ctypes.POINTER(MixerFusedIO), ctypes.POINTER(TdLossIO),
                                             ctypes.c_void_p, ctypes.c_void_p]
+    lib.macjd_mixer_fused_train_static.restype = ctypes.c_int
+    lib.macjd_mixer_fused_train_static.argtypes = [ctypes.POINTER(MixerFusedIO), ctypes.POINTER(MixerFusedIO), ctypes.POINTER(TdLossIO),
+                                                   ctypes.c_void_p, ctypes.POINTER(MixerStaticIO), ctypes.c_void_p]
     lib.macjd_td_mask_sum.restype = ctypes.c_int
     lib.macjd_td_mask_sum.argtypes = [ctypes.POINTER(TdLossIO), ctypes.c_void_p, ctypes.c_void_p]
     lib.macjd_qhead_taken_supported.restype = ctypes.c_int

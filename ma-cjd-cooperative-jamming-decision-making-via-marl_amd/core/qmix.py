@@ -443,6 +443,11 @@ class QMixLearner:
             tot_m = prefetched[2] if len(prefetched) > 2 else None
             # both mixers, the loss's gradient and the eval mixer's backward as one launch (ops.pair_mixer_train_with_next_fused)
             mixer_train = tot_m is not None and options.on("MIXER_TRAIN") and J in (2, 3)
+            # ... on a buffer that certifies static states (EpisodeReplayBuffer.state_static) with the mixer's weight-gradient
+            # operands summed per 16-row tile of one episode (ops._mixer_train)
+            mixer_static = (mixer_train and obs_static and bool(getattr(self, "_g_state_static", False))
+                            and options.on("MIXER_STATIC_STATE"))
+            self._g_mixer_static = mixer_static   # bookkeeping: what the (captured) update's mixer launch is
             train_gy = None
             try:   # (an argument block that a raising call leaves behind must not ride in a later, unrelated launch)
                 with torch.no_grad():
@@ -464,7 +469,8 @@ class QMixLearner:
                     if mixer_train:
                         target_q_tot, train_gy = self.target_qmix_net.forward_paired_with_next_fused(
                             tq_agents, st["state"], td=dict(reward=st["reward"], terminated=st["terminated"], filled=st["filled"],
-                                                            gamma=self.args.gamma, Tm1=T - 1, tot_m=tot_m))
+                                                            gamma=self.args.gamma, Tm1=T - 1, tot_m=tot_m,
+                                                            static_rows=mixer_static))
                     else:
                         target_q_tot = self.target_qmix_net.forward_paired_with_next_fused(tq_agents, st["state"])
                 eval_q_tot = self.eval_qmix_net(q_taken, st["state"])                           # qmix.py:151, 187
@@ -708,6 +714,10 @@ class QMixLearner:
         self._g_buffer, self._g_B, self._g_T = buffer, int(batch_size), int(buffer.episode_limit)
         # static observations in every stored episode (see _forward_backward_full): baked into the captured launches
         self._g_obs_static = bool(getattr(buffer, "obs_static", False)) and options.on("LEARNER_STATIC_OBS")
+        # static states too (the mixer's hyper-networks read only the state): the buffer's own certificate, under the same
+        # switch-off rule as the observations — a single stored episode clears both flags, and train_from_buffer refuses
+        self._g_state_static = self._g_obs_static and bool(getattr(buffer, "state_static", False))
+        self._g_mixer_static = False   # set by the update that takes the static-state mixer launch (_forward_backward_full)
         # the actor rows of each sequence's observation ride in the scan launch's prologue (MACJD_ACTOR_IN_SCAN=0: the
         # actor chain as its own launch on the origin stream)
         self._g_actor_in_scan = options.on("ACTOR_IN_SCAN")

@@ -20,6 +20,11 @@
 // whole chain waits for memory once.  ~200 VGPRs of fragments at 3j/4r; one wave per SIMD has 512.
 // Numerics: v_mfma_f32_16x16x4_f32 is an exact-f32 fmaf chain; the tail uses the same expressions (fmaf chain over the
 // agents starting from clamp(b1), expm1f) as mixer_tail_kernel.
+// Training.  The learner update's two forwards, the TD gradient and the backward are ONE launch (mixer_fused_train_kernel).
+// It writes what the five weight-gradient products of macjd_wgrad.hip read: per row (1 117 floats a row at J = 3: 14.4 MB
+// at M = 3232, K = 3232 in the split-K pass), or — STATIC, episodes whose state does not change in time — per 16-row tile
+// of ONE episode: the tile's row 0 of sn / xhat / act and the tile's SUMS of gout1 / g_w1raw / g_wfraw / g_v, formed on
+// chip in a fixed order (7 tiles x 32 episodes = 224 rows instead of 3232: under 1 MB, K = 224).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -192,10 +197,11 @@ struct MixerKeep {
 };
 
 // m0 = first row of the tile, wave = this wave's index among the body's four (the training kernel runs two bodies side
-// by side in one eight-wave workgroup).  KEEP: hand the tiles / vectors above to the caller.
-template <int J, int SQ, bool SAVE, bool LATE2 = false, bool KEEP = false, bool BF = false, bool NARROW = false>
+// by side in one eight-wave workgroup).  KEEP: hand the tiles / vectors above to the caller.  TILE (with SAVE): sn / xhat /
+// act are [n_tiles, ...] and get ONE row, this tile's row 0, at row `tile` (the static-state training launch).
+template <int J, int SQ, bool SAVE, bool LATE2 = false, bool KEEP = false, bool BF = false, bool NARROW = false, bool TILE = false>
 __device__ __forceinline__ void mixer_fused_forward_body(const macjd_mixerf_io& io, const int64_t m0, const int wave,
-                                                         MixerFwdLds<SQ>& L, MixerKeep<J>* keep = nullptr) {
+                                                         MixerFwdLds<SQ>& L, MixerKeep<J>* keep = nullptr, const int64_t tile = 0) {
     constexpr int LDA = 16 * SQ + 8;
     constexpr int T1W = MX_N1 / 16 / 4;   // 6 first-layer column tiles per wave
     auto& As = L.As;
@@ -273,7 +279,12 @@ __device__ __forceinline__ void mixer_fused_forward_body(const macjd_mixerf_io& 
             const float xh = live ? (x[c] - mean) * rstd : 0.0f;
             const float v = live ? xh * lnw[c] + lnb[c] : 0.0f;               // pad columns: 0 (they meet zero fragments)
             As[row * LDA + col] = v;
-            if (SAVE && live && m < io.M) {
+            if constexpr (TILE) {
+                if (SAVE && live && row == 0) {
+                    io.sn[tile * S + col] = v;
+                    io.xhat[tile * S + col] = xh;
+                }
+            } else if (SAVE && live && m < io.M) {
                 io.sn[m * S + col] = v;
                 io.xhat[m * S + col] = xh;
             }
@@ -314,7 +325,9 @@ __device__ __forceinline__ void mixer_fused_forward_body(const macjd_mixerf_io& 
                 float v = acc[i][r] + b1v[i];
                 v = (col < MX_RELU) ? fmaxf(v, 0.0f) : v;
                 Hs[row * MX_LDH + col] = v;
-                if (SAVE && m0 + row < io.M) io.act[(m0 + row) * MX_N1 + col] = v;
+                if constexpr (TILE) {
+                    if (SAVE && row == 0) io.act[tile * MX_N1 + col] = v;
+                } else if (SAVE && m0 + row < io.M) io.act[(m0 + row) * MX_N1 + col] = v;
             }
         }
     }
@@ -596,6 +609,18 @@ __global__ void __launch_bounds__(256) mixer_fused_backward_kernel(const macjd_m
 //   waves 0-7  one column tile each of the transposed second-layer products (gout1's first 2 Hh columns; the backward
 //              kernel's four waves do two each), dL/dq, the V head's outer product.
 // Every output is the same expression in the same order as the pair + backward launches: bit-identical.
+//
+// STATIC (macjd_mixer_fused_train_static): the state, hence sn / xhat / act, is the same in every row of an episode, so a
+// weight gradient sum_m g[m]^T x[m] is sum_tiles (sum of the tile's g rows)^T x[tile] as long as no tile straddles two
+// episodes.  Workgroup b * TPE + k (TPE = ceil(T1 / 16), T1 = td.gy_cols) owns rows t = 16 k .. 16 k + 15 of episode b; rows
+// with t >= T1 are dead: loads clamped into the episode (the target half's to the row behind it, which is where row
+// T1 - 1's target row lies), nothing stored, not `live` for the loss, so their gradient operands are exact zeros.  y, the
+// target's y and gq are per row, the same instruction sequence as above: bit-identical.  sn / xhat / act are [n_tiles, ...],
+// one row per tile taken from its row 0; gout1 / g_w1raw / g_wfraw / g_v are [n_tiles, ...] per-tile SUMS of the per-row
+// values above, each row under its own ReLU / clamp mask, in one fixed order and without atomics:
+//   g_w1raw, g_wfraw, g_v, gout1's V block   column sums over LDS rows 0, 1, .. 15
+//   gout1's h_w1 / h_wf / b1 blocks          accumulator-held: rows 4 g + (0, 1, 2, 3) in the lane, then + lane group g ^ 1,
+//                                            then + lane groups g ^ 2 (two xor shuffles)
 template <int J>
 struct MixerTrainLds {
     MixerFwdLds<J> ev, tg;
@@ -606,7 +631,7 @@ struct MixerTrainLds {
     float ys[16], tqs[16];   // eval Q_tot of row m0 + i, target Q_tot of row m0 + 1 + i
 };
 
-template <int J, bool BF, bool NARROW>
+template <int J, bool BF, bool NARROW, bool STATIC = false>
 __global__ void __launch_bounds__(512) mixer_fused_train_kernel(const macjd_mixerf_io io, const macjd_mixerf_io tio,
                                                                  const macjd_tdloss_io td, const float* __restrict__ tot_m) {
     constexpr int LDG = J * MX_EM + 8;
@@ -619,7 +644,16 @@ __global__ void __launch_bounds__(512) mixer_fused_train_kernel(const macjd_mixe
     const int wave = wave8 & 3;
     const bool eval_half = wave8 < 4;
     const int li = lane & 15, g = lane >> 4;
-    const int64_t m0 = (int64_t)blockIdx.x * 16;
+    // rows of this workgroup: [m0, m0 + 16) below Mev (eval) and [m0 + 1, m0 + 17) below Mtg (target)
+    const int64_t tile = blockIdx.x;
+    int64_t m0 = tile * 16, Mev = io.M, Mtg = io.M;
+    if constexpr (STATIC) {   // tile k of episode b: rows t = 16 k .. 16 k + 15 of that episode only, the rest of the tile is dead
+        const int T1 = (int)td.gy_cols, tpe = (T1 + 15) / 16;
+        const int b = (int)blockIdx.x / tpe, k = (int)blockIdx.x - b * tpe;
+        m0 = (int64_t)b * T1 + 16 * k;
+        Mev = (int64_t)(b + 1) * T1;
+        Mtg = Mev + 1 < io.M ? Mev + 1 : io.M;
+    }
     const float* Hs = L.ev.Hs;   // the eval mixer's first-layer output of the tile = `act`
 
     // the loss inputs of this lane's rows (4 g + r, and li for the V head), requested before the forward's loads
@@ -629,7 +663,7 @@ __global__ void __launch_bounds__(512) mixer_fused_train_kernel(const macjd_mixe
 #pragma unroll
         for (int r = 0; r < 5; ++r) {
             const int row = r < 4 ? 4 * g + r : li;
-            const int64_t mc = (m0 + row < io.M) ? m0 + row : io.M - 1;
+            const int64_t mc = (m0 + row < Mev) ? m0 + row : Mev - 1;
             const int cols = (int)td.gy_cols;
             const int b = (int)(mc / cols), t = (int)(mc - (int64_t)b * cols);
             const int tc = t < td.Tm1 ? t : td.Tm1 - 1;
@@ -643,11 +677,23 @@ __global__ void __launch_bounds__(512) mixer_fused_train_kernel(const macjd_mixe
     MixerKeep<J> K;
     f32x4 D1[KQ1], Df[KQF];
     if (eval_half) {
-        mixer_fused_forward_body<J, J, true, true, true, BF, NARROW>(io, m0, wave, L.ev, &K);
+        if constexpr (STATIC) {
+            macjd_mixerf_io eio = io;
+            eio.M = Mev;
+            mixer_fused_forward_body<J, J, true, true, true, BF, NARROW, true>(eio, m0, wave, L.ev, &K, tile);
+        } else {
+            mixer_fused_forward_body<J, J, true, true, true, BF, NARROW>(io, m0, wave, L.ev, &K);
+        }
         if (wave == 0 && g == 0) L.ys[li] = K.y;
     } else {
         MixerKeep<J> Kt;
-        mixer_fused_forward_body<J, J, false, true, true, BF, NARROW>(tio, m0 + 1, wave, L.tg, &Kt);
+        if constexpr (STATIC) {
+            macjd_mixerf_io etio = tio;
+            etio.M = Mtg;
+            mixer_fused_forward_body<J, J, false, true, true, BF, NARROW>(etio, m0 + 1, wave, L.tg, &Kt);
+        } else {
+            mixer_fused_forward_body<J, J, false, true, true, BF, NARROW>(tio, m0 + 1, wave, L.tg, &Kt);
+        }
         if (wave == 0 && g == 0) L.tqs[li] = Kt.y;
     }
     // transposed second-layer fragments of this wave's gout1 column tile n = 16 wave8 + li (B[k][n] = W2[k][n], k = 16 Q +
@@ -679,6 +725,7 @@ __global__ void __launch_bounds__(512) mixer_fused_train_kernel(const macjd_mixe
             gyv[r] = live[r] ? gv : 0.0f;
         }
         const int e = 16 * wave + li;
+        float gb1_sum = 0.0f;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int row = 4 * g + r;
@@ -697,7 +744,9 @@ __global__ void __launch_bounds__(512) mixer_fused_train_kernel(const macjd_mixe
             const float gwf = (wfr >= 0.0f && wfr <= 5.0f) ? gyv[r] * h : 0.0f;
             const float gb1 = (b1r >= -5.0f && b1r <= 5.0f) ? ghid : 0.0f;
             L.Gf[row * LDF + e] = gwf;
-            if (m < io.M) {
+            if constexpr (STATIC) {
+                gb1_sum = r == 0 ? gb1 : gb1_sum + gb1;
+            } else if (m < Mev) {
                 io.g_wfraw[m * MX_EM + e] = gwf;
                 io.gout1[m * MX_N1 + MX_RELU + e] = gb1;
             }
@@ -705,23 +754,28 @@ __global__ void __launch_bounds__(512) mixer_fused_train_kernel(const macjd_mixe
             for (int j = 0; j < J; ++j) {
                 const float gw = (w1r[j] >= 0.0f && w1r[j] <= 5.0f) ? ghid * K.qv[r][j] : 0.0f;
                 L.G1[row * LDG + j * MX_EM + e] = gw;
-                if (m < io.M) io.g_w1raw[m * (J * MX_EM) + j * MX_EM + e] = gw;
+                if (!STATIC && m < Mev) io.g_w1raw[m * (J * MX_EM) + j * MX_EM + e] = gw;
                 const float t = mx_sum16(ghid * mx_clamp(w1r[j], 0.0f, 5.0f));
                 if (li == 0) L.gq_part[wave][row][j] = t;
             }
+        }
+        if constexpr (STATIC) {   // the b1 block of gout1: this lane's four rows above, then the four lane groups
+            gb1_sum += __shfl_xor(gb1_sum, 16, 64);
+            gb1_sum += __shfl_xor(gb1_sum, 32, 64);
+            if (g == 0) io.gout1[tile * MX_N1 + MX_RELU + e] = gb1_sum;
         }
         if (wave == 0 && g == 0) {   // v = clamp(v_raw, -5, 5): row li
             const int64_t m = m0 + li;
             const float gv = (K.v_raw >= -5.0f && K.v_raw <= 5.0f) ? gyv[4] : 0.0f;
             L.gv_s[li] = gv;
-            if (m < io.M) io.g_v[m] = gv;
+            if (!STATIC && m < Mev) io.g_v[m] = gv;
         }
     }
     __syncthreads();
     // dL/dq: the four embed blocks' partial sums in fixed order
     if (threadIdx.x < 16 * J) {
         const int row = threadIdx.x / J, j = threadIdx.x - row * J;
-        if (m0 + row < io.M)
+        if (m0 + row < Mev)
             io.gq[(m0 + row) * J + j] = (L.gq_part[0][row][j] + L.gq_part[1][row][j]) + (L.gq_part[2][row][j] + L.gq_part[3][row][j]);
     }
     // input gradients of the second layers, masked by the first layer's ReLU: column tile n of [0, Hh) and of [Hh, 2 Hh)
@@ -749,22 +803,67 @@ __global__ void __launch_bounds__(512) mixer_fused_train_kernel(const macjd_mixe
             }
         }
         const int n = 16 * wave8 + li;
+        float s1 = 0.0f, sf = 0.0f;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int row = 4 * g + r;
             const int64_t m = m0 + row;
-            if (m < io.M) {
-                io.gout1[m * MX_N1 + n] = (Hs[row * MX_LDH + n] > 0.0f) ? a1[r] : 0.0f;
-                io.gout1[m * MX_N1 + MX_HH + n] = (Hs[row * MX_LDH + MX_HH + n] > 0.0f) ? af[r] : 0.0f;
+            const float v1 = (Hs[row * MX_LDH + n] > 0.0f) ? a1[r] : 0.0f;
+            const float vf = (Hs[row * MX_LDH + MX_HH + n] > 0.0f) ? af[r] : 0.0f;
+            if constexpr (STATIC) {
+                s1 = r == 0 ? v1 : s1 + v1;
+                sf = r == 0 ? vf : sf + vf;
+            } else if (m < Mev) {
+                io.gout1[m * MX_N1 + n] = v1;
+                io.gout1[m * MX_N1 + MX_HH + n] = vf;
             }
         }
+        if constexpr (STATIC) {   // this lane's four rows above, then the four lane groups
+            s1 += __shfl_xor(s1, 16, 64);
+            s1 += __shfl_xor(s1, 32, 64);
+            sf += __shfl_xor(sf, 16, 64);
+            sf += __shfl_xor(sf, 32, 64);
+            if (g == 0) {
+                io.gout1[tile * MX_N1 + n] = s1;
+                io.gout1[tile * MX_N1 + MX_HH + n] = sf;
+            }
+        }
+    }
+    if constexpr (STATIC) {
+        // column sums over the tile's LDS rows, row 0 first: g_w1raw / g_wfraw (threads 0 .. J Em + Em - 1), the V block of
+        // gout1 (threads 256 .. 256 + Em - 1, each row under its own ReLU mask) and g_v (thread 256 + Em)
+        const int c = threadIdx.x;
+        if (c < J * MX_EM) {
+            float s = L.G1[c];
+#pragma unroll
+            for (int row = 1; row < 16; ++row) s += L.G1[row * LDG + c];
+            io.g_w1raw[tile * (J * MX_EM) + c] = s;
+        } else if (c < J * MX_EM + MX_EM) {
+            const int cf = c - J * MX_EM;
+            float s = L.Gf[cf];
+#pragma unroll
+            for (int row = 1; row < 16; ++row) s += L.Gf[row * LDF + cf];
+            io.g_wfraw[tile * MX_EM + cf] = s;
+        } else if (c >= 256 && c < 256 + MX_EM) {
+            const int k = c - 256;   // wvo[0] = wV2[k]
+            float s = (Hs[2 * MX_HH + k] > 0.0f) ? L.gv_s[0] * wvo[0] : 0.0f;
+#pragma unroll
+            for (int row = 1; row < 16; ++row) s += (Hs[row * MX_LDH + 2 * MX_HH + k] > 0.0f) ? L.gv_s[row] * wvo[0] : 0.0f;
+            io.gout1[tile * MX_N1 + 2 * MX_HH + k] = s;
+        } else if (c == 256 + MX_EM) {
+            float s = L.gv_s[0];
+#pragma unroll
+            for (int row = 1; row < 16; ++row) s += L.gv_s[row];
+            io.g_v[tile] = s;
+        }
+        return;
     }
     // the V head's one-output second layer: outer product g_v wV2, masked: columns [2 Hh, 2 Hh + Em)
 #pragma unroll
     for (int i = 0; i < 16 * MX_EM / 512; ++i) {
         const int idx = threadIdx.x + 512 * i;
         const int row = idx / MX_EM, k = idx - row * MX_EM;
-        if (m0 + row < io.M)
+        if (m0 + row < Mev)
             io.gout1[(m0 + row) * MX_N1 + 2 * MX_HH + k] = (Hs[row * MX_LDH + 2 * MX_HH + k] > 0.0f) ? L.gv_s[row] * wvo[i] : 0.0f;
     }
 }
@@ -1315,6 +1414,38 @@ static void mixerf_launch_train(const macjd_mixerf_io* eval, const macjd_mixerf_
     else hipLaunchKernelGGL((mixer_fused_train_kernel<3, BF, NARROW>), grid, block, 0, s, *eval, *target, *td, tot_m);
 }
 
+template <bool BF, bool NARROW>
+static void mixerf_launch_train_static(const macjd_mixerf_io* eval, const macjd_mixerf_io* target, const macjd_tdloss_io* td,
+                                       const float* tot_m, dim3 grid, dim3 block, hipStream_t s) {
+    if (eval->J == 2) hipLaunchKernelGGL((mixer_fused_train_kernel<2, BF, NARROW, true>), grid, block, 0, s, *eval, *target, *td, tot_m);
+    else hipLaunchKernelGGL((mixer_fused_train_kernel<3, BF, NARROW, true>), grid, block, 0, s, *eval, *target, *td, tot_m);
+}
+
+// the argument checks the two training entry points share (`eval` with the output pointers its kernel writes through)
+static int mixerf_train_check(const char* fn, const macjd_mixerf_io* eval, const macjd_mixerf_io* target, const macjd_tdloss_io* td,
+                              const float* tot_m) {
+    int rc = mixerf_check(eval, false);
+    if (rc != MACJD_OK) return rc;
+    rc = mixerf_check(eval, true, true);
+    if (rc != MACJD_OK) return rc;
+    rc = mixerf_check(target, false);
+    if (rc != MACJD_OK) return rc;
+    if (!eval->save || target->save) return set_err(MACJD_EINVAL, "%s: the eval mixer saves, the target mixer does not", fn);
+    if (eval->J != target->J || eval->S != target->S || eval->M != target->M)
+        return set_err(MACJD_EINVAL, "%s: the two mixers differ in J / S / M", fn);
+    if (eval->operand_dtype != target->operand_dtype)
+        return set_err(MACJD_EINVAL, "%s: the two mixers differ in operand_dtype", fn);
+    if (eval->J != 2 && eval->J != 3) return set_err(MACJD_EINVAL, "%s: J must be 2 or 3", fn);
+    if (!td || !tot_m || td->B < 1 || td->Tm1 < 1 || !td->y || !td->tq || !td->reward || !td->terminated || !td->filled)
+        return set_err(MACJD_EINVAL, "%s: bad TD-loss argument", fn);
+    if (td->gy_cols < td->Tm1 + 1 || (int64_t)td->B * td->gy_cols != eval->M)
+        return set_err(MACJD_EINVAL, "%s: rows must be B x gy_cols with gy_cols > Tm1", fn);
+    // the loss reads eval row (b, t) and target row (b, t + 1) of the two outputs, which this launch keeps in LDS
+    if (td->y != eval->y || td->y_sb != td->gy_cols || td->tq != target->y + 1 || td->tq_sb != td->gy_cols)
+        return set_err(MACJD_EINVAL, "%s: td->y / td->tq must be eval->y / target->y + 1 with row pitch gy_cols", fn);
+    return MACJD_OK;
+}
+
 }  // namespace macjd
 
 extern "C" int macjd_mixer_fused_supported(int32_t J, int32_t S, int32_t Hh, int32_t Em) {
@@ -1397,25 +1528,8 @@ extern "C" int macjd_mixer_fused_backward_td(const macjd_mixerf_io* io, const ma
 extern "C" int macjd_mixer_fused_train(const macjd_mixerf_io* eval, const macjd_mixerf_io* target, const macjd_tdloss_io* td,
                                        const float* tot_m, void* hip_stream) {
     using namespace macjd;
-    int rc = mixerf_check(eval, false);
+    const int rc = mixerf_train_check("macjd_mixer_fused_train", eval, target, td, tot_m);
     if (rc != MACJD_OK) return rc;
-    rc = mixerf_check(eval, true, true);
-    if (rc != MACJD_OK) return rc;
-    rc = mixerf_check(target, false);
-    if (rc != MACJD_OK) return rc;
-    if (!eval->save || target->save) return set_err(MACJD_EINVAL, "%s", "macjd_mixer_fused_train: the eval mixer saves, the target mixer does not");
-    if (eval->J != target->J || eval->S != target->S || eval->M != target->M)
-        return set_err(MACJD_EINVAL, "%s", "macjd_mixer_fused_train: the two mixers differ in J / S / M");
-    if (eval->operand_dtype != target->operand_dtype)
-        return set_err(MACJD_EINVAL, "%s", "macjd_mixer_fused_train: the two mixers differ in operand_dtype");
-    if (eval->J != 2 && eval->J != 3) return set_err(MACJD_EINVAL, "%s", "macjd_mixer_fused_train: J must be 2 or 3");
-    if (!td || !tot_m || td->B < 1 || td->Tm1 < 1 || !td->y || !td->tq || !td->reward || !td->terminated || !td->filled)
-        return set_err(MACJD_EINVAL, "%s", "macjd_mixer_fused_train: bad TD-loss argument");
-    if (td->gy_cols < td->Tm1 + 1 || (int64_t)td->B * td->gy_cols != eval->M)
-        return set_err(MACJD_EINVAL, "%s", "macjd_mixer_fused_train: rows must be B x gy_cols with gy_cols > Tm1");
-    // the loss reads eval row (b, t) and target row (b, t + 1) of the two outputs, which this launch keeps in LDS
-    if (td->y != eval->y || td->y_sb != td->gy_cols || td->tq != target->y + 1 || td->tq_sb != td->gy_cols)
-        return set_err(MACJD_EINVAL, "%s", "macjd_mixer_fused_train: td->y / td->tq must be eval->y / target->y + 1 with row pitch gy_cols");
     if (eval->M == 0) return MACJD_OK;
     const dim3 grid((unsigned)((eval->M + 15) / 16)), block(512);
     hipStream_t s = (hipStream_t)hip_stream;
@@ -1424,5 +1538,34 @@ extern "C" int macjd_mixer_fused_train(const macjd_mixerf_io* eval, const macjd_
     else narrow ? mixerf_launch_train<false, true>(eval, target, td, tot_m, grid, block, s) : mixerf_launch_train<false, false>(eval, target, td, tot_m, grid, block, s);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_mixer_fused_train: %s", hipGetErrorString(err));
+    return MACJD_OK;
+}
+
+extern "C" int macjd_mixer_fused_train_static(const macjd_mixerf_io* eval, const macjd_mixerf_io* target, const macjd_tdloss_io* td,
+                                              const float* tot_m, const macjd_mixer_static_io* st, void* hip_stream) {
+    using namespace macjd;
+    const char* fn = "macjd_mixer_fused_train_static";
+    if (!eval || !st) return set_err(MACJD_EINVAL, "%s: NULL argument", fn);
+    if (!st->sn || !st->xhat || !st->act || !st->gout1_sum || !st->g_w1raw_sum || !st->g_wfraw_sum || !st->g_v_sum)
+        return set_err(MACJD_EINVAL, "%s: NULL compact output", fn);
+    // the per-row forms are not written here: a caller that passes one expects what this launch does not deliver
+    if (eval->sn || eval->xhat || eval->act || eval->gout1 || eval->g_w1raw || eval->g_wfraw || eval->g_v)
+        return set_err(MACJD_EINVAL, "%s: the per-row sn / xhat / act / gout1 / g_w1raw / g_wfraw / g_v must be NULL", fn);
+    // the kernel writes through the eval block's pointers: in this mode they are the [n_tiles, ...] buffers
+    macjd_mixerf_io ev = *eval;
+    ev.sn = st->sn; ev.xhat = st->xhat; ev.act = st->act;
+    ev.gout1 = st->gout1_sum; ev.g_w1raw = st->g_w1raw_sum; ev.g_wfraw = st->g_wfraw_sum; ev.g_v = st->g_v_sum;
+    const int rc = mixerf_train_check(fn, &ev, target, td, tot_m);
+    if (rc != MACJD_OK) return rc;
+    const int64_t n_tiles = (int64_t)td->B * ((td->gy_cols + 15) / 16);
+    if (st->n_tiles != n_tiles || n_tiles > 0x7fffffff)
+        return set_err(MACJD_EINVAL, "%s: n_tiles must be B x ceil(gy_cols / 16)", fn);
+    const dim3 grid((unsigned)n_tiles), block(512);
+    hipStream_t s = (hipStream_t)hip_stream;
+    const bool narrow = mixerf_narrow(&ev);
+    if (ev.operand_dtype) mixerf_launch_train_static<true, false>(&ev, target, td, tot_m, grid, block, s);
+    else narrow ? mixerf_launch_train_static<false, true>(&ev, target, td, tot_m, grid, block, s) : mixerf_launch_train_static<false, false>(&ev, target, td, tot_m, grid, block, s);
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_mixer_fused_train_static: %s", hipGetErrorString(err));
     return MACJD_OK;
 }

@@ -157,7 +157,7 @@ def _doubleq_io(h_eval, P_eval, head_eval, h_tgt, P_tgt, head_tgt, H, A, want_ar
 _PAIRED_DQ = None      # (macjd_doubleq_io, tensors kept alive, out) waiting for the next _QheadTaken.forward
 _PAIRED_MIXER = None   # (macjd_mixerf_io, tensors kept alive, y) waiting for the next saving mixer_fused_forward
 _PAIRED_TRAIN = None   # (target macjd_mixerf_io, macjd_tdloss_io, tensors kept alive, placeholder) waiting for the next
-                       # _FusedMixer.forward (pair_mixer_train_with_next_fused)
+                       # _FusedMixer.forward (pair_mixer_train_with_next_fused), static-rows marker
 
 
 def pair_double_q_with_next_taken(h_eval, P_eval, head_eval, h_tgt, P_tgt, head_tgt, H: int, A: int, p_row_map=None):
@@ -183,13 +183,14 @@ def pair_mixer_forward_with_next_fused(q, s, params):
     return y
 
 
-def pair_mixer_train_with_next_fused(q, s, params, reward, terminated, filled, gamma, Tm1, tot_m):
+def pair_mixer_train_with_next_fused(q, s, params, reward, terminated, filled, gamma, Tm1, tot_m, static_rows=False):
     """The target mixer ``mixer_fused_forward(q, s, params)``, the TD loss's gradient (``td_grad_in_mixer_backward``'s
     inputs with tq_off = 1) and the eval mixer's backward, all inside the launch of the NEXT differentiable ``mixer_fused``
     forward (macjd_mixer_fused_train): that forward's rows are [B, T1] with B = reward.shape[0].  Returns (target y [M, 1],
     placeholder): y is valid once that forward has run; the placeholder [B, T1, 1] is what the eval output's backward must
     be seeded with — its backward then only records the weight-gradient products.  The logged loss sums are the caller's
-    (``td_loss_sums_into``)."""
+    (``td_loss_sums_into``).  ``static_rows``: the caller vouches that the state rows of an episode are all equal — the launch
+    then writes the weight-gradient operands summed per 16-row tile of one episode (macjd_mixer_fused_train_static)."""
     global _PAIRED_TRAIN
     assert _PAIRED_TRAIN is None and _PAIRED_MIXER is None, "a paired mixer launch is already waiting"
     q, s = q.detach().float().contiguous(), _f32c(s.detach())
@@ -209,7 +210,7 @@ def pair_mixer_train_with_next_fused(q, s, params, reward, terminated, filled, g
     td.terminated, td.t_sb, td.t_st = terminated.data_ptr(), terminated.stride(0), terminated.stride(1)
     td.filled, td.f_sb, td.f_st = filled.data_ptr(), filled.stride(0), filled.stride(1)
     placeholder = torch.empty((B, T1, 1), dtype=torch.float32, device=q.device)   # never read
-    _PAIRED_TRAIN = (io, td, (q, s, params, reward, terminated, filled, tot_m, y), placeholder)
+    _PAIRED_TRAIN = (io, td, (q, s, params, reward, terminated, filled, tot_m, y), placeholder, bool(static_rows))
     return y, placeholder
 
 
@@ -806,9 +807,11 @@ class _FusedMixer(torch.autograd.Function):
 
 def _mixer_train(q, s, params, train):
     """macjd_mixer_fused_train with this (eval) mixer and the block of ``pair_mixer_train_with_next_fused``:
-    (y, q, (sn, xhat, act), (placeholder, (gq, gout1, g_w1raw, g_wfraw, g_v)))."""
+    (y, q, (sn, xhat, act), (placeholder, (gq, gout1, g_w1raw, g_wfraw, g_v))).  With the block's static-rows marker
+    (macjd_mixer_fused_train_static) sn / xhat / act and the four gradient operands are the compact [n_tiles, ...] forms: one
+    row, resp. the sum of the rows, per 16-row tile of one episode — ``_FusedMixer._wgrads`` takes either, K = rows."""
     lib = _native.load()
-    tio, td, keep, placeholder = train
+    tio, td, keep, placeholder, static_rows = train
     q, s = q.detach().float().contiguous(), _f32c(s.detach())
     M, S = s.shape
     J, dev = q.shape[1], q.device
@@ -816,19 +819,28 @@ def _mixer_train(q, s, params, train):
     y = torch.empty((M, 1), dtype=torch.float32, device=dev)
     io = _mixerf_io(q, s, params)
     width = 2 * io.Hh + 2 * io.Em
-    sn = torch.empty((M, S), dtype=torch.float32, device=dev)
-    xhat = torch.empty((M, S), dtype=torch.float32, device=dev)
-    act = torch.empty((M, width), dtype=torch.float32, device=dev)
+    R = td.B * ((td.gy_cols + 15) // 16) if static_rows else M   # rows of the weight-gradient operands
+    sn = torch.empty((R, S), dtype=torch.float32, device=dev)
+    xhat = torch.empty((R, S), dtype=torch.float32, device=dev)
+    act = torch.empty((R, width), dtype=torch.float32, device=dev)
     gq = torch.empty((M, J), dtype=torch.float32, device=dev)
-    gout1 = torch.empty((M, width), dtype=torch.float32, device=dev)
-    g_w1 = torch.empty((M, J * io.Em), dtype=torch.float32, device=dev)
-    g_wf = torch.empty((M, io.Em), dtype=torch.float32, device=dev)
-    g_v = torch.empty((M, 1), dtype=torch.float32, device=dev)
-    io.y, io.save, io.sn, io.xhat, io.act = y.data_ptr(), 1, sn.data_ptr(), xhat.data_ptr(), act.data_ptr()
-    io.gq, io.gout1 = gq.data_ptr(), gout1.data_ptr()
-    io.g_w1raw, io.g_wfraw, io.g_v = g_w1.data_ptr(), g_wf.data_ptr(), g_v.data_ptr()
+    gout1 = torch.empty((R, width), dtype=torch.float32, device=dev)
+    g_w1 = torch.empty((R, J * io.Em), dtype=torch.float32, device=dev)
+    g_wf = torch.empty((R, io.Em), dtype=torch.float32, device=dev)
+    g_v = torch.empty((R, 1), dtype=torch.float32, device=dev)
+    io.y, io.save, io.gq = y.data_ptr(), 1, gq.data_ptr()
     td.y = y.data_ptr()
     tot_m = keep[6]
+    if static_rows:
+        st = _native.MixerStaticIO()
+        st.n_tiles, st.sn, st.xhat, st.act = R, sn.data_ptr(), xhat.data_ptr(), act.data_ptr()
+        st.gout1_sum, st.g_w1raw_sum, st.g_wfraw_sum, st.g_v_sum = gout1.data_ptr(), g_w1.data_ptr(), g_wf.data_ptr(), g_v.data_ptr()
+        with torch.cuda.device(dev):
+            _native.check(lib.macjd_mixer_fused_train_static(ctypes.byref(io), ctypes.byref(tio), ctypes.byref(td), tot_m.data_ptr(),
+                                                             ctypes.byref(st), _stream(q)), "macjd_mixer_fused_train_static")
+        return y, q, (sn, xhat, act), (placeholder, (gq, gout1, g_w1, g_wf, g_v))
+    io.sn, io.xhat, io.act = sn.data_ptr(), xhat.data_ptr(), act.data_ptr()
+    io.gout1, io.g_w1raw, io.g_wfraw, io.g_v = gout1.data_ptr(), g_w1.data_ptr(), g_wf.data_ptr(), g_v.data_ptr()
     with torch.cuda.device(dev):
         _native.check(lib.macjd_mixer_fused_train(ctypes.byref(io), ctypes.byref(tio), ctypes.byref(td), tot_m.data_ptr(),
                                                   _stream(q)), "macjd_mixer_fused_train")

@@ -64,6 +64,11 @@ class EpisodeReplayBuffer:
         # (the batched runner says so when it stores; None = nothing stored yet).  The learner may then evaluate the
         # observation-only parts of the agent once per sampled episode instead of once per step.
         self.obs_static: Optional[bool] = None
+        # The same certificate for the ``state`` rows 0 .. T - 1 (the runner's ``_fill_static`` fills obs and state alike): the
+        # learner's mixer update then sums gradient operands over rows of an episode, which share a state
+        # (MACJD_MIXER_STATIC_STATE).  Only the storing calls set it: a caller that vouches for ``obs_static`` by hand has
+        # said nothing about the states.
+        self.state_static: Optional[bool] = None
         # which static (state / obs / avail_actions) content each slot already holds: a caller-chosen integer per
         # episode; a batched store skips re-copying those keys into slots that hold the very same content already
         self._static_tag = np.full(N, -1, dtype=np.int64)
@@ -83,7 +88,7 @@ class EpisodeReplayBuffer:
             print("Warning: EpisodeReplayBuffer expects batch_size=1 from runner")
         with self.lock:
             idx = int(self._get_storage_idx(inc=batch_size)[0])
-            self.obs_static = False          # nothing is known about a single stored episode
+            self.obs_static = self.state_static = False   # nothing is known about a single stored episode
             self._static_tag[idx] = -1
             ep = {k: v[0] for k, v in episode_batch.items()}
             L = int(ep["reward"].shape[0])
@@ -110,7 +115,8 @@ class EpisodeReplayBuffer:
         """E full-length episodes at once from the batched runner's TIME-MAJOR staging tensors
         (``stage[key]`` is [T(+1), E, ...] on this device): one transposing copy per key into a
         contiguous slot range (split in two when the ring wraps).  ``length`` < episode_limit pads like
-        ``store_episode``.  ``obs_static``: these episodes' observations are constant in time (see ``self.obs_static``).
+        ``store_episode``.  ``obs_static``: these episodes' observations and states are constant in time (see ``self.obs_static`` /
+        ``self.state_static``).
         ``static_tags`` (int64 [E], >= 0): identity of each episode's state / obs / avail_actions content — slots that
         already hold the same content (the same env's static rows, stored by an earlier rollout) are not rewritten,
         which saves the larger half of the store's traffic (obs + state + mask: 393 of 720 MB at 3j/4r, E = 4096)."""
@@ -119,6 +125,7 @@ class EpisodeReplayBuffer:
         with self.lock:
             idx = self._get_storage_idx(inc=n_episodes)
             self.obs_static = bool(obs_static) if self.obs_static is None else (self.obs_static and bool(obs_static))
+            self.state_static = bool(obs_static) if self.state_static is None else (self.state_static and bool(obs_static))
             runs = []  # contiguous (slot_lo, slot_hi, src_lo) runs
             start = 0
             for i in range(1, len(idx) + 1):
