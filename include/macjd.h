@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MACJD_ABI_VERSION 6
+#define MACJD_ABI_VERSION 7
 #define MACJD_PE_ROWS(R, J) (6 * (R) + 3 * (J) + (J) * (R))
 
 #define MACJD_OK          0

@@ -684,6 +684,44 @@ int macjd_qhead_double_q(const macjd_doubleq_io* io, void* hip_stream);
  * the caller launches macjd_qhead_double_q on its own. */
 int macjd_qheads_pair(const macjd_qtaken_io* taken, const macjd_doubleq_io* dq, void* hip_stream);
 
+/*
+ * Back-propagation through time of macjd_gru_sequence for ONE network: all T steps of the reverse chain for B*J
+ * independent sequences in one launch (the training counterpart of the scan; the reference never trains through its
+ * GRU unroll, so this has no line there).  The caller supplies the forward's inputs and outputs and the time-parallel
+ * product gh = W_hh h_{t-1} + b_hh for every step; the kernel recomputes the gates with the forward kernels' own
+ * sigmoid / tanh (so they are the gates that produced h_all) and walks t = T-1 ... 0.  With
+ *   g      = dh_all[t] + carry          (carry = 0 at t = T-1)
+ *   h_prev = h_all[t-1]                 (h0, or 0 when h0 is NULL, at t = 0)
+ * per hidden unit:
+ *   r = s(gi_r + gh_r)    z = s(gi_z + gh_z)    n = tanh(gi_n + r gh_n)
+ *   da_n = g (1 - z)(1 - n^2)
+ *   da_z = g (h_prev - n) z (1 - z)
+ *   da_r = da_n gh_n r (1 - r)
+ *   dgi[t] = (da_r, da_z, da_n)
+ *   dgh[t] = (da_r, da_z, da_n r)
+ *   carry  = g z + W_hh^T dgh[t]
+ * and dh0 = the final carry.  dh_all[t] is the gradient that reaches h_t from everything that READ h_t other than the
+ * recurrence itself.  The weight gradients are time-parallel and left to the caller:
+ *   dW_hh = dgh^T h_prev, db_hh = column sums of dgh, dW_ih / db_ih / dx from dgi.
+ * All tensors contiguous float32; every output element is written exactly once (deterministic, no atomics).
+ * NULL pointers (dh0 and h0 are optional) and non-positive B / T / J return MACJD_EINVAL; H other than 64 / 128 returns
+ * MACJD_EUNSUPPORTED.
+ */
+typedef struct macjd_gru_bwd_io {
+    int32_t B, T, J, H;            /* H = 64 or 128 */
+    const float* gi;      /* [B,T,J,3H]  W_ih x_t + b_ih, gate order r,z,n (as macjd_gru_io)            */
+    const float* gh;      /* [B,T,J,3H]  W_hh h_{t-1} + b_hh for every t: the caller's time-parallel product */
+    const float* h_all;   /* [B,T,J,H]   the forward scan's stored h_t                                   */
+    const float* h0;  int64_t h0_sb;   /* optional initial state, as macjd_gru_io (NULL = zeros)          */
+    const float* w_hh;    /* [3H,H] row-major                                                            */
+    const float* dh_all;  /* [B,T,J,H]   dL/dh_t from everything that READ h_t (not the recurrence)       */
+    float* dgi;           /* [B,T,J,3H]  out                                                             */
+    float* dgh;           /* [B,T,J,3H]  out (= dgi except the n gate: da_n * r)                         */
+    float* dh0;           /* [B,J,H]     out, optional                                                   */
+} macjd_gru_bwd_io;
+int macjd_gru_sequence_backward_supported(int32_t H);   /* 1 for 64 and 128, else 0 */
+int macjd_gru_sequence_backward(const macjd_gru_bwd_io* io, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

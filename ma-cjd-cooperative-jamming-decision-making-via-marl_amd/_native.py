@@ -14,7 +14,7 @@ LIB_NAME = "libmacjd_hip.so"
 # MACJD_LIB points at another build of the same sources (kernel A/B runs); the default is the in-tree library
 LIB_PATH = os.environ.get("MACJD_LIB") or os.path.join(_PKG_DIR, LIB_NAME)
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 STEP_ARITH_F64 = 1
 STEP_LANE_KERNEL = 2
 STEP_SLOT_KERNEL = 4
@@ -33,6 +33,7 @@ EXPORTS = [
     "macjd_scenario_set_scan", "macjd_env_step_scan", "macjd_env_reset_scan",
     "macjd_agent_env_episode_scan_supported", "macjd_agent_env_episode_scan",
     "macjd_scenario_set_scan_pattern",
+    "macjd_gru_sequence_backward_supported", "macjd_gru_sequence_backward",
 ]
 
 
@@ -125,6 +126,17 @@ class GruIO(ctypes.Structure):
         ("fc1_w", ctypes.c_void_p * 2), ("fc1_b", ctypes.c_void_p * 2), ("w_ih", ctypes.c_void_p * 2), ("b_ih", ctypes.c_void_p * 2),
         ("p_out", ctypes.c_void_p * 2), ("act_w", (ctypes.c_void_p * 3) * 2), ("act_b", (ctypes.c_void_p * 3) * 2),
         ("Ah", ctypes.c_int32), ("A", ctypes.c_int32),
+    ]
+
+
+class GruBwdIO(ctypes.Structure):
+    """ctypes mirror of ``macjd_gru_bwd_io`` (include/macjd_nets.h)."""
+    _fields_ = [
+        ("B", ctypes.c_int32), ("T", ctypes.c_int32), ("J", ctypes.c_int32), ("H", ctypes.c_int32),
+        ("gi", ctypes.c_void_p), ("gh", ctypes.c_void_p), ("h_all", ctypes.c_void_p),
+        ("h0", ctypes.c_void_p), ("h0_sb", ctypes.c_int64),
+        ("w_hh", ctypes.c_void_p), ("dh_all", ctypes.c_void_p),
+        ("dgi", ctypes.c_void_p), ("dgh", ctypes.c_void_p), ("dh0", ctypes.c_void_p),
     ]
 
 
@@ -398,6 +410,10 @@ def load() -> ctypes.CDLL:
     lib.macjd_qhead_select.argtypes = [ctypes.POINTER(QheadIO), ctypes.c_void_p]
     lib.macjd_gru_sequence.restype = ctypes.c_int
     lib.macjd_gru_sequence.argtypes = [ctypes.POINTER(GruIO), ctypes.c_void_p]
+    lib.macjd_gru_sequence_backward_supported.restype = ctypes.c_int
+    lib.macjd_gru_sequence_backward_supported.argtypes = [ctypes.c_int32]
+    lib.macjd_gru_sequence_backward.restype = ctypes.c_int
+    lib.macjd_gru_sequence_backward.argtypes = [ctypes.POINTER(GruBwdIO), ctypes.c_void_p]
     for name in ("macjd_mixer_tail_forward", "macjd_mixer_tail_backward"):
         getattr(lib, name).restype = ctypes.c_int
         getattr(lib, name).argtypes = [ctypes.POINTER(MixerIO), ctypes.c_void_p]

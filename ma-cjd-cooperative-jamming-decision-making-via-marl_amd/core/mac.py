@@ -81,6 +81,12 @@ class BasicMAC:
                 params, gi = self.agent.static_step_inputs(obs.reshape(E * J, S))
         self.static_inputs = (params, gi)
 
+    def invalidate_static_inputs(self):
+        """Forget the key of the cached static-observation inputs: the next ``prepare_static_obs`` recomputes them.  For
+        callers that change the agent body in a way the version counters of the key do not see (writes through
+        ``p.data`` views: the learner's fused optimiser step with ``train_agent_body``)."""
+        self._static_key = None
+
     def select_actions(self, obs_batch, avail_actions_batch, t_env, test_mode=False):
         device = next(self.agent.parameters()).device
         if obs_batch.device != device:

@@ -169,7 +169,13 @@ class RNNAgent(nn.Module):
         if ops.qhead_taken_supported(hidden_state, l1.weight, l2.weight, self.n_actions):
             # the learner's case on a HIP device: input rows, first layer + ReLU and the second layer's dot in ONE launch
             return ops.qhead_taken(hidden_state, idx, continuous_param, l1.weight, l1.bias, l2.weight, l2.bias, self.n_actions)
-        q_head_input = ops.qhead_input(hidden_state, idx, continuous_param, self.n_actions)   # [h, onehot(a), P]
+        if hidden_state.requires_grad and torch.is_grad_enabled():
+            # the hidden state carries a graph (the learner's train_agent_body unroll): the input rows are built with
+            # stock ops so that the Q-head's input gradient flows back into it (ops.qhead_input detaches: data only)
+            onehot = (idx.reshape(n, 1) == torch.arange(self.n_actions, device=idx.device, dtype=idx.dtype)).to(hidden_state.dtype)
+            q_head_input = torch.cat([hidden_state, onehot, continuous_param.reshape(n, 1).to(hidden_state.dtype)], dim=1)
+        else:
+            q_head_input = ops.qhead_input(hidden_state, idx, continuous_param, self.n_actions)   # [h, onehot(a), P]
         return ops.linear_relu_dot(q_head_input, l1.weight, l1.bias, l2.weight, l2.bias)
 
     def q_values_all_actions(self, hidden_state, continuous_params_all):

@@ -12,6 +12,12 @@ Reference behaviour that is reproduced on purpose:
   * the Double-DQN argmax does not apply the availability mask (qmix.py:141-142 is commented out);
   * the loss runs over steps 0..T-2 (``[:, :-1]`` slices, qmix.py:155,192).
 
+Opt-in departure, ``args.train_agent_body`` (off by default; main.py ``--train-agent-body``): ``q_taken`` is evaluated
+from the eval agent's own differentiable unroll instead of the buffered hidden states, so the loss also reaches fc1 and
+the GRU (back-propagation through time: ops.gru_sequence_train).  The actor stays frozen; target network, mixer, loss
+and target sync are unchanged.  With an untouched body the unrolled and the buffered hidden states are the same numbers,
+so the reference's loss is the special case.  Eager updates only (``train``): ``enable_graphs`` refuses.
+
 What changes is the schedule of the work, not the algebra.  The reference unrolls
 ``for t: for a:`` in Python — 2 x T x (3 + 5A) small launches per call (qmix.py:241-274).  Everything
 except the GRU recurrence is time-parallel, so here: fc1 / actor / GRU input transform / Q-head base are
@@ -52,6 +58,7 @@ class QMixLearner:
         self.state_shape = args.state_shape
         self.obs_shape = args.obs_shape
         self.device = torch.device(args.device if torch.cuda.is_available() and args.use_cuda else "cpu")
+        self.train_agent_body = bool(getattr(args, "train_agent_body", False))   # module docstring
 
         self.eval_qmix_net = QMixer(args)
         self.target_mac = copy.deepcopy(mac)
@@ -107,6 +114,8 @@ class QMixLearner:
         return same and self._body_is_shared()
 
     def _body_is_shared(self):
+        if self.train_agent_body:   # the fused optimiser writes fc1 / GRU through .data views: the counters do not see it
+            return False
         if not options.on("SHARED_BODY") or not self._body_versions:
             return False
         pe = self._body_params(self.mac.agent)
@@ -119,11 +128,13 @@ class QMixLearner:
     def _trainable(self):
         """Parameters the loss can reach: the Q-head and the mixer (see module docstring), in the order of the
         flat vectors: the mixer's four first-layer weights, then their biases (adjacent, so that the merged
-        first-layer GEMM reads them as ONE [2Hh+2Em, S] matrix without a torch.cat), then everything else."""
+        first-layer GEMM reads them as ONE [2Hh+2Em, S] matrix without a torch.cat), then everything else.
+        ``train_agent_body``: fc1 and the GRU of the eval agent follow at the end (the actor never does)."""
         first = self.eval_qmix_net.first_layer_params()
         ids = {id(p) for p in first}
         rest = [p for p in list(self.mac.agent.fc2_q_head.parameters()) + self.qmix_params if id(p) not in ids]
-        return first + rest
+        body = list(self.mac.agent.fc1.parameters()) + list(self.mac.agent.rnn.parameters()) if self.train_agent_body else []
+        return first + rest + body
 
     @staticmethod
     def _world_size():
@@ -267,8 +278,14 @@ class QMixLearner:
         # h_T (qmix.py:241,253); it only trains between episodes so nothing reads it.  Here training
         # may interleave with a running batched rollout, so the rollout state is put back.
         rollout_hidden = self.mac.hidden_states
+        h_eval = self._unroll_eval_body(obs) if self.train_agent_body else None   # [B, T, J, H] with autograd
         with torch.no_grad():
-            target_q_all, eval_q_all = self._all_action_q_multi([self.target_mac, self.mac], obs)  # [B, T, J, A]
+            if h_eval is not None:
+                # the target network as always; the eval network's all-action Q from the DETACHED unrolled states
+                target_q_all = self._all_action_q_multi([self.target_mac], obs)[0]
+                eval_q_all = self._all_action_q_from_hidden(self.mac, h_eval.detach(), obs)
+            else:
+                target_q_all, eval_q_all = self._all_action_q_multi([self.target_mac, self.mac], obs)  # [B, T, J, A]
             self.mac.hidden_states = rollout_hidden
             next_actions = eval_q_all[:, 1:].argmax(dim=3, keepdim=True)            # qmix.py:138-143 (no mask)
             target_q_taken = torch.gather(target_q_all[:, 1:], 3, next_actions).squeeze(3)  # qmix.py:147
@@ -279,8 +296,10 @@ class QMixLearner:
             q_taken = torch.empty((B, 0, self.n_agents), device=dev)
         else:
             n_eff = B * (T - 1) * self.n_agents
+            # (train_agent_body: the unrolled states — zero initial state, like the argmax's unroll — carry the graph)
+            h_taken = hidden_states if h_eval is None else h_eval
             q_taken = self.mac.agent.get_q_value_for_action(
-                hidden_states[:, :T - 1].reshape(n_eff, self.args.rnn_hidden_dim),
+                h_taken[:, :T - 1].reshape(n_eff, self.args.rnn_hidden_dim),
                 actions_discrete[:, :T - 1].reshape(n_eff, 1),
                 actions_continuous[:, :T - 1].reshape(n_eff, 1), validate=validate_actions).view(B, T - 1, self.n_agents)
         eval_q_mixer = self.eval_qmix_net(q_taken, states[:, :-1])                  # qmix.py:187
@@ -296,6 +315,27 @@ class QMixLearner:
         if self._world_size() > 1 or self._flat_param is not None:
             self._flatten_grads()   # one cat: the all-reduce buffer and the fused optimiser's input
         return loss.detach(), eval_mean.detach(), target_mean.detach()
+
+    def _unroll_eval_body(self, obs):
+        """The eval agent's recurrent body over whole episodes WITH autograd (``train_agent_body``): fc1 + ReLU and W_ih
+        time-parallel over all B*T*J rows, then the scan from the zero initial state (mac.init_hidden, qmix.py:241) whose
+        backward is one reverse-time launch on a HIP device (ops.gru_sequence_train).  Returns h_all [B, T, J, H]."""
+        B, T, J, S = obs.shape
+        a = self.mac.agent
+        H = a.rnn_hidden_dim
+        x = ops.linear_relu(obs.reshape(B * T * J, S), a.fc1.weight, a.fc1.bias)
+        gi = ops.linear(x, a.rnn.weight_ih, a.rnn.bias_ih).view(B, T, J, 3 * H)
+        return ops.gru_sequence_train(gi, a.rnn.weight_hh, a.rnn.bias_hh)
+
+    def _all_action_q_from_hidden(self, mac_controller, h_all, obs):
+        """All-action Q [B, T, J, A] of one controller from given hidden states (the tail of ``_all_action_q_multi``)."""
+        B, T, J, S = obs.shape
+        a = mac_controller.agent
+        H = a.rnn_hidden_dim
+        params = a.actor_forward(obs.reshape(B * T * J, S))
+        l1, l2 = a.fc2_q_head[0], a.fc2_q_head[2]
+        base = F.linear(h_all.reshape(B * T * J, H), l1.weight[:, :H], l1.bias)
+        return ops.qhead_all_actions(base, params, l1.weight, l2.weight, l2.bias, H, a.n_actions).view(B, T, J, a.n_actions)
 
     def _scan_from_ring_early(self):
         """Static observations: launch the scan (with its in-kernel input transform) on the side stream BEFORE the
@@ -686,6 +726,11 @@ class QMixLearner:
         loss, ev, tg = self._forward_backward(batch, int(batch["max_seq_len"]))
         self._allreduce_grads()
         grad_norm = self._clip_and_step()
+        if self.train_agent_body:
+            # the step wrote fc1 / GRU (through .data views on a HIP device, which no version counter sees): what the
+            # controllers cached from the body for a static observation is stale
+            for m in (self.mac, self.target_mac):
+                m.invalidate_static_inputs()
         self._after_step()
         if not sync_stats and torch.is_tensor(grad_norm) and grad_norm is self._grad_norm_tensor():
             grad_norm = grad_norm.clone()   # the fused optimiser step reuses ONE output tensor: hand out a snapshot
@@ -708,6 +753,9 @@ class QMixLearner:
         target syncs (in-place ``load_state_dict``) and new episodes are seen by the replayed graphs."""
         if self.device.type != "cuda":
             raise RuntimeError("enable_graphs needs the learner on a HIP device")
+        if self.train_agent_body:
+            raise RuntimeError("enable_graphs: train_agent_body is an eager-mode option (the captured, static-observation "
+                               "and shared-body updates are built on the frozen agent body); use train()")
         self.release_graphs()   # a re-capture destroys the previous graphs first, explicitly and at a quiet point
         self._verify_body_shared()   # (values, not version counters: catches writes made through .data)
         same_buffer = getattr(self, "_g_buffer", None) is buffer

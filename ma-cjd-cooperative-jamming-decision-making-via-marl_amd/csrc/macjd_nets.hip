@@ -28,6 +28,7 @@
 #include "macjd_err.h"
 #include "macjd_tdloss.h"
 #include "macjd_philox.h"
+#include "macjd_gru_math.h"   // gru_sigmoid / gru_tanh
 
 namespace macjd {
 
@@ -257,16 +258,6 @@ extern "C" int macjd_qhead_select(const macjd_qhead_io* io, void* hip_stream) {
 //     and are added in fixed wave order (deterministic);
 //   * gi for step t+1 is loaded while step t computes; wave 0 stores h' (256-B coalesced rows).
 namespace macjd {
-
-// v_rcp_f32 / v_exp_f32 directly (1 ulp each): __frcp_rn is the CORRECTLY ROUNDED reciprocal and expands to the full
-// div_scale / div_fmas / div_fixup sequence, ~12 instructions per gate on the serial per-step chain
-__device__ __forceinline__ float gru_sigmoid(float x) {
-    return __builtin_amdgcn_rcpf(1.0f + __expf(-x));
-}
-__device__ __forceinline__ float gru_tanh(float x) {
-    // tanh(x) = 1 - 2 / (exp(2x) + 1); saturates cleanly: exp -> inf gives 1, exp -> 0 gives -1
-    return 1.0f - 2.0f * __builtin_amdgcn_rcpf(__expf(2.0f * x) + 1.0f);
-}
 
 // Prologue of the scan kernels for a static observation (macjd_gru_io.obs); results: s_gi [3H] in LDS and, when asked,
 // io.p_out.  All NW waves of the workgroup take part; ends with a barrier.

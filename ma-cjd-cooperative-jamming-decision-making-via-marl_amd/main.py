@@ -243,6 +243,8 @@ def run(args):
     batch_envs = int(getattr(args, "batch_envs", 1) or 1)
     episodes_per_run = batch_envs
     use_graphs = bool(getattr(args, "hip_graphs", True)) and args.use_cuda and batch_envs > 1
+    if getattr(args, "train_agent_body", False):
+        use_graphs = False   # the recurrent update is eager (learner.train); the captured update is built on the frozen body
     # config/default.yaml is scaled for batch_envs = 4096 (epsilon annealed over 2500 steps PER ENV, 200 M collected steps);
     # the reference's own protocol (one env) anneals over 100 000 of its 2 M steps (reference config/default.yaml:21-23,60)
     if batch_envs == 1 and (args.epsilon_anneal_time < 20000 or args.total_env_steps > 20_000_000):
@@ -375,6 +377,9 @@ def main(argv=None):
     parser.add_argument("--resume", type=str, default=None)
     parser.add_argument("--randomize-scenarios", action="store_true",
                         help="batched runs: every env gets its own random variation of the scenario (per-env tables)")
+    parser.add_argument("--train-agent-body", action="store_true",
+                        help="also train fc1 and the GRU of the agent (back-propagation through the unrolled episode); "
+                             "eager updates, the actor stays frozen")
     a = parser.parse_args(argv)
     config = load_config(config_name=a.config, config_dir=a.config_dir)
     config.config, config.env_config, config.device_request = a.config, a.env_config, a.device
@@ -384,6 +389,8 @@ def main(argv=None):
     config.resume = a.resume
     if a.randomize_scenarios:
         config.randomize_scenarios = True
+    if a.train_agent_body:
+        config.train_agent_body = True
     return run(config)
 
 

@@ -466,6 +466,89 @@ def gru_sequence(gi: torch.Tensor, w_hh: torch.Tensor, b_hh: torch.Tensor,
     return gru_sequence_multi([gi], [w_hh], [b_hh], [h0])[0]
 
 
+def gru_sequence_backward(gi, gh, h_all, w_hh, dh_all, h0=None, want_dh0=False):
+    """One launch for the whole reverse-time chain of the scan (include/macjd_nets.h, macjd_gru_bwd_io): returns
+    (dgi [B,T,J,3H], dgh [B,T,J,3H], dh0 [B,J,H] or None).  HIP device, float32, H in {64, 128}."""
+    lib = _native.load()
+    B, T, J, H3 = gi.shape
+    H = H3 // 3
+    # the kernel reads DENSE tensors (the header's contract): a time-expanded gi or a permuted dh_all is copied here, as
+    # the forward copies its gi
+    gi, gh, h_all, w_hh, dh_all = (t.detach().float().contiguous() for t in (gi, gh, h_all, w_hh, dh_all))
+    assert gh.numel() == gi.numel() and h_all.numel() == B * T * J * H and dh_all.numel() == h_all.numel()   # (dense now)
+    assert tuple(w_hh.shape) == (H3, H)
+    io = _native.GruBwdIO()
+    io.B, io.T, io.J, io.H = B, T, J, H
+    io.gi, io.gh, io.h_all, io.w_hh, io.dh_all = (t.data_ptr() for t in (gi, gh, h_all, w_hh, dh_all))
+    if h0 is not None:
+        h0 = h0.detach().float().reshape(B, J, H) if h0.dim() != 3 else h0.detach().float()
+        if h0.stride(2) != 1 or h0.stride(1) != H or (B > 1 and h0.stride(0) < J * H):
+            h0 = h0.contiguous()
+        io.h0, io.h0_sb = h0.data_ptr(), (h0.stride(0) if B > 1 else 0)
+    dgi = torch.empty((B, T, J, H3), dtype=torch.float32, device=gi.device)
+    dgh = torch.empty((B, T, J, H3), dtype=torch.float32, device=gi.device)
+    dh0 = torch.empty((B, J, H), dtype=torch.float32, device=gi.device) if want_dh0 else None
+    io.dgi, io.dgh, io.dh0 = dgi.data_ptr(), dgh.data_ptr(), (dh0.data_ptr() if want_dh0 else None)
+    with torch.cuda.device(gi.device):
+        _native.check(lib.macjd_gru_sequence_backward(ctypes.byref(io), _stream(gi)), "macjd_gru_sequence_backward")
+    return dgi, dgh, dh0
+
+
+class _GruSequenceTrain(torch.autograd.Function):
+    """h_all = scan(gi, W_hh, b_hh, h0) with a backward: the forward is the ``gru_sequence`` launch; the backward is
+    the time-parallel product gh = W_hh h_{t-1} + b_hh over all rows (ONE library GEMM), the reverse-time launch, and
+    the time-parallel weight gradients dW_hh = dgh^T h_prev, db_hh = column sums of dgh."""
+
+    @staticmethod
+    def forward(ctx, gi, w_hh, b_hh, h0):
+        h_all = gru_sequence(gi, w_hh, b_hh, h0)
+        ctx.save_for_backward(gi, w_hh, b_hh, h_all, h0)
+        return h_all
+
+    @staticmethod
+    def backward(ctx, dh_all):
+        gi, w_hh, b_hh, h_all, h0 = ctx.saved_tensors
+        B, T, J, H3 = gi.shape
+        H = H3 // 3
+        nd = ctx.needs_input_grad
+        # h_{t-1} for every step: the initial state, then the stored states shifted by one step
+        h_prev = torch.empty((B, T, J, H), dtype=h_all.dtype, device=h_all.device)
+        if h0 is None:
+            h_prev[:, 0].zero_()
+        else:
+            h_prev[:, 0].copy_(h0.detach().reshape(B, J, H))
+        if T > 1:
+            h_prev[:, 1:].copy_(h_all[:, :T - 1])
+        rows_prev = h_prev.view(B * T * J, H)
+        gh = F.linear(rows_prev, w_hh.detach(), b_hh.detach())
+        dgi, dgh, dh0 = gru_sequence_backward(gi, gh, h_all, w_hh, dh_all, h0=h0, want_dh0=h0 is not None and nd[3])
+        dW = db = None
+        if nd[1] or nd[2]:
+            rows_g = dgh.view(B * T * J, H3)
+            if rows_g.shape[0] >= 1024:   # the split-K kernel's range (as ``linear``); flat-gradient destinations apply
+                dW, db = linear_wgrad(rows_g, rows_prev, want_bias=True, w_key=grad_key(w_hh), b_key=grad_key(b_hh),
+                                      need=(nd[1], nd[2]))
+            else:
+                dW, db = rows_g.t().matmul(rows_prev), rows_g.sum(0)
+        if dh0 is not None:
+            dh0 = dh0.view_as(h0)   # h0 may be [B*J, H] (the controllers' hidden_states layout)
+        return (dgi if nd[0] else None), (dW if nd[1] else None), (db if nd[2] else None), dh0
+
+
+def gru_sequence_train(gi: torch.Tensor, w_hh: torch.Tensor, b_hh: torch.Tensor,
+                       h0: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``gru_sequence`` that autograd can differentiate: gi [B,T,J,3H] -> h_all [B,T,J,H], gradients to gi, W_hh, b_hh
+    and h0.  HIP device, float32, H in {64, 128}: the scan launch forward and ONE reverse-time launch backward
+    (``_GruSequenceTrain``).  Elsewhere (host tensors, float64, other H): ``gru_sequence_reference`` under stock
+    autograd."""
+    H = gi.shape[-1] // 3
+    if (gi.is_cuda and gi.dtype == torch.float32 and w_hh.dtype == torch.float32 and b_hh.dtype == torch.float32
+            and (h0 is None or h0.dtype == torch.float32) and not torch.is_autocast_enabled() and gi.shape[1] > 0
+            and bool(_native.load().macjd_gru_sequence_backward_supported(int(H)))):
+        return _GruSequenceTrain.apply(gi, w_hh, b_hh, h0)
+    return gru_sequence_reference(gi, w_hh, b_hh, h0)
+
+
 def gru_sequence_from_obs(obs, obs_index, agents, B: int, J: int, n_steps: int, with_actor: bool = False):
     """Scan of up to two agents whose observation is static within an episode, with the input transform computed INSIDE
     the scan launch: sequence (b, j) reads the observation row ``obs[obs_index[b], 0, j]`` (``obs`` [N, T+1, J, S]: the
