@@ -197,7 +197,8 @@ int macjd_clip_adam_step(const macjd_adam_io* io, void* hip_stream);
  */
 typedef struct macjd_sampler_io {
     int64_t* idx_out;          /* [n] */
-    int32_t n, reserved;
+    int32_t n, reserved;       /* reserved >= 0: counter offset — the draw of counter value *counter + reserved, which
+                                  leaves *counter = that value + 1 (0: the plain draw; see macjd_prefetch_batch) */
     const int32_t* n_stored;   /* device scalar: stored episodes (the population) */
     int64_t* counter;          /* device scalar: draws made so far */
     uint64_t seed;
@@ -251,6 +252,35 @@ typedef struct macjd_gather_io {
 } macjd_gather_io;
 
 int macjd_gather_rows(const macjd_gather_io* io, void* hip_stream);
+
+/*
+ * The whole prefetch of a LATER update's batch inside a captured group of updates as ONE launch: what
+ * macjd_sample_episodes -> macjd_gather_rows -> macjd_td_mask_sum -> macjd_gru_sequence (static observation read from the
+ * replay ring, in-kernel input transform, actor rows) do one behind the other, with the same device code on the same data
+ * (bit-identical results).  The three short launches no longer stand in front of the latency-bound scan.
+ *   gru      the scan's arguments: n_nets = 1, H = 64, obs = the ring's observation tensor, p_out[0] set.  obs_index is
+ *            NOT read: sequence (b, j) reads ring row index(b).
+ *   gather   the gather's arguments: n_rows = B; idx is NOT read, dst_k[b, :] = src_k[index(b), :].
+ *   sampler  index(t) = element t of the draw of counter value *counter + reserved (reserved >= 0: the counter offset),
+ *            evaluated by every workgroup for the indices it needs.  The launch only READS the counter; one workgroup
+ *            stores idx_out[0..n) for later readers.  With *n_stored < 1 or no_draw != 0: index(t) = idx_out[t] as found.
+ *   mask     B, Tm1, filled / f_sb / f_st of the RING's `filled` tensor (rows index(b)); tot_m[0] = sum over B x Tm1.
+ * A group of K updates bakes offsets 0 .. K-2 into the prefetches of its updates 1 .. K-1 and closes with a draw of
+ * offset K-1 (macjd_sampler_io.reserved of macjd_clip_adam_step_sample's `next`), which leaves the counter K further:
+ * the counter values and the final counter of K sequential draws.
+ * gather_blocks: workgroups that share the copy (0 = default).
+ */
+typedef struct macjd_prefetch_io {
+    macjd_gru_io gru;
+    macjd_gather_io gather;
+    macjd_sampler_io sampler;
+    macjd_tdloss_io mask;
+    float* tot_m;
+    int32_t no_draw, gather_blocks;
+} macjd_prefetch_io;
+
+int macjd_prefetch_batch_supported(int32_t n_nets, int32_t H, int32_t B);   /* 1 / 0 */
+int macjd_prefetch_batch(const macjd_prefetch_io* io, void* hip_stream);
 
 /*
  * Input rows of the Q-head for the TAKEN action, out[n, :] = [h[n, 0..H-1], onehot_A(idx[n]), P[n]]  — the

@@ -34,6 +34,7 @@ EXPORTS = [
     "macjd_agent_env_episode_scan_supported", "macjd_agent_env_episode_scan",
     "macjd_scenario_set_scan_pattern",
     "macjd_gru_sequence_backward_supported", "macjd_gru_sequence_backward",
+    "macjd_prefetch_batch_supported", "macjd_prefetch_batch",
 ]
 
 
@@ -352,6 +353,14 @@ class GatherIO(ctypes.Structure):
     ]
 
 
+class PrefetchIO(ctypes.Structure):
+    """ctypes mirror of ``macjd_prefetch_io`` (include/macjd_nets.h)."""
+    _fields_ = [
+        ("gru", GruIO), ("gather", GatherIO), ("sampler", SamplerIO), ("mask", TdLossIO),
+        ("tot_m", ctypes.c_void_p), ("no_draw", ctypes.c_int32), ("gather_blocks", ctypes.c_int32),
+    ]
+
+
 class WgradIO(ctypes.Structure):
     """ctypes mirror of ``macjd_wgrad_io`` (include/macjd_nets.h)."""
     _fields_ = [
@@ -484,6 +493,10 @@ def load() -> ctypes.CDLL:
                                             ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]
     lib.macjd_sample_episodes.restype = ctypes.c_int
     lib.macjd_sample_episodes.argtypes = [ctypes.POINTER(SamplerIO), ctypes.c_void_p]
+    lib.macjd_prefetch_batch_supported.restype = ctypes.c_int
+    lib.macjd_prefetch_batch_supported.argtypes = [ctypes.c_int32] * 3
+    lib.macjd_prefetch_batch.restype = ctypes.c_int
+    lib.macjd_prefetch_batch.argtypes = [ctypes.POINTER(PrefetchIO), ctypes.c_void_p]
     lib.macjd_gather_rows.restype = ctypes.c_int
     lib.macjd_gather_rows.argtypes = [ctypes.POINTER(GatherIO), ctypes.c_void_p]
     lib.macjd_linear_wgrad.restype = ctypes.c_int

@@ -875,6 +875,7 @@ class QMixLearner:
         # update's batch comes from the previous update's last launch) and a single process (no all-reduce in between).
         K = int(updates_per_graph if updates_per_graph is not None else options.get("UPDATES_PER_GRAPH"))
         self._g_multi = None
+        self._g_prefetch_launch = False   # bookkeeping: the captured group's prefetches are single launches (ops.prefetch_batch)
         if K > 1 and self._g_single and self._g_dev_sampler and fused and self._g_stats4 is not None:
             gm, rows, single_norm = torch.cuda.CUDAGraph(), [], self._grad_norm
             # Inside the group the updates are software-pipelined: everything of update k + 1 that depends on neither the
@@ -885,6 +886,13 @@ class QMixLearner:
             # launches on the same data in an order that respects every dependence: same results (tested bitwise).
             pipelined = (self._g_scan_from_ring and self._g_actor_in_scan and options.get("UPDATE_STREAMS") != "1"
                          and options.on("PIPELINED_GROUP"))
+            # The prefetch as ONE launch (ops.prefetch_batch: every workgroup evaluates the sampler's formula for the indices it
+            # needs at a counter offset baked into the launch, so the draw, the gather and the mask sum run BESIDE the scan
+            # instead of in front of it) — shared frozen body at hidden size 64; MACJD_PREFETCH_LAUNCH=0 and every other shape:
+            # the four launches one behind the other.
+            launch_agents = [self.mac.agent] if self._body_is_shared() else [self.target_mac.agent, self.mac.agent]
+            self._g_prefetch_launch = bool(pipelined and options.on("PREFETCH_LAUNCH") and "filled" in keys
+                                           and ops.prefetch_batch_supported(launch_agents, self._g_B, srcs))
             stage2 = {k: torch.zeros_like(v) for k, v in stage.items()} if pipelined else None
             stages = [stage, stage2]
             # (the captured launches write and read the second staging set through baked addresses: it has to live as long
@@ -893,6 +901,8 @@ class QMixLearner:
             # first replay of the group at 12j/16r.)
             self._g_stages = stages
             origin_dev = self.device
+
+            unwritten = [0]   # draws of one-launch prefetches that no launch has added to the sampler's counter yet
 
             def prefetch(dst, fork=True, draw=True):
                 """draw + gather + scan of a LATER update on the side stream"""
@@ -904,6 +914,16 @@ class QMixLearner:
                     ts.wait_stream(origin)  # (fork off the origin stream) the previous users of idx / dst are done
                 shared = self._body_is_shared()
                 agents = [self.mac.agent] if shared else [self.target_mac.agent, self.mac.agent]
+                if self._g_prefetch_launch:
+                    with torch.cuda.stream(ts), torch.no_grad():
+                        h, ps, tot_m = ops.prefetch_batch(
+                            buffer.buffers["obs"], agents, self._g_B, self.n_agents, self._g_T + 1,
+                            (self._g_idx, self._g_n_stored, self._g_draws, self._sampler_seed()), srcs, [dst[k] for k in keys],
+                            buffer.buffers["filled"], self._g_T - 1, offset=unwritten[0], draw=draw)
+                        unwritten[0] += 1 if draw else 0   # (the launch only READS the counter, at this offset)
+                        ev = torch.cuda.Event()   # one launch: the gathered batch and the scan are there together
+                        ev.record(ts)
+                    return [h[0], h[0]], [ps[0], ps[0]], (ev, ev, tot_m)
                 with torch.cuda.stream(ts), torch.no_grad():
                     if draw:
                         ops.sample_episodes(self._g_idx, self._g_n_stored, self._g_draws, self._sampler_seed())
@@ -950,7 +970,13 @@ class QMixLearner:
                     if self._g_graphed_ar:
                         self._allreduce_grads(force=True)
                     # the update's last launch draws the next batch — unless the prefetch behind the join has done so
-                    self._clip_and_step(sample_next=None if nxt_batch is not None else nxt)
+                    # (one-launch prefetches read the counter at offsets 0 .. K-2 without advancing it: the group's closing draw
+                    # is the one of offset K-1 and leaves the counter K further, as K draws one after the other do)
+                    if nxt_batch is not None:
+                        self._clip_and_step(sample_next=None)
+                    else:
+                        self._clip_and_step(sample_next=nxt + (unwritten[0],))
+                        unwritten[0] = 0
                 if pipelined:
                     torch.cuda.current_stream(self.device).wait_stream(self._target_stream)   # every fork rejoins
             self._grad_norm = single_norm

@@ -264,8 +264,13 @@ namespace macjd {
 // The two halves are independent given the observation row, so a launch that wants both runs them in DIFFERENT
 // workgroups (blockIdx.z = 0: input transform + scan, blockIdx.z = 1: actor chain only): the actor's three mat-vecs
 // (~9 us) leave the scan's critical path.
+// row of sequence b's observation in io.obs (macjd_gru_io.obs_index); macjd_prefetch_batch computes it instead
+__device__ __forceinline__ int64_t scan_obs_row(const macjd_gru_io& io, const int b) {
+    return io.obs_index ? io.obs_index[b] : (int64_t)b;
+}
+
 template <int H, int NW>
-__device__ __forceinline__ void scan_prologue(const macjd_gru_io& io, const int net, const int b, const int j,
+__device__ __forceinline__ void scan_prologue(const macjd_gru_io& io, const int net, const int b, const int j, const int64_t row,
                                               float* __restrict__ s_pro, float* __restrict__ s_gi, const int lane,
                                               const int wave, const bool want_gi, const bool want_actor) {
     // Prologue for a static observation: this sequence's ONE observation row x -> gi = W_ih ReLU(fc1 x + b) + b_ih
@@ -275,7 +280,6 @@ __device__ __forceinline__ void scan_prologue(const macjd_gru_io& io, const int 
     float* xs = s_pro;              // [S]
     float* v1 = s_pro + 256;        // [<= 256] first hidden vector
     float* v2 = s_pro + 512;        // [<= 256] second hidden vector
-    const int64_t row = io.obs_index ? io.obs_index[b] : (int64_t)b;
     const float* x = io.obs + row * io.obs_sb + (int64_t)j * io.obs_sj;
     const int S = io.S;
     for (int k = threadIdx.x; k < S; k += 64 * NW) xs[k] = x[k];
@@ -361,7 +365,7 @@ __global__ void __launch_bounds__(64 * NW) gru_sequence_kernel(const macjd_gru_i
     __shared__ float s_gi[3 * H];   // in-kernel input transform (static observation), see macjd_gru_io.obs
     __shared__ float s_pro[768];    // prologue scratch: observation row + two hidden vectors
     if (blockIdx.z == 1) {   // actor-only workgroup of a launch that split the prologue
-        scan_prologue<H, NW>(io, net, b, j, s_pro, s_gi, lane, wave, false, true);
+        scan_prologue<H, NW>(io, net, b, j, scan_obs_row(io, b), s_pro, s_gi, lane, wave, false, true);
         return;
     }
 
@@ -393,7 +397,7 @@ __global__ void __launch_bounds__(64 * NW) gru_sequence_kernel(const macjd_gru_i
     // io.reserved != 0 ("gi_static"): gi is [B, 1, J, 3H], the same input transform at every step (static observation)
     const bool gi_inkernel = io.obs != nullptr;
     const bool gi_static = io.reserved != 0 || gi_inkernel;
-    if (gi_inkernel) scan_prologue<H, NW>(io, net, b, j, s_pro, s_gi, lane, wave, true, gridDim.z == 1);
+    if (gi_inkernel) scan_prologue<H, NW>(io, net, b, j, scan_obs_row(io, b), s_pro, s_gi, lane, wave, true, gridDim.z == 1);
     auto gi_row = [&](int t) -> const float* {
         return gi_inkernel ? (const float*)s_gi
                            : gi_static ? gi + ((int64_t)b * io.J + j) * (3 * H)
@@ -504,15 +508,19 @@ __device__ __forceinline__ float gru_tanh_folded(float x) {
     return fmaf(-2.0f, __builtin_amdgcn_rcpf(e + 1.0f), 1.0f);
 }
 
+// The workgroup's body for sequence `seq` (= b * J + j) of network `net`, shared by gru_sequence_units_kernel and
+// prefetch_batch_kernel.  actor_only: the actor-only workgroup of a launch that split the prologue; actor_in_scan: the scan
+// workgroup evaluates the actor chain itself (a launch without that second layer); obs_row: the sequence's row of io.obs
+// (read only with an in-kernel input transform).  LDS: s_h [2][64] 16-byte aligned, s_gi [192], s_pro [768].
 template <bool STATIC>
-__global__ void __launch_bounds__(256) gru_sequence_units_kernel(const macjd_gru_io io) {
+__device__ __forceinline__ void gru_units_body(const macjd_gru_io& io, const int net, const int seq, const int64_t obs_row,
+                                               const bool actor_only, const bool actor_in_scan, float (*s_h)[64],
+                                               float* s_gi, float* s_pro) {
     constexpr int H = 64, NW = 4;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int q = lane & 3;                // K-quarter
     const int u = 16 * wave + (lane >> 2); // hidden unit
-    const int net = blockIdx.y;
-    const int seq = blockIdx.x;  // b * J + j
     const int b = seq / io.J, j = seq - b * io.J;
     const int T = io.T;
     const float* __restrict__ gi = io.gi[net];
@@ -520,11 +528,8 @@ __global__ void __launch_bounds__(256) gru_sequence_units_kernel(const macjd_gru
     const float* __restrict__ bhh = io.b_hh[net];
     float* __restrict__ out = io.h_out[net];
 
-    __shared__ __attribute__((aligned(16))) float s_h[2][H];
-    __shared__ float s_gi[3 * H];
-    __shared__ float s_pro[768];
-    if (STATIC && blockIdx.z == 1) {   // actor-only workgroup of a launch that split the prologue
-        scan_prologue<H, NW>(io, net, b, j, s_pro, s_gi, lane, wave, false, true);
+    if (STATIC && actor_only) {
+        scan_prologue<H, NW>(io, net, b, j, obs_row, s_pro, s_gi, lane, wave, false, true);
         return;
     }
 
@@ -549,7 +554,7 @@ __global__ void __launch_bounds__(256) gru_sequence_units_kernel(const macjd_gru
     // gru_sequence_kernel) — by GLOBAL loads only: a pointer that may also address LDS compiles to flat loads, which
     // count on lgkmcnt as well, so the wait for the step's ds_reads would wait for the prefetch too.
     const bool gi_inkernel = STATIC && io.obs != nullptr;
-    if (gi_inkernel) scan_prologue<H, NW>(io, net, b, j, s_pro, s_gi, lane, wave, true, gridDim.z == 1);
+    if (gi_inkernel) scan_prologue<H, NW>(io, net, b, j, obs_row, s_pro, s_gi, lane, wave, true, actor_in_scan);
     float ring[3][3];
     if (STATIC) {
 #pragma unroll
@@ -602,6 +607,17 @@ __global__ void __launch_bounds__(256) gru_sequence_units_kernel(const macjd_gru
         if (t + 1 < T) step(std::integral_constant<int, 1>{}, t + 1);
         if (t + 2 < T) step(std::integral_constant<int, 2>{}, t + 2);
     }
+}
+
+template <bool STATIC>
+__global__ void __launch_bounds__(256) gru_sequence_units_kernel(const macjd_gru_io io) {
+    __shared__ __attribute__((aligned(16))) float s_h[2][64];
+    __shared__ float s_gi[3 * 64];
+    __shared__ float s_pro[768];
+    const int seq = blockIdx.x;  // b * J + j
+    const int64_t row = (STATIC && io.obs) ? scan_obs_row(io, seq / io.J) : 0;
+    // blockIdx.z == 1: actor-only workgroup of a launch that split the prologue
+    gru_units_body<STATIC>(io, blockIdx.y, seq, row, blockIdx.z == 1, gridDim.z == 1, s_h, s_gi, s_pro);
 }
 
 }  // namespace macjd
@@ -767,13 +783,14 @@ __global__ void __launch_bounds__(1024) td_loss_kernel(const macjd_tdloss_io io)
 namespace macjd {
 // sum of the loss mask of a batch (the tot_m of td_loss_kernel; sums of 0 / 1 are exact in any order): what
 // macjd_mixer_fused_backward_td needs of the loss's global sums, from the gathered batch alone
-__global__ void __launch_bounds__(1024) td_mask_sum_kernel(const macjd_tdloss_io io, float* __restrict__ out) {
-    __shared__ float s_w[16];
+// (one workgroup of any whole number of waves up to 16; row_of(b) = the row of io.filled that holds batch entry b; s_w [16])
+template <class RowOf>
+__device__ __forceinline__ void td_mask_sum_body(const macjd_tdloss_io& io, float* __restrict__ out, float* s_w, RowOf row_of) {
     const int M = io.B * io.Tm1;
     float s = 0.0f;
     for (int i = threadIdx.x; i < M; i += blockDim.x) {
         const int b = i / io.Tm1, t = i - b * io.Tm1;
-        s += io.filled[b * io.f_sb + t * io.f_st] ? 1.0f : 0.0f;
+        s += io.filled[row_of(b) * io.f_sb + t * io.f_st] ? 1.0f : 0.0f;
     }
     s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = s;
@@ -783,6 +800,11 @@ __global__ void __launch_bounds__(1024) td_mask_sum_kernel(const macjd_tdloss_io
         t = wave_sum(t);
         if (threadIdx.x == 0) out[0] = t;
     }
+}
+
+__global__ void __launch_bounds__(1024) td_mask_sum_kernel(const macjd_tdloss_io io, float* __restrict__ out) {
+    __shared__ float s_w[16];
+    td_mask_sum_body(io, out, s_w, [](int b) { return (int64_t)b; });
 }
 }  // namespace macjd
 
@@ -880,35 +902,49 @@ __device__ __forceinline__ uint32_t fmix32(uint32_t h) {   // MurmurHash3 finali
     h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
     return h;
 }
-// one block; every thread reads the counter, thread 0 advances it after the barrier
+// the keyed permutation of one draw: round keys of counter value c, and the split of the index bits for population N >= 1
+struct SamplerPerm { uint32_t key[8]; int rb; uint32_t rmask, lmask; };
+__device__ __forceinline__ SamplerPerm sampler_perm(const int64_t c, const uint64_t seed, const int64_t N) {
+    const Philox4 ka = philox4x32_10((uint32_t)c, (uint32_t)((uint64_t)c >> 32), 0x53414d50u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const Philox4 kb = philox4x32_10((uint32_t)c, (uint32_t)((uint64_t)c >> 32), 0x53414d50u, 1u, (uint32_t)seed, (uint32_t)(seed >> 32));
+    SamplerPerm p;
+    p.key[0] = ka.v[0]; p.key[1] = ka.v[1]; p.key[2] = ka.v[2]; p.key[3] = ka.v[3];
+    p.key[4] = kb.v[0]; p.key[5] = kb.v[1]; p.key[6] = kb.v[2]; p.key[7] = kb.v[3];
+    int k = 2;                                   // bits of the permuted domain: 2^k >= N
+    while (((int64_t)1 << k) < N) ++k;
+    const int lb = k / 2;                        // right / left half widths (rb >= lb >= 1)
+    p.rb = k - k / 2;
+    p.rmask = (1u << p.rb) - 1u; p.lmask = (1u << lb) - 1u;
+    return p;
+}
+// index t of the draw of n episodes from N >= 1 (a pure function of (counter, seed, N, t): any thread of any workgroup may
+// evaluate it)
+__device__ __forceinline__ int64_t sampler_index(const SamplerPerm& p, const int64_t N, const int n, const int t) {
+    if (N < n) return t % N;
+    uint32_t x = (uint32_t)t;
+    for (int walk = 0; walk < 64; ++walk) {  // cycle-walking: expected < 2 passes (2^k < 2 N)
+        uint32_t L = x >> p.rb, R = x & p.rmask;
+#pragma unroll
+        for (int r = 0; r < 8; r += 2) {
+            L = (L ^ fmix32(R ^ p.key[r])) & p.lmask;
+            R = (R ^ fmix32(L ^ p.key[r + 1])) & p.rmask;
+        }
+        x = (L << p.rb) | R;
+        if ((int64_t)x < N) break;
+    }
+    return ((int64_t)x < N) ? (int64_t)x : (int64_t)(x % (uint32_t)N);
+}
+// one block; every thread reads the counter, thread 0 advances it after the barrier.  sp.reserved = counter offset: the
+// draw is the one of counter value *counter + offset, and the counter is left behind that value (offset + 1 draws on: the
+// closing draw of a group whose other draws were made read-only by macjd_prefetch_batch at offsets 0 .. offset - 1)
 __device__ __forceinline__ void sample_episodes_block(const macjd_sampler_io& sp) {
-    const int64_t c = *sp.counter;
+    const int64_t c = *sp.counter + (int64_t)sp.reserved;
     const int64_t N = (int64_t)*sp.n_stored;
     __syncthreads();
     if (threadIdx.x == 0) *sp.counter = c + 1;
     if (N < 1) return;
-    const Philox4 ka = philox4x32_10((uint32_t)c, (uint32_t)((uint64_t)c >> 32), 0x53414d50u, 0u, (uint32_t)sp.seed, (uint32_t)(sp.seed >> 32));
-    const Philox4 kb = philox4x32_10((uint32_t)c, (uint32_t)((uint64_t)c >> 32), 0x53414d50u, 1u, (uint32_t)sp.seed, (uint32_t)(sp.seed >> 32));
-    const uint32_t key[8] = {ka.v[0], ka.v[1], ka.v[2], ka.v[3], kb.v[0], kb.v[1], kb.v[2], kb.v[3]};
-    int k = 2;                                   // bits of the permuted domain: 2^k >= N
-    while (((int64_t)1 << k) < N) ++k;
-    const int rb = k - k / 2, lb = k / 2;        // right / left half widths (rb >= lb >= 1)
-    const uint32_t rmask = (1u << rb) - 1u, lmask = (1u << lb) - 1u;
-    for (int t = threadIdx.x; t < sp.n; t += blockDim.x) {
-        if (N < sp.n) { sp.idx_out[t] = t % N; continue; }
-        uint32_t x = (uint32_t)t;
-        for (int walk = 0; walk < 64; ++walk) {  // cycle-walking: expected < 2 passes (2^k < 2 N)
-            uint32_t L = x >> rb, R = x & rmask;
-#pragma unroll
-            for (int r = 0; r < 8; r += 2) {
-                L = (L ^ fmix32(R ^ key[r])) & lmask;
-                R = (R ^ fmix32(L ^ key[r + 1])) & rmask;
-            }
-            x = (L << rb) | R;
-            if ((int64_t)x < N) break;
-        }
-        sp.idx_out[t] = ((int64_t)x < N) ? (int64_t)x : (int64_t)(x % (uint32_t)N);
-    }
+    const SamplerPerm perm = sampler_perm(c, sp.seed, N);
+    for (int t = threadIdx.x; t < sp.n; t += blockDim.x) sp.idx_out[t] = sampler_index(perm, N, sp.n, t);
 }
 
 __global__ void __launch_bounds__(256) sample_episodes_kernel(const macjd_sampler_io sp) { sample_episodes_block(sp); }
@@ -947,29 +983,82 @@ __global__ void __launch_bounds__(256) adam_update_kernel(const macjd_adam_io io
     if (SAMPLE && blockIdx.x == 0) sample_episodes_block(next);
 }
 
-__global__ void __launch_bounds__(256) gather_rows_kernel(const macjd_gather_io io) {
-    const int k = blockIdx.y;       // tensor
-    const int row = blockIdx.z;     // output row
+// part `part` of `parts` of the copy dst_k[row, :] = src_k[src_row, :] (tensor k, raw bytes), by one workgroup
+__device__ __forceinline__ void gather_rows_body(const macjd_gather_io& io, const int k, const int row, const int64_t src_row,
+                                                 const int part, const int parts) {
     const int64_t words = io.row_bytes[k] >> 2;
-    const uint32_t* __restrict__ src = (const uint32_t*)((const char*)io.src[k] + io.idx[row] * io.row_bytes[k]);
+    const uint32_t* __restrict__ src = (const uint32_t*)((const char*)io.src[k] + src_row * io.row_bytes[k]);
     const int64_t dpitch = io.dst_row_bytes[k] ? io.dst_row_bytes[k] : io.row_bytes[k];
     uint32_t* __restrict__ dst = (uint32_t*)((char*)io.dst[k] + (int64_t)row * dpitch);
     const bool vec = ((io.row_bytes[k] & 15) == 0) && ((dpitch & 15) == 0) && ((((uintptr_t)io.src[k]) & 15) == 0) &&
                      ((((uintptr_t)io.dst[k]) & 15) == 0);
     if (vec) {
         const int64_t n4 = words >> 2;
-        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x)
+        for (int64_t i = (int64_t)part * blockDim.x + threadIdx.x; i < n4; i += (int64_t)parts * blockDim.x)
             ((uint4*)dst)[i] = ((const uint4*)src)[i];
     } else {
-        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (int64_t)gridDim.x * blockDim.x)
+        for (int64_t i = (int64_t)part * blockDim.x + threadIdx.x; i < words; i += (int64_t)parts * blockDim.x)
             dst[i] = src[i];
+    }
+}
+
+__global__ void __launch_bounds__(256) gather_rows_kernel(const macjd_gather_io io) {
+    // blockIdx.y = tensor, blockIdx.z = output row, gridDim.x workgroups share a row
+    gather_rows_body(io, blockIdx.y, blockIdx.z, io.idx[blockIdx.z], blockIdx.x, gridDim.x);
+}
+
+// ---- the whole prefetch of a later update's batch as ONE launch (include/macjd_nets.h, macjd_prefetch_io) ----
+// 1-D grid in ranges (the idiom of qheads_pair_kernel), the long pole first:
+//   [0, BJ)               scan of sequence (b, j) with its in-kernel input transform   (gru_units_body)
+//   [BJ, 2 BJ)            actor rows of sequence (b, j)                                (gru_units_body, actor only)
+//   [2 BJ, 2 BJ + G)      gather: the 8 * n_tensors * B row parts of gather_rows_kernel's grid, dealt round-robin
+//   2 BJ + G              mask sum over the ring's `filled` rows; stores the drawn indices for later readers
+// Every workgroup evaluates the sampler's formula for the indices it needs (sampler_index is a pure function of the
+// counter value, the seed, the population and t): no workgroup reads what another one of this launch writes, and none
+// writes the counter — the group's closing draw (sample_episodes_block with the offset) advances it past all of them.
+constexpr int PREFETCH_MAX_B = 1024;    // the mask-sum workgroup keeps all B indices in LDS
+constexpr int PREFETCH_ROW_PARTS = 8;   // gather_rows_kernel's gridDim.x
+
+__global__ void __launch_bounds__(256) prefetch_batch_kernel(const macjd_prefetch_io io) {
+    __shared__ __attribute__((aligned(16))) float s_h[2][64];
+    __shared__ float s_gi[3 * 64];
+    __shared__ float s_pro[768];
+    __shared__ int64_t s_idx[PREFETCH_MAX_B];
+    __shared__ float s_w[16];
+    const int B = io.gru.B, BJ = B * io.gru.J, G = io.gather_blocks;
+    const int wg = blockIdx.x;
+    const int64_t N = (int64_t)*io.sampler.n_stored;
+    // no population yet, or "no draw": the indices already in idx_out (nothing in this launch writes them then)
+    const bool draw = !io.no_draw && N >= 1;
+    SamplerPerm perm = {};
+    if (draw) perm = sampler_perm(*io.sampler.counter + (int64_t)io.sampler.reserved, io.sampler.seed, N);
+    auto index_of = [&](int t) -> int64_t { return draw ? sampler_index(perm, N, io.sampler.n, t) : io.sampler.idx_out[t]; };
+    if (wg < 2 * BJ) {
+        const bool actor_only = wg >= BJ;
+        const int seq = actor_only ? wg - BJ : wg;
+        gru_units_body<true>(io.gru, 0, seq, index_of(seq / io.gru.J), actor_only, false, s_h, s_gi, s_pro);
+    } else if (wg < 2 * BJ + G) {
+        const int n_parts = PREFETCH_ROW_PARTS * io.gather.n_tensors * B;
+        for (int v = wg - 2 * BJ; v < n_parts; v += G) {
+            const int part = v % PREFETCH_ROW_PARTS, kr = v / PREFETCH_ROW_PARTS;
+            const int k = kr % io.gather.n_tensors, row = kr / io.gather.n_tensors;
+            gather_rows_body(io.gather, k, row, index_of(row), part, PREFETCH_ROW_PARTS);
+        }
+    } else {
+        for (int t = threadIdx.x; t < B; t += blockDim.x) {
+            const int64_t e = index_of(t);
+            s_idx[t] = e;
+            if (draw) io.sampler.idx_out[t] = e;
+        }
+        __syncthreads();
+        td_mask_sum_body(io.mask, io.tot_m, s_w, [&](int b) { return s_idx[b]; });
     }
 }
 
 }  // namespace macjd
 
 static int sampler_args_ok(const macjd_sampler_io* sp) {
-    return sp && sp->idx_out && sp->n >= 1 && sp->n_stored && sp->counter;
+    return sp && sp->idx_out && sp->n >= 1 && sp->n_stored && sp->counter && sp->reserved >= 0;
 }
 
 extern "C" int macjd_sample_episodes(const macjd_sampler_io* io, void* hip_stream) {
@@ -1025,16 +1114,61 @@ extern "C" int macjd_clip_adam_step_ln(const macjd_adam_io* io, const macjd_samp
     return MACJD_OK;
 }
 
+static int gather_tensors_ok(const macjd_gather_io* io) {
+    if (io->n_tensors < 1 || io->n_tensors > 8) return 0;
+    for (int k = 0; k < io->n_tensors; ++k)
+        if (!io->src[k] || !io->dst[k] || io->row_bytes[k] < 4 || (io->row_bytes[k] & 3) || (io->dst_row_bytes[k] & 3) ||
+            (io->dst_row_bytes[k] && io->dst_row_bytes[k] < io->row_bytes[k]))
+            return 0;
+    return 1;
+}
+
 extern "C" int macjd_gather_rows(const macjd_gather_io* io, void* hip_stream) {
     using namespace macjd;
     if (!io || io->n_tensors < 1 || io->n_tensors > 8 || io->n_rows < 0 || !io->idx)
         return set_nets_err(MACJD_EINVAL, "macjd_gather_rows: bad argument");
-    for (int k = 0; k < io->n_tensors; ++k)
-        if (!io->src[k] || !io->dst[k] || io->row_bytes[k] < 4 || (io->row_bytes[k] & 3) || (io->dst_row_bytes[k] & 3) ||
-            (io->dst_row_bytes[k] && io->dst_row_bytes[k] < io->row_bytes[k]))
-            return set_nets_err(MACJD_EINVAL, "macjd_gather_rows: bad tensor (row bytes must be a positive multiple of 4)");
+    if (!gather_tensors_ok(io))
+        return set_nets_err(MACJD_EINVAL, "macjd_gather_rows: bad tensor (row bytes must be a positive multiple of 4)");
     if (io->n_rows == 0) return MACJD_OK;
     hipLaunchKernelGGL(gather_rows_kernel, dim3(8, io->n_tensors, io->n_rows), dim3(256), 0, (hipStream_t)hip_stream, *io);
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return set_nets_err(MACJD_EDEVICE, hipGetErrorString(err));
+    return MACJD_OK;
+}
+
+extern "C" int macjd_prefetch_batch_supported(int32_t n_nets, int32_t H, int32_t B) {
+    return n_nets == 1 && H == 64 && B >= 1 && B <= macjd::PREFETCH_MAX_B && !macjd::env_options().gru_ksplit;
+}
+
+extern "C" int macjd_prefetch_batch(const macjd_prefetch_io* io, void* hip_stream) {
+    using namespace macjd;
+    if (!io) return set_nets_err(MACJD_EINVAL, "macjd_prefetch_batch: NULL io");
+    const macjd_gru_io& g = io->gru;
+    if (!macjd_prefetch_batch_supported(g.n_nets, g.H, g.B))
+        return set_nets_err(MACJD_EUNSUPPORTED, "macjd_prefetch_batch: needs one network, H = 64, 1 <= B <= 1024, the unit-split scan");
+    if (g.T < 1 || g.J < 1 || !g.obs || g.S < 1 || g.S > 256 || !g.w_hh[0] || !g.b_hh[0] || !g.h_out[0] || !g.fc1_w[0] ||
+        !g.fc1_b[0] || !g.w_ih[0] || !g.b_ih[0])
+        return set_nets_err(MACJD_EINVAL, "macjd_prefetch_batch: bad scan argument");
+    if (!g.p_out[0] || g.Ah < 1 || g.Ah > 256 || g.A < 1 || g.A > 64)
+        return set_nets_err(MACJD_EINVAL, "macjd_prefetch_batch: needs the in-kernel actor (Ah <= 256, A <= 64)");
+    for (int l = 0; l < 3; ++l)
+        if (!g.act_w[0][l] || !g.act_b[0][l]) return set_nets_err(MACJD_EINVAL, "macjd_prefetch_batch: needs the actor's three layers");
+    if (!sampler_args_ok(&io->sampler) || io->sampler.n != g.B)
+        return set_nets_err(MACJD_EINVAL, "macjd_prefetch_batch: bad sampler argument (n must be the batch size)");
+    if (io->gather.n_rows != g.B || !gather_tensors_ok(&io->gather))
+        return set_nets_err(MACJD_EINVAL, "macjd_prefetch_batch: bad gather argument (n_rows must be the batch size, row bytes "
+                                          "positive multiples of 4)");
+    if (io->mask.B != g.B || io->mask.Tm1 < 1 || !io->mask.filled || !io->tot_m)
+        return set_nets_err(MACJD_EINVAL, "macjd_prefetch_batch: bad mask-sum argument");
+    if (io->gather_blocks < 0) return set_nets_err(MACJD_EINVAL, "macjd_prefetch_batch: bad gather_blocks");
+    macjd_prefetch_io a = *io;
+    const int n_parts = PREFETCH_ROW_PARTS * a.gather.n_tensors * g.B;
+    // a row part is one load and one store per thread, i.e. one memory latency per pass of a gather workgroup's loop: 64
+    // workgroups (32 passes) outlast the scan by far, 256 (8 passes) end inside it; more buy nothing
+    if (a.gather_blocks == 0) a.gather_blocks = 256;
+    if (a.gather_blocks > n_parts) a.gather_blocks = n_parts;
+    const unsigned grid = 2u * (unsigned)(g.B * g.J) + (unsigned)a.gather_blocks + 1u;
+    hipLaunchKernelGGL(prefetch_batch_kernel, dim3(grid), dim3(256), 0, (hipStream_t)hip_stream, a);
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return set_nets_err(MACJD_EDEVICE, hipGetErrorString(err));
     return MACJD_OK;

@@ -557,40 +557,49 @@ def gru_sequence_from_obs(obs, obs_index, agents, B: int, J: int, n_steps: int, 
     dependence on a gather in front of the scan.  Returns [h_all [B, n_steps, J, H]] per agent (HIP device only);
     ``with_actor``: also the actor output of every sequence's observation row, ([h_all ...], [P [B, J, A] ...])."""
     lib = _native.load()
-    assert obs.is_cuda and obs.dtype == torch.float32 and obs.dim() == 4 and obs.stride(3) == 1 and obs.shape[2] == J
     outs, pouts = [], []
     for start in range(0, len(agents), 2):
-        part = agents[start:start + 2]
-        H = part[0].rnn_hidden_dim
-        if H not in (64, 128):
-            raise _native.NativeLibraryError(f"macjd_gru_sequence supports rnn_hidden_dim 64 or 128, got {H}")
-        io = _native.GruIO()
-        io.n_nets, io.B, io.T, io.J, io.H = len(part), int(B), int(n_steps), int(J), H
-        io.obs, io.obs_sb, io.obs_sj, io.S = obs.data_ptr(), obs.stride(0), obs.stride(2), obs.shape[3]
-        if obs_index is not None:
-            assert obs_index.dtype == torch.int64 and obs_index.is_cuda and obs_index.numel() >= B
-            io.obs_index = obs_index.data_ptr()
-        keep = []
-        for k, a in enumerate(part):
-            ts = [t.detach().float().contiguous() for t in (a.rnn.weight_hh, a.rnn.bias_hh, a.fc1.weight, a.fc1.bias,
-                                                            a.rnn.weight_ih, a.rnn.bias_ih)]
-            keep += ts
-            io.w_hh[k], io.b_hh[k], io.fc1_w[k], io.fc1_b[k], io.w_ih[k], io.b_ih[k] = [t.data_ptr() for t in ts]
-            o = torch.empty((B, n_steps, J, H), dtype=torch.float32, device=obs.device)
-            io.h_out[k] = o.data_ptr()
-            outs.append(o)
-            if with_actor:
-                layers = [(w.detach().float().contiguous(), b_.detach().float().contiguous()) for w, b_, _ in a.actor_layers()]
-                keep += [t for pair in layers for t in pair]
-                for l, (w, b_) in enumerate(layers):
-                    io.act_w[k][l], io.act_b[k][l] = w.data_ptr(), b_.data_ptr()
-                io.Ah, io.A = layers[0][0].shape[0], layers[2][0].shape[0]
-                pk_ = torch.empty((B, J, io.A), dtype=torch.float32, device=obs.device)
-                io.p_out[k] = pk_.data_ptr()
-                pouts.append(pk_)
+        io, o, p_, _keep = _gru_from_obs_io(obs, obs_index, agents[start:start + 2], B, J, n_steps, with_actor)
+        outs += o
+        pouts += p_
         with torch.cuda.device(obs.device):
             _native.check(lib.macjd_gru_sequence(ctypes.byref(io), _stream(obs)), "macjd_gru_sequence")
     return (outs, pouts) if with_actor else outs
+
+
+def _gru_from_obs_io(obs, obs_index, part, B: int, J: int, n_steps: int, with_actor: bool):
+    """The ``macjd_gru_io`` of one ``gru_sequence_from_obs`` launch (up to two agents): (io, [h_all ...], [P ...], tensors
+    the launch reads)."""
+    assert obs.is_cuda and obs.dtype == torch.float32 and obs.dim() == 4 and obs.stride(3) == 1 and obs.shape[2] == J
+    outs, pouts = [], []
+    H = part[0].rnn_hidden_dim
+    if H not in (64, 128):
+        raise _native.NativeLibraryError(f"macjd_gru_sequence supports rnn_hidden_dim 64 or 128, got {H}")
+    io = _native.GruIO()
+    io.n_nets, io.B, io.T, io.J, io.H = len(part), int(B), int(n_steps), int(J), H
+    io.obs, io.obs_sb, io.obs_sj, io.S = obs.data_ptr(), obs.stride(0), obs.stride(2), obs.shape[3]
+    if obs_index is not None:
+        assert obs_index.dtype == torch.int64 and obs_index.is_cuda and obs_index.numel() >= B
+        io.obs_index = obs_index.data_ptr()
+    keep = []
+    for k, a in enumerate(part):
+        ts = [t.detach().float().contiguous() for t in (a.rnn.weight_hh, a.rnn.bias_hh, a.fc1.weight, a.fc1.bias,
+                                                        a.rnn.weight_ih, a.rnn.bias_ih)]
+        keep += ts
+        io.w_hh[k], io.b_hh[k], io.fc1_w[k], io.fc1_b[k], io.w_ih[k], io.b_ih[k] = [t.data_ptr() for t in ts]
+        o = torch.empty((B, n_steps, J, H), dtype=torch.float32, device=obs.device)
+        io.h_out[k] = o.data_ptr()
+        outs.append(o)
+        if with_actor:
+            layers = [(w.detach().float().contiguous(), b_.detach().float().contiguous()) for w, b_, _ in a.actor_layers()]
+            keep += [t for pair in layers for t in pair]
+            for l, (w, b_) in enumerate(layers):
+                io.act_w[k][l], io.act_b[k][l] = w.data_ptr(), b_.data_ptr()
+            io.Ah, io.A = layers[0][0].shape[0], layers[2][0].shape[0]
+            pk_ = torch.empty((B, J, io.A), dtype=torch.float32, device=obs.device)
+            io.p_out[k] = pk_.data_ptr()
+            pouts.append(pk_)
+    return io, outs, pouts, keep
 
 
 def gru_sequence_multi(gis, w_hhs, b_hhs, h0s=None, n_steps=None):
@@ -1217,22 +1226,24 @@ def td_loss(y, tq, reward, terminated, filled, gamma):
 
 # ---------------------------------------------------------------------------------------------
 # Fused clip_grad_norm_ + Adam on flat vectors (reference core/qmix.py:199-200)
-def _sampler_io(idx_out, n_stored, counter, seed):
+def _sampler_io(idx_out, n_stored, counter, seed, offset=0):
     assert idx_out.dtype == torch.int64 and idx_out.is_contiguous() and n_stored.dtype == torch.int32 and counter.dtype == torch.int64
     assert idx_out.is_cuda and n_stored.device == idx_out.device and counter.device == idx_out.device
     sp = _native.SamplerIO()
     sp.idx_out, sp.n, sp.n_stored, sp.counter = idx_out.data_ptr(), idx_out.numel(), n_stored.data_ptr(), counter.data_ptr()
     sp.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    sp.reserved = int(offset)   # counter offset (macjd_sampler_io): the draw of counter + offset, counter left offset + 1 on
     return sp
 
 
-def sample_episodes(idx_out, n_stored, counter, seed):
+def sample_episodes(idx_out, n_stored, counter, seed, offset=0):
     """Device-side draw of ``idx_out.numel()`` distinct episode indices, uniform over [0, n_stored) (the reference's
     ``np.random.choice(current_size, batch, replace=False)``, utils/replay_buffer.py:89, without the host): a keyed
     pseudo-random permutation, see include/macjd_nets.h ``macjd_sampler_io``.  ``n_stored`` int32 [1] and ``counter``
-    int64 [1] live on the device; the counter advances by one."""
+    int64 [1] live on the device; the counter advances by one (``offset``: the draw of counter + offset, after which
+    the counter stands at counter + offset + 1 — the closing draw behind ``prefetch_batch`` launches)."""
     lib = _native.load()
-    sp = _sampler_io(idx_out, n_stored, counter, seed)
+    sp = _sampler_io(idx_out, n_stored, counter, seed, offset)
     with torch.cuda.device(idx_out.device):
         _native.check(lib.macjd_sample_episodes(ctypes.byref(sp), _stream(idx_out)), "macjd_sample_episodes")
 
@@ -1241,7 +1252,7 @@ def clip_adam_step(param, grad, exp_avg, exp_avg_sq, step, grad_norm, partials, 
                    lnparam=None):
     """In-place update of ``param`` / ``exp_avg`` / ``exp_avg_sq`` / ``step`` (all flat float32 on one HIP
     device); writes the pre-clip gradient norm into ``grad_norm``.  ``sample_next`` = (idx_out, n_stored, counter,
-    seed): the update launch also draws the NEXT update's episodes (``sample_episodes``) when it is done.
+    seed[, offset]): the update launch also draws the NEXT update's episodes (``sample_episodes``) when it is done.
     ``lnparam`` = LayerNorm-parameter launches held back by ``deferred_wgrad(hold_lnparam=True)``: a single one whose
     outputs are ranges of ``grad`` is evaluated inside the squared-norm launch; anything else is simply issued first."""
     lib = _native.load()
@@ -1274,17 +1285,54 @@ def gather_rows_supported(srcs) -> bool:
                                   for s in srcs)
 
 
+def _gather_io(n_rows, srcs, dsts):
+    io = _native.GatherIO()
+    io.n_tensors, io.n_rows = len(srcs), int(n_rows)
+    for k, (s_, d_) in enumerate(zip(srcs, dsts)):
+        assert d_.is_contiguous() and d_.dtype == s_.dtype and d_.shape[0] == n_rows and d_[0].numel() >= s_[0].numel()
+        io.src[k], io.dst[k], io.row_bytes[k] = s_.data_ptr(), d_.data_ptr(), s_[0].numel() * s_.element_size()
+        io.dst_row_bytes[k] = d_.stride(0) * d_.element_size()   # destination rows may be longer (padded steps)
+    return io
+
+
 def gather_rows(idx, srcs, dsts):
     """dst_k[i] = src_k[idx[i]] for up to 8 tensors in one launch (whole rows, raw bytes)."""
     lib = _native.load()
-    io = _native.GatherIO()
-    io.n_tensors, io.n_rows, io.idx = len(srcs), idx.numel(), idx.data_ptr()
-    for k, (s_, d_) in enumerate(zip(srcs, dsts)):
-        assert d_.is_contiguous() and d_.dtype == s_.dtype and d_.shape[0] == idx.numel() and d_[0].numel() >= s_[0].numel()
-        io.src[k], io.dst[k], io.row_bytes[k] = s_.data_ptr(), d_.data_ptr(), s_[0].numel() * s_.element_size()
-        io.dst_row_bytes[k] = d_.stride(0) * d_.element_size()   # destination rows may be longer (padded steps)
+    io = _gather_io(idx.numel(), srcs, dsts)
+    io.idx = idx.data_ptr()
     with torch.cuda.device(idx.device):
         _native.check(lib.macjd_gather_rows(ctypes.byref(io), _stream(idx)), "macjd_gather_rows")
+
+
+def prefetch_batch_supported(agents, B: int, srcs) -> bool:
+    """``prefetch_batch`` can stand for the four launches: one (shared, frozen) agent body at rnn_hidden_dim 64 with the
+    unit-split scan, a gatherable set of tensors, B <= 1024."""
+    return (len(agents) == 1 and gather_rows_supported(srcs)
+            and bool(_native.load().macjd_prefetch_batch_supported(len(agents), int(agents[0].rnn_hidden_dim), int(B))))
+
+
+def prefetch_batch(obs, agents, B: int, J: int, n_steps: int, sampler, srcs, dsts, filled, Tm1: int, offset: int = 0,
+                   draw: bool = True, gather_blocks: int = 0):
+    """``sample_episodes`` + ``gather_rows`` + ``td_mask_sum`` + ``gru_sequence_from_obs(with_actor=True)`` as ONE launch
+    (include/macjd_nets.h ``macjd_prefetch_io``), bit-identical to the four.  ``obs`` / ``filled``: the replay ring's
+    tensors (``filled`` [N, >= Tm1, 1] bool); ``sampler`` = (idx_out, n_stored, counter, seed); the draw is the one of
+    counter + ``offset`` and the counter is only READ — the caller's closing draw (``sample_episodes`` /
+    ``clip_adam_step(sample_next=(..., offset))``) advances it.  ``draw=False``: the indices already in idx_out.
+    Returns ([h_all [B, n_steps, J, H]], [P [B, J, A]], tot_m [1])."""
+    lib = _native.load()
+    if not prefetch_batch_supported(agents, B, srcs):
+        raise _native.NativeLibraryError("macjd_prefetch_batch: unsupported shape (one agent body, rnn_hidden_dim 64, B <= 1024)")
+    gio, outs, pouts, _keep = _gru_from_obs_io(obs, None, agents, B, J, n_steps, True)
+    assert sampler[0].numel() == B and filled.dtype == torch.bool and filled.device == obs.device and filled.shape[1] >= Tm1
+    io = _native.PrefetchIO()
+    io.gru, io.gather, io.sampler = gio, _gather_io(B, srcs, dsts), _sampler_io(*sampler[:4], offset)
+    io.mask.B, io.mask.Tm1 = int(B), int(Tm1)
+    io.mask.filled, io.mask.f_sb, io.mask.f_st = filled.data_ptr(), filled.stride(0), filled.stride(1)
+    tot_m = torch.empty(1, dtype=torch.float32, device=obs.device)
+    io.tot_m, io.no_draw, io.gather_blocks = tot_m.data_ptr(), 0 if draw else 1, int(gather_blocks)
+    with torch.cuda.device(obs.device):
+        _native.check(lib.macjd_prefetch_batch(ctypes.byref(io), _stream(obs)), "macjd_prefetch_batch")
+    return outs, pouts, tot_m
 
 
 # ---------------------------------------------------------------------------------------------

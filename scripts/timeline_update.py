@@ -25,18 +25,21 @@ print("periods of 44 consecutive updates from the middle of the run (us; a repla
 # a window whose period is the median one
 k = min(range(len(periods) // 3, 2 * len(periods) // 3), key=lambda i: abs(periods[i] - statistics.median(periods)))
 w0, w1 = ends[k], ends[k + 1]
-win = [(s, e, n, q) for s, e, n, q in ev if w0 - 100 <= s and e <= w1]
+# (every kernel that STARTS in the window: a side-stream launch that runs on into the next window — the next update's
+# prefetch — is listed with its full duration; the idle / busy sums below count it up to the window's end)
+win = [(s, e, n, q) for s, e, n, q in ev if w0 - 100 <= s < w1]
 print(f"window of update {k + 1} (t = 0 at the previous update's last kernel end; start us, duration us, queue, kernel):")
 for s, e, n, q in win:
     print(f"  {(s - w0) / 1e3:7.1f} {(e - s) / 1e3:6.1f}  q{q}  {n[:78]}")
 busy = sorted((s, e) for s, e, _, _ in win)
 idle, cur = 0, w0
 for s, e in busy:
+    e = min(e, w1)
     if s > cur:
         idle += s - cur
     cur = max(cur, e)
 print(f"  no kernel running for {idle / 1e3:.1f} us of the window's {(w1 - w0) / 1e3:.1f} us; sum of kernel time "
-      f"{sum(e - s for s, e, _, _ in win) / 1e3:.1f} us")
+      f"{sum(min(e, w1) - s for s, e, _, _ in win) / 1e3:.1f} us")
 # median duration per kernel name over the whole trace (update kernels only: those seen in the window)
 names = []
 for _, _, n, _ in win:
