@@ -752,6 +752,47 @@ typedef struct macjd_gru_bwd_io {
 int macjd_gru_sequence_backward_supported(int32_t H);   /* 1 for 64 and 128, else 0 */
 int macjd_gru_sequence_backward(const macjd_gru_bwd_io* io, void* hip_stream);
 
+/*
+ * Gradient of the MP-DQN actor objective (Bester et al.; the reference never trains its actor, so this has no line
+ * there) down to the OUTPUT gradients of the three actor layers, for N independent rows in ONE launch.  Per row n, with
+ * the Q-head a constant and nothing flowing into h (base = W1q[:, :H] h + b1q is the caller's GEMM, as for macjd_qhead_io):
+ *   a1 = relu(W1a x + b1a)   a2 = relu(W2a a1 + b2a)   u = W3a a2 + b3a   P = sigmoid(u)        (core/networks.py:116-129)
+ *   z_a = base + W1q[:, H + a] + W1q[:, H + A] P_a        Q_a = w2q . relu(z_a) + b2q            (core/networks.py:131-180)
+ *   L = - sum_n m[n] sum_a Q_na
+ *   s_a = sum_k w2q[k] W1q[k, H + A] [z_ak > 0]
+ *   g3[n, a] = dL/du = - m[n] s_a P_a (1 - P_a)
+ *   g2 = (g3 W3a) * [a2 > 0]        g1 = (g2 W2a) * [a1 > 0]        qsum[n] = sum_a Q_na
+ * The weight gradients are time-parallel products left to the caller (macjd_linear_wgrad):
+ *   dW3a = g3^T a2, dW2a = g2^T a1, dW1a = g1^T x, the bias gradients the column sums of g3 / g2 / g1.
+ * Exact float32 (v_mfma_f32_16x16x4_f32 for the three layers and the two transposed products, the weights in torch's own
+ * [out, in] layout both ways; the per-action term on VALU, [N, A, H] is never materialised); P comes from the forward
+ * kernels' sigmoid.  Every output element is written exactly once (no atomics, no workspace); a row with m[n] == 0
+ * gets exact zeros in g1 / g2 / g3 (a1, a2 and qsum are written all the same).  All outputs are contiguous.
+ * Supported: the actor chain within macjd_mlp_forward's limits (S <= 256, Ha <= 128 with ceil(Ha / 16) in {1,2,3,4,8},
+ * one layer's LDS image + the activation strips <= 160 KB), H = 64 or 128, A <= 33.  NULL required pointers, a
+ * non-positive size or a row stride smaller than its row return MACJD_EINVAL; an unsupported shape returns
+ * MACJD_EUNSUPPORTED with nothing launched.
+ */
+typedef struct macjd_actor_grad_io {
+    int64_t n_rows;                    /* N */
+    int32_t S, Ha, H, A;               /* observation width, actor hidden width, rnn_hidden_dim, n_actions */
+    const float* x;     int64_t x_ld;      /* [N,S] observation rows, row stride in elements */
+    const float* base;  int64_t base_ld;   /* [N,H] W1q[:, :H] h + b1q */
+    const float* m;                        /* [N] row weights */
+    const float* W1a; const float* b1a;    /* actor.0 [Ha,S], [Ha] */
+    const float* W2a; const float* b2a;    /* actor.2 [Ha,Ha], [Ha] */
+    const float* W3a; const float* b3a;    /* actor.4 [A,Ha], [A] */
+    const float* W1q;   int64_t w1_ld;     /* fc2_q_head.0.weight [H, H+A+1], row stride */
+    const float* w2q;                      /* fc2_q_head.2.weight [H] */
+    const float* b2q;                      /* fc2_q_head.2.bias [1] or NULL (= 0): enters qsum only */
+    float* a1; float* a2;                  /* out [N,Ha]: post-ReLU activations (weight-gradient operands) */
+    float* g3;                             /* out [N,A] */
+    float* g2; float* g1;                  /* out [N,Ha] */
+    float* qsum;                           /* out [N], optional (NULL skips it) */
+} macjd_actor_grad_io;
+int macjd_actor_gradient_supported(int32_t S, int32_t Ha, int32_t H, int32_t A);   /* 1 / 0 */
+int macjd_actor_gradient(const macjd_actor_grad_io* io, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,7 @@ EXPORTS = [
     "macjd_scenario_set_scan_pattern",
     "macjd_gru_sequence_backward_supported", "macjd_gru_sequence_backward",
     "macjd_prefetch_batch_supported", "macjd_prefetch_batch",
+    "macjd_actor_gradient_supported", "macjd_actor_gradient",
 ]
 
 
@@ -138,6 +139,21 @@ class GruBwdIO(ctypes.Structure):
         ("h0", ctypes.c_void_p), ("h0_sb", ctypes.c_int64),
         ("w_hh", ctypes.c_void_p), ("dh_all", ctypes.c_void_p),
         ("dgi", ctypes.c_void_p), ("dgh", ctypes.c_void_p), ("dh0", ctypes.c_void_p),
+    ]
+
+
+class ActorGradIO(ctypes.Structure):
+    """ctypes mirror of ``macjd_actor_grad_io`` (include/macjd_nets.h)."""
+    _fields_ = [
+        ("n_rows", ctypes.c_int64),
+        ("S", ctypes.c_int32), ("Ha", ctypes.c_int32), ("H", ctypes.c_int32), ("A", ctypes.c_int32),
+        ("x", ctypes.c_void_p), ("x_ld", ctypes.c_int64), ("base", ctypes.c_void_p), ("base_ld", ctypes.c_int64),
+        ("m", ctypes.c_void_p),
+        ("W1a", ctypes.c_void_p), ("b1a", ctypes.c_void_p), ("W2a", ctypes.c_void_p), ("b2a", ctypes.c_void_p),
+        ("W3a", ctypes.c_void_p), ("b3a", ctypes.c_void_p),
+        ("W1q", ctypes.c_void_p), ("w1_ld", ctypes.c_int64), ("w2q", ctypes.c_void_p), ("b2q", ctypes.c_void_p),
+        ("a1", ctypes.c_void_p), ("a2", ctypes.c_void_p), ("g3", ctypes.c_void_p), ("g2", ctypes.c_void_p),
+        ("g1", ctypes.c_void_p), ("qsum", ctypes.c_void_p),
     ]
 
 
@@ -423,6 +439,10 @@ def load() -> ctypes.CDLL:
     lib.macjd_gru_sequence_backward_supported.argtypes = [ctypes.c_int32]
     lib.macjd_gru_sequence_backward.restype = ctypes.c_int
     lib.macjd_gru_sequence_backward.argtypes = [ctypes.POINTER(GruBwdIO), ctypes.c_void_p]
+    lib.macjd_actor_gradient_supported.restype = ctypes.c_int
+    lib.macjd_actor_gradient_supported.argtypes = [ctypes.c_int32] * 4
+    lib.macjd_actor_gradient.restype = ctypes.c_int
+    lib.macjd_actor_gradient.argtypes = [ctypes.POINTER(ActorGradIO), ctypes.c_void_p]
     for name in ("macjd_mixer_tail_forward", "macjd_mixer_tail_backward"):
         getattr(lib, name).restype = ctypes.c_int
         getattr(lib, name).argtypes = [ctypes.POINTER(MixerIO), ctypes.c_void_p]

@@ -63,7 +63,7 @@ class BasicMAC:
         obs = obs_batch.to(device) if obs_batch.device != device else obs_batch
         E, J, S = obs.shape
         # the same observation tensor and an unchanged agent body (everything but the Q-head: frozen in reference-faithful
-        # training) give the same tensors as last time: nothing to launch (version counters see every in-place write)
+        # training; the learner's train_agent_body / train_actor options train it and invalidate this cache) give the same tensors as last time: nothing to launch (version counters see every in-place write)
         key = (obs.data_ptr(), obs._version, tuple(obs.shape), tuple(obs.stride()),
                tuple((p.data_ptr(), p._version) for n_, p in self.agent.named_parameters() if not n_.startswith("fc2_q_head")))
         capturing = obs.is_cuda and torch.cuda.is_current_stream_capturing()   # a captured rollout recomputes at every replay
@@ -84,7 +84,7 @@ class BasicMAC:
     def invalidate_static_inputs(self):
         """Forget the key of the cached static-observation inputs: the next ``prepare_static_obs`` recomputes them.  For
         callers that change the agent body in a way the version counters of the key do not see (writes through
-        ``p.data`` views: the learner's fused optimiser step with ``train_agent_body``)."""
+        ``p.data`` views: the learner's fused optimiser step with ``train_agent_body`` / ``train_actor``)."""
         self._static_key = None
 
     def select_actions(self, obs_batch, avail_actions_batch, t_env, test_mode=False):

@@ -135,7 +135,8 @@ class RNNAgent(nn.Module):
         return ops.gru_gates(gi, gh, h_in, out2=h_out2)
 
     def actor_forward(self, inputs):
-        """Continuous parameter for EVERY discrete action, [N, A] in (0,1)  (networks.py:116-129)."""
+        """Continuous parameter for EVERY discrete action, [N, A] in (0,1)  (networks.py:116-129).  Trained only by the
+        learner's opt-in ``train_actor`` (ops.actor_gradient: this chain and its backward in one launch)."""
         if self.fused_actor and self._fused_ok(inputs):
             a = self.actor
             out = ops.mlp_forward(inputs.reshape(-1, inputs.shape[-1]),

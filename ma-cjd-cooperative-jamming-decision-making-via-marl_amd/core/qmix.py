@@ -8,15 +8,25 @@ Same public surface: ``QMixLearner(mac, args)``; ``train(batch, train_info) -> {
 Reference behaviour that is reproduced on purpose:
   * only the Q-head and the mixer ever receive gradients: ``q_taken`` is evaluated from the BUFFERED
     hidden states and continuous actions (qmix.py:161-184); the unrolled eval network feeds an argmax
-    only (qmix.py:134-143), so actor / fc1 / GRU parameters keep ``grad is None`` for ever;
+    only (qmix.py:134-143), so actor / fc1 / GRU parameters keep ``grad is None`` for ever (by default: see the two
+    opt-in departures below);
   * the Double-DQN argmax does not apply the availability mask (qmix.py:141-142 is commented out);
   * the loss runs over steps 0..T-2 (``[:, :-1]`` slices, qmix.py:155,192).
 
 Opt-in departure, ``args.train_agent_body`` (off by default; main.py ``--train-agent-body``): ``q_taken`` is evaluated
 from the eval agent's own differentiable unroll instead of the buffered hidden states, so the loss also reaches fc1 and
-the GRU (back-propagation through time: ops.gru_sequence_train).  The actor stays frozen; target network, mixer, loss
-and target sync are unchanged.  With an untouched body the unrolled and the buffered hidden states are the same numbers,
+the GRU (back-propagation through time: ops.gru_sequence_train).  The actor is not reached by it; target network, mixer,
+loss and target sync are unchanged.  With an untouched body the unrolled and the buffered hidden states are the same numbers,
 so the reference's loss is the special case.  Eager updates only (``train``): ``enable_graphs`` refuses.
+
+Opt-in departure, ``args.train_actor`` (off by default; main.py ``--train-actor``; independent of ``train_agent_body``, the
+two combine): the actor gets the standard MP-DQN actor objective (Bester et al.) next to the TD loss,
+``L_actor = -sum_n m_n sum_a Q(h_n, a, x_a(o_n))`` over the rows n = (b, t, j), t < T-1, of ``q_taken``, with
+``m_n = actor_loss_coef * filled[b,t] / (J * sum filled)``, the Q-head held fixed and ``h_n`` (the hidden state ``q_taken``
+uses for the row) detached.  Its gradient goes to the six actor tensors only and joins the ONE flat gradient vector, clip
+and Adam step; the actor reads the observation alone, so the whole gradient is time-parallel: one launch
+(ops.actor_gradient) and three split-K weight gradients.  ``train`` then also returns ``actor_q_avg`` =
+``sum_n m_n sum_a Q_na / actor_loss_coef``.  Eager updates only, like ``train_agent_body``.
 
 What changes is the schedule of the work, not the algebra.  The reference unrolls
 ``for t: for a:`` in Python — 2 x T x (3 + 5A) small launches per call (qmix.py:241-274).  Everything
@@ -59,6 +69,9 @@ class QMixLearner:
         self.obs_shape = args.obs_shape
         self.device = torch.device(args.device if torch.cuda.is_available() and args.use_cuda else "cpu")
         self.train_agent_body = bool(getattr(args, "train_agent_body", False))   # module docstring
+        self.train_actor = bool(getattr(args, "train_actor", False))             # module docstring
+        self.actor_loss_coef = float(getattr(args, "actor_loss_coef", 1.0))
+        self._last_actor_q = None
 
         self.eval_qmix_net = QMixer(args)
         self.target_mac = copy.deepcopy(mac)
@@ -87,7 +100,8 @@ class QMixLearner:
     # ------------------------------------------------------------------ frozen agent body
     @staticmethod
     def _body_params(agent):
-        """fc1 / GRU / actor: the parameters the loss never reaches (module docstring)."""
+        """fc1 / GRU / actor: the parameters the reference's loss never reaches (module docstring; ``train_agent_body`` and
+        ``train_actor`` train the eval agent's, and the two bodies then differ between target syncs)."""
         return list(agent.fc1.parameters()) + list(agent.rnn.parameters()) + list(agent.actor.parameters())
 
     def _mark_body_shared(self):
@@ -114,8 +128,8 @@ class QMixLearner:
         return same and self._body_is_shared()
 
     def _body_is_shared(self):
-        if self.train_agent_body:   # the fused optimiser writes fc1 / GRU through .data views: the counters do not see it
-            return False
+        if self.train_agent_body or self.train_actor:   # the fused optimiser writes fc1 / GRU / the actor through .data
+            return False                                # views: the counters do not see it
         if not options.on("SHARED_BODY") or not self._body_versions:
             return False
         pe = self._body_params(self.mac.agent)
@@ -129,12 +143,14 @@ class QMixLearner:
         """Parameters the loss can reach: the Q-head and the mixer (see module docstring), in the order of the
         flat vectors: the mixer's four first-layer weights, then their biases (adjacent, so that the merged
         first-layer GEMM reads them as ONE [2Hh+2Em, S] matrix without a torch.cat), then everything else.
-        ``train_agent_body``: fc1 and the GRU of the eval agent follow at the end (the actor never does)."""
+        ``train_agent_body``: fc1 and the GRU of the eval agent follow at the end; ``train_actor``: the eval agent's six
+        actor tensors come last of all (``self.params`` keeps its order either way)."""
         first = self.eval_qmix_net.first_layer_params()
         ids = {id(p) for p in first}
         rest = [p for p in list(self.mac.agent.fc2_q_head.parameters()) + self.qmix_params if id(p) not in ids]
         body = list(self.mac.agent.fc1.parameters()) + list(self.mac.agent.rnn.parameters()) if self.train_agent_body else []
-        return first + rest + body
+        actor = list(self.mac.agent.actor.parameters()) if self.train_actor else []
+        return first + rest + body + actor
 
     @staticmethod
     def _world_size():
@@ -311,10 +327,43 @@ class QMixLearner:
 
         for p in self.params:   # autograd then ASSIGNS fresh gradients (no accumulate-add kernels, no memset);
             p.grad = None       # parameters the graph never reaches keep grad None, as in the reference
-        loss.backward()
+        if self.train_actor:
+            # the weight-gradient launches of this update — the TD loss's where they are split-K products, and the actor's
+            # — write into the flat gradient vector's slices (HIP device) and run grouped when the context closes
+            with ops.deferred_wgrad(grad_dst=getattr(self, "_grad_dst", None)):
+                loss.backward()
+                self._last_actor_q = self._actor_backward(obs, hidden_states if h_eval is None else h_eval.detach(), filled, T)
+        else:
+            loss.backward()
         if self._world_size() > 1 or self._flat_param is not None:
             self._flatten_grads()   # one cat: the all-reduce buffer and the fused optimiser's input
         return loss.detach(), eval_mean.detach(), target_mean.detach()
+
+    def _actor_backward(self, obs, h_taken, filled, T):
+        """``train_actor``: gradient of L_actor (module docstring) into the six actor tensors' ``.grad``; returns
+        actor_q_avg as a 0-dim tensor.  The Q-head is data here (its ``.grad`` is the TD loss's alone), nothing flows into
+        ``h_taken`` [B, >= T-1, J, H].  An empty loss (T <= 1) or an all-zero mask gives zero gradients.  No host sync."""
+        a = self.mac.agent
+        params = list(a.actor.parameters())   # actor.0.weight, .0.bias, .2.weight, .2.bias, .4.weight, .4.bias
+        B, J, H, A = obs.shape[0], self.n_agents, self.args.rnn_hidden_dim, self.n_actions
+        if T <= 1:
+            for p in params:
+                p.grad = torch.zeros_like(p)
+            return torch.zeros((), dtype=torch.float32, device=obs.device)
+        n = B * (T - 1) * J
+        with torch.no_grad():
+            f = filled[:, :T - 1].reshape(B, T - 1).to(torch.float32)
+            tot = f.sum()
+            w = torch.where(tot > 0, f / (J * tot), torch.zeros_like(f))           # m_n / actor_loss_coef per (b, t)
+            w = w.unsqueeze(2).expand(B, T - 1, J).reshape(n)
+            x = obs[:, :T - 1].reshape(n, -1)
+            l1, l2 = a.fc2_q_head[0], a.fc2_q_head[2]
+            base = F.linear(h_taken[:, :T - 1].reshape(n, H), l1.weight[:, :H], l1.bias)
+            a1, a2, g3, g2, g1, qsum = ops.actor_gradient(x, base, self.actor_loss_coef * w, a.actor_layers(), l1.weight,
+                                                           l2.weight, l2.bias, H, A)
+            for p, g in zip(params, ops.actor_weight_grads(x, a1, a2, g3, g2, g1, params=params)):
+                p.grad = g
+            return (w * qsum).sum()
 
     def _unroll_eval_body(self, obs):
         """The eval agent's recurrent body over whole episodes WITH autograd (``train_agent_body``): fc1 + ReLU and W_ih
@@ -712,8 +761,10 @@ class QMixLearner:
             self._update_targets()
             self.last_target_update_step = self.train_step
 
-    def _pack_stats(self, loss, grad_norm, ev, tg, sync_stats):
+    def _pack_stats(self, loss, grad_norm, ev, tg, sync_stats, actor_q=None):
         stats = {"loss": loss, "grad_norm": grad_norm, "eval_qtot_avg": ev, "target_qtot_avg": tg}
+        if actor_q is not None:   # train_actor only: the default dict keeps exactly the reference's four keys
+            stats["actor_q_avg"] = actor_q
         if sync_stats:  # the reference returns Python floats (4 x .item(), qmix.py:209-214)
             stacked = torch.stack([torch.as_tensor(v, device=self.device, dtype=torch.float32).reshape(())
                                    for v in stats.values()])
@@ -726,15 +777,15 @@ class QMixLearner:
         loss, ev, tg = self._forward_backward(batch, int(batch["max_seq_len"]))
         self._allreduce_grads()
         grad_norm = self._clip_and_step()
-        if self.train_agent_body:
-            # the step wrote fc1 / GRU (through .data views on a HIP device, which no version counter sees): what the
-            # controllers cached from the body for a static observation is stale
+        if self.train_agent_body or self.train_actor:
+            # the step wrote fc1 / GRU / the actor (through .data views on a HIP device, which no version counter sees):
+            # what the controllers cached from the body for a static observation is stale
             for m in (self.mac, self.target_mac):
                 m.invalidate_static_inputs()
         self._after_step()
         if not sync_stats and torch.is_tensor(grad_norm) and grad_norm is self._grad_norm_tensor():
             grad_norm = grad_norm.clone()   # the fused optimiser step reuses ONE output tensor: hand out a snapshot
-        return self._pack_stats(loss, grad_norm, ev, tg, sync_stats)
+        return self._pack_stats(loss, grad_norm, ev, tg, sync_stats, actor_q=self._last_actor_q if self.train_actor else None)
 
     def _grad_norm_tensor(self):
         return getattr(self, "_grad_norm", None)
@@ -756,6 +807,9 @@ class QMixLearner:
         if self.train_agent_body:
             raise RuntimeError("enable_graphs: train_agent_body is an eager-mode option (the captured, static-observation "
                                "and shared-body updates are built on the frozen agent body); use train()")
+        if self.train_actor:
+            raise RuntimeError("enable_graphs: train_actor is an eager-mode option (the captured, static-observation and "
+                               "shared-body updates are built on the frozen actor); use train()")
         self.release_graphs()   # a re-capture destroys the previous graphs first, explicitly and at a quiet point
         self._verify_body_shared()   # (values, not version counters: catches writes made through .data)
         same_buffer = getattr(self, "_g_buffer", None) is buffer

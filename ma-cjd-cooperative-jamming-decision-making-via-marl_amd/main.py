@@ -243,8 +243,8 @@ def run(args):
     batch_envs = int(getattr(args, "batch_envs", 1) or 1)
     episodes_per_run = batch_envs
     use_graphs = bool(getattr(args, "hip_graphs", True)) and args.use_cuda and batch_envs > 1
-    if getattr(args, "train_agent_body", False):
-        use_graphs = False   # the recurrent update is eager (learner.train); the captured update is built on the frozen body
+    if getattr(args, "train_agent_body", False) or getattr(args, "train_actor", False):
+        use_graphs = False   # these updates are eager (learner.train); the captured update is built on the frozen body
     # config/default.yaml is scaled for batch_envs = 4096 (epsilon annealed over 2500 steps PER ENV, 200 M collected steps);
     # the reference's own protocol (one env) anneals over 100 000 of its 2 M steps (reference config/default.yaml:21-23,60)
     if batch_envs == 1 and (args.epsilon_anneal_time < 20000 or args.total_env_steps > 20_000_000):
@@ -262,7 +262,7 @@ def run(args):
     log_stats = {k: deque(maxlen=args.log_interval) for k in
                  ("episode_return", "episode_length", "avg_step_reward", "reward_r_d", "reward_r_p", "reward_r_j",
                   "avg_power", "action_dist")}
-    log_stats.update({k: deque(maxlen=n_upd) for k in ("loss", "grad_norm", "eval_qtot_avg", "target_qtot_avg")})
+    log_stats.update({k: deque(maxlen=n_upd) for k in ("loss", "grad_norm", "eval_qtot_avg", "target_qtot_avg", "actor_q_avg")})
     start_time = last_log_time = time.time()
     next_test = total_steps + getattr(args, "test_interval", 0) if getattr(args, "test_interval", 0) else None
     graphs_on = False
@@ -313,6 +313,8 @@ def run(args):
                 for st in pending:
                     for k in ("loss", "grad_norm", "eval_qtot_avg", "target_qtot_avg"):
                         log_stats[k].append(st[k])
+                    if "actor_q_avg" in st:   # train_actor only
+                        log_stats["actor_q_avg"].append(st["actor_q_avg"])
                 writer.add_scalar("Loss/train_episode_avg", float(np.mean([p["loss"] for p in pending])), total_steps)
 
         if next_test is not None and total_steps >= next_test:
@@ -335,6 +337,9 @@ def run(args):
             print(f"  Avg Rewards (r_d/r_p/r_j): {m('reward_r_d'):.4f} / {m('reward_r_p'):.4f} / {m('reward_r_j'):.4f}")
             print(f"  Avg QTot (Eval/Target): {m('eval_qtot_avg'):.4f} / {m('target_qtot_avg'):.4f} | "
                   f"Avg Grad Norm: {m('grad_norm'):.4f}")
+            if log_stats["actor_q_avg"]:
+                print(f"  Avg Actor Q (sum over actions): {m('actor_q_avg'):.4f}")
+                writer.add_scalar("QValues/actor_q_avg", m("actor_q_avg"), total_steps)
             print(f"  Avg Power: {m('avg_power'):.3f} | Action Dist: [{' / '.join(f'{p:.2f}' for p in dist)}] "
                   f"(0=Idle, 1=S0, 2=D0, ...)")
             print(f"  Buffer Size: {len(buffer)}")
@@ -379,7 +384,12 @@ def main(argv=None):
                         help="batched runs: every env gets its own random variation of the scenario (per-env tables)")
     parser.add_argument("--train-agent-body", action="store_true",
                         help="also train fc1 and the GRU of the agent (back-propagation through the unrolled episode); "
-                             "eager updates, the actor stays frozen")
+                             "eager updates, the actor stays frozen unless --train-actor is given")
+    parser.add_argument("--train-actor", action="store_true",
+                        help="also train the actor with the MP-DQN objective (maximise the sum over actions of Q(h, a, x_a(o)) "
+                             "with the Q-head held fixed); eager updates; combines with --train-agent-body")
+    parser.add_argument("--actor-loss-coef", type=float, default=None, metavar="X",
+                        help="weight of the actor objective in the one clipped Adam step (default 1.0)")
     a = parser.parse_args(argv)
     config = load_config(config_name=a.config, config_dir=a.config_dir)
     config.config, config.env_config, config.device_request = a.config, a.env_config, a.device
@@ -391,6 +401,10 @@ def main(argv=None):
         config.randomize_scenarios = True
     if a.train_agent_body:
         config.train_agent_body = True
+    if a.train_actor:
+        config.train_actor = True
+    if a.actor_loss_coef is not None:
+        config.actor_loss_coef = a.actor_loss_coef
     return run(config)
 
 

@@ -1927,3 +1927,79 @@ def linear(x, weight, bias=None):
             and x.stride(-1) == 1):
         return _LinearSplitK.apply(x, weight, bias)
     return F.linear(x, weight, bias)
+
+
+# ------------------------------------------------------------------ MP-DQN actor objective (learner, train_actor)
+def actor_gradient_reference(x, base, m, layers, W1q, w2q, b2q, H: int, A: int):
+    """Stock-torch form of ``actor_gradient`` (same outputs), through autograd: host tensors, float64, shapes the kernel
+    does not take.  Materialises [N, A, H]."""
+    (W1a, b1a), (W2a, b2a), (W3a, b3a) = [(l[0].detach(), l[1].detach()) for l in layers]
+    x, base, m, W1q, w2q = x.detach(), base.detach(), m.detach().reshape(-1), W1q.detach(), w2q.detach().reshape(-1)
+    with torch.enable_grad():
+        p1 = F.linear(x, W1a, b1a).requires_grad_(True)
+        a1 = F.relu(p1)
+        p2 = F.linear(a1, W2a, b2a)
+        a2 = F.relu(p2)
+        u = F.linear(a2, W3a, b3a)
+        P = torch.sigmoid(u)
+        z = base.unsqueeze(1) + W1q[:, H:H + A].t().unsqueeze(0) + P.unsqueeze(2) * W1q[:, H + A].view(1, 1, -1)   # [N, A, H]
+        Q = F.relu(z) @ w2q
+        if b2q is not None:
+            Q = Q + b2q.detach().reshape(())
+        qsum = Q.sum(1)
+        g3, g2, g1 = torch.autograd.grad(-(m * qsum).sum(), [u, p2, p1])
+    return a1.detach(), a2.detach(), g3, g2, g1, qsum.detach()
+
+
+def actor_gradient_supported(x, S: int, Ha: int, H: int, A: int) -> bool:
+    """The one-launch kernel applies: float32 rows on a HIP device and a shape inside macjd_actor_gradient's range."""
+    return bool(x.is_cuda and x.dtype == torch.float32 and not torch.is_autocast_enabled()
+                and _native.load().macjd_actor_gradient_supported(int(S), int(Ha), int(H), int(A)))
+
+
+def actor_gradient(x, base, m, layers, W1q, w2q, b2q, H: int, A: int):
+    """Output gradients of the three actor layers under L = -sum_n m[n] sum_a Q(h_n, a, P_a(x_n)) with the Q-head held
+    fixed (include/macjd_nets.h, macjd_actor_grad_io): returns (a1 [N,Ha], a2 [N,Ha], g3 [N,A], g2 [N,Ha], g1 [N,Ha],
+    qsum [N]).  ``x`` [N,S] observation rows, ``base`` [N,H] = W1q[:, :H] h + b1q, ``m`` [N], ``layers`` = the actor's
+    three (weight, bias[, act]) entries (RNNAgent.actor_layers).  ONE launch on a HIP device; elsewhere, and for shapes
+    outside the kernel's range, ``actor_gradient_reference``."""
+    S, Ha = int(layers[0][0].shape[1]), int(layers[0][0].shape[0])
+    if x.shape[0] == 0 or not actor_gradient_supported(x, S, Ha, H, A):
+        return actor_gradient_reference(x, base, m, layers, W1q, w2q, b2q, H, A)
+    lib = _native.load()
+    x, base, W1q = _f32c(x.detach()), _f32c(base.detach()), _f32c(W1q.detach())
+    m = m.detach().float().reshape(-1).contiguous()
+    w2q = w2q.detach().float().reshape(-1).contiguous()
+    ws = [(l[0].detach().float().contiguous(), l[1].detach().float().contiguous()) for l in layers]
+    N = x.shape[0]
+    assert base.shape == (N, H) and m.numel() == N and W1q.shape == (H, H + A + 1) and w2q.numel() == H
+    assert ws[1][0].shape == (Ha, Ha) and ws[2][0].shape == (A, Ha)
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=x.device)
+    a1, a2, g3, g2, g1, qsum = new(N, Ha), new(N, Ha), new(N, A), new(N, Ha), new(N, Ha), new(N)
+    io = _native.ActorGradIO()
+    io.n_rows, io.S, io.Ha, io.H, io.A = N, S, Ha, H, A
+    io.x, io.x_ld, io.base, io.base_ld, io.m = x.data_ptr(), x.stride(0), base.data_ptr(), base.stride(0), m.data_ptr()
+    (io.W1a, io.b1a), (io.W2a, io.b2a), (io.W3a, io.b3a) = [(w.data_ptr(), b.data_ptr()) for w, b in ws]
+    io.W1q, io.w1_ld, io.w2q = W1q.data_ptr(), W1q.stride(0), w2q.data_ptr()
+    b2c = None if b2q is None else b2q.detach().float().reshape(-1).contiguous()
+    io.b2q = None if b2c is None else b2c.data_ptr()
+    io.a1, io.a2, io.g3, io.g2, io.g1, io.qsum = (t.data_ptr() for t in (a1, a2, g3, g2, g1, qsum))
+    with torch.cuda.device(x.device):
+        _native.check(lib.macjd_actor_gradient(ctypes.byref(io), _stream(x)), "macjd_actor_gradient")
+    return a1, a2, g3, g2, g1, qsum
+
+
+def actor_weight_grads(x, a1, a2, g3, g2, g1, params=None):
+    """The six actor gradients from ``actor_gradient``'s outputs: (dW1a, db1a, dW2a, db2a, dW3a, db3a) with
+    dW3a = g3^T a2, dW2a = g2^T a1, dW1a = g1^T x and the column sums.  HIP device: the split-K weight-gradient kernel
+    (``linear_wgrad``); with ``params`` = the six parameters in that order, results land in the gradient destinations of
+    the active ``deferred_wgrad`` context (the learner's flat gradient slices).  Host tensors: plain matmuls."""
+    keys = [grad_key(p) for p in params] if params is not None else [None] * 6
+    out = []
+    for i, (g, inp) in enumerate(((g1, x), (g2, a1), (g3, a2))):
+        if g.is_cuda and g.dtype == torch.float32 and g.shape[0] > 0:
+            dW, db = linear_wgrad(g, inp, want_bias=True, w_key=keys[2 * i], b_key=keys[2 * i + 1])
+        else:
+            dW, db = g.t().matmul(inp.to(g.dtype)), g.sum(0)
+        out += [dW, db]
+    return tuple(out)
