@@ -28,8 +28,9 @@
 extern "C" {
 #endif
 
-#define MACJD_ABI_VERSION 7
+#define MACJD_ABI_VERSION 8
 #define MACJD_PE_ROWS(R, J) (6 * (R) + 3 * (J) + (J) * (R))
+#define MACJD_PE_SCAN_ROWS(R, J) (10 * (R) + (J) * (R))
 
 #define MACJD_OK          0
 #define MACJD_EINVAL     -1  /* bad argument (shape, NULL, stride)            */
@@ -224,6 +225,21 @@ typedef struct macjd_scan_io {
     float*  snr_no;   int64_t sn_se, sn_sx; /* optional [E,R] per-step SNR without jamming (main or side lobe)     */
 } macjd_scan_io;
 
+/*
+ * Per-env scanning tables of a step / reset on per-env scenario tables (macjd_step_io.pe_tables): every env has its own
+ * macjd_scan_desc quantities.  `tables` is a float64 device array of MACJD_PE_SCAN_ROWS(R, J) rows in the order
+ *   half_beam[R] | sweep[R] | sweep_mod[R] | az0[R] | bear_tgt[R] | GaPs_side[R] | snr_no[R] | snr_no_side[R] |
+ *   pd_no_side[R] | gr_side[R] | bear_jam[J*R] (j-major)
+ * laid out like the step's own pe_tables: plain (pe_tile == 0), row t of env e at tables[t * stride + e]; tiled
+ * (pe_tile > 0), at tables[((e / pe_tile) * MACJD_PE_SCAN_ROWS + t) * pe_tile + e % pe_tile], the last tile padded, stride
+ * ignored.  `full` is not carried: it equals (sweep + 2 half_beam >= 360.0) in float64 (2 half_beam is exact), which the
+ * device recomputes with the same bits.  The main-lobe GaPs / pd_no / gr are those of pe_tables.
+ */
+typedef struct macjd_scan_pe_io {
+    const double* tables;
+    int64_t stride;   /* >= n_envs when pe_tile == 0 */
+} macjd_scan_pe_io;
+
 /* library / device */
 int         macjd_abi_version(void);
 const char* macjd_last_error(void);
@@ -263,12 +279,22 @@ int macjd_scenario_set_scan(macjd_scenario* s, const macjd_scan_desc* d);
    launch their pattern variants: no other call changes. */
 int macjd_scenario_set_scan_pattern(macjd_scenario* s, const macjd_scan_pattern_desc* d);
 /* macjd_env_step with scanning beams (see macjd_scan_desc); needs macjd_scenario_set_scan first.  Always the one-lane-
-   per-env kernel; per-env scenario tables (pe_tables) are refused. */
+   per-env kernel; per-env scenario tables (pe_tables) are refused here: macjd_env_step_scan_pe takes them. */
 int macjd_env_step_scan(const macjd_scenario* s, const macjd_step_io* io, const macjd_scan_io* scan, void* hip_stream);
 /* beam part of a reset, issued next to macjd_env_reset with the same mask: theta_a[e,:] = az0 (and the state
    columns = (float)az0) for envs with mask != 0 (all when mask == NULL) */
 int macjd_env_reset_scan(const macjd_scenario* s, int64_t n_envs, const macjd_scan_io* scan, const uint8_t* mask,
                          void* hip_stream);
+
+/* macjd_env_step_scan on per-env scenario tables: needs io->pe_tables (with io->pe_tile choosing the layout of both table
+   sets) and a scanning handle WITHOUT pattern levels; the handle supplies R, J, episode_limit, the r_p bounds and the Pd
+   constants, every table value comes from the env's own columns.  Results are bit-identical to a single-scenario
+   macjd_env_step_scan of the same env in its all-float64 form (MACJD_ENV_PD32=0). */
+int macjd_env_step_scan_pe(const macjd_scenario* s, const macjd_step_io* io, const macjd_scan_io* scan,
+                           const macjd_scan_pe_io* scan_pe, void* hip_stream);
+/* macjd_env_reset_scan with az0 from each env's column: theta_a[e,r] = az0_e[r], state columns = (float)az0_e[r] */
+int macjd_env_reset_scan_pe(const macjd_scenario* s, int64_t n_envs, const macjd_scan_io* scan, const macjd_scan_pe_io* scan_pe,
+                            int32_t pe_tile, const uint8_t* mask, void* hip_stream);
 
 /* T consecutive steps of all E environments in ONE launch, given the actions of all T steps (time-major: step t of
    env e at offset t * t_stride + e * se + k * sx of T / P32; outputs reward / terminated / r_dpj likewise at

@@ -14,7 +14,7 @@ LIB_NAME = "libmacjd_hip.so"
 # MACJD_LIB points at another build of the same sources (kernel A/B runs); the default is the in-tree library
 LIB_PATH = os.environ.get("MACJD_LIB") or os.path.join(_PKG_DIR, LIB_NAME)
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 STEP_ARITH_F64 = 1
 STEP_LANE_KERNEL = 2
 STEP_SLOT_KERNEL = 4
@@ -31,6 +31,7 @@ EXPORTS = [
     "macjd_qhead_double_q_supported", "macjd_qhead_double_q", "macjd_qhead_taken_supported", "macjd_qhead_taken",
     "macjd_qheads_pair", "macjd_mixer_fused_forward_pair", "macjd_mixer_fused_train", "macjd_mixer_fused_train_static",
     "macjd_scenario_set_scan", "macjd_env_step_scan", "macjd_env_reset_scan",
+    "macjd_env_step_scan_pe", "macjd_env_reset_scan_pe",
     "macjd_agent_env_episode_scan_supported", "macjd_agent_env_episode_scan",
     "macjd_scenario_set_scan_pattern",
     "macjd_gru_sequence_backward_supported", "macjd_gru_sequence_backward",
@@ -92,6 +93,11 @@ class ScanIO(ctypes.Structure):
         ("state", ctypes.c_void_p), ("st_se", ctypes.c_int64), ("st_col0", ctypes.c_int32), ("st_col_step", ctypes.c_int32),
         ("snr_no", ctypes.c_void_p), ("sn_se", ctypes.c_int64), ("sn_sx", ctypes.c_int64),
     ]
+
+
+class ScanPeIO(ctypes.Structure):
+    """ctypes mirror of ``macjd_scan_pe_io`` (include/macjd.h): the per-env scan SoA, MACJD_PE_SCAN_ROWS(R, J) rows."""
+    _fields_ = [("tables", ctypes.c_void_p), ("stride", ctypes.c_int64)]
 
 
 class QheadIO(ctypes.Structure):
@@ -427,6 +433,12 @@ def load() -> ctypes.CDLL:
     lib.macjd_env_step_scan.argtypes = [ctypes.c_void_p, ctypes.POINTER(StepIO), ctypes.POINTER(ScanIO), ctypes.c_void_p]
     lib.macjd_env_reset_scan.restype = ctypes.c_int
     lib.macjd_env_reset_scan.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ScanIO), ctypes.c_void_p, ctypes.c_void_p]
+    lib.macjd_env_step_scan_pe.restype = ctypes.c_int
+    lib.macjd_env_step_scan_pe.argtypes = [ctypes.c_void_p, ctypes.POINTER(StepIO), ctypes.POINTER(ScanIO),
+                                           ctypes.POINTER(ScanPeIO), ctypes.c_void_p]
+    lib.macjd_env_reset_scan_pe.restype = ctypes.c_int
+    lib.macjd_env_reset_scan_pe.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ScanIO), ctypes.POINTER(ScanPeIO),
+                                            ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
     lib.macjd_env_step.argtypes = [ctypes.c_void_p, ctypes.POINTER(StepIO), ctypes.c_void_p]
     lib.macjd_env_step_timed.restype = ctypes.c_int
     lib.macjd_env_step_timed.argtypes = [ctypes.c_void_p, ctypes.POINTER(StepIO), ctypes.c_int, ctypes.c_void_p,

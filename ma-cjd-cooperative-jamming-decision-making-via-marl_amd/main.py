@@ -20,7 +20,9 @@ What is added (build flags, all optional):
                   broadcast from rank 0, every update all-reduces the flat gradient (RCCL); rank 0 logs and saves.
   ``hip_graphs``  (default True on a HIP device with batch_envs > 1) replay rollouts / updates from HIP graphs.
   ``randomize_scenarios`` / ``--randomize-scenarios`` (batched runs): every env trains on its own random variation
-                  of the scenario file (positions, threat levels, powers; ``scenario.ScenarioBatch``).
+                  of the scenario file (positions, threat levels, powers; ``scenario.ScenarioBatch``), scanning
+                  radars included; ``randomize_azimuth_jitter`` (degrees, default 0) also moves every radar's
+                  initial beam azimuth.
   ``--resume DIR`` restores agent, mixer, optimiser and ``trainer_state.json`` (env steps, episodes, epsilon
                   clock, learner step counters, and the positions of the three random streams: exploration counter,
                   replay sampler, per-env Monte-Carlo episode index) — the reference saves the optimiser but never
@@ -118,7 +120,8 @@ def build_components(args, sim_config_path):
             from .scenario import ScenarioBatch
             with open(sim_config_path) as f:
                 base = yaml.safe_load(f)
-            batch = ScenarioBatch.randomized(base, batch_envs, seed=args.seed, config=args, env_offset=off)
+            batch = ScenarioBatch.randomized(base, batch_envs, seed=args.seed, config=args, env_offset=off,
+                                             azimuth_jitter=float(getattr(args, "randomize_azimuth_jitter", 0.0) or 0.0))
         env = BatchedElectromagneticEnvironment(args, sim_config_path, batch_envs=batch_envs, seed=args.seed,
                                                 env_offset=off, verbose=True, scenario_batch=batch)
     else:

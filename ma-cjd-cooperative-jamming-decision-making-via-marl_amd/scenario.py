@@ -529,13 +529,25 @@ class Scenario:
 # Row order of the per-env SoA table (include/macjd.h, macjd_step_io.pe_tables)
 _PE_RADAR_ROWS = ("radar_GaPs", "radar_Pn", "radar_D", "radar_pd_no", "radar_rd_pen", "radar_gr")
 _PE_JAMMER_ROWS = ("jam_pmin", "jam_pmax", "jam_gj")
+# Row order of the per-env scan SoA (include/macjd.h, macjd_scan_pe_io): R rows each, then bear_jam's J*R (j-major).
+# "snr_no" is the main-lobe row of Scenario.tables; the others are Scenario.scan_tables arrays.
+PE_SCAN_ROWS = ("half_beam", "sweep", "sweep_mod", "az0", "bear_tgt", "GaPs_side", "snr_no", "snr_no_side", "pd_no_side",
+                "gr_side", "bear_jam")
+
+
+def pe_scan_rows(n_radars: int, n_jammers: int) -> int:
+    """MACJD_PE_SCAN_ROWS(R, J) of include/macjd.h."""
+    return 10 * n_radars + n_jammers * n_radars
 
 
 def randomized_scenario_dict(base: dict, rng: np.random.Generator, position_jitter: float = 60.0,
-                             threat_jitter: float = 0.15, power_jitter: float = 0.2) -> dict:
+                             threat_jitter: float = 0.15, power_jitter: float = 0.2, azimuth_jitter: float = 0.0) -> dict:
     """One random variation of a scenario dict in the reference's schema: radar and jammer
     positions moved by N(0, position_jitter) metres per axis, threat levels by N(0, threat_jitter), radar peak
-    power ``pt`` and jammer ``power_max`` scaled by exp(N(0, power_jitter)).  Everything else is kept."""
+    power ``pt`` and jammer ``power_max`` scaled by exp(N(0, power_jitter)); with ``azimuth_jitter`` > 0 every radar's
+    initial beam azimuth ``theta_a`` moved by N(0, azimuth_jitter) degrees (scanning radars).  Everything else is kept.
+    The azimuth draws come after all the others and only when the jitter is > 0: without it the dict and the
+    generator's state afterwards are what they were before the option existed."""
     import copy
     d = copy.deepcopy(base)
     for r in d["radars"]:
@@ -547,6 +559,9 @@ def randomized_scenario_dict(base: dict, rng: np.random.Generator, position_jitt
         x, y = (float(v) for v in np.array(j["position"]).flatten()[:2])
         j["position"] = [x + float(rng.normal(0.0, position_jitter)), y + float(rng.normal(0.0, position_jitter))]
         j["power_max"] = float(j.get("power_max", 100.0) * np.exp(rng.normal(0.0, power_jitter)))
+    if azimuth_jitter > 0:
+        for r in d["radars"]:
+            r["theta_a"] = float(r.get("theta_a", 0.0)) + float(rng.normal(0.0, azimuth_jitter))
     return d
 
 
@@ -554,9 +569,15 @@ class ScenarioBatch:
     """E scenarios of one shape (same R, J, episode limit, r_p bounds, Pd constants), compiled one by one with
     :class:`Scenario` (so each env's tables are exactly what a single-scenario environment would use) and stacked
     as the per-env SoA the step kernel streams: ``tables`` float64 [6R + 3J + JR, E], ``flags`` uint8 [JR, E],
-    plus the per-env observation vectors ``state_vectors`` f32 [E, S] and ``snr_no`` f64 [E, R]."""
+    plus the per-env observation vectors ``state_vectors`` f32 [E, S] and ``snr_no`` f64 [E, R].
 
-    def __init__(self, scenarios: List[Scenario]):
+    ``scan=True`` makes a batch of SCANNING scenarios: all of them scan with one ``radar_scan`` dict (shared by the batch
+    like the r_p bounds) and no stepped antenna pattern; their scan tables are stacked as ``scan_tables`` float64
+    [10R + JR, E] in the row order ``PE_SCAN_ROWS`` (include/macjd.h, macjd_scan_pe_io), column e bit-identical to
+    scenario e's own arrays.  ``full`` is not carried (the device recomputes sweep + 2 half_beam >= 360 with the same
+    bits).  Without ``scan`` a scanning scenario is refused and ``scan_tables`` is None."""
+
+    def __init__(self, scenarios: List[Scenario], *, scan: bool = False):
         if not scenarios:
             raise ValueError("ScenarioBatch needs at least one scenario")
         s0 = scenarios[0]
@@ -567,9 +588,19 @@ class ScenarioBatch:
             if not same:
                 raise ValueError(f"ScenarioBatch: scenario {i} differs from scenario 0 in shape / episode limit / "
                                  f"r_p bounds / Pd constants (these are shared by the whole batch)")
-        if any(sc.scanning for sc in scenarios):
+        if not scan and any(sc.scanning for sc in scenarios):
             raise ValueError("ScenarioBatch: scanning radars (environment_params.radar_scan) are not supported with per-env "
-                             "scenario batches")
+                             "scenario batches unless the batch is built with scan=True")
+        for i, sc in enumerate(scenarios if scan else ()):
+            if not sc.scanning:
+                raise ValueError(f"ScenarioBatch(scan=True): scenario {i} has no environment_params.radar_scan (every "
+                                 f"scenario of a scanning batch must scan)")
+            if "pattern" in sc.radar_scan:
+                raise ValueError(f"ScenarioBatch(scan=True): scenario {i} has a radar_scan.pattern (the stepped antenna "
+                                 f"pattern is not supported with per-env scenario batches)")
+            if sc.radar_scan != s0.radar_scan:
+                raise ValueError(f"ScenarioBatch(scan=True): scenario {i}'s radar_scan {sc.radar_scan} differs from scenario "
+                                 f"0's {s0.radar_scan} (it is shared by the whole batch)")
         self.scenarios = list(scenarios)
         self.base = s0
         self.n_envs = len(scenarios)
@@ -583,6 +614,19 @@ class ScenarioBatch:
         self.snr_no = np.stack([sc.tables["radar_snr_no"] for sc in scenarios]).astype(np.float64)
         R, J = s0.num_radars, s0.num_jammers
         assert self.tables.shape == (6 * R + 3 * J + J * R, self.n_envs)
+        self.scan_tables = None
+        if scan:
+            def scan_row(sc, key):
+                return sc.tables["radar_snr_no"] if key == "snr_no" else sc.scan_tables[key]
+            self.scan_tables = np.ascontiguousarray(np.concatenate(
+                [np.stack([np.asarray(scan_row(sc, key), dtype=np.float64).reshape(-1) for sc in scenarios], axis=1)
+                 for key in PE_SCAN_ROWS], axis=0))                                           # [10R + JR, E]
+            assert self.scan_tables.shape == (pe_scan_rows(R, J), self.n_envs)
+
+    @property
+    def scanning(self) -> bool:
+        """The batch carries per-env scan tables (built with ``scan=True``)."""
+        return self.scan_tables is not None
 
     def tile(self, n_envs: int) -> "ScenarioBatch":
         """A batch of ``n_envs`` envs that cycles through this batch's scenarios (env e runs scenario e mod E) —
@@ -595,19 +639,22 @@ class ScenarioBatch:
         out.flags = np.ascontiguousarray(np.tile(self.flags, (1, reps))[:, :n_envs])
         out.state_vectors = np.ascontiguousarray(np.tile(self.state_vectors, (reps, 1))[:n_envs])
         out.snr_no = np.ascontiguousarray(np.tile(self.snr_no, (reps, 1))[:n_envs])
+        out.scan_tables = (None if self.scan_tables is None
+                           else np.ascontiguousarray(np.tile(self.scan_tables, (1, reps))[:, :n_envs]))
         return out
 
     @classmethod
     def randomized(cls, base_dict: dict, n_envs: int, seed: int = 0, config: Any = None, env_offset: int = 0,
                    **jitter) -> "ScenarioBatch":
         """``n_envs`` random variations of ``base_dict``; env e of the batch is variation number ``env_offset + e``
-        of the stream keyed by ``seed`` (shard-invariant: a rank's shard of a bigger batch is the same scenarios)."""
+        of the stream keyed by ``seed`` (shard-invariant: a rank's shard of a bigger batch is the same scenarios).  A base
+        with ``environment_params.radar_scan`` gives a scanning batch (``scan=True``)."""
         scs = []
         for e in range(n_envs):
             rng = np.random.default_rng([int(seed), int(env_offset) + e])
             scs.append(Scenario.from_dict(randomized_scenario_dict(base_dict, rng, **jitter), config=config,
                                           source=f"<randomized {seed}:{env_offset + e}>"))
-        return cls(scs)
+        return cls(scs, scan=scs[0].scanning)
 
 
 def ring_scenario_dict(n_jammers: int, n_radars: int) -> dict:

@@ -70,7 +70,8 @@ class BatchedElectromagneticEnvironment:
                  scenario_batch: Optional[ScenarioBatch] = None):
         """``scenario_batch``: one scenario PER ENV (radar / jammer positions, threat levels, powers differing
         between envs — SURVEY.md 8f-3); its tables live in HBM as an SoA that every step streams, and the
-        observation becomes a per-env [E, S] tensor (still constant in time)."""
+        observation becomes a per-env [E, S] tensor (still constant in time).  A scanning batch
+        (``ScenarioBatch(..., scan=True)``) also streams each env's scan tables; its theta_a columns move."""
         self.scenario_batch = scenario_batch
         if scenario_batch is not None:
             scenario = scenario_batch.base
@@ -80,8 +81,10 @@ class BatchedElectromagneticEnvironment:
                 raise ValueError(f"batch_envs ({batch_envs}) != scenarios in the batch ({scenario_batch.n_envs})")
         self.scenario = scenario if scenario is not None else Scenario.from_yaml(sim_config_path, config)
         sc = self.scenario
-        if sc.scanning and scenario_batch is not None:
-            raise ValueError("scanning radars (environment_params.radar_scan) are not supported with per-env scenario batches")
+        pe_scan = scenario_batch is not None and getattr(scenario_batch, "scan_tables", None) is not None
+        if sc.scanning and scenario_batch is not None and not pe_scan:
+            raise ValueError("scanning radars (environment_params.radar_scan) need a scanning per-env scenario batch "
+                             "(ScenarioBatch(..., scan=True)); this batch carries no scan tables")
         # scanning beams (environment_params.radar_scan): theta_a moves every step, so the observation does too
         self.observation_is_static = not sc.scanning
         self.num_jammers, self.num_radars = sc.num_jammers, sc.num_radars
@@ -122,6 +125,7 @@ class BatchedElectromagneticEnvironment:
             # contiguous block per step (the plain [rows, E] SoA is 6R+3J+JR streams E*8 bytes apart)
             self._pe_tile = self.PE_TILE if getattr(self, "pe_tiled", True) else 0
             tb, fl = scenario_batch.tables, scenario_batch.flags
+            stb = scenario_batch.scan_tables if pe_scan else None
             if self._pe_tile:
                 w = self._pe_tile
                 n_tiles = (E + w - 1) // w
@@ -129,13 +133,25 @@ class BatchedElectromagneticEnvironment:
                 tile = lambda a: np.ascontiguousarray(
                     np.pad(a, ((0, 0), (0, pad))).reshape(a.shape[0], n_tiles, w).transpose(1, 0, 2))
                 tb, fl = tile(tb), tile(fl)
+                stb = tile(stb) if pe_scan else None
             self._pe_tables = torch.from_numpy(tb).to(dev)       # f64 [rows, E] or [n_tiles, rows, w]
             self._pe_flags = torch.from_numpy(fl).to(dev)        # u8  [J*R, E] or [n_tiles, J*R, w]
             self._state_vecs = torch.from_numpy(scenario_batch.state_vectors).to(dev)   # f32 [E, S]
             self._snr_no = torch.from_numpy(scenario_batch.snr_no).to(dev)          # f64 [E, R]
         self._theta_a = self._state_dyn = self._snr_no_step = None
-        self._scan_io = None
-        if sc.scanning:
+        self._scan_io = self._scan_pe_io = self._scan_pe_tables = None
+        if pe_scan:
+            # per-env scan tables (include/macjd.h, macjd_scan_pe_io) in the device form of pe_tables; beams, state rows
+            # and the per-step SNR without jamming start from each env's own az0 / state vector / main-lobe snr_no
+            self._scan_pe_tables = torch.from_numpy(stb).to(dev)     # f64 [10R + JR, E] or [n_tiles, 10R + JR, w]
+            az0 = torch.from_numpy(np.ascontiguousarray(scenario_batch.scan_tables[3 * R:4 * R])).to(dev)   # f64 [R, E]
+            self._theta_a = az0.contiguous()
+            self._state_dyn = self._state_vecs.clone()
+            self._state_dyn[:, sc.theta_a_columns] = az0.t().to(torch.float32)
+            self._snr_no_step = self._snr_no.t().to(torch.float32).contiguous()
+            sp = self._scan_pe_io = _native.ScanPeIO()
+            sp.tables, sp.stride = self._scan_pe_tables.data_ptr(), E
+        elif sc.scanning:
             # beam azimuths f64 [R, E] (radar-major like track), the per-env state rows f32 [E, S] whose theta_a columns the
             # kernel rewrites every step (get_state / get_obs are views of it: one address for captured graphs), and the
             # per-step SNR without jamming (main or side lobe) f32 [R, E]
@@ -146,6 +162,7 @@ class BatchedElectromagneticEnvironment:
             self._state_dyn = st.view(1, -1).repeat(E, 1).contiguous()
             self._snr_no_step = torch.from_numpy(sc.tables["radar_snr_no"]).to(dev).to(torch.float32).view(R, 1).repeat(1, E)
             self._snr_no_step = self._snr_no_step.contiguous()
+        if sc.scanning:
             si = self._scan_io = _native.ScanIO()
             si.theta_a, si.a_se, si.a_sx = self._theta_a.data_ptr(), 1, E
             si.state, si.st_se = self._state_dyn.data_ptr(), self._state_dyn.stride(0)
@@ -215,7 +232,11 @@ class BatchedElectromagneticEnvironment:
                                                     1, self.batch_envs, self._step.data_ptr(), mptr,
                                                     self._episode.data_ptr(), stream),
                           "macjd_env_reset")
-            if self._scan_io is not None:
+            if self._scan_pe_io is not None:
+                _native.check(self._lib.macjd_env_reset_scan_pe(self._handle.ptr, self.batch_envs, ctypes.byref(self._scan_io),
+                                                                ctypes.byref(self._scan_pe_io), self._pe_tile, mptr, stream),
+                              "macjd_env_reset_scan_pe")
+            elif self._scan_io is not None:
                 _native.check(self._lib.macjd_env_reset_scan(self._handle.ptr, self.batch_envs, ctypes.byref(self._scan_io),
                                                              mptr, stream), "macjd_env_reset_scan")
         self._keep_mask = mask
@@ -304,7 +325,10 @@ class BatchedElectromagneticEnvironment:
                            rdpj_sum)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         with torch.cuda.device(self.device):
-            if self._scan_io is not None:
+            if self._scan_pe_io is not None:
+                _native.check(self._lib.macjd_env_step_scan_pe(self._handle.ptr, ctypes.byref(io), ctypes.byref(self._scan_io),
+                                                               ctypes.byref(self._scan_pe_io), stream), "macjd_env_step_scan_pe")
+            elif self._scan_io is not None:
                 _native.check(self._lib.macjd_env_step_scan(self._handle.ptr, ctypes.byref(io), ctypes.byref(self._scan_io),
                                                             stream), "macjd_env_step_scan")
             else:

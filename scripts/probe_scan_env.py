@@ -18,7 +18,14 @@ kernel choice, one process per run, the two alternating three times; every run a
     python scripts/probe_scan_env.py --eager static|scan|pattern [--E 4096] [--iters 2000] [--reps 5] [--label L] [--out FILE]
 
 times the host side of the launch path instead: `iters` eager env.step calls (no graph) on that scenario, wall clock per
-call up to the last call's return (enqueue) and up to the device's completion (total), median of `reps` repetitions."""
+call up to the last call's return (enqueue) and up to the device's completion (total), median of `reps` repetitions.
+
+    python scripts/probe_scan_env.py --per-env [--sizes 3x4,12x16] [--Es 4096,1048576] [--out FILE]
+
+compares scanning on per-env scenario batches (macjd_env_step_scan_pe) with its two neighbours: shared-table scanning
+(`scan_shared`), per-env static tables (`pe_static`) and per-env scanning (`pe_scan`; 25 randomised ring scenarios with a
+45 degree azimuth jitter, tiled to E), production configuration, graph-replayed steps timed with HIP events, one process
+per run, the three alternating `--alternations` times; every run appends one JSON line to --out."""
 import argparse
 import json
 import os
@@ -35,7 +42,7 @@ import torch  # noqa: E402
 
 import macjd_amd  # noqa: E402,F401
 from macjd_amd import _native  # noqa: E402
-from macjd_amd.scenario import Scenario, ring_scenario_dict  # noqa: E402
+from macjd_amd.scenario import Scenario, ScenarioBatch, ring_scenario_dict  # noqa: E402
 from macjd_amd.simulation.environment import BatchedElectromagneticEnvironment  # noqa: E402
 
 
@@ -134,6 +141,32 @@ def pattern_run(tag, E, iters, reps, out):
     emit(line, out)
 
 
+PER_ENV_TAGS = ("scan_shared", "pe_static", "pe_scan")
+
+
+def per_env_run(tag, J, R, E, iters, reps, out):
+    """One (scan_shared | pe_static | pe_scan, size, E) measurement in this process."""
+    d = ring_scenario_dict(J, R)
+    if tag != "pe_static":
+        d["environment_params"] = dict(d["environment_params"], radar_scan={"step_seconds": 0.25, "sidelobe_db": -30.0})
+    if tag == "scan_shared":
+        env = BatchedElectromagneticEnvironment(scenario=Scenario.from_dict(d), batch_envs=E, device="cuda", seed=1)
+    else:
+        jitter = {"azimuth_jitter": 45.0} if tag == "pe_scan" else {}
+        batch = ScenarioBatch.randomized(d, 25, seed=9, **jitter).tile(E)
+        env = BatchedElectromagneticEnvironment(scenario_batch=batch, device="cuda", seed=1)
+        del batch
+    rng = np.random.default_rng(0)
+    T = torch.from_numpy(rng.integers(0, 2 * R + 1, size=(J, E)).astype(np.int32)).cuda().t()   # agent-major
+    P = torch.from_numpy(rng.random((J, E), dtype=np.float32)).cuda().t()
+    n = iters if E < (1 << 20) else max(20, iters // 10)
+    ms = timed(env, T, P, n, reps)
+    env.close()
+    emit({"probe": "scan_pe_env", "variant": tag, "J": J, "R": R, "E": E, "iters": n, "reps": reps,
+          "us_per_step_median": round(ms * 1e3, 3), "device": torch.cuda.get_device_name(0),
+          "time": time.strftime("%Y-%m-%dT%H:%M:%S")}, out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=None, help="default 200 (--eager: 2000)")
@@ -144,11 +177,28 @@ def main():
     ap.add_argument("--eager", choices=["static", "scan", "pattern"], help="host cost of eager env.step calls on that scenario")
     ap.add_argument("--E", type=int, default=4096, help="batch size of --eager")
     ap.add_argument("--label", default="", help="copied into the line of --eager (A/B runs: MACJD_LIB names the library)")
+    ap.add_argument("--per-env", action="store_true", help="shared-table scanning vs per-env static vs per-env scanning")
+    ap.add_argument("--sizes", default="3x4,12x16", help="JxR sizes of --per-env")
+    ap.add_argument("--Es", default="4096,1048576", help="batch sizes of --per-env")
+    ap.add_argument("--one-per-env", nargs=4, metavar=("VARIANT", "J", "R", "E"), help="(internal) one run of --per-env")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     a.iters = a.iters or (2000 if a.eager else 200)
     if a.eager:
         return eager_run(a.eager, a.E, a.iters, a.reps, a.out, a.label)
+    if a.one_per_env:
+        tag, J, R, E = a.one_per_env
+        return per_env_run(tag, int(J), int(R), int(E), a.iters, a.reps, a.out)
+    if a.per_env:
+        for size in a.sizes.split(","):
+            J, R = size.split("x")
+            for E in a.Es.split(","):
+                for _ in range(a.alternations):
+                    for tag in PER_ENV_TAGS:   # a failing run ends the sequence: nothing more is started on the device
+                        subprocess.run([sys.executable, os.path.abspath(__file__), "--one-per-env", tag, J, R, E, "--iters",
+                                        str(a.iters), "--reps", str(a.reps)] + (["--out", a.out] if a.out else []),
+                                       check=True, timeout=600)
+        return
     a.out = a.out or PATTERN_OUT
     if a.one:
         return pattern_run(a.one[0], int(a.one[1]), a.iters, a.reps, a.out)
