@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MACJD_ABI_VERSION 8
+#define MACJD_ABI_VERSION 9
 #define MACJD_PE_ROWS(R, J) (6 * (R) + 3 * (J) + (J) * (R))
 #define MACJD_PE_SCAN_ROWS(R, J) (10 * (R) + (J) * (R))
 

@@ -240,6 +240,40 @@ int macjd_linear_wgrad(const macjd_wgrad_io* io, void* hip_stream);
 int macjd_linear_wgrad_many(const macjd_wgrad_io* ios, int32_t n, void* hip_stream);
 
 /*
+ * macjd_linear_wgrad_many whose launch pair also leaves what the optimiser step needs of the gradients it writes, so
+ * that macjd_clip_adam_step_reduced can follow as ONE launch (no squared-norm / LayerNorm launch in between):
+ *   * problem `ln_problem` (-1: none) is LayerNorm-CONTRACTED: G = gout^T inp [M, N <= 64] is never written.  Its work
+ *     item (row tile, chunk) multiplies its 64 x N accumulators by W[m, n] (rows past M count zero), sums over its rows
+ *     in a fixed order (registers, across lanes, across the waves through LDS; no atomics) and stores two rows of N
+ *     floats into slot [tile * n_chunks + chunk][2][N] of the problem's workspace:
+ *         dgamma_part[n] = sum_m W[m, n] G_part[m, n]      dbeta_part[n] = sum_m W[m, n] gb_part[m]
+ *     (gb_part = the chunk's column sums of gout).  The reduce launch sums the slots into dgamma[n] / dbeta[n]:
+ *     macjd_lnparam_io's outputs with gb = the column sums of this problem's gout.  Its dW / db are ignored (db must be
+ *     NULL); the workspace size is that of the ordinary problem.
+ *   * every reduce workgroup w writes partials[w] = sum of the squares of the values it STORED (dW, db, dgamma, dbeta),
+ *     w < macjd_linear_wgrad_many_norm_partials(...) <= 8192 <= partials_cap;
+ *   * the reduce launch advances the optimiser's step counter (*step += 1), as the squared-norm launch of
+ *     macjd_clip_adam_step does.
+ * The ordinary problems' dW / db are bit-identical to macjd_linear_wgrad_many's.
+ */
+typedef struct macjd_wgrad_norm_io {
+    int32_t ln_problem, partials_cap;
+    const float* W; int64_t w_ld;          /* [M, N] of problem ln_problem: the Linear layer behind the LayerNorm */
+    float* dgamma; float* dbeta;           /* [N] out */
+    float* partials;                       /* [partials_cap] out */
+    float* step;                           /* device scalar, read-modify-written */
+} macjd_wgrad_norm_io;
+
+int32_t macjd_linear_wgrad_many_norm_partials(const macjd_wgrad_io* ios, int32_t n, int32_t ln_problem);   /* < 0: bad argument */
+int macjd_linear_wgrad_many_norm(const macjd_wgrad_io* ios, int32_t n, const macjd_wgrad_norm_io* norm, void* hip_stream);
+
+/* The optimiser step of macjd_clip_adam_step_sample as ONE launch behind macjd_linear_wgrad_many_norm: every workgroup sums
+   io->partials[0 .. n_partials) itself (all 256 threads: loads first, then per thread in index order, across the wave,
+   four waves as (p0 + p1) + (p2 + p3)), clips, applies Adam with the ALREADY advanced step counter, writes grad_norm and
+   draws the next batch (next may be NULL).  Every element of io->grad that is not zero must be counted in the partials. */
+int macjd_clip_adam_step_reduced(const macjd_adam_io* io, int32_t n_partials, const macjd_sampler_io* next, void* hip_stream);
+
+/*
  * Gather `n_rows` whole rows (episodes) of up to 8 tensors in ONE launch: dst_k[i, :] = src_k[idx[i], :] as raw
  * bytes (row_bytes[k] each, multiples of 4).  Replaces the per-key index_select of
  * EpisodeReplayBuffer.sample (reference utils/replay_buffer.py:181-183).

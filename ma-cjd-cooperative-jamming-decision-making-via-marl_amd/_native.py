@@ -14,7 +14,7 @@ LIB_NAME = "libmacjd_hip.so"
 # MACJD_LIB points at another build of the same sources (kernel A/B runs); the default is the in-tree library
 LIB_PATH = os.environ.get("MACJD_LIB") or os.path.join(_PKG_DIR, LIB_NAME)
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 STEP_ARITH_F64 = 1
 STEP_LANE_KERNEL = 2
 STEP_SLOT_KERNEL = 4
@@ -37,6 +37,7 @@ EXPORTS = [
     "macjd_gru_sequence_backward_supported", "macjd_gru_sequence_backward",
     "macjd_prefetch_batch_supported", "macjd_prefetch_batch",
     "macjd_actor_gradient_supported", "macjd_actor_gradient",
+    "macjd_linear_wgrad_many_norm", "macjd_linear_wgrad_many_norm_partials", "macjd_clip_adam_step_reduced",
 ]
 
 
@@ -393,6 +394,15 @@ class WgradIO(ctypes.Structure):
     ]
 
 
+class WgradNormIO(ctypes.Structure):
+    """ctypes mirror of ``macjd_wgrad_norm_io`` (include/macjd_nets.h)."""
+    _fields_ = [
+        ("ln_problem", ctypes.c_int32), ("partials_cap", ctypes.c_int32),
+        ("W", ctypes.c_void_p), ("w_ld", ctypes.c_int64), ("dgamma", ctypes.c_void_p), ("dbeta", ctypes.c_void_p),
+        ("partials", ctypes.c_void_p), ("step", ctypes.c_void_p),
+    ]
+
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -533,6 +543,12 @@ def load() -> ctypes.CDLL:
     lib.macjd_gather_rows.argtypes = [ctypes.POINTER(GatherIO), ctypes.c_void_p]
     lib.macjd_linear_wgrad.restype = ctypes.c_int
     lib.macjd_linear_wgrad.argtypes = [ctypes.POINTER(WgradIO), ctypes.c_void_p]
+    lib.macjd_linear_wgrad_many_norm.restype = ctypes.c_int
+    lib.macjd_linear_wgrad_many_norm.argtypes = [ctypes.POINTER(WgradIO), ctypes.c_int32, ctypes.POINTER(WgradNormIO), ctypes.c_void_p]
+    lib.macjd_linear_wgrad_many_norm_partials.restype = ctypes.c_int32
+    lib.macjd_linear_wgrad_many_norm_partials.argtypes = [ctypes.POINTER(WgradIO), ctypes.c_int32, ctypes.c_int32]
+    lib.macjd_clip_adam_step_reduced.restype = ctypes.c_int
+    lib.macjd_clip_adam_step_reduced.argtypes = [ctypes.POINTER(AdamIO), ctypes.c_int32, ctypes.POINTER(SamplerIO), ctypes.c_void_p]
     lib.macjd_linear_wgrad_many.restype = ctypes.c_int
     lib.macjd_linear_wgrad_many.argtypes = [ctypes.POINTER(WgradIO), ctypes.c_int32, ctypes.c_void_p]
     lib.macjd_linear_wgrad_workspace_floats.restype = ctypes.c_int64

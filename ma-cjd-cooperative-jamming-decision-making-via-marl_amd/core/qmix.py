@@ -157,6 +157,14 @@ class QMixLearner:
         import torch.distributed as dist
         return dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
 
+    def _norm_in_reduce(self):
+        """The fused update may ask its grouped weight-gradient launch pair for the LayerNorm gradients and the squared
+        gradient norm (ops.deferred_wgrad(norm=...)): flat vectors, a single process (with ranks the all-reduce sits
+        between the reduce and the norm) and the default learner, whose every gradient that pair writes —
+        ``train_agent_body`` / ``train_actor`` add gradients from other launches."""
+        return (self._flat_param is not None and self._world_size() <= 1 and not self.train_agent_body
+                and not self.train_actor and options.on("NORM_IN_REDUCE"))
+
     def _flatten_trainable(self):
         """HIP device: make the trainable parameters (Q-head + mixer) views of ONE flat vector, with flat Adam
         moments, so clipping + Adam is a fused two-kernel step (ops.clip_adam_step) instead of ~20 foreach
@@ -180,7 +188,8 @@ class QMixLearner:
         self._flat_exp_avg_sq = torch.zeros_like(flat)
         self._adam_step = torch.zeros((), dtype=torch.float32, device=flat.device)
         self._grad_norm = torch.zeros((), dtype=torch.float32, device=flat.device)
-        self._adam_partials = torch.zeros(256 + 1024, dtype=torch.float32, device=flat.device)   # + LayerNorm partials
+        # 256 + LayerNorm partials of the squared-norm launch, or one per workgroup (<= 8192) of the weight-gradient reduce
+        self._adam_partials = torch.zeros(8192, dtype=torch.float32, device=flat.device)
         for p, off in zip(tr, self._flat_offsets):
             n = p.numel()
             p.data = flat[off:off + n].view_as(p)
@@ -190,6 +199,9 @@ class QMixLearner:
         # straight into its slices (ops.deferred_wgrad(grad_dst=...)), so nothing packs the gradients afterwards
         self._flat_grad = torch.zeros_like(flat)
         self._grad_dst = {}
+        esz = self._flat_grad.element_size()
+        # byte ranges of the flat gradient vector that hold gradients (everything but the padding, which stays zero)
+        self._grad_cover = [(self._flat_grad.data_ptr() + off * esz, p.numel() * esz) for p, off in zip(tr, self._flat_offsets)]
         for p, off in zip(tr, self._flat_offsets):
             n = p.numel()
             self._grad_dst[ops.grad_key(p)] = self._flat_grad[off:off + n].view_as(p)
@@ -722,10 +734,14 @@ class QMixLearner:
             # (single process: the LayerNorm-parameter launch behind the grouped products is held back and evaluated
             # inside the optimiser step's squared-norm launch — with more ranks the all-reduce needs it done first)
             hold = self._flat_param is not None and self._world_size() <= 1 and options.on("LN_IN_SQNORM")
-            with ops.deferred_wgrad(grad_dst=getattr(self, "_grad_dst", None), hold_lnparam=hold) as dw:
+            # ... and where that one launch pair writes EVERY gradient of the flat vector (ops.norm_in_reduce_plan decides
+            # from the recorded problems) it also forms the LayerNorm gradients and the squared norm: the optimiser step
+            # behind it is then one launch
+            norm = (self._adam_partials, self._adam_step, self._grad_cover) if self._norm_in_reduce() else None
+            with ops.deferred_wgrad(grad_dst=getattr(self, "_grad_dst", None), hold_lnparam=hold, norm=norm) as dw:
                 eval_q_tot.backward(gy)
             assert ops._PENDING_TD is None, "the fused mixer's backward did not take the TD loss's inputs"
-            self._held_ln = dw.held
+            self._held_ln, self._norm_partials = dw.held, dw.norm_partials
             if side_work is not None:
                 # side-stream launches whose forks lie earlier (side_work: its own fork; the logged sums: head_done),
                 # captured behind the chain's launches so that the chain's nodes stay first dependents of each other
@@ -748,9 +764,10 @@ class QMixLearner:
         if self._flat_param is not None:   # HIP device: fused clip_grad_norm_ + Adam on the flat vectors
             g = self.optimizer.param_groups[0]
             held, self._held_ln = getattr(self, "_held_ln", None), None
+            reduced, self._norm_partials = getattr(self, "_norm_partials", None), None
             ops.clip_adam_step(self._flat_param, self._flat_grad, self._flat_exp_avg, self._flat_exp_avg_sq,
                                self._adam_step, self._grad_norm, self._adam_partials, g["lr"], g["betas"], g["eps"],
-                               self.args.grad_norm_clip, sample_next=sample_next, lnparam=held)
+                               self.args.grad_norm_clip, sample_next=sample_next, lnparam=held, reduced=reduced)
             return self._grad_norm
         grad_norm = torch.nn.utils.clip_grad_norm_(self.params, self.args.grad_norm_clip)  # qmix.py:199
         self.optimizer.step()
@@ -1072,7 +1089,7 @@ class QMixLearner:
         self._g_multi = self._g_stages = None
         self._graph_a = self._graph_b = None
         self._graph_body_a = None
-        self._g_out_a = self._g_out_b = self._g_stats4 = self._last_stats4 = self._held_ln = None
+        self._g_out_a = self._g_out_b = self._g_stats4 = self._last_stats4 = self._held_ln = self._norm_partials = None
         if self._flat_param is not None and any(g is not None for g in graphs):
             # the gradient norm was re-pointed at a static output row of the pool being released
             self._grad_norm = torch.zeros((), dtype=torch.float32, device=self._flat_param.device)

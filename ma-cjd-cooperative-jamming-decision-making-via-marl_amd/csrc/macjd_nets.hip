@@ -983,6 +983,59 @@ __global__ void __launch_bounds__(256) adam_update_kernel(const macjd_adam_io io
     if (SAMPLE && blockIdx.x == 0) sample_episodes_block(next);
 }
 
+// adam_update_kernel's step from the gradient norm on, expression for expression: the same clip coefficient gives the same
+// bits (tests/test_norm_in_reduce_gpu.py).  That kernel keeps its own text — sharing this function changed its code object,
+// which the two- and three-launch entries were measured with.
+template <bool SAMPLE>
+__device__ __forceinline__ void adam_apply(const macjd_adam_io& io, const float total_norm, const macjd_sampler_io& next) {
+    float coef = io.max_norm / (total_norm + 1e-6f);
+    coef = coef < 1.0f ? coef : 1.0f;
+    const float step = io.step[0];   // already advanced by the launch that left the partials (wgrad_reduce_many_norm_kernel)
+    const float bc1 = 1.0f - powf(io.beta1, step);
+    const float bc2 = 1.0f - powf(io.beta2, step);
+    const float step_size = io.lr / bc1;
+    const float bc2_sqrt = sqrtf(bc2);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < io.n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float g = io.grad[i] * coef;
+        io.grad[i] = g;   // clip_grad_norm_ scales the gradients in place: .grad holds the clipped values afterwards
+        float m = io.exp_avg[i], v = io.exp_avg_sq[i];
+        m = m + (1.0f - io.beta1) * (g - m);
+        v = v * io.beta2 + (1.0f - io.beta2) * g * g;
+        io.exp_avg[i] = m;
+        io.exp_avg_sq[i] = v;
+        const float denom = sqrtf(v) / bc2_sqrt + io.eps;
+        io.param[i] -= step_size * (m / denom);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) io.grad_norm[0] = total_norm;
+    // every reader of the current batch's indices ran in an earlier launch of this stream: the next batch is drawn here
+    if (SAMPLE && blockIdx.x == 0) sample_episodes_block(next);
+}
+
+// The same step as ONE launch behind macjd_linear_wgrad_many_norm, whose reduce workgroups left the squares of everything
+// they stored in io.partials and advanced the step counter.  n_partials is ~900 for the learner's update: all 256 threads
+// take them (rounds of 8 x 256; a thread's 8 loads are issued before its first add — one L2 latency per round, where one
+// wave walking them in a dependent loop measured +4.4 us).  Order: thread t adds partials[2048 r + 256 j + t] for
+// j = 0..7, r = 0, 1, ..; wave_sum; the four waves as (p0 + p1) + (p2 + p3).
+template <bool SAMPLE>
+__global__ void __launch_bounds__(256) adam_update_reduced_kernel(const macjd_adam_io io, const int n_partials, const macjd_sampler_io next) {
+    __shared__ float s_w[4];
+    float s = 0.0f;
+    for (int base = 0; base < n_partials; base += 8 * 256) {
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {   // (no branch around a load: past the end the last partial is read and dropped)
+            const int i = base + j * 256 + (int)threadIdx.x;
+            v[j] = io.partials[i < n_partials ? i : n_partials - 1];
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s += (base + j * 256 + (int)threadIdx.x < n_partials) ? v[j] : 0.0f;
+    }
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = s;
+    __syncthreads();
+    adam_apply<SAMPLE>(io, sqrtf((s_w[0] + s_w[1]) + (s_w[2] + s_w[3])), next);
+}
+
 // part `part` of `parts` of the copy dst_k[row, :] = src_k[src_row, :] (tensor k, raw bytes), by one workgroup
 __device__ __forceinline__ void gather_rows_body(const macjd_gather_io& io, const int k, const int row, const int64_t src_row,
                                                  const int part, const int parts) {
@@ -1082,6 +1135,22 @@ extern "C" int macjd_clip_adam_step_sample(const macjd_adam_io* io, const macjd_
     hipLaunchKernelGGL(adam_sqnorm_kernel, dim3(blocks), dim3(256), 0, s, *io);
     if (next) hipLaunchKernelGGL(adam_update_kernel<true>, dim3(blocks), dim3(256), 0, s, *io, blocks, *next);
     else hipLaunchKernelGGL(adam_update_kernel<false>, dim3(blocks), dim3(256), 0, s, *io, blocks, macjd_sampler_io{});
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return set_nets_err(MACJD_EDEVICE, hipGetErrorString(err));
+    return MACJD_OK;
+}
+
+extern "C" int macjd_clip_adam_step_reduced(const macjd_adam_io* io, int32_t n_partials, const macjd_sampler_io* next, void* hip_stream) {
+    using namespace macjd;
+    if (!io || io->n < 1 || !io->param || !io->grad || !io->exp_avg || !io->exp_avg_sq || !io->step || !io->grad_norm ||
+        !io->partials || n_partials < 1)
+        return set_nets_err(MACJD_EINVAL, "macjd_clip_adam_step_reduced: bad argument");
+    if (next && !sampler_args_ok(next)) return set_nets_err(MACJD_EINVAL, "macjd_clip_adam_step_reduced: bad sampler argument");
+    hipStream_t s = (hipStream_t)hip_stream;
+    int blocks = (int)((io->n + 255) / 256);
+    if (blocks > ADAM_BLOCKS) blocks = ADAM_BLOCKS;
+    if (next) hipLaunchKernelGGL(adam_update_reduced_kernel<true>, dim3(blocks), dim3(256), 0, s, *io, n_partials, *next);
+    else hipLaunchKernelGGL(adam_update_reduced_kernel<false>, dim3(blocks), dim3(256), 0, s, *io, n_partials, macjd_sampler_io{});
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return set_nets_err(MACJD_EDEVICE, hipGetErrorString(err));
     return MACJD_OK;

@@ -13,6 +13,9 @@
 //   * the chunk's partial tile goes to workspace[chunk][M][N]; the bias partial (column sums of the staged gout
 //     chunk) is produced by the workgroups of N-tile 0;
 //   * wgrad_reduce_kernel sums the chunks in index order (deterministic, no float atomics).
+// The grouped pair exists a second time (wgrad_*_many_norm_kernel, macjd_linear_wgrad_many_norm) for the learner's update:
+// one problem contracted with a weight matrix into LayerNorm-parameter gradients in the partial launch's epilogue, the
+// squares of every stored gradient and the optimiser's step counter in the reduce launch.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -51,8 +54,13 @@ struct WgradProb {
     bool want_db;
     const float* outer_vec;   // see macjd_wgrad_io
     const float* outer_w;
+    const float* ln_W;        // LN bodies only: the problem is LayerNorm-contracted with this [M, N] matrix (macjd_wgrad_norm_io)
+    int64_t ln_ld;
 };
 
+// LN: the body of the launch that knows LayerNorm-contracted problems (io.ln_W != nullptr, uniform per work item); the
+// LN = false instantiation is the kernels' code as it was before that launch existed
+template <bool LN>
 __device__ __forceinline__ void wgrad_partial_body(const WgradProb& io, const int tn, const int tm, const int chunk,
                                                    float* __restrict__ sA, float* __restrict__ sB) {
     const int Mp = io.Mp, Np = io.Np;
@@ -148,9 +156,33 @@ __device__ __forceinline__ void wgrad_partial_body(const WgradProb& io, const in
         for (int b = 0; b < 2; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
     const float* pa = sA + lk * WG_PITCH + wm + li;
     const float* pb = sB + lk * WG_PITCH + wn + li;
-    const bool bias_lane = io.want_db && tn == 0 && tid < WG_BM;
+    bool contract = false;
+    if constexpr (LN) contract = io.ln_W != nullptr;
+    const bool bias_lane = (io.want_db || contract) && tn == 0 && tid < WG_BM;
     float bias_sum = 0.0f;
-    const int n_pieces = (int)((((io.K - k0) < (int64_t)WG_ROWS ? (io.K - k0) : (int64_t)WG_ROWS) + WG_KC - 1) / WG_KC);
+    // contracted problem: the 16 elements of W under this lane's accumulators, loaded here — before the products — from
+    // clamped addresses and zeroed past M / N by selects (any other problem: 16 reads of one valid address, unused)
+    float wl[2][2][4];
+    if constexpr (LN) {
+        const float* wbase = contract ? io.ln_W : io.gout;
+        const int64_t wld = contract ? io.ln_ld : 0;
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int m = m0 + wm + a * 16 + lk * 4 + r, n = n0 + wn + b * 16 + li;
+                    const int mc = m < io.M ? m : io.M - 1, nc = n < io.N ? n : io.N - 1;
+                    const float v = wbase[(int64_t)mc * wld + (contract ? nc : 0)];
+                    wl[a][b][r] = (contract && m < io.M && n < io.N) ? v : 0.0f;
+                }
+    }
+    // (LN bodies say what the expression amounts to with one piece per work item — k0 < K for every chunk: the loop's
+    // "more" half, and the registers of a second piece in flight, then do not exist and the 16 values of W fit beside
+    // the rest at three workgroups per CU)
+    const int n_pieces = (LN && WG_SUB == 1) ? 1
+        : (int)((((io.K - k0) < (int64_t)WG_ROWS ? (io.K - k0) : (int64_t)WG_ROWS) + WG_KC - 1) / WG_KC);
     load_piece(0);
     store_piece();
     __syncthreads();
@@ -200,6 +232,39 @@ __device__ __forceinline__ void wgrad_partial_body(const WgradProb& io, const in
             __syncthreads();
         }
     }
+    if constexpr (LN) {
+        if (contract) {   // (one N tile: n0 = 0) sum over this work item's 64 rows of W G_part and of W gb_part, fixed order
+            __syncthreads();                       // every wave is done with the staged pieces: their LDS is reused
+            float* gbs = sA;                       // [64] column sums of the gout piece = gb_part of rows m0 ..
+            float* red = sB;                       // [2 row halves][dgamma, dbeta][64]
+            if (tid < WG_BM) gbs[tid] = bias_sum;
+            __syncthreads();
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                float sg = 0.0f, sb = 0.0f;        // registers: a = 0 (r = 0..3), a = 1 (r = 0..3)
+#pragma unroll
+                for (int a = 0; a < 2; ++a)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        sg = fmaf(wl[a][b][r], acc[a][b][r], sg);
+                        sb = fmaf(wl[a][b][r], gbs[wm + a * 16 + lk * 4 + r], sb);
+                    }
+                sg += __shfl_xor(sg, 16, 64); sg += __shfl_xor(sg, 32, 64);   // the four row groups of a wave: (g0 + g1) + (g2 + g3)
+                sb += __shfl_xor(sb, 16, 64); sb += __shfl_xor(sb, 32, 64);
+                if (lk == 0) {
+                    red[((wave >> 1) * 2 + 0) * WG_BN + wn + b * 16 + li] = sg;
+                    red[((wave >> 1) * 2 + 1) * WG_BN + wn + b * 16 + li] = sb;
+                }
+            }
+            __syncthreads();
+            if (tid < 2 * WG_BN) {                 // the two row halves: upper + lower
+                const int which = tid >> 6, n = tid & 63;
+                const float v = red[which * WG_BN + n] + red[(2 + which) * WG_BN + n];
+                if (n < io.N) io.workspace[((int64_t)tm * io.n_chunks + chunk) * 2 * io.N + which * io.N + n] = v;
+            }
+            return;
+        }
+    }
     float* ws = io.workspace + (int64_t)chunk * Mp * Np;
 #pragma unroll
     for (int a = 0; a < 2; ++a)
@@ -214,6 +279,13 @@ __device__ __forceinline__ void wgrad_partial_body(const WgradProb& io, const in
     if (bias_lane) io.workspace[(int64_t)io.n_chunks * Mp * Np + (int64_t)chunk * Mp + m0 + tid] = bias_sum;
 }
 
+// sum over the 64 lanes (every lane gets it): x + lane^32, then ^16 .. ^1 — the order of the optimiser's wave_sum
+__device__ __forceinline__ float wgrad_wave_sum(float x) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
+    return x;
+}
+
 __global__ void __launch_bounds__(256) wgrad_partial_kernel(const macjd_wgrad_io io, const int Mp, const int Np) {
     __shared__ float sA[WG_KC * WG_PITCH];   // gout chunk  [k][m]
     __shared__ float sB[WG_KC * WG_PITCH];   // inp chunk   [k][n]
@@ -221,7 +293,7 @@ __global__ void __launch_bounds__(256) wgrad_partial_kernel(const macjd_wgrad_io
     p.K = io.K; p.gout_ld = io.gout_ld; p.inp_ld = io.inp_ld; p.M = io.M; p.N = io.N; p.Mp = Mp; p.Np = Np;
     p.n_chunks = (int)gridDim.z; p.gout = io.gout; p.inp = io.inp; p.workspace = io.workspace; p.want_db = io.db != nullptr;
     p.outer_vec = io.outer_vec; p.outer_w = io.outer_w;
-    wgrad_partial_body(p, blockIdx.x, blockIdx.y, blockIdx.z, sA, sB);
+    wgrad_partial_body<false>(p, blockIdx.x, blockIdx.y, blockIdx.z, sA, sB);
 }
 
 // Sum of the K-chunk partials, fixed order (deterministic).  A workgroup owns 64 consecutive output elements; consecutive
@@ -310,11 +382,10 @@ __global__ void __launch_bounds__(256) wgrad_partial_many_kernel(const WgradBatc
     for (int q = 1; q < MACJD_WGRAD_MAX_BATCH; ++q) {
         if (q < b.n && w >= b.wg_start[q]) { MACJD_PICK(q) }
     }
-#undef MACJD_PICK
     const int local = (int)(w - start);
     const int tn = local % tiles_n, rest = local / tiles_n;
     const int tm = rest % tiles_m, chunk = rest / tiles_m;
-    wgrad_partial_body(p, tn, tm, chunk, sA, sB);
+    wgrad_partial_body<false>(p, tn, tm, chunk, sA, sB);
 }
 
 __global__ void __launch_bounds__(256) wgrad_reduce_many_kernel(const WgradBatch b) {
@@ -346,6 +417,85 @@ __global__ void __launch_bounds__(256) wgrad_reduce_many_kernel(const WgradBatch
         if (wave == 0 && g0 + lane < total_all) {
             if (is_w) dW[(int64_t)m * dw_ld + n] = v;
             else if (db) db[m] = v;
+        }
+    }
+}
+
+// ---- the grouped launch pair that also serves the optimiser step (include/macjd_nets.h, macjd_wgrad_norm_io) ----
+struct WgradNorm {
+    int problem;             // the LayerNorm-contracted problem (-1: none)
+    int slots;               // its tiles_m * n_chunks partial slots of [2][N]
+    const float* W; int64_t w_ld;
+    float* dgamma; float* dbeta;
+    float* partials; float* step;
+};
+
+__global__ void __launch_bounds__(256) wgrad_partial_many_norm_kernel(const WgradBatch b, const WgradNorm ln) {
+    __shared__ float sA[WG_KC * WG_PITCH];
+    __shared__ float sB[WG_KC * WG_PITCH];
+    const int64_t w = blockIdx.x;
+    WgradProb p;
+    int tiles_n = b.tiles_n[0], tiles_m = b.tiles_m[0];
+    int64_t start = 0;
+    MACJD_PICK(0)
+    p.ln_W = ln.problem == 0 ? ln.W : nullptr;
+#pragma unroll
+    for (int q = 1; q < MACJD_WGRAD_MAX_BATCH; ++q) {
+        if (q < b.n && w >= b.wg_start[q]) { MACJD_PICK(q) p.ln_W = ln.problem == q ? ln.W : nullptr; }
+    }
+    p.ln_ld = ln.w_ld;
+    const int local = (int)(w - start);
+    const int tn = local % tiles_n, rest = local / tiles_n;
+    const int tm = rest % tiles_m, chunk = rest / tiles_m;
+    wgrad_partial_body<true>(p, tn, tm, chunk, sA, sB);
+}
+#undef MACJD_PICK
+
+// wgrad_reduce_many_kernel with (1) the contracted problem's 2 N outputs (item i = which * N + n sums element i of its
+// `slots` slots of 2 N floats), (2) partials[workgroup] = sum of the squares of what the workgroup stored: per lane of
+// wave 0 in item order, then wgrad_wave_sum, (3) the step counter.
+__global__ void __launch_bounds__(256) wgrad_reduce_many_norm_kernel(const WgradBatch b, const WgradNorm ln) {
+    __shared__ float part[4][WG_RED];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t total_all = b.out_start[b.n];
+    float sq = 0.0f;
+    for (int64_t g0 = (int64_t)blockIdx.x * WG_RED; g0 < total_all; g0 += (int64_t)gridDim.x * WG_RED) {
+        const int64_t g = g0 + lane < total_all ? g0 + lane : total_all - 1;
+        int M = b.io[0].M, N = b.io[0].N, Mp = b.Mp[0], Np = b.Np[0], n_chunks = b.chunks[0], prob = 0;
+        int64_t start = 0, dw_ld = b.io[0].dw_ld;
+        const float* workspace = b.io[0].workspace;
+        float* dW = b.io[0].dW;
+        float* db = b.io[0].db;
+#pragma unroll
+        for (int q = 1; q < MACJD_WGRAD_MAX_BATCH; ++q) {
+            if (q < b.n && g >= b.out_start[q]) {
+                M = b.io[q].M; N = b.io[q].N; Mp = b.Mp[q]; Np = b.Np[q]; n_chunks = b.chunks[q]; prob = q;
+                start = b.out_start[q]; dw_ld = b.io[q].dw_ld; workspace = b.io[q].workspace; dW = b.io[q].dW; db = b.io[q].db;
+            }
+        }
+        const int64_t i = g - start;
+        const int64_t total = (int64_t)M * N;
+        const bool is_ln = prob == ln.problem;
+        const bool is_w = i < total;
+        const int m = is_w ? (int)(i / N) : (int)(i - total);
+        const int n = is_w ? (int)(i - (int64_t)m * N) : 0;
+        const float* src = is_ln ? workspace + i : is_w ? workspace + (int64_t)m * Np + n : workspace + (int64_t)n_chunks * Mp * Np + m;
+        const int64_t stride = is_ln ? (int64_t)2 * N : is_w ? (int64_t)Mp * Np : (int64_t)Mp;
+        const float v = wgrad_meet(part, wgrad_sum_rounds(src, stride, is_ln ? ln.slots : n_chunks, wave), wave, lane);
+        if (wave == 0 && g0 + lane < total_all) {
+            // (a problem without a bias output still owns M items behind its M N: summed, dropped, and not counted)
+            float* dst = is_ln ? (i < N ? ln.dgamma + i : ln.dbeta + (i - N)) : is_w ? dW + (int64_t)m * dw_ld + n : db ? db + m : nullptr;
+            if (dst) {
+                *dst = v;
+                sq = fmaf(v, v, sq);
+            }
+        }
+    }
+    if (wave == 0) {
+        sq = wgrad_wave_sum(sq);
+        if (lane == 0) {
+            ln.partials[blockIdx.x] = sq;
+            if (blockIdx.x == 0) ln.step[0] += 1.0f;   // nothing in this launch reads it; the optimiser launch reads the advanced value
         }
     }
 }
@@ -416,5 +566,79 @@ extern "C" int macjd_linear_wgrad_many(const macjd_wgrad_io* ios, int32_t n, voi
     hipLaunchKernelGGL(wgrad_reduce_many_kernel, dim3(rblocks), dim3(256), 0, s, b);
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_linear_wgrad_many: %s", hipGetErrorString(err));
+    return MACJD_OK;
+}
+
+// validation and tables of the grouped launches that know a contracted problem; returns MACJD_OK or the error set
+static int wgrad_norm_batch(const macjd_wgrad_io* ios, int32_t n, int32_t ln_problem, macjd::WgradBatch* out, const char* who) {
+    using namespace macjd;
+    if (!ios || n < 1 || n > MACJD_WGRAD_MAX_BATCH || ln_problem < -1 || ln_problem >= n)
+        return set_err(MACJD_EINVAL, "%s: 1..MACJD_WGRAD_MAX_BATCH problems, ln_problem -1 or one of them", who);
+    WgradBatch& b = *out;
+    b = WgradBatch{};
+    b.n = n;
+    for (int p = 0; p < n; ++p) {
+        const macjd_wgrad_io* io = &ios[p];
+        const bool is_ln = p == ln_problem;
+        if (io->K < 1 || io->M < 1 || io->N < 1 || !io->gout || !io->inp || (!io->dW && !is_ln) || !io->workspace)
+            return set_err(MACJD_EINVAL, "%s: bad argument", who);
+        if (io->gout_ld < io->M || io->inp_ld < io->N || (!is_ln && io->dw_ld < io->N))
+            return set_err(MACJD_EINVAL, "%s: bad leading dimension", who);
+        if ((io->outer_vec == nullptr) != (io->outer_w == nullptr))
+            return set_err(MACJD_EINVAL, "%s: outer_vec and outer_w go together", who);
+        if (is_ln && (io->N > WG_BN || io->db))
+            return set_err(MACJD_EUNSUPPORTED, "%s: the contracted problem has N <= 64 and no bias output", who);
+        b.io[p] = *io;
+        b.Mp[p] = (int)wg_pad(io->M, WG_BM);
+        b.Np[p] = (int)wg_pad(io->N, WG_BN);
+        b.chunks[p] = (int)((io->K + WG_ROWS - 1) / WG_ROWS);
+        b.tiles_n[p] = b.Np[p] / WG_BN;
+        b.tiles_m[p] = b.Mp[p] / WG_BM;
+        b.wg_start[p + 1] = b.wg_start[p] + (int64_t)b.tiles_n[p] * b.tiles_m[p] * b.chunks[p];
+        b.out_start[p + 1] = b.out_start[p] + (is_ln ? (int64_t)2 * io->N : (int64_t)io->M * io->N + io->M);
+    }
+    for (int p = n; p < MACJD_WGRAD_MAX_BATCH; ++p) {
+        b.wg_start[p + 1] = b.wg_start[n];
+        b.out_start[p + 1] = b.out_start[n];
+        b.tiles_n[p] = b.tiles_m[p] = 1;
+    }
+    if (b.wg_start[n] > 0x7fffffff) return set_err(MACJD_EUNSUPPORTED, "%s: too many work items", who);
+    return MACJD_OK;
+}
+
+static unsigned wgrad_reduce_blocks(int64_t total) {
+    using namespace macjd;
+    return (unsigned)((total + WG_RED - 1) / WG_RED < 8192 ? (total + WG_RED - 1) / WG_RED : 8192);
+}
+
+extern "C" int32_t macjd_linear_wgrad_many_norm_partials(const macjd_wgrad_io* ios, int32_t n, int32_t ln_problem) {
+    macjd::WgradBatch b;
+    if (wgrad_norm_batch(ios, n, ln_problem, &b, "macjd_linear_wgrad_many_norm_partials") != MACJD_OK) return -1;
+    return (int32_t)wgrad_reduce_blocks(b.out_start[n]);
+}
+
+extern "C" int macjd_linear_wgrad_many_norm(const macjd_wgrad_io* ios, int32_t n, const macjd_wgrad_norm_io* norm, void* hip_stream) {
+    using namespace macjd;
+    const char* who = "macjd_linear_wgrad_many_norm";
+    if (!norm || !norm->partials || !norm->step) return set_err(MACJD_EINVAL, "%s: bad argument", who);
+    WgradBatch b;
+    const int rc = wgrad_norm_batch(ios, n, norm->ln_problem, &b, who);
+    if (rc != MACJD_OK) return rc;
+    WgradNorm ln{};
+    ln.problem = norm->ln_problem;
+    ln.partials = norm->partials; ln.step = norm->step;
+    if (ln.problem >= 0) {
+        if (!norm->W || !norm->dgamma || !norm->dbeta || norm->w_ld < ios[ln.problem].N)
+            return set_err(MACJD_EINVAL, "%s: bad LayerNorm argument", who);
+        ln.W = norm->W; ln.w_ld = norm->w_ld; ln.dgamma = norm->dgamma; ln.dbeta = norm->dbeta;
+        ln.slots = b.tiles_m[ln.problem] * b.chunks[ln.problem];
+    }
+    const unsigned rblocks = wgrad_reduce_blocks(b.out_start[n]);
+    if ((int64_t)rblocks > (int64_t)norm->partials_cap) return set_err(MACJD_EINVAL, "%s: partials_cap too small", who);
+    hipStream_t s = (hipStream_t)hip_stream;
+    hipLaunchKernelGGL(wgrad_partial_many_norm_kernel, dim3((unsigned)b.wg_start[n]), dim3(256), 0, s, b, ln);
+    hipLaunchKernelGGL(wgrad_reduce_many_norm_kernel, dim3(rblocks), dim3(256), 0, s, b, ln);
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_linear_wgrad_many_norm: %s", hipGetErrorString(err));
     return MACJD_OK;
 }

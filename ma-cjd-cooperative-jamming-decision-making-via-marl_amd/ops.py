@@ -1249,12 +1249,14 @@ def sample_episodes(idx_out, n_stored, counter, seed, offset=0):
 
 
 def clip_adam_step(param, grad, exp_avg, exp_avg_sq, step, grad_norm, partials, lr, betas, eps, max_norm, sample_next=None,
-                   lnparam=None):
+                   lnparam=None, reduced=None):
     """In-place update of ``param`` / ``exp_avg`` / ``exp_avg_sq`` / ``step`` (all flat float32 on one HIP
     device); writes the pre-clip gradient norm into ``grad_norm``.  ``sample_next`` = (idx_out, n_stored, counter,
     seed[, offset]): the update launch also draws the NEXT update's episodes (``sample_episodes``) when it is done.
     ``lnparam`` = LayerNorm-parameter launches held back by ``deferred_wgrad(hold_lnparam=True)``: a single one whose
-    outputs are ranges of ``grad`` is evaluated inside the squared-norm launch; anything else is simply issued first."""
+    outputs are ranges of ``grad`` is evaluated inside the squared-norm launch; anything else is simply issued first.
+    ``reduced`` = ``deferred_wgrad(norm=...).norm_partials`` when that context's launch pair already left the squares of
+    every gradient in ``partials`` and advanced ``step``: the step is then ONE launch (macjd_clip_adam_step_reduced)."""
     lib = _native.load()
     io = _native.AdamIO()
     io.n, io.lr, io.beta1, io.beta2, io.eps, io.max_norm = param.numel(), lr, betas[0], betas[1], eps, max_norm
@@ -1271,6 +1273,11 @@ def clip_adam_step(param, grad, exp_avg, exp_avg_sq, step, grad_norm, partials, 
                 and 0 <= b_off <= grad.numel() - lio.K and partials.numel() >= 256 + lio.K):
             fuse = (lio, int(g_off), int(b_off))
     with torch.cuda.device(param.device):
+        if reduced is not None:
+            assert not held, "clip_adam_step: the reduce launch already formed the LayerNorm gradients"
+            _native.check(lib.macjd_clip_adam_step_reduced(ctypes.byref(io), int(reduced), spp, _stream(param)),
+                          "macjd_clip_adam_step_reduced")
+            return
         if fuse is not None:
             _native.check(lib.macjd_clip_adam_step_ln(ctypes.byref(io), spp, ctypes.byref(fuse[0]), fuse[1], fuse[2],
                                                       _stream(param)), "macjd_clip_adam_step_ln")
@@ -1367,7 +1374,7 @@ class deferred_wgrad:
     the flush: read them only after the context — and let autograd (or the caller) be their only owner until then.
     A parameter used twice in the graph is handled (its second gradient forces the recorded ones out first)."""
 
-    def __init__(self, grad_dst=None, hold_lnparam=False):
+    def __init__(self, grad_dst=None, hold_lnparam=False, norm=None):
         # {grad_key(parameter): preallocated gradient tensor of the parameter's shape}: inside the context the
         # weight / bias gradients of those parameters are written straight into these tensors (slices of the
         # learner's flat gradient vector) and autograd receives fresh views of them — no packing copy afterwards
@@ -1376,6 +1383,11 @@ class deferred_wgrad:
         # collected in ``held`` — the caller passes them to ``clip_adam_step(lnparam=...)``, whose squared-norm launch
         # evaluates them (one launch less), or calls them itself
         self._hold, self.held = bool(hold_lnparam), []
+        # norm = (partials, step, cover): when ``norm_in_reduce_plan`` allows it, the grouped launch pair is
+        # macjd_linear_wgrad_many_norm — it forms the LayerNorm-parameter gradients and the squares of everything it
+        # stores itself and advances ``step`` — and ``norm_partials`` tells ``clip_adam_step(reduced=...)`` how many
+        # partials to sum; otherwise ``norm_partials`` stays None and everything is as without ``norm``
+        self._norm, self.norm_partials = norm, None
 
     def __enter__(self):
         global _DEFERRED_WGRAD, _DEFERRED_POST, _GRAD_DST, _DEFERRED_SEEN
@@ -1390,6 +1402,13 @@ class deferred_wgrad:
         pending, _DEFERRED_WGRAD = _DEFERRED_WGRAD, self._prev
         post, _DEFERRED_POST = _DEFERRED_POST, self._prev_post
         _GRAD_DST, _DEFERRED_SEEN = self._prev_dst, self._prev_seen
+        if exc[0] is None and self._norm is not None and pending:
+            partials, step, cover = self._norm
+            lns = [fn.lnparam for fn in post if hasattr(fn, "lnparam")]
+            q = norm_in_reduce_plan([io for io, _ in pending], lns, cover) if len(lns) == len(post) else None
+            if q is not None:
+                self.norm_partials = self._flush_norm(pending, q, lns[0], partials, step)
+                return False
         self._flush(exc, pending)
         if exc[0] is None:
             for fn in post:      # launches that consume the flushed products (e.g. LayerNorm parameter gradients)
@@ -1410,6 +1429,69 @@ class deferred_wgrad:
                 with torch.cuda.device(dev):
                     _native.check(lib.macjd_linear_wgrad_many(arr, len(part), _stream(part[0][1][0])),
                                   "macjd_linear_wgrad_many")
+
+    @staticmethod
+    def _flush_norm(pending, q, lio, partials, step):
+        """The recorded problems as macjd_linear_wgrad_many_norm with problem ``q`` contracted by ``lio``; returns the number
+        of partials it leaves in ``partials``."""
+        lib = _native.load()
+        arr = (_native.WgradIO * len(pending))(*[io for io, _ in pending])
+        n_partials = int(lib.macjd_linear_wgrad_many_norm_partials(arr, len(pending), q))
+        if n_partials < 1 or n_partials > partials.numel():
+            raise _native.NativeLibraryError("macjd_linear_wgrad_many_norm: partials buffer too small or bad problem set")
+        nio = _native.WgradNormIO()
+        nio.ln_problem, nio.partials_cap = q, partials.numel()
+        nio.W, nio.w_ld, nio.dgamma, nio.dbeta = lio.W, lio.w_ld, lio.dgamma, lio.dbeta
+        nio.partials, nio.step = partials.data_ptr(), step.data_ptr()
+        t0 = pending[0][1][0]
+        with torch.cuda.device(t0.device):
+            _native.check(lib.macjd_linear_wgrad_many_norm(arr, len(pending), ctypes.byref(nio), _stream(t0)),
+                          "macjd_linear_wgrad_many_norm")
+        return n_partials
+
+
+def norm_in_reduce_plan(ios, lns, cover):
+    """Whether ONE macjd_linear_wgrad_many_norm launch pair can stand for the grouped weight gradients ``ios`` (WgradIO),
+    the LayerNorm-parameter launches ``lns`` (LnParamIO) behind them and the optimiser's squared-norm launch over a gradient
+    vector whose non-zero elements are the byte ranges ``cover`` [(address, bytes)]: returns the index of the problem to
+    contract, or None.  It can when
+      * the problems fit one launch pair and exactly one LayerNorm launch waits for them;
+      * that launch's G is the (bias-less, N <= 64) output of one of the problems, its gb the bias output of another one
+        with the SAME [K, M] operand (so the contracted problem's own column sums are gb), its W has G's shape;
+      * every range of ``cover`` is written by the pair: by contiguous dW / db outputs of the other problems or by
+        dgamma / dbeta — then the squares it counts are the whole norm."""
+    if not ios or len(ios) > 8 or len(lns) != 1:
+        return None
+    ln = lns[0]
+    qs = [k for k, io in enumerate(ios) if io.dW == ln.G and not io.db]
+    if len(qs) != 1:
+        return None
+    q = qs[0]
+    g = ios[q]
+    if g.N > 64 or g.M != ln.C or g.N != ln.K or g.dw_ld != ln.g_ld or not ln.W or ln.w_ld < ln.K:
+        return None
+    same_operand = [io for k, io in enumerate(ios) if k != q and io.db and io.db == ln.gb and
+                    (io.gout, io.gout_ld, io.K, io.M, io.outer_vec, io.outer_w) == (g.gout, g.gout_ld, g.K, g.M, g.outer_vec, g.outer_w)]
+    if not same_operand:
+        return None
+    written = [(ln.dgamma, 4 * ln.K), (ln.dbeta, 4 * ln.K)]
+    for k, io in enumerate(ios):
+        if k == q:
+            continue
+        if io.dw_ld == io.N:
+            written.append((io.dW, 4 * io.M * io.N))
+        if io.db:
+            written.append((io.db, 4 * io.M))
+    merged = []
+    for lo, nb in sorted(written):
+        if merged and lo <= merged[-1][1]:
+            merged[-1][1] = max(merged[-1][1], lo + nb)
+        else:
+            merged.append([lo, lo + nb])
+    for lo, nb in cover:
+        if not any(a <= lo and lo + nb <= b for a, b in merged):
+            return None
+    return q
 
 
 def linear_wgrad(gout, inp, want_bias=True, w_key=None, b_key=None, need=(True, True), outer=None):

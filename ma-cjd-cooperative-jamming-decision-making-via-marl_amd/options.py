@@ -12,6 +12,9 @@ for normal operation.
     MACJD_ACTOR_IN_SCAN       1 | 0      actor rows in the scan launch's prologue / as their own launch
     MACJD_DEVICE_SAMPLER      1 | 0      next batch drawn by the update's last launch / host draw + pinned upload
     MACJD_LN_IN_SQNORM        1 | 0      LayerNorm-parameter gradients inside the optimiser's first launch
+    MACJD_NORM_IN_REDUCE      1 | 0      single process, default learner: LayerNorm-parameter gradients and the squared gradient norm
+                                         formed by the weight-gradient launch pair, optimiser step as ONE launch / the
+                                         squared-norm (+ LayerNorm) launch between the two
     MACJD_WGRAD_OUTER         1 | 0      Q-head ReLU-backward operand formed inside the weight-gradient launch
     MACJD_QHEAD_TAKEN         1 | 0      taken-action Q-head as one launch / input rows + GEMM + row-dot
     MACJD_QHEAD_DOUBLE_Q      1 | 0      Double-DQN target values as one launch from the hidden states / library GEMM bases +
@@ -35,7 +38,7 @@ import os
 
 _DEFAULTS = {
     "UPDATE_STREAMS": "2", "UPDATES_PER_GRAPH": "1", "PIPELINED_GROUP": "1", "SHARED_BODY": "1",
-    "LEARNER_STATIC_OBS": "1", "ACTOR_IN_SCAN": "1", "DEVICE_SAMPLER": "1", "LN_IN_SQNORM": "1", "WGRAD_OUTER": "1",
+    "LEARNER_STATIC_OBS": "1", "ACTOR_IN_SCAN": "1", "DEVICE_SAMPLER": "1", "LN_IN_SQNORM": "1", "NORM_IN_REDUCE": "1", "WGRAD_OUTER": "1",
     "QHEAD_TAKEN": "1", "QHEAD_DOUBLE_Q": "1", "QHEAD_DOUBLE_Q_H128": "0", "PAIRED_HEADS": "1", "MIXER_TRAIN": "1", "MIXER_STATIC_STATE": "1", "GRAPHED_ALLREDUCE": "0",
     "PREFETCH_LAUNCH": "1",
     "CLOSED_LOOP_ROLLOUT": "0",

@@ -1,5 +1,5 @@
 """Kernel timeline of the replayed learner updates in a rocprofv3 --kernel-trace CSV (bench.py --mode train): one update =
-the window from the end of an update's last kernel (adam_update_kernel) to the end of the next one's; inside a replayed
+the window from the end of an update's last kernel (adam_update_kernel / adam_update_reduced_kernel) to the end of the next one's; inside a replayed
 group the next update's draw / gather / scan run on the side stream beside the current update's tail, so they show in
 the window of the update BEFORE the one that consumes them.  Prints one window from the middle of the run, the median
 period over all windows and the median duration of every kernel.  Usage:
@@ -11,7 +11,7 @@ import sys
 
 rows = list(csv.DictReader(open(sys.argv[1])))
 ev = sorted(((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"], r.get("Queue_Id", "?")) for r in rows))
-ends = [e[1] for e in ev if "adam_update_kernel" in e[2]]
+ends = [e[1] for e in ev if "adam_update_kernel" in e[2] or "adam_update_reduced_kernel" in e[2]]
 if len(ends) < 8:
     sys.exit("fewer than 8 updates in the trace")
 periods = [(b - a) / 1e3 for a, b in zip(ends[:-1], ends[1:])]
