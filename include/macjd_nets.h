@@ -317,6 +317,24 @@ int macjd_prefetch_batch_supported(int32_t n_nets, int32_t H, int32_t B);   /* 1
 int macjd_prefetch_batch(const macjd_prefetch_io* io, void* hip_stream);
 
 /*
+ * The prefetches of n consecutive later updates (1 <= n <= MACJD_PREFETCH_MAX_BATCHES) as ONE launch: for every batch i
+ * what macjd_prefetch_batch(&ios[i]) does, bit for bit, in one grid — the scan workgroups of every batch first, then the
+ * actor rows, the gather workgroups (gather_blocks PER batch) and one mask-sum workgroup per batch.  A second batch is
+ * another B * J sequences on compute units that the latency-bound scan of the first leaves idle, so the launch takes
+ * little longer than a one-batch launch (inside the learner's update 71 us for two batches against 60 us for one), and
+ * a group of updates that issues it two updates ahead takes the prefetch off its critical cycle.  macjd_prefetch_batch
+ * is the case n = 1.
+ * All batches share the ring tensors and the weights, B / J / T and the gather sources, the sampler's counter, n_stored
+ * and seed, the mask geometry and gather_blocks: ios[i] must equal ios[0] in everything but
+ *     sampler.reserved (the counter offset), no_draw, sampler.idx_out,
+ *     gather.dst[] / gather.dst_row_bytes[], gru.h_out[0], gru.p_out[0], tot_m,
+ * and no two batches may share one of these outputs (MACJD_EINVAL otherwise).  The launch only reads the counter.
+ */
+#define MACJD_PREFETCH_MAX_BATCHES 4
+int macjd_prefetch_batches_supported(int32_t n_nets, int32_t H, int32_t B, int32_t n);   /* 1 / 0 */
+int macjd_prefetch_batches(const macjd_prefetch_io* ios, int32_t n, void* hip_stream);
+
+/*
  * Input rows of the Q-head for the TAKEN action, out[n, :] = [h[n, 0..H-1], onehot_A(idx[n]), P[n]]  — the
  * F.one_hot / torch.cat sequence of RNNAgent.get_q_value_for_action (reference core/networks.py:160-174)
  * as one launch.  idx outside [0, A) gives an all-zero one-hot block (the caller validates indices when asked to).

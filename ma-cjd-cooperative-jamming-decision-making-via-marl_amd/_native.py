@@ -38,6 +38,7 @@ EXPORTS = [
     "macjd_prefetch_batch_supported", "macjd_prefetch_batch",
     "macjd_actor_gradient_supported", "macjd_actor_gradient",
     "macjd_linear_wgrad_many_norm", "macjd_linear_wgrad_many_norm_partials", "macjd_clip_adam_step_reduced",
+    "macjd_prefetch_batches_supported", "macjd_prefetch_batches",
 ]
 
 
@@ -539,6 +540,10 @@ def load() -> ctypes.CDLL:
     lib.macjd_prefetch_batch_supported.argtypes = [ctypes.c_int32] * 3
     lib.macjd_prefetch_batch.restype = ctypes.c_int
     lib.macjd_prefetch_batch.argtypes = [ctypes.POINTER(PrefetchIO), ctypes.c_void_p]
+    lib.macjd_prefetch_batches_supported.restype = ctypes.c_int
+    lib.macjd_prefetch_batches_supported.argtypes = [ctypes.c_int32] * 4
+    lib.macjd_prefetch_batches.restype = ctypes.c_int
+    lib.macjd_prefetch_batches.argtypes = [ctypes.POINTER(PrefetchIO), ctypes.c_int32, ctypes.c_void_p]
     lib.macjd_gather_rows.restype = ctypes.c_int
     lib.macjd_gather_rows.argtypes = [ctypes.POINTER(GatherIO), ctypes.c_void_p]
     lib.macjd_linear_wgrad.restype = ctypes.c_int

@@ -41,6 +41,7 @@ clipping; every rank then takes the identical Adam step.
 """
 from __future__ import annotations
 
+import collections
 import copy
 import os
 
@@ -51,6 +52,30 @@ import torch.optim as optim
 
 from .. import hipgraph, ops, options
 from .networks import QMixer
+
+
+PrefetchLaunch = collections.namedtuple("PrefetchLaunch", "issue_at updates offsets sets")
+
+
+def prefetch_plan(K: int, ahead: int):
+    """The one-launch prefetches of a captured group of K pipelined updates (``enable_graphs``): (launches, n_sets).  A
+    launch is issued behind the Q-head grid of update ``issue_at`` and prefetches the batches of ``updates`` at the sampler's
+    counter ``offsets`` into the staging ``sets``; update u reads set u % n_sets and its batch is the draw of offset u - 1
+    (update 0 runs on the batch drawn before the group; the group's closing draw has offset K - 1).
+      ahead = 1  one launch per update 1 .. K-1, issued by the update before it; two staging sets.
+      ahead = 2  one launch per PAIR (a, a + 1), a = 1, 3, 5, .., issued by update max(0, a - 2) — two updates before its
+                 first consumer, so that in steady state a launch has two update periods to finish and no update waits for
+                 its scan; a one-batch launch for the last update when K - 1 is odd; four staging sets: the launch for
+                 (a, a + 1) is in flight beside the updates a - 2 and a - 1, which read the two other sets."""
+    if ahead not in (1, 2):
+        raise ValueError("prefetch_plan: ahead must be 1 or 2")
+    n_sets = 2 * ahead
+    launches = []
+    for a in range(1, K, ahead):
+        updates = tuple(range(a, min(a + ahead, K)))
+        launches.append(PrefetchLaunch(max(0, a - ahead), updates, tuple(u - 1 for u in updates),
+                                       tuple(u % n_sets for u in updates)))
+    return launches, n_sets
 
 
 def _to(x, dtype, device):
@@ -947,6 +972,8 @@ class QMixLearner:
         K = int(updates_per_graph if updates_per_graph is not None else options.get("UPDATES_PER_GRAPH"))
         self._g_multi = None
         self._g_prefetch_launch = False   # bookkeeping: the captured group's prefetches are single launches (ops.prefetch_batch)
+        self._g_prefetch_ahead = 1        # ... issued one update ahead, or in pairs two updates ahead (prefetch_plan)
+        self._g_prefetch_held = None
         if K > 1 and self._g_single and self._g_dev_sampler and fused and self._g_stats4 is not None:
             gm, rows, single_norm = torch.cuda.CUDAGraph(), [], self._grad_norm
             # Inside the group the updates are software-pipelined: everything of update k + 1 that depends on neither the
@@ -964,8 +991,16 @@ class QMixLearner:
             launch_agents = [self.mac.agent] if self._body_is_shared() else [self.target_mac.agent, self.mac.agent]
             self._g_prefetch_launch = bool(pipelined and options.on("PREFETCH_LAUNCH") and "filled" in keys
                                            and ops.prefetch_batch_supported(launch_agents, self._g_B, srcs))
-            stage2 = {k: torch.zeros_like(v) for k, v in stage.items()} if pipelined else None
-            stages = [stage, stage2]
+            # ... and TWO updates ahead (MACJD_PREFETCH_AHEAD, prefetch_plan): one launch prefetches the batches of a pair of
+            # updates and is issued two updates before the first of them, so no Q-head grid waits for its scan — the
+            # prefetch leaves the cycle that bounded the update.  "1": one launch per update, issued by
+            # the update before it.
+            plan = None
+            if self._g_prefetch_launch and options.get("PREFETCH_AHEAD") != "1":
+                plan, n_sets = prefetch_plan(K, 2)
+            self._g_prefetch_ahead = 2 if plan is not None else 1
+            stages = [stage] + ([{k: torch.zeros_like(v) for k, v in stage.items()} for _ in range(n_sets - 1 if plan else 1)]
+                                if pipelined else [None])
             # (the captured launches write and read the second staging set through baked addresses: it has to live as long
             # as the graph.  Until round 3 nothing held it once this function returned — the freed blocks stayed cached, so
             # it went unnoticed until another capture's torch.cuda.empty_cache() unmapped them: a GPU memory fault in the
@@ -1008,13 +1043,54 @@ class QMixLearner:
                     ev_s.record(ts)
                 return (([h[0], h[0]] if shared else h), ([ps[0], ps[0]] if shared else ps), (ev_g, ev_s, tot_m))
 
+            # two updates ahead: every batch of a launch has its own index row, scan output, actor rows and mask sum; the
+            # captured launches write and read them through baked addresses, so they are held like the staging sets
+            ready = {}        # update -> (h, P, (gather_done, scan_done, tot_m)) of its prefetched batch
+            issues = {l.issue_at: l for l in plan} if plan is not None else {}
+            idx_rows = (torch.zeros(len(stages), self._g_B, dtype=torch.int64, device=self.device) if plan is not None else None)
+            self._g_prefetch_held = [idx_rows]
+            paired = plan is not None and self._paired_heads_ok(stage, self._g_T)
+
+            def prefetch_many(launch, fork=True):
+                """draw + gather + scan of the later updates ``launch.updates`` as ONE launch on the side stream"""
+                origin = torch.cuda.current_stream(origin_dev)
+                ts = self._target_stream
+                if isinstance(fork, torch.cuda.Event):
+                    ts.wait_event(fork)
+                elif fork:
+                    ts.wait_stream(origin)
+                assert launch.offsets[0] == unwritten[0] and self._body_is_shared()
+                with torch.cuda.stream(ts), torch.no_grad():
+                    res = ops.prefetch_batches(
+                        buffer.buffers["obs"], [self.mac.agent], self._g_B, self.n_agents, self._g_T + 1,
+                        (self._g_n_stored, self._g_draws, self._sampler_seed()), srcs,
+                        [(off, True, [stages[s][k] for k in keys], idx_rows[s]) for off, s in zip(launch.offsets, launch.sets)],
+                        buffer.buffers["filled"], self._g_T - 1)
+                    unwritten[0] += len(launch.updates)   # (the launch only READS the counter, at these offsets)
+                    ev = torch.cuda.Event()
+                    ev.record(ts)
+                self._g_prefetch_held.append(res)
+                for i, (u, (h, p, tot_m)) in enumerate(zip(launch.updates, res)):
+                    # the first consumer waits for the launch; on the chain's stream that wait covers the later ones (the
+                    # paired update takes "no event"; the other forms wait where they always do, for an event long set)
+                    e = ev if (i == 0 or not paired) else None
+                    ready[u] = ([h, h], [p, p], (e, e, tot_m))
+
             with hipgraph.capture(gm, pool=self._graph_a.pool()):
                 nxt_batch = None
                 for k_upd in range(K):
                     last = k_upd == K - 1
                     box = {}
                     hook = (lambda fork=True: box.__setitem__("next", prefetch(stages[(k_upd + 1) % 2], fork))) if (pipelined and not last) else None
-                    if pipelined and nxt_batch is not None:
+                    if plan is not None:
+                        launch = issues.get(k_upd)
+                        hook = (lambda fork=True, launch=launch: prefetch_many(launch, fork)) if launch is not None else None
+                        nxt_batch = ready.pop(k_upd, None)
+                    if plan is not None and nxt_batch is not None:
+                        h_pre, p_pre, evs = nxt_batch
+                        self._forward_backward_full(stages[k_upd % len(stages)], self._g_T, pre_scan=h_pre, pre_actor=p_pre,
+                                                    prefetched=evs, after_join=hook)
+                    elif pipelined and nxt_batch is not None:
                         h_pre, p_pre, evs = nxt_batch
                         self._forward_backward_full(stages[k_upd % 2], self._g_T, pre_scan=h_pre, pre_actor=p_pre,
                                                     prefetched=evs, after_join=hook)
@@ -1043,7 +1119,7 @@ class QMixLearner:
                     # the update's last launch draws the next batch — unless the prefetch behind the join has done so
                     # (one-launch prefetches read the counter at offsets 0 .. K-2 without advancing it: the group's closing draw
                     # is the one of offset K-1 and leaves the counter K further, as K draws one after the other do)
-                    if nxt_batch is not None:
+                    if nxt_batch is not None or (plan is not None and not last):
                         self._clip_and_step(sample_next=None)
                     else:
                         self._clip_and_step(sample_next=nxt + (unwritten[0],))
@@ -1086,7 +1162,7 @@ class QMixLearner:
             graphs.append(m[1])
         graphs += [getattr(self, "_graph_b", None), getattr(self, "_graph_a", None)]
         self._graphs_ready = False
-        self._g_multi = self._g_stages = None
+        self._g_multi = self._g_stages = self._g_prefetch_held = None
         self._graph_a = self._graph_b = None
         self._graph_body_a = None
         self._g_out_a = self._g_out_b = self._g_stats4 = self._last_stats4 = self._held_ln = self._norm_partials = None

@@ -1036,15 +1036,17 @@ __global__ void __launch_bounds__(256) adam_update_reduced_kernel(const macjd_ad
     adam_apply<SAMPLE>(io, sqrtf((s_w[0] + s_w[1]) + (s_w[2] + s_w[3])), next);
 }
 
-// part `part` of `parts` of the copy dst_k[row, :] = src_k[src_row, :] (tensor k, raw bytes), by one workgroup
-__device__ __forceinline__ void gather_rows_body(const macjd_gather_io& io, const int k, const int row, const int64_t src_row,
-                                                 const int part, const int parts) {
+// part `part` of `parts` of the copy dst_k[row, :] = src_k[src_row, :] (tensor k, raw bytes), by one workgroup.  The
+// destination (base, row pitch: 0 = row bytes) is given apart from io: a multi-batch prefetch launch keeps one per batch.
+__device__ __forceinline__ void gather_rows_body(const macjd_gather_io& io, void* const dst_base, const int64_t dst_row_bytes,
+                                                 const int k, const int row, const int64_t src_row, const int part,
+                                                 const int parts) {
     const int64_t words = io.row_bytes[k] >> 2;
     const uint32_t* __restrict__ src = (const uint32_t*)((const char*)io.src[k] + src_row * io.row_bytes[k]);
-    const int64_t dpitch = io.dst_row_bytes[k] ? io.dst_row_bytes[k] : io.row_bytes[k];
-    uint32_t* __restrict__ dst = (uint32_t*)((char*)io.dst[k] + (int64_t)row * dpitch);
+    const int64_t dpitch = dst_row_bytes ? dst_row_bytes : io.row_bytes[k];
+    uint32_t* __restrict__ dst = (uint32_t*)((char*)dst_base + (int64_t)row * dpitch);
     const bool vec = ((io.row_bytes[k] & 15) == 0) && ((dpitch & 15) == 0) && ((((uintptr_t)io.src[k]) & 15) == 0) &&
-                     ((((uintptr_t)io.dst[k]) & 15) == 0);
+                     ((((uintptr_t)dst_base) & 15) == 0);
     if (vec) {
         const int64_t n4 = words >> 2;
         for (int64_t i = (int64_t)part * blockDim.x + threadIdx.x; i < n4; i += (int64_t)parts * blockDim.x)
@@ -1057,54 +1059,82 @@ __device__ __forceinline__ void gather_rows_body(const macjd_gather_io& io, cons
 
 __global__ void __launch_bounds__(256) gather_rows_kernel(const macjd_gather_io io) {
     // blockIdx.y = tensor, blockIdx.z = output row, gridDim.x workgroups share a row
-    gather_rows_body(io, blockIdx.y, blockIdx.z, io.idx[blockIdx.z], blockIdx.x, gridDim.x);
+    gather_rows_body(io, io.dst[blockIdx.y], io.dst_row_bytes[blockIdx.y], blockIdx.y, blockIdx.z, io.idx[blockIdx.z], blockIdx.x,
+                     gridDim.x);
 }
 
-// ---- the whole prefetch of a later update's batch as ONE launch (include/macjd_nets.h, macjd_prefetch_io) ----
-// 1-D grid in ranges (the idiom of qheads_pair_kernel), the long pole first:
-//   [0, BJ)               scan of sequence (b, j) with its in-kernel input transform   (gru_units_body)
-//   [BJ, 2 BJ)            actor rows of sequence (b, j)                                (gru_units_body, actor only)
-//   [2 BJ, 2 BJ + G)      gather: the 8 * n_tensors * B row parts of gather_rows_kernel's grid, dealt round-robin
-//   2 BJ + G              mask sum over the ring's `filled` rows; stores the drawn indices for later readers
+// ---- the whole prefetch of n later updates' batches as ONE launch (include/macjd_nets.h, macjd_prefetch_io) ----
+// 1-D grid in ranges (the idiom of qheads_pair_kernel), the long pole first across all n batches; inside a range batch i
+// takes the i-th share:
+//   [0, n BJ)                      scan of sequence (b, j) with its in-kernel input transform   (gru_units_body)
+//   [n BJ, 2 n BJ)                 actor rows of sequence (b, j)                                (gru_units_body, actor only)
+//   [2 n BJ, 2 n BJ + n G)         gather: G workgroups per batch, each batch's 8 * n_tensors * B row parts of
+//                                  gather_rows_kernel's grid dealt round-robin to its own G
+//   [2 n BJ + n G, .. + n)         mask sum over the ring's `filled` rows; stores the drawn indices for later readers
 // Every workgroup evaluates the sampler's formula for the indices it needs (sampler_index is a pure function of the
 // counter value, the seed, the population and t): no workgroup reads what another one of this launch writes, and none
 // writes the counter — the group's closing draw (sample_episodes_block with the offset) advances it past all of them.
+// The batches share everything of macjd_prefetch_io but what PrefetchSlot holds (the kernel argument carries the shared
+// part once: n whole structs would not fit the 4 KiB of kernel arguments).
 constexpr int PREFETCH_MAX_B = 1024;    // the mask-sum workgroup keeps all B indices in LDS
 constexpr int PREFETCH_ROW_PARTS = 8;   // gather_rows_kernel's gridDim.x
 
-__global__ void __launch_bounds__(256) prefetch_batch_kernel(const macjd_prefetch_io io) {
+struct PrefetchSlot {
+    int64_t* idx_out;             // sampler.idx_out
+    float* h_out; float* p_out;   // gru.h_out[0], gru.p_out[0]
+    float* tot_m;
+    void* dst[8]; int64_t dst_row_bytes[8];   // gather.dst, gather.dst_row_bytes
+    int32_t offset, no_draw;      // sampler.reserved, no_draw
+};
+struct PrefetchArgs {
+    macjd_prefetch_io sh;         // batch 0's arguments; of the per-batch fields only the slots are read
+    int32_t n, reserved;
+    PrefetchSlot slot[MACJD_PREFETCH_MAX_BATCHES];
+};
+static_assert(sizeof(PrefetchArgs) <= 4096, "prefetch_batch_kernel: kernel arguments");
+
+__global__ void __launch_bounds__(256) prefetch_batch_kernel(const PrefetchArgs a) {
     __shared__ __attribute__((aligned(16))) float s_h[2][64];
     __shared__ float s_gi[3 * 64];
     __shared__ float s_pro[768];
     __shared__ int64_t s_idx[PREFETCH_MAX_B];
     __shared__ float s_w[16];
-    const int B = io.gru.B, BJ = B * io.gru.J, G = io.gather_blocks;
+    const int B = a.sh.gru.B, BJ = B * a.sh.gru.J, G = a.sh.gather_blocks, n = a.n;
     const int wg = blockIdx.x;
-    const int64_t N = (int64_t)*io.sampler.n_stored;
+    // range, batch and place inside the batch's share of the range
+    const int r0 = n * BJ, r1 = 2 * r0, r2 = r1 + n * G;
+    const int share = wg < r1 ? BJ : (wg < r2 ? G : 1);
+    const int in_range = wg < r0 ? wg : (wg < r1 ? wg - r0 : (wg < r2 ? wg - r1 : wg - r2));
+    const int bi = in_range / share, local = in_range - bi * share;
+    const PrefetchSlot& sl = a.slot[bi];
+    const int64_t N = (int64_t)*a.sh.sampler.n_stored;
     // no population yet, or "no draw": the indices already in idx_out (nothing in this launch writes them then)
-    const bool draw = !io.no_draw && N >= 1;
+    const bool draw = !sl.no_draw && N >= 1;
+    int64_t* const idx_out = sl.idx_out;
     SamplerPerm perm = {};
-    if (draw) perm = sampler_perm(*io.sampler.counter + (int64_t)io.sampler.reserved, io.sampler.seed, N);
-    auto index_of = [&](int t) -> int64_t { return draw ? sampler_index(perm, N, io.sampler.n, t) : io.sampler.idx_out[t]; };
-    if (wg < 2 * BJ) {
-        const bool actor_only = wg >= BJ;
-        const int seq = actor_only ? wg - BJ : wg;
-        gru_units_body<true>(io.gru, 0, seq, index_of(seq / io.gru.J), actor_only, false, s_h, s_gi, s_pro);
-    } else if (wg < 2 * BJ + G) {
-        const int n_parts = PREFETCH_ROW_PARTS * io.gather.n_tensors * B;
-        for (int v = wg - 2 * BJ; v < n_parts; v += G) {
+    if (draw) perm = sampler_perm(*a.sh.sampler.counter + (int64_t)sl.offset, a.sh.sampler.seed, N);
+    auto index_of = [&](int t) -> int64_t { return draw ? sampler_index(perm, N, a.sh.sampler.n, t) : idx_out[t]; };
+    if (wg < r1) {
+        const bool actor_only = wg >= r0;
+        macjd_gru_io g = a.sh.gru;
+        g.h_out[0] = sl.h_out;
+        g.p_out[0] = sl.p_out;
+        gru_units_body<true>(g, 0, local, index_of(local / g.J), actor_only, false, s_h, s_gi, s_pro);
+    } else if (wg < r2) {
+        const int n_parts = PREFETCH_ROW_PARTS * a.sh.gather.n_tensors * B;
+        for (int v = local; v < n_parts; v += G) {
             const int part = v % PREFETCH_ROW_PARTS, kr = v / PREFETCH_ROW_PARTS;
-            const int k = kr % io.gather.n_tensors, row = kr / io.gather.n_tensors;
-            gather_rows_body(io.gather, k, row, index_of(row), part, PREFETCH_ROW_PARTS);
+            const int k = kr % a.sh.gather.n_tensors, row = kr / a.sh.gather.n_tensors;
+            gather_rows_body(a.sh.gather, sl.dst[k], sl.dst_row_bytes[k], k, row, index_of(row), part, PREFETCH_ROW_PARTS);
         }
     } else {
         for (int t = threadIdx.x; t < B; t += blockDim.x) {
             const int64_t e = index_of(t);
             s_idx[t] = e;
-            if (draw) io.sampler.idx_out[t] = e;
+            if (draw) idx_out[t] = e;
         }
         __syncthreads();
-        td_mask_sum_body(io.mask, io.tot_m, s_w, [&](int b) { return s_idx[b]; });
+        td_mask_sum_body(a.sh.mask, sl.tot_m, s_w, [&](int b) { return s_idx[b]; });
     }
 }
 
@@ -1209,9 +1239,40 @@ extern "C" int macjd_prefetch_batch_supported(int32_t n_nets, int32_t H, int32_t
     return n_nets == 1 && H == 64 && B >= 1 && B <= macjd::PREFETCH_MAX_B && !macjd::env_options().gru_ksplit;
 }
 
-extern "C" int macjd_prefetch_batch(const macjd_prefetch_io* io, void* hip_stream) {
+extern "C" int macjd_prefetch_batches_supported(int32_t n_nets, int32_t H, int32_t B, int32_t n) {
+    return n >= 1 && n <= MACJD_PREFETCH_MAX_BATCHES && macjd_prefetch_batch_supported(n_nets, H, B);
+}
+
+// batch i of a multi-batch launch may differ from batch 0 only in its per-batch fields (macjd_prefetch_batches)
+static int prefetch_shares_with_first(const macjd_prefetch_io* first, const macjd_prefetch_io* io) {
+    macjd_gru_io g = io->gru;
+    g.h_out[0] = first->gru.h_out[0];
+    g.p_out[0] = first->gru.p_out[0];
+    if (memcmp(&g, &first->gru, sizeof(g)) != 0) return 0;
+    macjd_sampler_io sp = io->sampler;
+    sp.idx_out = first->sampler.idx_out;
+    sp.reserved = first->sampler.reserved;
+    if (memcmp(&sp, &first->sampler, sizeof(sp)) != 0) return 0;
+    if (memcmp(&io->mask, &first->mask, sizeof(io->mask)) != 0) return 0;
+    if (io->gather.n_tensors != first->gather.n_tensors || io->gather.n_rows != first->gather.n_rows ||
+        io->gather_blocks != first->gather_blocks)
+        return 0;
+    for (int k = 0; k < first->gather.n_tensors; ++k)
+        if (io->gather.src[k] != first->gather.src[k] || io->gather.row_bytes[k] != first->gather.row_bytes[k]) return 0;
+    return 1;
+}
+
+// the per-batch outputs of two batches of one launch must be different tensors (their workgroups run side by side)
+static int prefetch_outputs_distinct(const macjd_prefetch_io* x, const macjd_prefetch_io* y) {
+    if (x->gru.h_out[0] == y->gru.h_out[0] || x->gru.p_out[0] == y->gru.p_out[0] || x->tot_m == y->tot_m) return 0;
+    if (x->sampler.idx_out == y->sampler.idx_out && !(x->no_draw && y->no_draw)) return 0;
+    for (int k = 0; k < x->gather.n_tensors; ++k)
+        if (x->gather.dst[k] == y->gather.dst[k]) return 0;
+    return 1;
+}
+
+static int prefetch_one_ok(const macjd_prefetch_io* io) {
     using namespace macjd;
-    if (!io) return set_nets_err(MACJD_EINVAL, "macjd_prefetch_batch: NULL io");
     const macjd_gru_io& g = io->gru;
     if (!macjd_prefetch_batch_supported(g.n_nets, g.H, g.B))
         return set_nets_err(MACJD_EUNSUPPORTED, "macjd_prefetch_batch: needs one network, H = 64, 1 <= B <= 1024, the unit-split scan");
@@ -1230,17 +1291,56 @@ extern "C" int macjd_prefetch_batch(const macjd_prefetch_io* io, void* hip_strea
     if (io->mask.B != g.B || io->mask.Tm1 < 1 || !io->mask.filled || !io->tot_m)
         return set_nets_err(MACJD_EINVAL, "macjd_prefetch_batch: bad mask-sum argument");
     if (io->gather_blocks < 0) return set_nets_err(MACJD_EINVAL, "macjd_prefetch_batch: bad gather_blocks");
-    macjd_prefetch_io a = *io;
-    const int n_parts = PREFETCH_ROW_PARTS * a.gather.n_tensors * g.B;
+    return MACJD_OK;
+}
+
+extern "C" int macjd_prefetch_batches(const macjd_prefetch_io* ios, int32_t n, void* hip_stream) {
+    using namespace macjd;
+    if (!ios) return set_nets_err(MACJD_EINVAL, "macjd_prefetch_batch: NULL io");
+    if (n < 1 || n > MACJD_PREFETCH_MAX_BATCHES)
+        return set_nets_err(MACJD_EINVAL, "macjd_prefetch_batches: 1 <= n <= MACJD_PREFETCH_MAX_BATCHES");
+    for (int i = 0; i < n; ++i) {
+        const int rc = prefetch_one_ok(&ios[i]);
+        if (rc != MACJD_OK) return rc;
+        if (i > 0 && !prefetch_shares_with_first(&ios[0], &ios[i]))
+            return set_nets_err(MACJD_EINVAL, "macjd_prefetch_batches: the batches of a launch differ only in the counter offset, no_draw, "
+                                              "idx_out, gather.dst / dst_row_bytes, h_out, p_out and tot_m");
+        for (int j = 0; j < i; ++j)
+            if (!prefetch_outputs_distinct(&ios[j], &ios[i]))
+                return set_nets_err(MACJD_EINVAL, "macjd_prefetch_batches: two batches share an output");
+    }
+    PrefetchArgs a = {};
+    a.sh = ios[0];
+    a.n = n;
+    for (int i = 0; i < n; ++i) {
+        PrefetchSlot& sl = a.slot[i];
+        sl.idx_out = ios[i].sampler.idx_out;
+        sl.h_out = ios[i].gru.h_out[0];
+        sl.p_out = ios[i].gru.p_out[0];
+        sl.tot_m = ios[i].tot_m;
+        for (int k = 0; k < ios[i].gather.n_tensors; ++k) {
+            sl.dst[k] = ios[i].gather.dst[k];
+            sl.dst_row_bytes[k] = ios[i].gather.dst_row_bytes[k];
+        }
+        sl.offset = ios[i].sampler.reserved;
+        sl.no_draw = ios[i].no_draw;
+    }
+    const macjd_gru_io& g = a.sh.gru;
+    const int n_parts = PREFETCH_ROW_PARTS * a.sh.gather.n_tensors * g.B;
     // a row part is one load and one store per thread, i.e. one memory latency per pass of a gather workgroup's loop: 64
-    // workgroups (32 passes) outlast the scan by far, 256 (8 passes) end inside it; more buy nothing
-    if (a.gather_blocks == 0) a.gather_blocks = 256;
-    if (a.gather_blocks > n_parts) a.gather_blocks = n_parts;
-    const unsigned grid = 2u * (unsigned)(g.B * g.J) + (unsigned)a.gather_blocks + 1u;
+    // workgroups (32 passes) outlast the scan by far, 256 (8 passes) end inside it; more buy nothing.
+    // The count is per batch: the copy of n batches takes no more passes per workgroup than the copy of one.
+    if (a.sh.gather_blocks == 0) a.sh.gather_blocks = 256;
+    if (a.sh.gather_blocks > n_parts) a.sh.gather_blocks = n_parts;
+    const unsigned grid = (unsigned)n * (2u * (unsigned)(g.B * g.J) + (unsigned)a.sh.gather_blocks + 1u);
     hipLaunchKernelGGL(prefetch_batch_kernel, dim3(grid), dim3(256), 0, (hipStream_t)hip_stream, a);
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return set_nets_err(MACJD_EDEVICE, hipGetErrorString(err));
     return MACJD_OK;
+}
+
+extern "C" int macjd_prefetch_batch(const macjd_prefetch_io* io, void* hip_stream) {
+    return macjd_prefetch_batches(io, 1, hip_stream);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1342,6 +1342,43 @@ def prefetch_batch(obs, agents, B: int, J: int, n_steps: int, sampler, srcs, dst
     return outs, pouts, tot_m
 
 
+PREFETCH_MAX_BATCHES = 4   # MACJD_PREFETCH_MAX_BATCHES (include/macjd_nets.h)
+
+
+def prefetch_batches(obs, agents, B: int, J: int, n_steps: int, sampler, srcs, batches, filled, Tm1: int,
+                     gather_blocks: int = 0):
+    """The ``prefetch_batch`` launches of up to four consecutive later updates as ONE launch (include/macjd_nets.h
+    ``macjd_prefetch_batches``), bit-identical to them.  ``sampler`` = (n_stored, counter, seed), shared; ``batches`` = a
+    list of (offset, draw, dsts, idx_out), one per batch: its counter offset, whether it draws (False: the indices already
+    in its ``idx_out``), its staging tensors and its own index row.  The counter is only READ.  Returns one
+    (h_all [B, n_steps, J, H], P [B, J, A], tot_m [1]) per batch, all different tensors."""
+    lib = _native.load()
+    n = len(batches)
+    if not (1 <= n <= PREFETCH_MAX_BATCHES and prefetch_batch_supported(agents, B, srcs)
+            and lib.macjd_prefetch_batches_supported(len(agents), int(agents[0].rnn_hidden_dim), int(B), n)):
+        raise _native.NativeLibraryError("macjd_prefetch_batches: unsupported shape (1 to 4 batches, one agent body, "
+                                         "rnn_hidden_dim 64, B <= 1024)")
+    n_stored, counter, seed = sampler
+    assert filled.dtype == torch.bool and filled.device == obs.device and filled.shape[1] >= Tm1
+    gio, outs, pouts, _keep = _gru_from_obs_io(obs, None, agents, B, J, n_steps, True)
+    ios, res = (_native.PrefetchIO * n)(), []
+    for i, (offset, draw, dsts, idx_out) in enumerate(batches):
+        assert idx_out.numel() == B
+        io = ios[i]
+        io.gru = gio   # (a copy: what follows changes this batch's only)
+        h, p = (outs[0], pouts[0]) if i == 0 else (torch.empty_like(outs[0]), torch.empty_like(pouts[0]))
+        io.gru.h_out[0], io.gru.p_out[0] = h.data_ptr(), p.data_ptr()
+        io.gather, io.sampler = _gather_io(B, srcs, dsts), _sampler_io(idx_out, n_stored, counter, seed, offset)
+        io.mask.B, io.mask.Tm1 = int(B), int(Tm1)
+        io.mask.filled, io.mask.f_sb, io.mask.f_st = filled.data_ptr(), filled.stride(0), filled.stride(1)
+        tot_m = torch.empty(1, dtype=torch.float32, device=obs.device)
+        io.tot_m, io.no_draw, io.gather_blocks = tot_m.data_ptr(), 0 if draw else 1, int(gather_blocks)
+        res.append((h, p, tot_m))
+    with torch.cuda.device(obs.device):
+        _native.check(lib.macjd_prefetch_batches(ios, n, _stream(obs)), "macjd_prefetch_batches")
+    return res
+
+
 # ---------------------------------------------------------------------------------------------
 # Linear with a split-K MFMA weight / bias gradient (csrc/macjd_wgrad.hip)
 _DEFERRED_WGRAD = None   # list of (WgradIO, keep-alive tensors) while a ``deferred_wgrad`` context is active

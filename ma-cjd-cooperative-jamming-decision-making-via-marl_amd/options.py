@@ -29,6 +29,8 @@ for normal operation.
                                          summed per 16-row tile of one episode ([n_tiles, ...], K = n_tiles) / written per row
     MACJD_PREFETCH_LAUNCH     1 | 0      pipelined group: a later update's draw, gather, mask sum and scan as ONE launch, the
                                          draw read-only at a baked counter offset / the four launches one behind the other
+    MACJD_PREFETCH_AHEAD      2 | 1      that launch for the batches of TWO consecutive updates, issued two updates before the
+                                         first of them (four staging sets) / one launch per update, issued by the one before it
     MACJD_GRAPHED_ALLREDUCE   0 | 1      with ranks: RCCL all-reduce captured inside the update graph
     MACJD_CLOSED_LOOP_ROLLOUT 0 | 1      scanning radars: step-by-step rollout / agent and env of an episode batch in one launch
 """
@@ -40,7 +42,7 @@ _DEFAULTS = {
     "UPDATE_STREAMS": "2", "UPDATES_PER_GRAPH": "1", "PIPELINED_GROUP": "1", "SHARED_BODY": "1",
     "LEARNER_STATIC_OBS": "1", "ACTOR_IN_SCAN": "1", "DEVICE_SAMPLER": "1", "LN_IN_SQNORM": "1", "NORM_IN_REDUCE": "1", "WGRAD_OUTER": "1",
     "QHEAD_TAKEN": "1", "QHEAD_DOUBLE_Q": "1", "QHEAD_DOUBLE_Q_H128": "0", "PAIRED_HEADS": "1", "MIXER_TRAIN": "1", "MIXER_STATIC_STATE": "1", "GRAPHED_ALLREDUCE": "0",
-    "PREFETCH_LAUNCH": "1",
+    "PREFETCH_LAUNCH": "1", "PREFETCH_AHEAD": "2",
     "CLOSED_LOOP_ROLLOUT": "0",
 }
 _values = None

@@ -22,29 +22,51 @@ print(f"{len(ends)} updates; period between the ends of consecutive updates: med
 mid = len(periods) // 2
 print("periods of 44 consecutive updates from the middle of the run (us; a replayed group shows as a repeating pattern): "
       + " ".join(f"{p:.0f}" for p in periods[mid - 22:mid + 22]))
-# a window whose period is the median one
-k = min(range(len(periods) // 3, 2 * len(periods) // 3), key=lambda i: abs(periods[i] - statistics.median(periods)))
-w0, w1 = ends[k], ends[k + 1]
-# (every kernel that STARTS in the window: a side-stream launch that runs on into the next window — the next update's
-# prefetch — is listed with its full duration; the idle / busy sums below count it up to the window's end)
-win = [(s, e, n, q) for s, e, n, q in ev if w0 - 100 <= s < w1]
-print(f"window of update {k + 1} (t = 0 at the previous update's last kernel end; start us, duration us, queue, kernel):")
-for s, e, n, q in win:
-    print(f"  {(s - w0) / 1e3:7.1f} {(e - s) / 1e3:6.1f}  q{q}  {n[:78]}")
-busy = sorted((s, e) for s, e, _, _ in win)
-idle, cur = 0, w0
-for s, e in busy:
-    e = min(e, w1)
-    if s > cur:
-        idle += s - cur
-    cur = max(cur, e)
-print(f"  no kernel running for {idle / 1e3:.1f} us of the window's {(w1 - w0) / 1e3:.1f} us; sum of kernel time "
-      f"{sum(min(e, w1) - s for s, e, _, _ in win) / 1e3:.1f} us")
-# median duration per kernel name over the whole trace (update kernels only: those seen in the window)
+# two consecutive windows whose mean period is the median one of all such pairs (windows with and without a prefetch launch
+# take turns, so one window alone is either the short or the long kind; a pair at a group's boundary is far off the median)
+pairs = [(a + b) / 2 for a, b in zip(periods[:-1], periods[1:])]
+k = min(range(len(pairs) // 3, 2 * len(pairs) // 3), key=lambda i: abs(pairs[i] - statistics.median(pairs)))
+# (every kernel that STARTS in a window: a side-stream launch that runs on into the next window — a later update's
+# prefetch — is listed with its full duration; the idle / busy sums below count it up to the window's end.)  Two windows
+# one behind the other: with the prefetch of two updates per launch (MACJD_PREFETCH_AHEAD=2) only every other one starts one.
 names = []
-for _, _, n, _ in win:
-    if n not in names:
-        names.append(n)
+for kk in (k, k + 1):
+    if kk + 1 >= len(ends):
+        break
+    w0, w1 = ends[kk], ends[kk + 1]
+    win = [(s, e, n, q) for s, e, n, q in ev if w0 - 100 <= s < w1]
+    n_pre = sum(1 for s, _, n, _ in win if "prefetch_batch_kernel" in n and s >= w0)
+    print(f"window of update {kk + 1} (t = 0 at the previous update's last kernel end; start us, duration us, queue, kernel); "
+          f"prefetch launches started in it: {n_pre}:")
+    for s, e, n, q in win:
+        print(f"  {(s - w0) / 1e3:7.1f} {(e - s) / 1e3:6.1f}  q{q}  {n[:78]}")
+    busy = sorted((s, e) for s, e, _, _ in win)
+    idle, cur = 0, w0
+    for s, e in busy:
+        e = min(e, w1)
+        if s > cur:
+            idle += s - cur
+        cur = max(cur, e)
+    print(f"  no kernel running for {idle / 1e3:.1f} us of the window's {(w1 - w0) / 1e3:.1f} us; sum of kernel time "
+          f"{sum(min(e, w1) - s for s, e, _, _ in win) / 1e3:.1f} us")
+    for _, _, n, _ in win:
+        if n not in names:
+            names.append(n)
+# how long the chain's first kernel (the Q-head pair) starts after the previous update's last kernel, over all ordinary windows,
+# and how many windows start a prefetch launch
+heads = [s for s, _, n, _ in ev if "qheads_pair_kernel" in n]
+gaps, hi = [], 0
+for a, b in zip(ends[:-1], ends[1:]):
+    while hi < len(heads) and heads[hi] < a:
+        hi += 1
+    if hi < len(heads) and heads[hi] < b and (b - a) / 1e3 < 3 * statistics.median(periods):
+        gaps.append((heads[hi] - a) / 1e3)
+if gaps:
+    print(f"qheads_pair_kernel starts a median {statistics.median(gaps):.1f} us after the previous update's last kernel ends "
+          f"({len(gaps)} windows; 10th / 90th percentile {sorted(gaps)[len(gaps) // 10]:.1f} / {sorted(gaps)[9 * len(gaps) // 10]:.1f} us)")
+n_launch = sum(1 for _, _, n, _ in ev if "prefetch_batch_kernel" in n)
+print(f"prefetch_batch_kernel launches: {n_launch} for {len(ends)} updates")
+# median duration per kernel name over the whole trace (update kernels only: those seen in the two windows)
 print("median duration over the trace:")
 for n in names:
     d = [(e - s) / 1e3 for s, e, nn, _ in ev if nn == n]
