@@ -41,7 +41,6 @@ clipping; every rank then takes the identical Adam step.
 """
 from __future__ import annotations
 
-import collections
 import copy
 import os
 
@@ -52,30 +51,7 @@ import torch.optim as optim
 
 from .. import hipgraph, ops, options
 from .networks import QMixer
-
-
-PrefetchLaunch = collections.namedtuple("PrefetchLaunch", "issue_at updates offsets sets")
-
-
-def prefetch_plan(K: int, ahead: int):
-    """The one-launch prefetches of a captured group of K pipelined updates (``enable_graphs``): (launches, n_sets).  A
-    launch is issued behind the Q-head grid of update ``issue_at`` and prefetches the batches of ``updates`` at the sampler's
-    counter ``offsets`` into the staging ``sets``; update u reads set u % n_sets and its batch is the draw of offset u - 1
-    (update 0 runs on the batch drawn before the group; the group's closing draw has offset K - 1).
-      ahead = 1  one launch per update 1 .. K-1, issued by the update before it; two staging sets.
-      ahead = 2  one launch per PAIR (a, a + 1), a = 1, 3, 5, .., issued by update max(0, a - 2) — two updates before its
-                 first consumer, so that in steady state a launch has two update periods to finish and no update waits for
-                 its scan; a one-batch launch for the last update when K - 1 is odd; four staging sets: the launch for
-                 (a, a + 1) is in flight beside the updates a - 2 and a - 1, which read the two other sets."""
-    if ahead not in (1, 2):
-        raise ValueError("prefetch_plan: ahead must be 1 or 2")
-    n_sets = 2 * ahead
-    launches = []
-    for a in range(1, K, ahead):
-        updates = tuple(range(a, min(a + ahead, K)))
-        launches.append(PrefetchLaunch(max(0, a - ahead), updates, tuple(u - 1 for u in updates),
-                                       tuple(u % n_sets for u in updates)))
-    return launches, n_sets
+from .update_group import PrefetchLaunch, UpdateGroup, group_schedule, prefetch_plan  # noqa: F401 (the schedule: re-exported)
 
 
 def _to(x, dtype, device):
@@ -423,18 +399,26 @@ class QMixLearner:
         base = F.linear(h_all.reshape(B * T * J, H), l1.weight[:, :H], l1.bias)
         return ops.qhead_all_actions(base, params, l1.weight, l2.weight, l2.bias, H, a.n_actions).view(B, T, J, a.n_actions)
 
+    def _update_stream(self):
+        """The update's side stream (scan, target branch, prefetches, logged sums), created on first use."""
+        if getattr(self, "_target_stream", None) is None:
+            self._target_stream = torch.cuda.Stream(device=self.device)
+        return self._target_stream
+
+    def _body_agents(self):
+        """(agents whose body is evaluated, f): one agent when the frozen body is shared, else [target, eval]; f expands the
+        per-agent outputs of such an evaluation to [target, eval]."""
+        if self._body_is_shared():
+            return [self.mac.agent], lambda outs: [outs[0], outs[0]]
+        return [self.target_mac.agent, self.mac.agent], lambda outs: outs
+
     def _scan_from_ring_early(self):
         """Static observations: launch the scan (with its in-kernel input transform) on the side stream BEFORE the
         gather — it reads the sampled episodes' step-0 observation rows straight from the replay ring through the index
         tensor, so the longest kernel of the update starts at time zero.  Returns the per-agent hidden states (side stream)."""
-        dev = self.device
-        origin = torch.cuda.current_stream(dev)
-        if getattr(self, "_target_stream", None) is None:
-            self._target_stream = torch.cuda.Stream(device=dev)
-        ts = self._target_stream
-        ts.wait_stream(origin)                                                                  # fork
-        shared = self._body_is_shared()
-        agents = [self.mac.agent] if shared else [self.target_mac.agent, self.mac.agent]
+        ts = self._update_stream()
+        ts.wait_stream(torch.cuda.current_stream(self.device))                                  # fork
+        agents, both = self._body_agents()
         with torch.cuda.stream(ts), torch.no_grad():
             # (the frozen actor chain of each sequence's observation row rides in the scan launch's prologue as well.
             # With the K-split scan (65 us) the prologue was on the update's critical path and the separate actor launch
@@ -443,9 +427,7 @@ class QMixLearner:
             res = ops.gru_sequence_from_obs(self._g_buffer.buffers["obs"], self._g_idx, agents, self._g_B, self.n_agents,
                                             self._g_T + 1, with_actor=self._g_actor_in_scan)
             h, ps = res if self._g_actor_in_scan else (res, None)
-        if not self._g_actor_in_scan:
-            return ([h[0], h[0]] if shared else h), None
-        return ([h[0], h[0]] if shared else h), ([ps[0], ps[0]] if shared else ps)
+        return both(h), (both(ps) if ps is not None else None)
 
     def _forward_backward_full(self, st, T, pre_scan=None, pre_actor=None, prefetched=None, after_join=None):
         """Same update as ``_forward_backward`` for a batch of FULL-LENGTH episodes held in contiguous staging
@@ -455,7 +437,7 @@ class QMixLearner:
         Rows that the reference never evaluates (eval step T-1 and T, target step 0) cost ~2 % extra arithmetic,
         receive zero gradient and do not enter the loss: the result equals ``_forward_backward`` (tested).
 
-        ``prefetched`` = (gather_done, scan_done) events: ``st`` was gathered and ``pre_scan`` / ``pre_actor`` were
+        ``prefetched`` = ``Prefetched`` (gather_done, scan_done, tot_m): ``st`` was gathered and ``pre_scan`` / ``pre_actor`` were
         computed on the side stream during the PREVIOUS update (enable_graphs, pipelined group) — no fork here, the
         origin stream waits for the two events where it needs the data.  ``after_join()`` is called right behind the join:
         the place from which the next update's batch is prefetched."""
@@ -564,9 +546,9 @@ class QMixLearner:
             fork_at = torch.cuda.Event()
             if after_join is not None:
                 side_work = lambda: after_join(fork_at)
-            if prefetched[1] is not None:        # (None: a wait earlier on this stream already covers this update's prefetch)
-                origin.wait_event(prefetched[1])  # the prefetched scan (hence the gather before it on that stream) is there
-            tot_m = prefetched[2] if len(prefetched) > 2 else None
+            if prefetched.scan_done is not None:        # (None: a wait earlier on this stream already covers this update's prefetch)
+                origin.wait_event(prefetched.scan_done)  # the prefetched scan (hence the gather before it on that stream) is there
+            tot_m = prefetched.tot_m
             # both mixers, the loss's gradient and the eval mixer's backward as one launch (ops.pair_mixer_train_with_next_fused)
             mixer_train = tot_m is not None and options.on("MIXER_TRAIN") and J in (2, 3)
             # ... on a buffer that certifies static states (EpisodeReplayBuffer.state_static) with the mixer's weight-gradient
@@ -607,7 +589,7 @@ class QMixLearner:
                                        train_gy=train_gy)
         elif target_beside_head:
             origin = torch.cuda.current_stream(dev)
-            ts = self._target_stream
+            ts = self._update_stream()
             ts.wait_stream(origin)           # (fork) the previous update's Adam has written the Q-head this branch reads
             with torch.cuda.stream(ts), torch.no_grad():
                 # scan outputs, actor rows and the gathered batch were produced on this very stream: stream order
@@ -623,16 +605,14 @@ class QMixLearner:
                 # previous Adam), so it needs no wait for this stream and overlaps the eval head and the loss rather than
                 # the weight-gradient launch (0.1461 -> 0.1440 ms)
                 after_join(False)
-            origin.wait_event(prefetched[0])                                                    # the gathered batch is there
+            origin.wait_event(prefetched.gather_done)                                           # the gathered batch is there
             eval_q_tot = eval_forward()
             origin.wait_event(target_done)                                                      # join
             target_q_tot.record_stream(origin)
-            return self._finish_update(st, T, eval_q_tot, target_q_tot, tot_m=prefetched[2] if len(prefetched) > 2 else None)
+            return self._finish_update(st, T, eval_q_tot, target_q_tot, tot_m=prefetched.tot_m)
         elif two_streams:
             origin = torch.cuda.current_stream(dev)
-            if getattr(self, "_target_stream", None) is None:
-                self._target_stream = torch.cuda.Stream(device=dev)
-            ts = self._target_stream
+            ts = self._update_stream()
             if prefetched is None:
                 ts.wait_stream(origin)                                                          # fork
                 with torch.cuda.stream(ts), torch.no_grad():
@@ -640,7 +620,7 @@ class QMixLearner:
                     p_target = None if (shared or pre_actor is not None) else actor_all(macs[0].agent)
             else:
                 assert pre_scan is not None and pre_actor is not None
-                origin.wait_event(prefetched[0])                                                # the gathered batch is there
+                origin.wait_event(prefetched.gather_done)                                       # the gathered batch is there
                 bases, p_target = scan_chain(), None                                            # (views of pre_scan: no launch)
             if pre_actor is not None:      # [B, J, A] per controller, from the scan launch's prologue: [target, eval]
                 p_target, p_eval = (None if shared else pre_actor[0]), pre_actor[1]
@@ -655,7 +635,7 @@ class QMixLearner:
                 if prefetched is None:
                     origin.wait_stream(ts)                                                      # join
                 else:
-                    origin.wait_event(prefetched[1])                                            # join (the scan ended long ago)
+                    origin.wait_event(prefetched.scan_done)                                     # join (the scan ended long ago)
                 if after_join is not None:
                     after_join()
                 for t_ in list(bases) + ([p_target] if p_target is not None else []) + ([p_eval] if pre_actor is not None else []):
@@ -708,7 +688,7 @@ class QMixLearner:
                 # the side stream, captured behind the chain's launches and behind the next update's prefetch (it forks
                 # from the end of the mixer launch; the optimiser writes the gradient norm into row[3], the sums row[0:3])
                 origin = torch.cuda.current_stream(eval_q_tot.device)
-                ts = self._target_stream
+                ts = self._update_stream()
                 head_done = torch.cuda.Event()
                 head_done.record(origin)
                 row = self._last_stats4 = torch.empty(4, dtype=torch.float32, device=eval_q_tot.device)
@@ -728,7 +708,7 @@ class QMixLearner:
                 # — for the logged sums — on the side stream, ordered before the optimiser writes the gradient norm into
                 # the same row
                 origin = torch.cuda.current_stream(eval_q_tot.device)
-                ts = self._target_stream
+                ts = self._update_stream()
                 head_done = torch.cuda.Event()
                 if not sums_in_backward:
                     head_done.record(origin)
@@ -966,169 +946,11 @@ class QMixLearner:
         if not self._g_single:
             with hipgraph.capture(self._graph_b, pool=self._graph_a.pool()):
                 self._g_out_b = self._clip_and_step(sample_next=nxt)
-        # K consecutive updates as ONE graph (train_from_buffer_many): between two replayed graphs the stream pays a
-        # launch-to-launch hand-over (~20 us here) that an edge inside a graph does not.  Needs the device-side draw (every
-        # update's batch comes from the previous update's last launch) and a single process (no all-reduce in between).
+        # K consecutive updates as ONE graph (train_from_buffer_many; core/update_group.py): needs the device-side draw and
+        # a single process (no eager all-reduce in between)
         K = int(updates_per_graph if updates_per_graph is not None else options.get("UPDATES_PER_GRAPH"))
-        self._g_multi = None
-        self._g_prefetch_launch = False   # bookkeeping: the captured group's prefetches are single launches (ops.prefetch_batch)
-        self._g_prefetch_ahead = 1        # ... issued one update ahead, or in pairs two updates ahead (prefetch_plan)
-        self._g_prefetch_held = None
         if K > 1 and self._g_single and self._g_dev_sampler and fused and self._g_stats4 is not None:
-            gm, rows, single_norm = torch.cuda.CUDAGraph(), [], self._grad_norm
-            # Inside the group the updates are software-pipelined: everything of update k + 1 that depends on neither the
-            # weights nor update k's results — the draw of its episodes, the gather into the OTHER staging set, the scan
-            # launch (frozen body) — is issued on the side stream right behind update k's join and runs beside update k's
-            # serial tail; update k + 1 then starts at its taken-action Q-head and finds the scan done at its join
-            # (-17 us per pipelined update: the gather, its hand-over and the wait for the scan leave the chain).  Same
-            # launches on the same data in an order that respects every dependence: same results (tested bitwise).
-            pipelined = (self._g_scan_from_ring and self._g_actor_in_scan and options.get("UPDATE_STREAMS") != "1"
-                         and options.on("PIPELINED_GROUP"))
-            # The prefetch as ONE launch (ops.prefetch_batch: every workgroup evaluates the sampler's formula for the indices it
-            # needs at a counter offset baked into the launch, so the draw, the gather and the mask sum run BESIDE the scan
-            # instead of in front of it) — shared frozen body at hidden size 64; MACJD_PREFETCH_LAUNCH=0 and every other shape:
-            # the four launches one behind the other.
-            launch_agents = [self.mac.agent] if self._body_is_shared() else [self.target_mac.agent, self.mac.agent]
-            self._g_prefetch_launch = bool(pipelined and options.on("PREFETCH_LAUNCH") and "filled" in keys
-                                           and ops.prefetch_batch_supported(launch_agents, self._g_B, srcs))
-            # ... and TWO updates ahead (MACJD_PREFETCH_AHEAD, prefetch_plan): one launch prefetches the batches of a pair of
-            # updates and is issued two updates before the first of them, so no Q-head grid waits for its scan — the
-            # prefetch leaves the cycle that bounded the update.  "1": one launch per update, issued by
-            # the update before it.
-            plan = None
-            if self._g_prefetch_launch and options.get("PREFETCH_AHEAD") != "1":
-                plan, n_sets = prefetch_plan(K, 2)
-            self._g_prefetch_ahead = 2 if plan is not None else 1
-            stages = [stage] + ([{k: torch.zeros_like(v) for k, v in stage.items()} for _ in range(n_sets - 1 if plan else 1)]
-                                if pipelined else [None])
-            # (the captured launches write and read the second staging set through baked addresses: it has to live as long
-            # as the graph.  Until round 3 nothing held it once this function returned — the freed blocks stayed cached, so
-            # it went unnoticed until another capture's torch.cuda.empty_cache() unmapped them: a GPU memory fault in the
-            # first replay of the group at 12j/16r.)
-            self._g_stages = stages
-            origin_dev = self.device
-
-            unwritten = [0]   # draws of one-launch prefetches that no launch has added to the sampler's counter yet
-
-            def prefetch(dst, fork=True, draw=True):
-                """draw + gather + scan of a LATER update on the side stream"""
-                origin = torch.cuda.current_stream(origin_dev)
-                ts = self._target_stream
-                if isinstance(fork, torch.cuda.Event):
-                    ts.wait_event(fork)     # (fork recorded earlier on the origin stream)
-                elif fork:
-                    ts.wait_stream(origin)  # (fork off the origin stream) the previous users of idx / dst are done
-                shared = self._body_is_shared()
-                agents = [self.mac.agent] if shared else [self.target_mac.agent, self.mac.agent]
-                if self._g_prefetch_launch:
-                    with torch.cuda.stream(ts), torch.no_grad():
-                        h, ps, tot_m = ops.prefetch_batch(
-                            buffer.buffers["obs"], agents, self._g_B, self.n_agents, self._g_T + 1,
-                            (self._g_idx, self._g_n_stored, self._g_draws, self._sampler_seed()), srcs, [dst[k] for k in keys],
-                            buffer.buffers["filled"], self._g_T - 1, offset=unwritten[0], draw=draw)
-                        unwritten[0] += 1 if draw else 0   # (the launch only READS the counter, at this offset)
-                        ev = torch.cuda.Event()   # one launch: the gathered batch and the scan are there together
-                        ev.record(ts)
-                    return [h[0], h[0]], [ps[0], ps[0]], (ev, ev, tot_m)
-                with torch.cuda.stream(ts), torch.no_grad():
-                    if draw:
-                        ops.sample_episodes(self._g_idx, self._g_n_stored, self._g_draws, self._sampler_seed())
-                    ops.gather_rows(self._g_idx, srcs, [dst[k] for k in keys])
-                    tot_m = ops.td_mask_sum(dst["filled"], self._g_T - 1)     # the loss's only global sum the gradient needs
-                    ev_g = torch.cuda.Event()
-                    ev_g.record(ts)
-                    h, ps = ops.gru_sequence_from_obs(buffer.buffers["obs"], self._g_idx, agents, self._g_B, self.n_agents,
-                                                      self._g_T + 1, with_actor=True)
-                    ev_s = torch.cuda.Event()
-                    ev_s.record(ts)
-                return (([h[0], h[0]] if shared else h), ([ps[0], ps[0]] if shared else ps), (ev_g, ev_s, tot_m))
-
-            # two updates ahead: every batch of a launch has its own index row, scan output, actor rows and mask sum; the
-            # captured launches write and read them through baked addresses, so they are held like the staging sets
-            ready = {}        # update -> (h, P, (gather_done, scan_done, tot_m)) of its prefetched batch
-            issues = {l.issue_at: l for l in plan} if plan is not None else {}
-            idx_rows = (torch.zeros(len(stages), self._g_B, dtype=torch.int64, device=self.device) if plan is not None else None)
-            self._g_prefetch_held = [idx_rows]
-            paired = plan is not None and self._paired_heads_ok(stage, self._g_T)
-
-            def prefetch_many(launch, fork=True):
-                """draw + gather + scan of the later updates ``launch.updates`` as ONE launch on the side stream"""
-                origin = torch.cuda.current_stream(origin_dev)
-                ts = self._target_stream
-                if isinstance(fork, torch.cuda.Event):
-                    ts.wait_event(fork)
-                elif fork:
-                    ts.wait_stream(origin)
-                assert launch.offsets[0] == unwritten[0] and self._body_is_shared()
-                with torch.cuda.stream(ts), torch.no_grad():
-                    res = ops.prefetch_batches(
-                        buffer.buffers["obs"], [self.mac.agent], self._g_B, self.n_agents, self._g_T + 1,
-                        (self._g_n_stored, self._g_draws, self._sampler_seed()), srcs,
-                        [(off, True, [stages[s][k] for k in keys], idx_rows[s]) for off, s in zip(launch.offsets, launch.sets)],
-                        buffer.buffers["filled"], self._g_T - 1)
-                    unwritten[0] += len(launch.updates)   # (the launch only READS the counter, at these offsets)
-                    ev = torch.cuda.Event()
-                    ev.record(ts)
-                self._g_prefetch_held.append(res)
-                for i, (u, (h, p, tot_m)) in enumerate(zip(launch.updates, res)):
-                    # the first consumer waits for the launch; on the chain's stream that wait covers the later ones (the
-                    # paired update takes "no event"; the other forms wait where they always do, for an event long set)
-                    e = ev if (i == 0 or not paired) else None
-                    ready[u] = ([h, h], [p, p], (e, e, tot_m))
-
-            with hipgraph.capture(gm, pool=self._graph_a.pool()):
-                nxt_batch = None
-                for k_upd in range(K):
-                    last = k_upd == K - 1
-                    box = {}
-                    hook = (lambda fork=True: box.__setitem__("next", prefetch(stages[(k_upd + 1) % 2], fork))) if (pipelined and not last) else None
-                    if plan is not None:
-                        launch = issues.get(k_upd)
-                        hook = (lambda fork=True, launch=launch: prefetch_many(launch, fork)) if launch is not None else None
-                        nxt_batch = ready.pop(k_upd, None)
-                    if plan is not None and nxt_batch is not None:
-                        h_pre, p_pre, evs = nxt_batch
-                        self._forward_backward_full(stages[k_upd % len(stages)], self._g_T, pre_scan=h_pre, pre_actor=p_pre,
-                                                    prefetched=evs, after_join=hook)
-                    elif pipelined and nxt_batch is not None:
-                        h_pre, p_pre, evs = nxt_batch
-                        self._forward_backward_full(stages[k_upd % 2], self._g_T, pre_scan=h_pre, pre_actor=p_pre,
-                                                    prefetched=evs, after_join=hook)
-                    elif pipelined:
-                        pre = self._scan_from_ring_early()
-                        ops.gather_rows(self._g_idx, srcs, [stage[k] for k in keys])
-                        if self._paired_heads_ok(stage, self._g_T):
-                            # the group's first update in the paired form too: its scan (side stream) and its gather + mask
-                            # sum (this stream) run beside each other, then the same chain as every other update — and the
-                            # second update's prefetch forks as early as everyone's (first two updates of a group:
-                            # 169 + 134 -> 150 + 111 us)
-                            tot_m0 = ops.td_mask_sum(stage["filled"], self._g_T - 1)
-                            scan_done = torch.cuda.Event()
-                            scan_done.record(self._target_stream)
-                            self._forward_backward_full(stage, self._g_T, pre_scan=pre[0], pre_actor=pre[1],
-                                                        prefetched=(None, scan_done, tot_m0), after_join=hook)
-                        else:
-                            self._forward_backward_full(stage, self._g_T, pre_scan=pre[0], pre_actor=pre[1], after_join=hook)
-                    else:
-                        body_a()
-                    nxt_batch = box.get("next")
-                    rows.append(self._last_stats4)          # this update's (loss, mean Q_tot, mean target, grad norm)
-                    self._grad_norm = rows[-1][3]
-                    if self._g_graphed_ar:
-                        self._allreduce_grads(force=True)
-                    # the update's last launch draws the next batch — unless the prefetch behind the join has done so
-                    # (one-launch prefetches read the counter at offsets 0 .. K-2 without advancing it: the group's closing draw
-                    # is the one of offset K-1 and leaves the counter K further, as K draws one after the other do)
-                    if nxt_batch is not None or (plan is not None and not last):
-                        self._clip_and_step(sample_next=None)
-                    else:
-                        self._clip_and_step(sample_next=nxt + (unwritten[0],))
-                        unwritten[0] = 0
-                if pipelined:
-                    torch.cuda.current_stream(self.device).wait_stream(self._target_stream)   # every fork rejoins
-            self._grad_norm = single_norm
-            self._g_multi = (K, gm, rows)
-            self._g_pipelined = pipelined
+            self._bind_group(UpdateGroup(self, K, stage, keys, srcs, body_a, pool=self._graph_a.pool()))
         self._g_shared_body = self._body_is_shared()   # baked into the captured launches
         assert self._g_obs_static == (bool(getattr(buffer, "obs_static", False)) and options.on("LEARNER_STATIC_OBS"))
         # Prime the graphs: the FIRST launch of an instantiated graph pays one-off costs (its streams get their hardware
@@ -1151,6 +973,17 @@ class QMixLearner:
             self._g_draws.copy_(keep[0]); self._g_idx.copy_(keep[1]); self._g_n_stored.copy_(keep[2])
         self._graphs_ready = True
 
+    def _bind_group(self, g):
+        """The captured group of updates (``UpdateGroup``, or None) and the names under which tests, scripts and the bench
+        read it: plain references into the object, which owns what they name."""
+        self._g_group = g
+        self._g_multi = (g.K, g.graph, g.rows) if g else None
+        self._g_stages = g.stages if g else None
+        self._g_prefetch_held = (g.idx_rows, g.batches) if g else None   # the other baked addresses
+        self._g_pipelined = bool(g and g.pipelined)
+        self._g_prefetch_launch = bool(g and g.prefetch_launch)   # its prefetches are single launches ...
+        self._g_prefetch_ahead = g.prefetch_ahead if g else 1     # ... of one batch, or of two, two updates ahead
+
     def release_graphs(self):
         """Destroy the captured update graphs and everything that lives in their memory pool (staging tensors, static
         outputs, the side stream's events) — explicitly, with the device idle, the grouped graph and graph B (captured
@@ -1162,7 +995,7 @@ class QMixLearner:
             graphs.append(m[1])
         graphs += [getattr(self, "_graph_b", None), getattr(self, "_graph_a", None)]
         self._graphs_ready = False
-        self._g_multi = self._g_stages = self._g_prefetch_held = None
+        self._bind_group(None)
         self._graph_a = self._graph_b = None
         self._graph_body_a = None
         self._g_out_a = self._g_out_b = self._g_stats4 = self._last_stats4 = self._held_ln = self._norm_partials = None

@@ -1321,25 +1321,14 @@ def prefetch_batch_supported(agents, B: int, srcs) -> bool:
 def prefetch_batch(obs, agents, B: int, J: int, n_steps: int, sampler, srcs, dsts, filled, Tm1: int, offset: int = 0,
                    draw: bool = True, gather_blocks: int = 0):
     """``sample_episodes`` + ``gather_rows`` + ``td_mask_sum`` + ``gru_sequence_from_obs(with_actor=True)`` as ONE launch
-    (include/macjd_nets.h ``macjd_prefetch_io``), bit-identical to the four.  ``obs`` / ``filled``: the replay ring's
-    tensors (``filled`` [N, >= Tm1, 1] bool); ``sampler`` = (idx_out, n_stored, counter, seed); the draw is the one of
-    counter + ``offset`` and the counter is only READ — the caller's closing draw (``sample_episodes`` /
-    ``clip_adam_step(sample_next=(..., offset))``) advances it.  ``draw=False``: the indices already in idx_out.
-    Returns ([h_all [B, n_steps, J, H]], [P [B, J, A]], tot_m [1])."""
-    lib = _native.load()
-    if not prefetch_batch_supported(agents, B, srcs):
-        raise _native.NativeLibraryError("macjd_prefetch_batch: unsupported shape (one agent body, rnn_hidden_dim 64, B <= 1024)")
-    gio, outs, pouts, _keep = _gru_from_obs_io(obs, None, agents, B, J, n_steps, True)
-    assert sampler[0].numel() == B and filled.dtype == torch.bool and filled.device == obs.device and filled.shape[1] >= Tm1
-    io = _native.PrefetchIO()
-    io.gru, io.gather, io.sampler = gio, _gather_io(B, srcs, dsts), _sampler_io(*sampler[:4], offset)
-    io.mask.B, io.mask.Tm1 = int(B), int(Tm1)
-    io.mask.filled, io.mask.f_sb, io.mask.f_st = filled.data_ptr(), filled.stride(0), filled.stride(1)
-    tot_m = torch.empty(1, dtype=torch.float32, device=obs.device)
-    io.tot_m, io.no_draw, io.gather_blocks = tot_m.data_ptr(), 0 if draw else 1, int(gather_blocks)
-    with torch.cuda.device(obs.device):
-        _native.check(lib.macjd_prefetch_batch(ctypes.byref(io), _stream(obs)), "macjd_prefetch_batch")
-    return outs, pouts, tot_m
+    (include/macjd_nets.h ``macjd_prefetch_io``), bit-identical to the four: the one-batch call of ``prefetch_batches``.
+    ``obs`` / ``filled``: the replay ring's tensors (``filled`` [N, >= Tm1, 1] bool); ``sampler`` = (idx_out, n_stored,
+    counter, seed); the draw is the one of counter + ``offset`` and the counter is only READ — the caller's closing draw
+    (``sample_episodes`` / ``clip_adam_step(sample_next=(..., offset))``) advances it.  ``draw=False``: the indices already
+    in idx_out.  Returns ([h_all [B, n_steps, J, H]], [P [B, J, A]], tot_m [1])."""
+    (h, p, tot_m), = prefetch_batches(obs, agents, B, J, n_steps, sampler[1:4], srcs, [(offset, draw, dsts, sampler[0])],
+                                      filled, Tm1, gather_blocks=gather_blocks)
+    return [h], [p], tot_m
 
 
 PREFETCH_MAX_BATCHES = 4   # MACJD_PREFETCH_MAX_BATCHES (include/macjd_nets.h)

@@ -1,5 +1,6 @@
-"""The prefetch two updates ahead (``prefetch_plan`` in core/qmix.py, ``macjd_prefetch_batches`` in include/macjd_nets.h)
-without a GPU: the plan's coverage, lead and staging-set hazards, its switch, and the new entry points' header / exports."""
+"""The prefetch two updates ahead (``prefetch_plan`` in core/update_group.py, ``macjd_prefetch_batches`` in
+include/macjd_nets.h) without a GPU: the plan's coverage, lead and staging-set hazards, the schedule of every form of a
+captured group (``group_schedule``), its switch, and the new entry points' header / exports."""
 import ctypes
 import re
 import os
@@ -11,6 +12,8 @@ from _harness import REPO
 
 from macjd_amd import _native, options
 from macjd_amd.core.qmix import prefetch_plan
+from macjd_amd.core.update_group import GroupStep, group_schedule
+from test_prefetch_launch_cpu import _draw
 
 
 def _reads(u, n_sets):
@@ -62,6 +65,64 @@ def test_pair_plan_of_a_group_of_twenty():
     launches, _ = prefetch_plan(20, 2)
     assert [(l.issue_at, l.updates) for l in launches[:4]] == [(0, (1, 2)), (1, (3, 4)), (3, (5, 6)), (5, (7, 8))]
     assert launches[-1].updates == (19,) and launches[-1].issue_at == 17 and launches[-1].offsets == (18,)
+
+
+FORMS = {  # form -> (pipelined, one_launch, ahead of the schedule, ahead of the plan it must issue)
+    "unpipelined": (False, False, 1, None), "four launches": (True, False, 1, 1), "four launches, ahead ignored": (True, False, 2, 1),
+    "one launch, ahead 1": (True, True, 1, 1), "one launch, ahead 2": (True, True, 2, 2),
+}
+
+
+@pytest.mark.parametrize("K", [1, 2, 3, 4, 5, 20])
+@pytest.mark.parametrize("form", list(FORMS))
+def test_group_schedule_serves_every_update_once_and_leaves_the_counter_of_k_draws(K, form):
+    """``group_schedule`` walked the way the capture walks it, with the sampler's counter on the host: who prepares each
+    update's batch, into which set, which optimiser launches draw at which offset, and what the counter and the drawn
+    indices are afterwards — against K draws one behind the other."""
+    pipelined, one_launch, ahead, plan_ahead = FORMS[form]
+    steps, n_sets = group_schedule(K, pipelined, one_launch, ahead)
+    assert len(steps) == K and all(isinstance(s, GroupStep) for s in steps)
+    n, N, seed, c0 = 4, 33, 0x1234ABCD5678, 7
+    seq = [_draw(n, N, c0 + i, seed) for i in range(K)]        # K sequential draws: the batches of updates 1 .. K-1, then
+    counter, in_set, idx, drawn = c0, {}, None, []             # ... the batch the group leaves behind; counter c0 + K
+    issued = []
+    for u, s in enumerate(steps):
+        assert 0 <= s.reads < n_sets
+        if u == 0 or not pipelined:
+            assert s.prefetched is False                       # prepares its own batch (from the index row as it stands)
+        else:
+            assert s.prefetched is True
+            by = [l for l in issued if u in l.updates]
+            assert len(by) == 1 and by[0].issue_at < u         # exactly one earlier update issued it
+            assert by[0].sets[by[0].updates.index(u)] == s.reads and in_set.pop(s.reads) == u   # ... into the set it reads
+        if s.issues is not None:
+            l = s.issues
+            assert pipelined and l.issue_at == u
+            issued.append(l)
+            for v, off, st in zip(l.updates, l.offsets, l.sets):
+                assert st not in in_set and st != s.reads      # no set is overwritten before its reader, or under it
+                in_set[st] = v
+                if one_launch:                                 # reads the counter at its offset
+                    drawn.append(_draw(n, N, counter + off, seed))
+                else:                                          # the four launches: a draw of offset 0 that advances it
+                    drawn.append(_draw(n, N, counter, seed))
+                    counter += 1
+        if s.draw is not None:                                 # the optimiser launch's draw: counter + offset, then + 1
+            idx = _draw(n, N, counter + s.draw, seed)
+            drawn.append(idx)
+            counter += s.draw + 1
+        if pipelined:
+            assert (s.draw is not None) == (u == K - 1)        # only the last step draws ...
+            if u == K - 1:
+                assert s.draw == (K - 1 if one_launch else 0)  # ... at the closing offset of the form
+        else:
+            assert s.draw == 0 and s.issues is None and s.reads == 0
+    assert not in_set                                          # every prefetched batch was consumed
+    assert counter == c0 + K and drawn == seq and idx == seq[-1]
+    if pipelined:
+        assert issued == prefetch_plan(K, plan_ahead)[0] and n_sets == prefetch_plan(K, plan_ahead)[1]
+    else:
+        assert issued == [] and n_sets == 1
 
 
 def test_switch_is_declared_and_documented():

@@ -218,3 +218,45 @@ def test_group_two_updates_ahead_equals_one_update_ahead(monkeypatch, K, Bsz, li
     la.release_graphs()
     lb.release_graphs()
     assert la._g_prefetch_held is None and la._g_stages is None
+
+
+def test_recapture_that_changes_the_number_of_staging_sets_equals_one_capture(monkeypatch):
+    """A group captured with MACJD_PREFETCH_AHEAD=1 (two staging sets and index rows), released, and captured again with
+    the default (four), against a learner captured once with the default: two replayed groups of K = 5 after the cache was
+    emptied — weights, Adam moments and step, every update's statistics, the drawn batch and the counter bit-equal.  What
+    the first group held is gone by then: a launch of the second capture that baked an address of it would read freed
+    memory."""
+    from macjd_amd import options
+    K, Bsz, limit, E = 5, 4, 8, 16
+    assert options._DEFAULTS["PREFETCH_AHEAD"] == "2"
+    la, ba = _learner(monkeypatch, "1", K, Bsz, limit, E)
+    assert la._g_prefetch_ahead == 1 and len(la._g_stages) == 2 and la._g_prefetch_held[0].shape[0] == 2
+    la.release_graphs()
+    assert la._g_multi is None and la._g_stages is None and la._g_prefetch_held is None
+    monkeypatch.delenv("MACJD_PREFETCH_AHEAD")
+    options.reload()
+    la.enable_graphs(ba, Bsz, updates_per_graph=K)
+    gc.collect()
+    torch.cuda.empty_cache()
+    lb, bb = _learner(monkeypatch, "2", K, Bsz, limit, E)
+    for l in (la, lb):
+        assert l._g_pipelined and l._g_prefetch_launch is True and l._g_prefetch_ahead == 2 and l._g_multi[0] == K
+        assert len(l._g_stages) == 4 and l._g_prefetch_held[0].shape[0] == 4
+    for k in ba.buffers:
+        assert torch.equal(ba.buffers[k], bb.buffers[k]), k
+    seen = set()
+    for group in (1, 2):
+        sa, sb = torch.zeros(K, 4, device=DEV), torch.zeros(K, 4, device=DEV)
+        la.train_from_buffer_many(K, stats_out=sa)
+        lb.train_from_buffer_many(K, stats_out=sb)
+        torch.cuda.synchronize()
+        assert la.train_step == lb.train_step == group * K
+        assert torch.equal(sa, sb) and bool(torch.isfinite(sa).all())
+        for i, (pa, pb) in enumerate(zip(la.params, lb.params)):
+            assert torch.equal(pa, pb), i
+        for name in ("_flat_exp_avg", "_flat_exp_avg_sq", "_adam_step", "_g_idx", "_g_draws"):
+            assert torch.equal(getattr(la, name), getattr(lb, name)), name
+        seen |= {float(x) for x in sa[:, 0]}
+    assert len(seen) == 2 * K                       # every update saw its own batch and weights
+    la.release_graphs()
+    lb.release_graphs()
