@@ -28,9 +28,10 @@
 extern "C" {
 #endif
 
-#define MACJD_ABI_VERSION 9
+#define MACJD_ABI_VERSION 10
 #define MACJD_PE_ROWS(R, J) (6 * (R) + 3 * (J) + (J) * (R))
 #define MACJD_PE_SCAN_ROWS(R, J) (10 * (R) + (J) * (R))
+#define MACJD_PE_SCAN_PATTERN_ROWS(R, L) ((R) + 4 * ((L) + 2) * (R))
 
 #define MACJD_OK          0
 #define MACJD_EINVAL     -1  /* bad argument (shape, NULL, stride)            */
@@ -240,6 +241,25 @@ typedef struct macjd_scan_pe_io {
     int64_t stride;   /* >= n_envs when pe_tile == 0 */
 } macjd_scan_pe_io;
 
+/*
+ * Per-env stepped antenna pattern of a scanning step on per-env scenario tables (macjd_env_step_scan_pe_pattern): every env
+ * has its own macjd_scan_pattern_desc quantities; L = n_levels is shared by the batch.  `tables` is a float64 device array of
+ * MACJD_PE_SCAN_PATTERN_ROWS(R, L) rows in the order
+ *   inv_width[R] | GaPs_lvl[(L+2)*R] | snr_no_lvl[(L+2)*R] | pd_no_lvl[(L+2)*R] | gr_lvl[(L+2)*R]
+ * each level table level-major, level k of radar r at row k * R + r of its block: level 0 holds the env's main-lobe values
+ * (the bits of its pe_tables GaPs / pd_no / gr rows and of macjd_scan_pe_io's snr_no row), levels 1..L the pattern's
+ * (macjd_scan_pattern_desc), level L + 1 its side-lobe values (the bits of macjd_scan_pe_io's _side rows) — so the device
+ * picks an object's level with one address-selected load per table.  Laid out like the step's own pe_tables: plain
+ * (pe_tile == 0), row t of env e at tables[t * stride + e]; tiled (pe_tile > 0), at
+ * tables[((e / pe_tile) * MACJD_PE_SCAN_PATTERN_ROWS + t) * pe_tile + e % pe_tile], the last tile padded, stride ignored.
+ */
+typedef struct macjd_scan_pe_pattern_io {
+    const double* tables;
+    int64_t stride;     /* >= n_envs when pe_tile == 0 */
+    int32_t n_levels;   /* L, 1..MACJD_MAX_PATTERN_LEVELS */
+    int32_t reserved;
+} macjd_scan_pe_pattern_io;
+
 /* library / device */
 int         macjd_abi_version(void);
 const char* macjd_last_error(void);
@@ -295,6 +315,15 @@ int macjd_env_step_scan_pe(const macjd_scenario* s, const macjd_step_io* io, con
 /* macjd_env_reset_scan with az0 from each env's column: theta_a[e,r] = az0_e[r], state columns = (float)az0_e[r] */
 int macjd_env_reset_scan_pe(const macjd_scenario* s, int64_t n_envs, const macjd_scan_io* scan, const macjd_scan_pe_io* scan_pe,
                             int32_t pe_tile, const uint8_t* mask, void* hip_stream);
+
+/* macjd_env_step_scan_pe under a stepped antenna pattern whose level tables differ per env: needs io->pe_tables and a
+   scanning handle; the handle supplies only R, J, episode_limit, the r_p bounds and the Pd constants — every level value
+   comes from the env's column of `pattern`, the handle's own level tables are never read (a handle that has pattern levels
+   is accepted only if its L equals pattern->n_levels).  Results are bit-identical to a single-scenario macjd_env_step_scan
+   of the same env with macjd_scenario_set_scan_pattern, in its all-float64 form (MACJD_ENV_PD32=0).  The reset is
+   macjd_env_reset_scan_pe on a handle without pattern levels: az0 does not depend on the pattern. */
+int macjd_env_step_scan_pe_pattern(const macjd_scenario* s, const macjd_step_io* io, const macjd_scan_io* scan,
+                                   const macjd_scan_pe_io* scan_pe, const macjd_scan_pe_pattern_io* pattern, void* hip_stream);
 
 /* T consecutive steps of all E environments in ONE launch, given the actions of all T steps (time-major: step t of
    env e at offset t * t_stride + e * se + k * sx of T / P32; outputs reward / terminated / r_dpj likewise at

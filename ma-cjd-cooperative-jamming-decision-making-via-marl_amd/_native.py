@@ -14,7 +14,7 @@ LIB_NAME = "libmacjd_hip.so"
 # MACJD_LIB points at another build of the same sources (kernel A/B runs); the default is the in-tree library
 LIB_PATH = os.environ.get("MACJD_LIB") or os.path.join(_PKG_DIR, LIB_NAME)
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 STEP_ARITH_F64 = 1
 STEP_LANE_KERNEL = 2
 STEP_SLOT_KERNEL = 4
@@ -31,7 +31,7 @@ EXPORTS = [
     "macjd_qhead_double_q_supported", "macjd_qhead_double_q", "macjd_qhead_taken_supported", "macjd_qhead_taken",
     "macjd_qheads_pair", "macjd_mixer_fused_forward_pair", "macjd_mixer_fused_train", "macjd_mixer_fused_train_static",
     "macjd_scenario_set_scan", "macjd_env_step_scan", "macjd_env_reset_scan",
-    "macjd_env_step_scan_pe", "macjd_env_reset_scan_pe",
+    "macjd_env_step_scan_pe", "macjd_env_reset_scan_pe", "macjd_env_step_scan_pe_pattern",
     "macjd_agent_env_episode_scan_supported", "macjd_agent_env_episode_scan",
     "macjd_scenario_set_scan_pattern",
     "macjd_gru_sequence_backward_supported", "macjd_gru_sequence_backward",
@@ -100,6 +100,12 @@ class ScanIO(ctypes.Structure):
 class ScanPeIO(ctypes.Structure):
     """ctypes mirror of ``macjd_scan_pe_io`` (include/macjd.h): the per-env scan SoA, MACJD_PE_SCAN_ROWS(R, J) rows."""
     _fields_ = [("tables", ctypes.c_void_p), ("stride", ctypes.c_int64)]
+
+
+class ScanPePatternIO(ctypes.Structure):
+    """ctypes mirror of ``macjd_scan_pe_pattern_io`` (include/macjd.h): the per-env pattern SoA,
+    MACJD_PE_SCAN_PATTERN_ROWS(R, L) rows."""
+    _fields_ = [("tables", ctypes.c_void_p), ("stride", ctypes.c_int64), ("n_levels", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 class QheadIO(ctypes.Structure):
@@ -447,6 +453,9 @@ def load() -> ctypes.CDLL:
     lib.macjd_env_step_scan_pe.restype = ctypes.c_int
     lib.macjd_env_step_scan_pe.argtypes = [ctypes.c_void_p, ctypes.POINTER(StepIO), ctypes.POINTER(ScanIO),
                                            ctypes.POINTER(ScanPeIO), ctypes.c_void_p]
+    lib.macjd_env_step_scan_pe_pattern.restype = ctypes.c_int
+    lib.macjd_env_step_scan_pe_pattern.argtypes = [ctypes.c_void_p, ctypes.POINTER(StepIO), ctypes.POINTER(ScanIO),
+                                                   ctypes.POINTER(ScanPeIO), ctypes.POINTER(ScanPePatternIO), ctypes.c_void_p]
     lib.macjd_env_reset_scan_pe.restype = ctypes.c_int
     lib.macjd_env_reset_scan_pe.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ScanIO), ctypes.POINTER(ScanPeIO),
                                             ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
@@ -578,7 +587,10 @@ def check(rc: int, what: str) -> None:
 class ScenarioHandle:
     """Owns a ``macjd_scenario*`` (device copy of the scenario tables)."""
 
-    def __init__(self, scenario):
+    def __init__(self, scenario, scan_pattern: bool = True):
+        """``scan_pattern=False`` leaves a scenario's stepped antenna pattern off the handle: for per-env scenario batches,
+        which bring every env's level tables themselves (macjd_env_step_scan_pe_pattern) and reset through
+        macjd_env_reset_scan_pe, an entry point for handles without pattern levels."""
         lib = load()
         desc, keep = scenario.c_desc()
         h = ctypes.c_void_p()
@@ -590,7 +602,7 @@ class ScenarioHandle:
             sdesc, skeep = scenario.c_scan_desc()
             check(lib.macjd_scenario_set_scan(h, ctypes.byref(sdesc)), "macjd_scenario_set_scan")
             del skeep
-            if getattr(scenario, "scan_pattern_levels", 0):
+            if scan_pattern and getattr(scenario, "scan_pattern_levels", 0):
                 pdesc, pkeep = scenario.c_scan_pattern_desc()
                 check(lib.macjd_scenario_set_scan_pattern(h, ctypes.byref(pdesc)), "macjd_scenario_set_scan_pattern")
                 del pkeep

@@ -825,13 +825,78 @@ static int launch_step_scan_pe(const macjd_scenario* s, const macjd_step_io* io,
     return launch_status("macjd_env_step_scan_pe");
 }
 
-static int validate_scan_pe(const macjd_scenario* s, const macjd_scan_pe_io* sp, int64_t n_envs, int32_t pe_tile, const char* what) {
+// SCAN launches under a stepped antenna pattern on per-env tables (include/macjd.h, macjd_env_step_scan_pe_pattern): the
+// production variant or the general one at the sizes scan_pe_compiled covers, the generic-size kernel for the others
+static int launch_step_scan_pe_pattern(const macjd_scenario* s, const macjd_step_io* io, const macjd_scan_io* sc,
+                                       const macjd_scan_pe_io* sp, const macjd_scan_pe_pattern_io* pp, hipStream_t stream) {
+    const int64_t E = io->n_envs;
+    const int J = s->host.J, R = s->host.R;
+    const LaneGrid lg = lane_grid(E);
+    const dim3 gf((unsigned)lg.blocks), g(lg.strided), b(lg.block);
+    const bool fast = production_io(io, J, R, lg.blocks, 0, 0) && scan_spans_ok(sc, E, R);
+    macjd::ScanPePatStepIO<macjd::FastStepIO> f{};
+    macjd::ScanPePatStepIO<macjd_step_io> w{};
+    static_cast<macjd_step_io&>(w) = *io;
+    fill_scan(w, sc);
+    w.sp_tables = sp->tables; w.sp_stride = sp->stride;
+    w.pp_tables = pp->tables; w.pp_stride = pp->stride; w.pat_levels = pp->n_levels;
+    if (fast) {
+        fill_fast(f, io, 0, 0);
+        f.pe_tables = io->pe_tables; f.pe_flags = io->pe_flags; f.pe_stride = io->pe_stride; f.pe_tile = io->pe_tile;
+        fill_scan(f, sc);
+        f.sp_tables = sp->tables; f.sp_stride = sp->stride;
+        f.pp_tables = pp->tables; f.pp_stride = pp->stride; f.pat_levels = pp->n_levels;
+    }
+    // launch_lanes<JT, RT, PE = true, FAST, REG = false, PD32 = false, SCAN = true, PAT = true>
+    with_compiled_size(J, R, [&](auto jt, auto rt) -> int {
+        constexpr int JT = decltype(jt)::value, RT = decltype(rt)::value;
+        if constexpr (!scan_pe_compiled(JT)) macjd::launch_scan_pe_pattern_generic(g, b, stream, s->dev, w);
+        else if (fast) launch_lanes<JT, RT, true, true, false, false, true, true>(gf, b, stream, s, f);
+        else launch_lanes<JT, RT, true, false, false, false, true, true>(g, b, stream, s, w);
+        return MACJD_OK;
+    });
+    return launch_status("macjd_env_step_scan_pe_pattern");
+}
+
+// `pattern_ok`: the caller brings the pattern's levels per env (macjd_env_step_scan_pe_pattern); the handle's are not read
+static int validate_scan_pe(const macjd_scenario* s, const macjd_scan_pe_io* sp, int64_t n_envs, int32_t pe_tile, const char* what,
+                            bool pattern_ok = false) {
     if (!sp || !sp->tables) return set_err(MACJD_EINVAL, "%s: NULL per-env scan tables", what);
     if (pe_tile < 0 || (pe_tile == 0 && sp->stride < n_envs))
         return set_err(MACJD_EINVAL, "%s: per-env scan tables need stride >= n_envs (or pe_tile > 0)", what);
-    if (s->host.pat_levels > 0)
+    if (s->host.pat_levels > 0 && !pattern_ok)
         return set_err(MACJD_EUNSUPPORTED, "%s: a stepped antenna pattern is not supported with per-env scan tables", what);
     return MACJD_OK;
+}
+
+static int validate_scan_pe_pattern(const macjd_scenario* s, const macjd_scan_pe_pattern_io* pp, int64_t n_envs, int32_t pe_tile,
+                                    const char* what) {
+    if (!pp || !pp->tables) return set_err(MACJD_EINVAL, "%s: NULL per-env pattern tables", what);
+    if (pe_tile < 0 || (pe_tile == 0 && pp->stride < n_envs))
+        return set_err(MACJD_EINVAL, "%s: per-env pattern tables need stride >= n_envs (or pe_tile > 0)", what);
+    if (pp->n_levels < 1 || pp->n_levels > MACJD_MAX_PATTERN_LEVELS)
+        return set_err(MACJD_EINVAL, "%s: n_levels outside 1..MACJD_MAX_PATTERN_LEVELS", what);
+    if (s->host.pat_levels > 0 && s->host.pat_levels != pp->n_levels)
+        return set_err(MACJD_EINVAL, "%s: n_levels differs from the pattern levels of the scenario handle", what);
+    return MACJD_OK;
+}
+
+int macjd_env_step_scan_pe_pattern(const macjd_scenario* s, const macjd_step_io* io, const macjd_scan_io* scan,
+                                   const macjd_scan_pe_io* scan_pe, const macjd_scan_pe_pattern_io* pattern, void* hip_stream) {
+    const char* me = "macjd_env_step_scan_pe_pattern";
+    int rc = validate_io(s, io);
+    if (rc != MACJD_OK) return rc;
+    rc = validate_scan(s, scan, me);
+    if (rc != MACJD_OK) return rc;
+    if (!io->pe_tables) return set_err(MACJD_EINVAL, "%s: needs per-env scenario tables (io->pe_tables); macjd_env_step_scan takes the handle's", me);
+    rc = validate_scan_pe(s, scan_pe, io->n_envs, io->pe_tile, me, true);
+    if (rc != MACJD_OK) return rc;
+    rc = validate_scan_pe_pattern(s, pattern, io->n_envs, io->pe_tile, me);
+    if (rc != MACJD_OK) return rc;
+    if (io->flags & MACJD_STEP_SLOT_KERNEL)
+        return set_err(MACJD_EUNSUPPORTED, "%s: the (env x slot) kernel has no per-env pattern variant (one lane per env only)", me);
+    if (io->n_envs == 0) return MACJD_OK;
+    return launch_step_scan_pe_pattern(s, io, scan, scan_pe, pattern, (hipStream_t)hip_stream);
 }
 
 int macjd_env_step_scan_pe(const macjd_scenario* s, const macjd_step_io* io, const macjd_scan_io* scan, const macjd_scan_pe_io* scan_pe,

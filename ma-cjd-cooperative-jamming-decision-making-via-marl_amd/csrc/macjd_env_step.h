@@ -109,6 +109,14 @@ struct ScanPeStepIO : ScanStepIO<Base> {
     const double* sp_tables;
     int64_t sp_stride;
 };
+// ... under a stepped antenna pattern: plus the per-env pattern SoA (include/macjd.h, macjd_scan_pe_pattern_io), laid out
+// like the two above.  A separate type again: the pattern-free per-env instantiations keep their argument block and code.
+template <class Base>
+struct ScanPePatStepIO : ScanPeStepIO<Base> {
+    const double* pp_tables;
+    int64_t pp_stride;
+    int32_t pat_levels, pp_reserved;
+};
 
 // Per-lane pattern state of an env-step: the number of levels and the target's level at each radar, four bits per radar
 // in 64-bit words (word r >> 4; shifts only, so the per-lane index of the PD32 re-evaluation loop — compiled sizes,
@@ -154,15 +162,25 @@ struct PatLanes<true, NR> {
 // PAT = SCAN under a stepped antenna pattern (include/macjd.h, macjd_scan_pattern_desc; the same ScanStepIO<...> block):
 // the two-way selects become a level 0..L + 1 per object (beam_level) that indexes the [L + 2, R] level tables staged in
 // LDS; the target's R levels of an env are packed four bits each into 64-bit words (shifts by compile-time amounts, never
-// a register array indexed per lane).  (PAT was first switched by the type of the argument block, so that the kernel
+// a register array indexed per lane).
+// PAT && PE (IO = ScanPePatStepIO<...>): inv_width and the four level tables come from this env's column of the per-env
+// pattern SoA (MACJD_PE_SCAN_PATTERN_ROWS rows: inv_width[R] | GaPs_lvl | snr_no_lvl | pd_no_lvl | gr_lvl, each [(L + 2) R]
+// level-major with level 0 = the env's main-lobe values and level L + 1 its side-lobe ones), L from the argument block; the
+// handle's level tables are never read and nothing is staged in LDS.  The level tables are NOT requested up front (32 R
+// rows at L = 6): once an object's level is known, the one selected row per (table, radar) is loaded by address,
+// as the pattern-free per-env kernel loads its snr_no row.  beam_level, arithmetic, order, RNG slots, beam advance and
+// stores are those of the shared-table PAT kernel in its general all-float64 form: bit-identical results.
+// (PAT was first switched by the type of the argument block, so that the kernel
 // kept its template parameter list; the parameter changes only the kernels' names, profiles/r10_env_isa_check.txt.)
 template <int JT, int RT, bool PE, bool FAST, class IO, bool REG = false, bool PD32 = false, bool SCAN = false, bool PAT = false>
 __global__ void __launch_bounds__(256) env_step_kernel(const DevTables* __restrict__ tb, const IO io) {
     static_assert(!REG || (FAST && !PE && JT && RT), "REG: production variant on shared tables, compiled sizes");
     static_assert(!PD32 || REG, "PD32: float32 detection-probability filter of the regular production variant");
     static_assert(!PAT || SCAN, "PAT: stepped antenna pattern of the scanning beams");
-    static_assert(!PAT || !PE, "PAT: shared scenario tables only");
     constexpr bool SPE = SCAN && PE;    // scanning beams on per-env tables
+    constexpr bool SPP = PAT && PE;     // ... under a stepped pattern: level tables from the env's column
+    constexpr bool PSH = PAT && !PE;    // the pattern's level tables of the handle (LDS copies)
+    static_assert(!SPP || !FAST || (JT && RT), "PAT on per-env tables: production variant at compiled sizes only");
     constexpr bool SSH = SCAN && !PE;   // ... on the shared tables (LDS copies of the gathered ones)
     constexpr int NJ = JT ? JT : MAXJ;
     constexpr int NR = RT ? RT : MAXR;
@@ -190,9 +208,9 @@ __global__ void __launch_bounds__(256) env_step_kernel(const DevTables* __restri
     __shared__ double s_bj[SSH ? NJ * NR : 1];
     __shared__ uint8_t s_full[SSH ? NR : 1];
     // PAT: level tables [L + 2, R] (row 0 main, 1..L the pattern's levels, L + 1 side lobe), indexed by the per-lane level
-    __shared__ double s_lgr[PAT ? MAXLV * NR : 1], s_lGaPs[PAT ? MAXLV * NR : 1], s_lpdno[PAT ? MAXLV * NR : 1];
-    __shared__ double s_lsnrno[PAT ? MAXLV * NR : 1], s_invw[PAT ? NR : 1];
-    if constexpr (PAT) {
+    __shared__ double s_lgr[PSH ? MAXLV * NR : 1], s_lGaPs[PSH ? MAXLV * NR : 1], s_lpdno[PSH ? MAXLV * NR : 1];
+    __shared__ double s_lsnrno[PSH ? MAXLV * NR : 1], s_invw[PSH ? NR : 1];
+    if constexpr (PSH) {
         const int pat_L = tb->pat_levels;
         for (int i = threadIdx.x; i < (pat_L + 2) * R; i += blockDim.x) {
             s_lgr[i] = tb->lv_gr[i];
@@ -330,6 +348,19 @@ __global__ void __launch_bounds__(256) env_step_kernel(const DevTables* __restri
         double sv_half[SHOIST ? NR : 1], sv_sweep[SHOIST ? NR : 1], sv_swm[SHOIST ? NR : 1], sv_bt[SHOIST ? NR : 1];
         double sv_GaPs_side[SHOIST ? NR : 1], sv_pdno_side[SHOIST ? NR : 1], sv_snrno[SHOIST ? NR : 1];
         double gs_half[SHOIST ? NJ : 1], gs_sweep[SHOIST ? NJ : 1], gs_grs[SHOIST ? NJ : 1], gs_bj[SHOIST ? NJ : 1];
+        // PAT on per-env tables: this env's column of the pattern SoA — inv_width requested with the rows above (per radar,
+        // and gathered by a jammer's chosen radar); of the level tables only the rows an object's level selects, later
+        const double* __restrict__ pp = nullptr;
+        int64_t pps = 0, pp_lv = 0;   // pp_lv = (L + 2) R: rows of one level table
+        if constexpr (SPP) {
+            pps = io.pe_tile > 0 ? (int64_t)io.pe_tile : io.pp_stride;
+            pp_lv = (int64_t)(io.pat_levels + 2) * R;
+            pp = io.pp_tables + pe_tile_idx * (R + 4 * pp_lv) * pps + pe_col;
+        }
+        constexpr bool PHOIST = SPP && HOIST;
+        enum { PP_GAPS = 0, PP_SNR_NO, PP_PD_NO, PP_GR };   // level table k at rows R + k (L + 2) R
+        double sv_invw[PHOIST ? NR : 1], gs_invw[PHOIST ? NJ : 1];
+        double lv_GaPs[PHOIST ? NR : 1], lv_pdno[PHOIST ? NR : 1], lv_snrno[PHOIST ? NR : 1];
         if constexpr (SHOIST) {
 #pragma unroll
             for (int r = 0; r < NR; ++r) {
@@ -337,8 +368,12 @@ __global__ void __launch_bounds__(256) env_step_kernel(const DevTables* __restri
                 sv_sweep[r] = sp[(int64_t)(SP_SWEEP * R + r) * sps];
                 sv_swm[r] = sp[(int64_t)(SP_SWM * R + r) * sps];
                 sv_bt[r] = sp[(int64_t)(SP_BT * R + r) * sps];
-                sv_GaPs_side[r] = sp[(int64_t)(SP_GAPS_SIDE * R + r) * sps];
-                sv_pdno_side[r] = sp[(int64_t)(SP_PD_NO_SIDE * R + r) * sps];
+                if constexpr (PHOIST) {
+                    sv_invw[r] = pp[(int64_t)r * pps];
+                } else {
+                    sv_GaPs_side[r] = sp[(int64_t)(SP_GAPS_SIDE * R + r) * sps];
+                    sv_pdno_side[r] = sp[(int64_t)(SP_PD_NO_SIDE * R + r) * sps];
+                }
             }
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
@@ -346,10 +381,13 @@ __global__ void __launch_bounds__(256) env_step_kernel(const DevTables* __restri
                 const int tj = ((Tj >= 1) && (Tj <= 2 * R)) ? ((Tj + 1) / 2 - 1) : 0;
                 gs_half[j] = sp[(int64_t)(SP_HALF * R + tj) * sps];
                 gs_sweep[j] = sp[(int64_t)(SP_SWEEP * R + tj) * sps];
-                gs_grs[j] = sp[(int64_t)(SP_GR_SIDE * R + tj) * sps];
+                if constexpr (PHOIST) gs_invw[j] = pp[(int64_t)tj * pps];
+                else gs_grs[j] = sp[(int64_t)(SP_GR_SIDE * R + tj) * sps];
                 gs_bj[j] = sp[(int64_t)(SP_BJ * R + j * R + tj) * sps];
             }
         }
+        // row of level k of radar r in level table `tab` of this env's pattern column
+        auto pp_row = [&](int tab, int k, int r) -> double { return pp[((int64_t)R + tab * pp_lv + (int64_t)(k * R + r)) * pps]; };
         // scan tables of radar r (static index): the env's column or the handle's tables
         auto c_half = [&](int r) -> double {
             if constexpr (SHOIST) return sv_half[r]; else if constexpr (SPE) return sp[(int64_t)(SP_HALF * R + r) * sps]; else return tb->half[r];
@@ -395,7 +433,7 @@ __global__ void __launch_bounds__(256) env_step_kernel(const DevTables* __restri
         uint32_t s_bits = 0, in_t = 0;   // bit r: radar r was TRACKing / sees the target in its main lobe
         PatLanes<PAT, NR> pl;
         if constexpr (PAT) {
-            pl.L = tb->pat_levels;
+            if constexpr (SPP) pl.L = io.pat_levels; else pl.L = tb->pat_levels;
 #pragma unroll
             for (int i = 0; i < (NR + 15) / 16; ++i) pl.w[i] = 0;
         }
@@ -408,7 +446,17 @@ MACJD_ENV_UNROLL_SIZED(NR)
                 if (PRE) az[PRE ? r : 0] = a;
                 s_bits |= s ? (1u << r) : 0u;
                 const double lim = (s ? 0.0 : c_sweep(r)) + c_h2(r);
-                if constexpr (PAT) {
+                if constexpr (SPP) {
+                    const double iw = PHOIST ? sv_invw[PHOIST ? r : 0] : pp[(int64_t)r * pps];
+                    const int k = beam_level(c_bt(r), a, c_half(r), lim, c_full(r), iw, pl.L);
+                    pl.set(r, k);
+                    in_t |= (k == 0) ? (1u << r) : 0u;
+                    if constexpr (PHOIST) {   // the level's rows, by address (generic sizes load them where they are used)
+                        lv_GaPs[r] = pp_row(PP_GAPS, k, r);
+                        lv_pdno[r] = pp_row(PP_PD_NO, k, r);
+                        if (io.snr_no) lv_snrno[r] = pp_row(PP_SNR_NO, k, r);
+                    }
+                } else if constexpr (PAT) {
                     const int k = beam_level(tb->bt[r], a, tb->half[r], lim, tb->full[r] != 0, tb->pat_inv_width[r], pl.L);
                     pl.set(r, k);
                     in_t |= (k == 0) ? (1u << r) : 0u;
@@ -429,10 +477,16 @@ MACJD_ENV_UNROLL_SIZED(NR)
                 if constexpr (SPE) {   // the chosen radar's rows of this env's column (compiled sizes: requested up front)
                     const double half_t = SHOIST ? gs_half[SHOIST ? j : 0] : sp[(int64_t)(SP_HALF * R + t) * sps];
                     const double sweep_t = SHOIST ? gs_sweep[SHOIST ? j : 0] : sp[(int64_t)(SP_SWEEP * R + t) * sps];
-                    const double grs_t = SHOIST ? gs_grs[SHOIST ? j : 0] : sp[(int64_t)(SP_GR_SIDE * R + t) * sps];
+                    // (PAT reads no side-lobe row: its level L + 1 holds it.  The load keeps its place among the others:
+                    // moved behind them, the pattern-free generic-size kernel compiles to other code)
+                    const double grs_t = SPP ? 0.0 : SHOIST ? gs_grs[SHOIST ? j : 0] : sp[(int64_t)(SP_GR_SIDE * R + t) * sps];
                     const double bj_t = SHOIST ? gs_bj[SHOIST ? j : 0] : sp[(int64_t)(SP_BJ * R + j * R + t) * sps];
                     const double h2_t = 2.0 * half_t;
                     const double lim_t = (((s_bits >> t) & 1u) ? 0.0 : sweep_t) + h2_t;
+                    if constexpr (SPP) {   // the jammer's level at its chosen radar selects the gr row, loaded here
+                        const double iw_t = PHOIST ? gs_invw[PHOIST ? j : 0] : pp[(int64_t)t * pps];
+                        return pp_row(PP_GR, beam_level(bj_t, a_t, half_t, lim_t, sweep_t + h2_t >= 360.0, iw_t, pl.L), t);
+                    }
                     return in_main_lobe(bj_t, a_t, half_t, lim_t, sweep_t + h2_t >= 360.0) ? g_gr(j, t) : grs_t;
                 }
                 const double lim = (((s_bits >> t) & 1u) ? 0.0 : s_sweep[t]) + s_h2[t];
@@ -445,14 +499,16 @@ MACJD_ENV_UNROLL_SIZED(NR)
         };
         // target-path tables of radar r: main or side lobe (SCAN)
         auto r_GaPs = [&](int r) -> double {
-            if constexpr (PAT) return s_lGaPs[pl.lv(r) * R + r];
+            if constexpr (SPP) return PHOIST ? lv_GaPs[PHOIST ? r : 0] : pp_row(PP_GAPS, pl.lv(r), r);
+            else if constexpr (PAT) return s_lGaPs[pl.lv(r) * R + r];
             else if constexpr (SPE)
                 return ((in_t >> r) & 1u) ? t_GaPs(r) : (SHOIST ? sv_GaPs_side[SHOIST ? r : 0] : sp[(int64_t)(SP_GAPS_SIDE * R + r) * sps]);
             else if constexpr (SCAN) return ((in_t >> r) & 1u) ? tb->GaPs[r] : tb->GaPs_side[r];
             else return t_GaPs(r);
         };
         auto r_pdno = [&](int r) -> double {
-            if constexpr (PAT) return s_lpdno[pl.lv(r) * R + r];
+            if constexpr (SPP) return PHOIST ? lv_pdno[PHOIST ? r : 0] : pp_row(PP_PD_NO, pl.lv(r), r);
+            else if constexpr (PAT) return s_lpdno[pl.lv(r) * R + r];
             else if constexpr (SPE)
                 return ((in_t >> r) & 1u) ? t_pdno(r) : (SHOIST ? sv_pdno_side[SHOIST ? r : 0] : sp[(int64_t)(SP_PD_NO_SIDE * R + r) * sps]);
             else if constexpr (SCAN) return ((in_t >> r) & 1u) ? tb->pd_no[r] : tb->pd_no_side[r];
@@ -741,7 +797,11 @@ MACJD_ENV_UNROLL_SIZED(NR)
             if (!FAST && io.snr64) io.snr64[e * R + r] = snr_rep;
             if constexpr (SCAN) {   // beam advance (include/macjd.h, macjd_scan_desc)
                 const bool in = (in_t >> r) & 1u;
-                if constexpr (PAT) {
+                if constexpr (SPP) {
+                    if (io.snr_no)
+                        at(io.snr_no, e, io.sn_se, r, io.sn_sx) =
+                            (float)(PHOIST ? lv_snrno[PHOIST ? r : 0] : pp_row(PP_SNR_NO, pl.lv(r), r));
+                } else if constexpr (PAT) {
                     if (io.snr_no) at(io.snr_no, e, io.sn_se, r, io.sn_sx) = (float)s_lsnrno[pl.lv(r) * R + r];
                 } else if constexpr (SPE) {
                     if (io.snr_no)
@@ -796,5 +856,8 @@ MACJD_ENV_UNROLL_SIZED(NR)
 // macjd_env_scan_pe.hip: the generic-size SCAN kernel on per-env tables, env_step_kernel<0, 0, PE = true, FAST = false, ...,
 // SCAN = true>, built there with its size-bounded loops unrolled by count (see MACJD_ENV_UNROLL_SIZED)
 void launch_scan_pe_generic(dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev, const ScanPeStepIO<macjd_step_io>& io);
+// ... and its PAT form (ScanPePatStepIO), built there with the same unrolling
+void launch_scan_pe_pattern_generic(dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
+                                    const ScanPePatStepIO<macjd_step_io>& io);
 
 }  // namespace macjd

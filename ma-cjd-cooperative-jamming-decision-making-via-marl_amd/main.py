@@ -21,7 +21,7 @@ What is added (build flags, all optional):
   ``hip_graphs``  (default True on a HIP device with batch_envs > 1) replay rollouts / updates from HIP graphs.
   ``randomize_scenarios`` / ``--randomize-scenarios`` (batched runs): every env trains on its own random variation
                   of the scenario file (positions, threat levels, powers; ``scenario.ScenarioBatch``), scanning
-                  radars included; ``randomize_azimuth_jitter`` (degrees, default 0) also moves every radar's
+                  radars and their stepped antenna pattern included; ``randomize_azimuth_jitter`` (degrees, default 0) also moves every radar's
                   initial beam azimuth.
   ``--resume DIR`` restores agent, mixer, optimiser and ``trainer_state.json`` (env steps, episodes, epsilon
                   clock, learner step counters, and the positions of the three random streams: exploration counter,

@@ -535,9 +535,34 @@ PE_SCAN_ROWS = ("half_beam", "sweep", "sweep_mod", "az0", "bear_tgt", "GaPs_side
                 "gr_side", "bear_jam")
 
 
+# Row order of the per-env pattern SoA (include/macjd.h, macjd_scan_pe_pattern_io): inv_width's R rows, then four level
+# tables of (L + 2) R rows each, level-major (level k of radar r at row k * R + r of its block).  Per table: (level 0 =
+# the main-lobe array of Scenario.tables, levels 1..L = the Scenario.scan_tables array [L, R], level L + 1 = the side-lobe
+# array of Scenario.scan_tables).
+PE_SCAN_PATTERN_ROWS = ("inv_width", "GaPs_lvl", "snr_no_lvl", "pd_no_lvl", "gr_lvl")
+_PE_PATTERN_LEVEL_SOURCES = {
+    "GaPs_lvl": ("radar_GaPs", "pat_GaPs", "GaPs_side"), "snr_no_lvl": ("radar_snr_no", "pat_snr_no", "snr_no_side"),
+    "pd_no_lvl": ("radar_pd_no", "pat_pd_no", "pd_no_side"), "gr_lvl": ("radar_gr", "pat_gr", "gr_side"),
+}
+
+
 def pe_scan_rows(n_radars: int, n_jammers: int) -> int:
     """MACJD_PE_SCAN_ROWS(R, J) of include/macjd.h."""
     return 10 * n_radars + n_jammers * n_radars
+
+
+def pe_scan_pattern_rows(n_radars: int, n_levels: int) -> int:
+    """MACJD_PE_SCAN_PATTERN_ROWS(R, L) of include/macjd.h."""
+    return n_radars + 4 * (n_levels + 2) * n_radars
+
+
+def _pattern_column(sc: "Scenario") -> np.ndarray:
+    """Scenario ``sc``'s own arrays in the row order ``PE_SCAN_PATTERN_ROWS``, as one float64 vector (copied, not recomputed)."""
+    parts = [sc.scan_tables["pat_inv_width"]]
+    for key in PE_SCAN_PATTERN_ROWS[1:]:
+        main, levels, side = _PE_PATTERN_LEVEL_SOURCES[key]
+        parts += [sc.tables[main], sc.scan_tables[levels], sc.scan_tables[side]]
+    return np.concatenate([np.asarray(a, dtype=np.float64).reshape(-1) for a in parts])
 
 
 def randomized_scenario_dict(base: dict, rng: np.random.Generator, position_jitter: float = 60.0,
@@ -575,11 +600,21 @@ class ScenarioBatch:
     like the r_p bounds) and no stepped antenna pattern; their scan tables are stacked as ``scan_tables`` float64
     [10R + JR, E] in the row order ``PE_SCAN_ROWS`` (include/macjd.h, macjd_scan_pe_io), column e bit-identical to
     scenario e's own arrays.  ``full`` is not carried (the device recomputes sweep + 2 half_beam >= 360 with the same
-    bits).  Without ``scan`` a scanning scenario is refused and ``scan_tables`` is None."""
+    bits).  Without ``scan`` a scanning scenario is refused and ``scan_tables`` is None.
 
-    def __init__(self, scenarios: List[Scenario], *, scan: bool = False):
+    ``scan=True, pattern=True`` makes a scanning batch under a stepped antenna pattern: every scenario has a
+    ``radar_scan.pattern`` (part of the shared ``radar_scan`` dict, so ``level_width``, ``gain_db`` and L are the batch's),
+    and the level tables are stacked as ``pattern_tables`` float64 [R + 4 (L + 2) R, E] in the row order
+    ``PE_SCAN_PATTERN_ROWS`` (include/macjd.h, macjd_scan_pe_pattern_io), column e again scenario e's own arrays bit for bit.
+    Without ``pattern`` a scenario that has one is refused and ``pattern_tables`` is None."""
+
+    def __init__(self, scenarios: List[Scenario], *, scan: bool = False, pattern: bool = False):
         if not scenarios:
             raise ValueError("ScenarioBatch needs at least one scenario")
+        if pattern and not scan:
+            i = next((k for k, sc in enumerate(scenarios) if sc.scan_pattern_levels), 0)
+            raise ValueError(f"ScenarioBatch(pattern=True) needs scan=True (scenario {i}: the stepped antenna pattern belongs "
+                             f"to scanning radars)")
         s0 = scenarios[0]
         for i, sc in enumerate(scenarios):
             same = (sc.num_radars == s0.num_radars and sc.num_jammers == s0.num_jammers
@@ -595,9 +630,13 @@ class ScenarioBatch:
             if not sc.scanning:
                 raise ValueError(f"ScenarioBatch(scan=True): scenario {i} has no environment_params.radar_scan (every "
                                  f"scenario of a scanning batch must scan)")
-            if "pattern" in sc.radar_scan:
+            if pattern and "pattern" not in sc.radar_scan:
+                raise ValueError(f"ScenarioBatch(scan=True, pattern=True): scenario {i} has no radar_scan.pattern (every "
+                                 f"scenario of such a batch must have the stepped antenna pattern)")
+            if not pattern and "pattern" in sc.radar_scan:
                 raise ValueError(f"ScenarioBatch(scan=True): scenario {i} has a radar_scan.pattern (the stepped antenna "
-                                 f"pattern is not supported with per-env scenario batches)")
+                                 f"pattern is not supported with per-env scenario batches unless the batch is built "
+                                 f"with pattern=True)")
             if sc.radar_scan != s0.radar_scan:
                 raise ValueError(f"ScenarioBatch(scan=True): scenario {i}'s radar_scan {sc.radar_scan} differs from scenario "
                                  f"0's {s0.radar_scan} (it is shared by the whole batch)")
@@ -622,11 +661,20 @@ class ScenarioBatch:
                 [np.stack([np.asarray(scan_row(sc, key), dtype=np.float64).reshape(-1) for sc in scenarios], axis=1)
                  for key in PE_SCAN_ROWS], axis=0))                                           # [10R + JR, E]
             assert self.scan_tables.shape == (pe_scan_rows(R, J), self.n_envs)
+        self.pattern_tables = None
+        if pattern:
+            self.pattern_tables = np.ascontiguousarray(np.stack([_pattern_column(sc) for sc in scenarios], axis=1))
+            assert self.pattern_tables.shape == (pe_scan_pattern_rows(R, s0.scan_pattern_levels), self.n_envs)
 
     @property
     def scanning(self) -> bool:
         """The batch carries per-env scan tables (built with ``scan=True``)."""
         return self.scan_tables is not None
+
+    @property
+    def scan_pattern_levels(self) -> int:
+        """L of the batch's stepped antenna pattern (built with ``pattern=True``), 0 without one."""
+        return self.base.scan_pattern_levels if self.pattern_tables is not None else 0
 
     def tile(self, n_envs: int) -> "ScenarioBatch":
         """A batch of ``n_envs`` envs that cycles through this batch's scenarios (env e runs scenario e mod E) —
@@ -641,6 +689,8 @@ class ScenarioBatch:
         out.snr_no = np.ascontiguousarray(np.tile(self.snr_no, (reps, 1))[:n_envs])
         out.scan_tables = (None if self.scan_tables is None
                            else np.ascontiguousarray(np.tile(self.scan_tables, (1, reps))[:, :n_envs]))
+        out.pattern_tables = (None if self.pattern_tables is None
+                              else np.ascontiguousarray(np.tile(self.pattern_tables, (1, reps))[:, :n_envs]))
         return out
 
     @classmethod
@@ -648,13 +698,14 @@ class ScenarioBatch:
                    **jitter) -> "ScenarioBatch":
         """``n_envs`` random variations of ``base_dict``; env e of the batch is variation number ``env_offset + e``
         of the stream keyed by ``seed`` (shard-invariant: a rank's shard of a bigger batch is the same scenarios).  A base
-        with ``environment_params.radar_scan`` gives a scanning batch (``scan=True``)."""
+        with ``environment_params.radar_scan`` gives a scanning batch (``scan=True``), one with ``radar_scan.pattern`` a
+        scanning batch under that pattern (``pattern=True``)."""
         scs = []
         for e in range(n_envs):
             rng = np.random.default_rng([int(seed), int(env_offset) + e])
             scs.append(Scenario.from_dict(randomized_scenario_dict(base_dict, rng, **jitter), config=config,
                                           source=f"<randomized {seed}:{env_offset + e}>"))
-        return cls(scs, scan=scs[0].scanning)
+        return cls(scs, scan=scs[0].scanning, pattern=scs[0].scan_pattern_levels > 0)
 
 
 def ring_scenario_dict(n_jammers: int, n_radars: int) -> dict:

@@ -71,7 +71,8 @@ class BatchedElectromagneticEnvironment:
         """``scenario_batch``: one scenario PER ENV (radar / jammer positions, threat levels, powers differing
         between envs — SURVEY.md 8f-3); its tables live in HBM as an SoA that every step streams, and the
         observation becomes a per-env [E, S] tensor (still constant in time).  A scanning batch
-        (``ScenarioBatch(..., scan=True)``) also streams each env's scan tables; its theta_a columns move."""
+        (``ScenarioBatch(..., scan=True)``) also streams each env's scan tables; its theta_a columns move.  With
+        ``pattern=True`` each env's stepped antenna pattern tables are streamed too (macjd_env_step_scan_pe_pattern)."""
         self.scenario_batch = scenario_batch
         if scenario_batch is not None:
             scenario = scenario_batch.base
@@ -82,6 +83,7 @@ class BatchedElectromagneticEnvironment:
         self.scenario = scenario if scenario is not None else Scenario.from_yaml(sim_config_path, config)
         sc = self.scenario
         pe_scan = scenario_batch is not None and getattr(scenario_batch, "scan_tables", None) is not None
+        pe_pattern = pe_scan and getattr(scenario_batch, "pattern_tables", None) is not None
         if sc.scanning and scenario_batch is not None and not pe_scan:
             raise ValueError("scanning radars (environment_params.radar_scan) need a scanning per-env scenario batch "
                              "(ScenarioBatch(..., scan=True)); this batch carries no scan tables")
@@ -102,7 +104,9 @@ class BatchedElectromagneticEnvironment:
         self.device = _require_device(device)
         self._lib = _native.load()
         with torch.cuda.device(self.device):
-            self._handle = _native.ScenarioHandle(sc)
+            # a batch under a stepped pattern brings every env's level tables itself: the handle stays pattern-free, so
+            # that macjd_env_reset_scan_pe (az0 per env does not depend on the pattern) takes it
+            self._handle = _native.ScenarioHandle(sc, scan_pattern=not pe_pattern)
         E, R, J = self.batch_envs, self.num_radars, self.num_jammers
         dev = self.device
         self._track = torch.zeros((R, E), dtype=torch.uint8, device=dev)
@@ -126,6 +130,7 @@ class BatchedElectromagneticEnvironment:
             self._pe_tile = self.PE_TILE if getattr(self, "pe_tiled", True) else 0
             tb, fl = scenario_batch.tables, scenario_batch.flags
             stb = scenario_batch.scan_tables if pe_scan else None
+            ptb = scenario_batch.pattern_tables if pe_pattern else None
             if self._pe_tile:
                 w = self._pe_tile
                 n_tiles = (E + w - 1) // w
@@ -134,12 +139,14 @@ class BatchedElectromagneticEnvironment:
                     np.pad(a, ((0, 0), (0, pad))).reshape(a.shape[0], n_tiles, w).transpose(1, 0, 2))
                 tb, fl = tile(tb), tile(fl)
                 stb = tile(stb) if pe_scan else None
+                ptb = tile(ptb) if pe_pattern else None
             self._pe_tables = torch.from_numpy(tb).to(dev)       # f64 [rows, E] or [n_tiles, rows, w]
             self._pe_flags = torch.from_numpy(fl).to(dev)        # u8  [J*R, E] or [n_tiles, J*R, w]
             self._state_vecs = torch.from_numpy(scenario_batch.state_vectors).to(dev)   # f32 [E, S]
             self._snr_no = torch.from_numpy(scenario_batch.snr_no).to(dev)          # f64 [E, R]
         self._theta_a = self._state_dyn = self._snr_no_step = None
         self._scan_io = self._scan_pe_io = self._scan_pe_tables = None
+        self._scan_pe_pattern_io = self._scan_pe_pattern_tables = None
         if pe_scan:
             # per-env scan tables (include/macjd.h, macjd_scan_pe_io) in the device form of pe_tables; beams, state rows
             # and the per-step SNR without jamming start from each env's own az0 / state vector / main-lobe snr_no
@@ -151,6 +158,11 @@ class BatchedElectromagneticEnvironment:
             self._snr_no_step = self._snr_no.t().to(torch.float32).contiguous()
             sp = self._scan_pe_io = _native.ScanPeIO()
             sp.tables, sp.stride = self._scan_pe_tables.data_ptr(), E
+            if pe_pattern:
+                # per-env level tables (include/macjd.h, macjd_scan_pe_pattern_io), same device form
+                self._scan_pe_pattern_tables = torch.from_numpy(ptb).to(dev)   # f64 [R + 4(L+2)R, E] or [n_tiles, ..., w]
+                pp = self._scan_pe_pattern_io = _native.ScanPePatternIO()
+                pp.tables, pp.stride, pp.n_levels = self._scan_pe_pattern_tables.data_ptr(), E, scenario_batch.scan_pattern_levels
         elif sc.scanning:
             # beam azimuths f64 [R, E] (radar-major like track), the per-env state rows f32 [E, S] whose theta_a columns the
             # kernel rewrites every step (get_state / get_obs are views of it: one address for captured graphs), and the
@@ -325,7 +337,11 @@ class BatchedElectromagneticEnvironment:
                            rdpj_sum)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         with torch.cuda.device(self.device):
-            if self._scan_pe_io is not None:
+            if self._scan_pe_pattern_io is not None:
+                _native.check(self._lib.macjd_env_step_scan_pe_pattern(
+                    self._handle.ptr, ctypes.byref(io), ctypes.byref(self._scan_io), ctypes.byref(self._scan_pe_io),
+                    ctypes.byref(self._scan_pe_pattern_io), stream), "macjd_env_step_scan_pe_pattern")
+            elif self._scan_pe_io is not None:
                 _native.check(self._lib.macjd_env_step_scan_pe(self._handle.ptr, ctypes.byref(io), ctypes.byref(self._scan_io),
                                                                ctypes.byref(self._scan_pe_io), stream), "macjd_env_step_scan_pe")
             elif self._scan_io is not None:

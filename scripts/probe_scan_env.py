@@ -25,7 +25,9 @@ call up to the last call's return (enqueue) and up to the device's completion (t
 compares scanning on per-env scenario batches (macjd_env_step_scan_pe) with its two neighbours: shared-table scanning
 (`scan_shared`), per-env static tables (`pe_static`) and per-env scanning (`pe_scan`; 25 randomised ring scenarios with a
 45 degree azimuth jitter, tiled to E), production configuration, graph-replayed steps timed with HIP events, one process
-per run, the three alternating `--alternations` times; every run appends one JSON line to --out."""
+per run, the three alternating `--alternations` times; every run appends one JSON line to --out.  `--tags pe_scan,pe_pattern`
+alternates other variants of that list: `pe_pattern` is `pe_scan` under the stepped pattern {1.5, [-3, -12, -17, -25]}
+(macjd_env_step_scan_pe_pattern; the same 25 geometries, the level tables per env)."""
 import argparse
 import json
 import os
@@ -142,17 +144,20 @@ def pattern_run(tag, E, iters, reps, out):
 
 
 PER_ENV_TAGS = ("scan_shared", "pe_static", "pe_scan")
+PER_ENV_ALL_TAGS = PER_ENV_TAGS + ("pe_pattern",)
 
 
 def per_env_run(tag, J, R, E, iters, reps, out):
-    """One (scan_shared | pe_static | pe_scan, size, E) measurement in this process."""
+    """One (scan_shared | pe_static | pe_scan | pe_pattern, size, E) measurement in this process."""
     d = ring_scenario_dict(J, R)
     if tag != "pe_static":
         d["environment_params"] = dict(d["environment_params"], radar_scan={"step_seconds": 0.25, "sidelobe_db": -30.0})
+    if tag == "pe_pattern":
+        d["environment_params"]["radar_scan"]["pattern"] = {"level_width": 1.5, "gain_db": [-3, -12, -17, -25]}
     if tag == "scan_shared":
         env = BatchedElectromagneticEnvironment(scenario=Scenario.from_dict(d), batch_envs=E, device="cuda", seed=1)
     else:
-        jitter = {"azimuth_jitter": 45.0} if tag == "pe_scan" else {}
+        jitter = {"azimuth_jitter": 45.0} if tag != "pe_static" else {}
         batch = ScenarioBatch.randomized(d, 25, seed=9, **jitter).tile(E)
         env = BatchedElectromagneticEnvironment(scenario_batch=batch, device="cuda", seed=1)
         del batch
@@ -180,6 +185,7 @@ def main():
     ap.add_argument("--per-env", action="store_true", help="shared-table scanning vs per-env static vs per-env scanning")
     ap.add_argument("--sizes", default="3x4,12x16", help="JxR sizes of --per-env")
     ap.add_argument("--Es", default="4096,1048576", help="batch sizes of --per-env")
+    ap.add_argument("--tags", default=",".join(PER_ENV_TAGS), help=f"variants of --per-env, of {','.join(PER_ENV_ALL_TAGS)}")
     ap.add_argument("--one-per-env", nargs=4, metavar=("VARIANT", "J", "R", "E"), help="(internal) one run of --per-env")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -190,11 +196,14 @@ def main():
         tag, J, R, E = a.one_per_env
         return per_env_run(tag, int(J), int(R), int(E), a.iters, a.reps, a.out)
     if a.per_env:
+        tags = a.tags.split(",")
+        if not set(tags) <= set(PER_ENV_ALL_TAGS):
+            ap.error(f"--tags: unknown variant in {tags}")
         for size in a.sizes.split(","):
             J, R = size.split("x")
             for E in a.Es.split(","):
                 for _ in range(a.alternations):
-                    for tag in PER_ENV_TAGS:   # a failing run ends the sequence: nothing more is started on the device
+                    for tag in tags:   # a failing run ends the sequence: nothing more is started on the device
                         subprocess.run([sys.executable, os.path.abspath(__file__), "--one-per-env", tag, J, R, E, "--iters",
                                         str(a.iters), "--reps", str(a.reps)] + (["--out", a.out] if a.out else []),
                                        check=True, timeout=600)
