@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MACJD_ABI_VERSION 10
+#define MACJD_ABI_VERSION 11
 #define MACJD_PE_ROWS(R, J) (6 * (R) + 3 * (J) + (J) * (R))
 #define MACJD_PE_SCAN_ROWS(R, J) (10 * (R) + (J) * (R))
 #define MACJD_PE_SCAN_PATTERN_ROWS(R, L) ((R) + 4 * ((L) + 2) * (R))
@@ -299,7 +299,9 @@ int macjd_scenario_set_scan(macjd_scenario* s, const macjd_scan_desc* d);
    launch their pattern variants: no other call changes. */
 int macjd_scenario_set_scan_pattern(macjd_scenario* s, const macjd_scan_pattern_desc* d);
 /* macjd_env_step with scanning beams (see macjd_scan_desc); needs macjd_scenario_set_scan first.  Always the one-lane-
-   per-env kernel; per-env scenario tables (pe_tables) are refused here: macjd_env_step_scan_pe takes them. */
+   per-env kernel; per-env scenario tables (pe_tables) are refused here: macjd_env_step_scan_pe takes them.  (Likewise the
+   closed-loop launch, include/macjd_nets.h: macjd_agent_env_episode_scan refuses pe_tables, macjd_agent_env_episode_scan_pe
+   takes them; macjd_env_step_many and the whole-episode launches on a static observation do not apply to scanning beams.) */
 int macjd_env_step_scan(const macjd_scenario* s, const macjd_step_io* io, const macjd_scan_io* scan, void* hip_stream);
 /* beam part of a reset, issued next to macjd_env_reset with the same mask: theta_a[e,:] = az0 (and the state
    columns = (float)az0) for envs with mask != 0 (all when mask == NULL) */

@@ -690,7 +690,8 @@ int macjd_agent_episode(const macjd_agent_episode_io* io, void* hip_stream);
  * The kernel writes ONLY the theta_a columns (scan.st_col0 + r * scan.st_col_step) of the staging rows t < T; their
  * static columns are the caller's.  At exit theta_a, track, step, the theta_a columns of the env's state rows
  * (scan.state), scan.snr_no (last step's lobe), rdpj_sum and h_final hold what T single steps would have left.
- * Needs macjd_scenario_set_scan; shared scenario tables only (pe_tables must be NULL).
+ * Needs macjd_scenario_set_scan; shared scenario tables only (pe_tables must be NULL; macjd_agent_env_episode_scan_pe below
+ * takes per-env tables).
  * Supported: H = 64, actor_hidden = 128, (J, R, A) in {(3, 4, 9), (2, 2, 5)}; MACJD_EUNSUPPORTED otherwise.
  */
 typedef struct macjd_agent_env_episode_scan_io {
@@ -734,6 +735,34 @@ typedef struct macjd_agent_env_episode_scan_io {
 
 int macjd_agent_env_episode_scan_supported(int32_t J, int32_t R, int32_t H, int32_t A);
 int macjd_agent_env_episode_scan(const macjd_scenario* scenario, const macjd_agent_env_episode_scan_io* io, void* hip_stream);
+
+/*
+ * macjd_agent_env_episode_scan on per-env scenario tables (a scanning scenario batch, with or without a stepped antenna
+ * pattern per env): the same launch, outputs and hand-over, with every table value read from the env's own columns.
+ *   base       the shared call's block; base.pe_tables = the batch's scenario tables (macjd_step_io.pe_tables), non-NULL
+ *   pe_flags, pe_stride, pe_tile   as macjd_step_io: pe_tile == 0 is the plain layout (every stride >= n_envs), pe_tile > 0
+ *              the tiled one of ALL table sets (any width, also below the 16 envs of a workgroup; last tile padded)
+ *   scan_pe    the per-env scan tables (macjd_scan_pe_io)
+ *   pattern    tables == NULL: no pattern; else the per-env level tables (macjd_scan_pe_pattern_io), n_levels = L
+ * The scenario handle is the batch's scanning handle: it supplies only J, R, episode_limit, the r_p bounds and the Pd
+ * constants (macjd_env_step_scan_pe's rule).  A handle that carries pattern levels is accepted only with pattern.tables of
+ * the same L (MACJD_EUNSUPPORTED otherwise).  MACJD_EINVAL: NULL base.pe_tables / pe_flags / scan_pe.tables, a stride below
+ * n_envs in the plain layout, pe_tile < 0, L outside 1..MACJD_MAX_PATTERN_LEVELS, a handle without scan tables; every check
+ * returns before any launch.  Results are bit-identical to T single macjd_env_step_scan_pe(_pattern) steps on the actions the
+ * agent half chose; scan.snr_no ends as the last step's value from the env's own snr_no / snr_no_side row, or under a
+ * pattern from its snr_no_lvl row of the last level.  Supported sizes: those of macjd_agent_env_episode_scan.
+ */
+typedef struct macjd_agent_env_episode_scan_pe_io {
+    macjd_agent_env_episode_scan_io base;
+    const uint8_t* pe_flags;
+    int64_t pe_stride;
+    int32_t pe_tile, reserved;
+    macjd_scan_pe_io scan_pe;
+    macjd_scan_pe_pattern_io pattern;
+} macjd_agent_env_episode_scan_pe_io;
+
+int macjd_agent_env_episode_scan_pe_supported(int32_t J, int32_t R, int32_t H, int32_t A);
+int macjd_agent_env_episode_scan_pe(const macjd_scenario* scenario, const macjd_agent_env_episode_scan_pe_io* io, void* hip_stream);
 
 /*
  * Double-DQN target values straight from the unrolled hidden states (reference core/qmix.py:138-147): for every row n

@@ -14,7 +14,7 @@ LIB_NAME = "libmacjd_hip.so"
 # MACJD_LIB points at another build of the same sources (kernel A/B runs); the default is the in-tree library
 LIB_PATH = os.environ.get("MACJD_LIB") or os.path.join(_PKG_DIR, LIB_NAME)
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 STEP_ARITH_F64 = 1
 STEP_LANE_KERNEL = 2
 STEP_SLOT_KERNEL = 4
@@ -33,6 +33,7 @@ EXPORTS = [
     "macjd_scenario_set_scan", "macjd_env_step_scan", "macjd_env_reset_scan",
     "macjd_env_step_scan_pe", "macjd_env_reset_scan_pe", "macjd_env_step_scan_pe_pattern",
     "macjd_agent_env_episode_scan_supported", "macjd_agent_env_episode_scan",
+    "macjd_agent_env_episode_scan_pe_supported", "macjd_agent_env_episode_scan_pe",
     "macjd_scenario_set_scan_pattern",
     "macjd_gru_sequence_backward_supported", "macjd_gru_sequence_backward",
     "macjd_prefetch_batch_supported", "macjd_prefetch_batch",
@@ -242,6 +243,15 @@ class AgentEnvEpisodeScanIO(ctypes.Structure):
         ("hidden", ctypes.c_void_p), ("T_out", ctypes.c_void_p), ("P_out", ctypes.c_void_p), ("h_final", ctypes.c_void_p),
         ("st_state", ctypes.c_void_p), ("st_obs", ctypes.c_void_p), ("reward", ctypes.c_void_p), ("terminated", ctypes.c_void_p),
         ("rdpj_sum", ctypes.c_void_p),
+    ]
+
+
+class AgentEnvEpisodeScanPeIO(ctypes.Structure):
+    """ctypes mirror of ``macjd_agent_env_episode_scan_pe_io`` (include/macjd_nets.h)."""
+    _fields_ = [
+        ("base", AgentEnvEpisodeScanIO),
+        ("pe_flags", ctypes.c_void_p), ("pe_stride", ctypes.c_int64), ("pe_tile", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("scan_pe", ScanPeIO), ("pattern", ScanPePatternIO),
     ]
 
 
@@ -490,6 +500,10 @@ def load() -> ctypes.CDLL:
     lib.macjd_agent_env_episode_scan_supported.argtypes = [ctypes.c_int32] * 4
     lib.macjd_agent_env_episode_scan.restype = ctypes.c_int
     lib.macjd_agent_env_episode_scan.argtypes = [ctypes.c_void_p, ctypes.POINTER(AgentEnvEpisodeScanIO), ctypes.c_void_p]
+    lib.macjd_agent_env_episode_scan_pe_supported.restype = ctypes.c_int
+    lib.macjd_agent_env_episode_scan_pe_supported.argtypes = [ctypes.c_int32] * 4
+    lib.macjd_agent_env_episode_scan_pe.restype = ctypes.c_int
+    lib.macjd_agent_env_episode_scan_pe.argtypes = [ctypes.c_void_p, ctypes.POINTER(AgentEnvEpisodeScanPeIO), ctypes.c_void_p]
     lib.macjd_env_step_many.restype = ctypes.c_int
     lib.macjd_env_step_many.argtypes = [ctypes.c_void_p, ctypes.POINTER(StepIO), ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p]
     lib.macjd_env_step_many_timed.restype = ctypes.c_int

@@ -33,7 +33,13 @@
 // last step are kept four bits per radar for the hand-over's snr_no.  (The two variants were first compiled from one text
 // included twice under two names, so that the variant without a pattern kept its name; the parameter changes only the
 // name: both variants compile to the same code either way, profiles/r10_episode_isa_check.txt.)
+//
+// Per-env scenario batches (include/macjd_nets.h, macjd_agent_env_episode_scan_pe_io): PE, the next template parameter,
+// with the argument block EpScanPeIO — the same kernel with every table read taken from the env's own column (see the
+// comment on the kernel).  Again only the names of the existing variants change, profiles/r18_episode_isa_check.txt.
 #pragma once
+
+#include <type_traits>
 
 #include "macjd_env_dev.h"
 
@@ -54,10 +60,55 @@ struct EpScanTab {   // LDS copy of what the env half reads from the scenario ha
     uint8_t flags[J * R], full[R];
 };
 
-template <int J, int R, int A, int SQ, bool PAT>
-__global__ void __launch_bounds__(256) agent_env_episode_scan_kernel(const DevTables* __restrict__ tb,
-                                                                     const macjd_agent_env_episode_scan_io io) {
+// PE: what the handle still supplies when every env brings its own tables
+struct EpScanConsts {
+    double rp_min, rp_max, pd_A, pd_c1, pd_denB;
+    int32_t episode_limit;
+};
+
+// Argument block of the launch on per-env scenario tables (include/macjd_nets.h, macjd_agent_env_episode_scan_pe_io): the
+// shared launch's block, whose pe_tables are the batch's scenario tables here, plus the flag bytes, the per-env scan SoA
+// and, under a stepped pattern, the per-env level tables — all laid out by pe_tile (include/macjd.h, macjd_step_io).
+struct EpScanPeIO : macjd_agent_env_episode_scan_io {
+    const uint8_t* pe_flags;
+    int64_t pe_stride;
+    const double* sp_tables;
+    int64_t sp_stride;
+    const double* pp_tables;
+    int64_t pp_stride;
+    int32_t pe_tile, pat_levels;
+};
+
+// Rows of the per-env LDS block [row][16] of the PE variants (lane er reads [row * 16 + er]): the env's pe_tables rows in
+// their own order, then the scan rows the step reads, then (PAT) inv_width.
+template <int J, int R>
+struct EpScanPeRows {
+    enum {
+        GAPS = 0, PN = R, D = 2 * R, PD_NO = 3 * R, RD_PEN = 4 * R, GR = 5 * R, PMIN = 6 * R, PMAX = 6 * R + J, GJ = 6 * R + 2 * J,
+        DENOM = 6 * R + 3 * J, NPE = 6 * R + 3 * J + J * R,
+        HALF = NPE, SWEEP = NPE + R, SWM = NPE + 2 * R, BT = NPE + 3 * R, GAPS_SIDE = NPE + 4 * R, PD_NO_SIDE = NPE + 5 * R,
+        GR_SIDE = NPE + 6 * R, BJ = NPE + 7 * R, NSCAN = 7 * R + J * R, INVW = NPE + NSCAN,
+        NSP = 10 * R + J * R   // rows of macjd_scan_pe_io
+    };
+    // source row in macjd_scan_pe_io of staged scan row k: half | sweep | sweep_mod | (az0) | bear_tgt | GaPs_side | (snr_no) |
+    // (snr_no_side) | pd_no_side | gr_side | bear_jam — the rows in brackets are not staged
+    static __device__ __forceinline__ int sp_src(int k) {
+        const int b = k / R;
+        return k < 7 * R ? (b < 3 ? b : (b < 5 ? b + 1 : b + 3)) * R + (k - b * R) : 10 * R + (k - 7 * R);
+    }
+};
+
+// PE (with IO = EpScanPeIO): every env reads its own tables.  The loop-invariant rows of the workgroup's 16 envs are staged
+// once per launch into an LDS block [row][16] of float64 (13R + 3J + 2JR rows, + R under a pattern) and lane er of the env
+// half reads column er — sixteen consecutive doubles, conflict-free also when the row is picked per lane by the chosen
+// radar; h2 and full are formed per lane as env_step_kernel<.., SCAN && PE> does.  Under a pattern the level tables stay in
+// HBM (96 rows at L = 6 do not fit beside the rest): the one row an object's level selects is loaded from the env's
+// column by address, 2R + J loads per lane and step, as env_step_kernel<.., PAT && PE> does.  The handle supplies only the
+// r_p bounds, the Pd constants and episode_limit.  The agent half (S1-S4), keying and barriers are the shared kernel's.
+template <int J, int R, int A, int SQ, bool PAT, bool PE = false, class IO = macjd_agent_env_episode_scan_io>
+__global__ void __launch_bounds__(256) agent_env_episode_scan_kernel(const DevTables* __restrict__ tb, const IO io) {
     static_assert(J <= 4, "one wave per agent tile in the Q-head phase");
+    static_assert(PE == std::is_same_v<IO, EpScanPeIO>, "PE: the argument block with the per-env tables");
     static_assert(!PAT || R <= 8, "PAT: the target's levels are packed four bits per radar into 32 bits");
     static_assert(16 * A <= 256, "actor layer 3: one thread per (env, action)");
     constexpr int OLD = 16 * SQ + 8;   // LDS pitch of the observation tile (S <= 16 SQ columns, zero-padded)
@@ -74,12 +125,19 @@ __global__ void __launch_bounds__(256) agent_env_episode_scan_kernel(const DevTa
     __shared__ double s_az[R][16];                                        // theta_a (gathered by a jammer's chosen radar)
     __shared__ int Tl[J][16];                                             // chosen actions of the current step
     __shared__ float Pcl[J][16];
-    __shared__ EpScanTab<J, R> tab;
+    __shared__ std::conditional_t<PE, EpScanConsts, EpScanTab<J, R>> tab;
+    // PE: the 16 envs' own table rows and flag bytes
+    using PR = EpScanPeRows<J, R>;
+    constexpr int PTN = PR::INVW + (PAT ? R : 0);
+    __shared__ double pt[PE ? PTN * 16 : 1];
+    __shared__ uint8_t pfl[PE ? J * R * 16 : 1];
     // PAT: level tables [L + 2, R] packed [k * R + r] (row 0 main, 1..L the pattern's levels, L + 1 side lobe), 1 / width
-    constexpr int LVN = PAT ? MAXLV * R : 1;
-    __shared__ double lv_GaPs[LVN], lv_pd_no[LVN], lv_gr[LVN], lv_invw[PAT ? R : 1];
+    constexpr int LVN = (PAT && !PE) ? MAXLV * R : 1;
+    __shared__ double lv_GaPs[LVN], lv_pd_no[LVN], lv_gr[LVN], lv_invw[(PAT && !PE) ? R : 1];
     int pat_L = 0;
-    if constexpr (PAT) {
+    if constexpr (PAT && PE) {
+        pat_L = io.pat_levels;
+    } else if constexpr (PAT) {
         pat_L = tb->pat_levels;
         if (threadIdx.x < (pat_L + 2) * R) {
             lv_GaPs[threadIdx.x] = tb->lv_GaPs[threadIdx.x];
@@ -174,6 +232,32 @@ __global__ void __launch_bounds__(256) agent_env_episode_scan_kernel(const DevTa
     }
     const float b2 = io.b2[0];
     // env tables -> LDS
+    if constexpr (PE) {
+        // thread -> (column tid & 15 = env of the workgroup, rows tid >> 4, + 16, ...): one env column per thread, so the
+        // tile arithmetic is done once; sixteen consecutive envs of a row are 128 contiguous bytes (a tile boundary aside)
+        const int c = tid & 15;
+        bool live;
+        const int64_t e = env_of(c, live);
+        const bool tiled = io.pe_tile > 0;
+        const int64_t tl = tiled ? e / io.pe_tile : 0;
+        const int64_t cl = tiled ? e - tl * io.pe_tile : e;
+        const int64_t ps = tiled ? (int64_t)io.pe_tile : io.pe_stride, sps = tiled ? (int64_t)io.pe_tile : io.sp_stride;
+        const double* __restrict__ pe = io.pe_tables + tl * PR::NPE * ps + cl;
+        const uint8_t* __restrict__ pf = io.pe_flags + tl * (J * R) * ps + cl;
+        const double* __restrict__ sp = io.sp_tables + tl * PR::NSP * sps + cl;
+        for (int row = tid >> 4; row < PR::INVW; row += 16)
+            pt[row * 16 + c] = row < PR::NPE ? pe[(int64_t)row * ps] : sp[(int64_t)PR::sp_src(row - PR::NPE) * sps];
+        for (int row = tid >> 4; row < J * R; row += 16) pfl[row * 16 + c] = pf[(int64_t)row * ps];
+        if constexpr (PAT) {   // inv_width: the first R rows of the env's pattern column
+            const int64_t pps = tiled ? (int64_t)io.pe_tile : io.pp_stride;
+            const double* __restrict__ pp = io.pp_tables + tl * (R + 4 * (int64_t)(pat_L + 2) * R) * pps + cl;
+            if (tid < 16 * R) pt[(PR::INVW + (tid >> 4)) * 16 + c] = pp[(int64_t)(tid >> 4) * pps];
+        }
+        if (tid == 0) {
+            tab.rp_min = tb->rp_min; tab.rp_max = tb->rp_max; tab.pd_A = tb->pd_A; tab.pd_c1 = tb->pd_c1;
+            tab.pd_denB = tb->pd_denB; tab.episode_limit = tb->episode_limit;
+        }
+    } else {
     if (tid < R) {
         const int r = tid;
         tab.GaPs[r] = tb->GaPs[r]; tab.GaPs_side[r] = tb->GaPs_side[r]; tab.Pn[r] = tb->Pn[r]; tab.D[r] = tb->D[r];
@@ -191,6 +275,7 @@ __global__ void __launch_bounds__(256) agent_env_episode_scan_kernel(const DevTa
     if (tid == 0) {
         tab.rp_min = tb->rp_min; tab.rp_max = tb->rp_max; tab.pd_A = tb->pd_A; tab.pd_c1 = tb->pd_c1;
         tab.pd_denB = tb->pd_denB; tab.episode_limit = tb->episode_limit;
+    }
     }
     // ---- hidden state ----
     float hreg[J][4];
@@ -251,6 +336,42 @@ __global__ void __launch_bounds__(256) agent_env_episode_scan_kernel(const DevTa
     }
     __syncthreads();
     const PdConsts pdk = pd_consts(tab.pd_A, tab.pd_c1, tab.pd_denB);
+    // table reads of the env half: the shared LDS struct, or (PE) this lane's column er of the per-env block
+#define ES_TAB(name, ROW, member)                                     \
+    auto name = [&](int i) -> double {                                \
+        if constexpr (PE) return pt[(PR::ROW + i) * 16 + er];         \
+        else return tab.member[i];                                    \
+    }
+    ES_TAB(t_GaPs, GAPS, GaPs); ES_TAB(t_GaPs_side, GAPS_SIDE, GaPs_side); ES_TAB(t_Pn, PN, Pn); ES_TAB(t_D, D, D);
+    ES_TAB(t_pd_no, PD_NO, pd_no); ES_TAB(t_pd_no_side, PD_NO_SIDE, pd_no_side); ES_TAB(t_rd_pen, RD_PEN, rd_pen);
+    ES_TAB(t_gr, GR, gr); ES_TAB(t_gr_side, GR_SIDE, gr_side); ES_TAB(t_half, HALF, half); ES_TAB(t_sweep, SWEEP, sweep);
+    ES_TAB(t_swm, SWM, swm); ES_TAB(t_bt, BT, bt); ES_TAB(t_pmin, PMIN, pmin); ES_TAB(t_pmax, PMAX, pmax); ES_TAB(t_gj, GJ, gj);
+    ES_TAB(t_bj, BJ, bj);
+#undef ES_TAB
+    auto t_h2 = [&](int r) -> double {      // PE: 2 half and (sweep + 2 half >= 360) restate the host's values exactly
+        if constexpr (PE) return 2.0 * t_half(r); else return tab.h2[r];
+    };
+    auto t_full = [&](int r) -> bool {
+        if constexpr (PE) return t_sweep(r) + 2.0 * t_half(r) >= 360.0; else return tab.full[r] != 0;
+    };
+    auto t_flags = [&](int i) -> uint8_t {
+        if constexpr (PE) return pfl[i * 16 + er]; else return tab.flags[i];
+    };
+    auto t_invw = [&](int r) -> double {
+        if constexpr (PE) return pt[(PR::INVW + r) * 16 + er]; else return lv_invw[r];
+    };
+    // PAT on per-env tables: this lane's column of the pattern SoA (inv_width[R] | GaPs_lvl | snr_no_lvl | pd_no_lvl | gr_lvl,
+    // each [(L + 2) R]); row of level k of radar r in level table `lt`
+    enum { PP_GAPS = 0, PP_SNR_NO, PP_PD_NO, PP_GR };
+    const double* __restrict__ pp_lane = nullptr;
+    int64_t pps = 0;
+    if constexpr (PAT && PE) {
+        const bool tiled = io.pe_tile > 0;
+        const int64_t tl = tiled ? ee / io.pe_tile : 0;
+        pps = tiled ? (int64_t)io.pe_tile : io.pp_stride;
+        pp_lane = io.pp_tables + tl * (R + 4 * (int64_t)(pat_L + 2) * R) * pps + (tiled ? ee - tl * io.pe_tile : ee);
+    }
+    auto pp_row = [&](int lt, int k, int r) -> double { return pp_lane[(int64_t)(R + (lt * (pat_L + 2) + k) * R + r) * pps]; };
 
     for (int t = 0; t < T; ++t) {
         const int cur = t & 1, nxt = cur ^ 1;
@@ -488,13 +609,20 @@ __global__ void __launch_bounds__(256) agent_env_episode_scan_kernel(const DevTa
             }
             uint32_t in_t = 0;   // bit r: radar r sees the target in its main lobe (start-of-step azimuth and FSM state)
             uint32_t lv_t = 0;   // PAT: the target's level at radar r, bits [4r, 4r + 4)
+            double pl_GaPs[(PAT && PE) ? R : 1], pl_pd_no[(PAT && PE) ? R : 1];   // the target's level rows of the env's column
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                const double lim = (((s_bits >> r) & 1u) ? 0.0 : tab.sweep[r]) + tab.h2[r];
-                if constexpr (PAT)
-                    lv_t |= (uint32_t)beam_level(tab.bt[r], az[r], tab.half[r], lim, tab.full[r] != 0, lv_invw[r], pat_L) << (4 * r);
-                else
-                    in_t |= in_main_lobe(tab.bt[r], az[r], tab.half[r], lim, tab.full[r] != 0) ? (1u << r) : 0u;
+                const double lim = (((s_bits >> r) & 1u) ? 0.0 : t_sweep(r)) + t_h2(r);
+                if constexpr (PAT) {
+                    const int k = beam_level(t_bt(r), az[r], t_half(r), lim, t_full(r), t_invw(r), pat_L);
+                    lv_t |= (uint32_t)k << (4 * r);
+                    if constexpr (PE) {   // requested here, by address, so that they are in flight over the jammer pass
+                        pl_GaPs[r] = pp_row(PP_GAPS, k, r);
+                        pl_pd_no[r] = pp_row(PP_PD_NO, k, r);
+                    }
+                } else {
+                    in_t |= in_main_lobe(t_bt(r), az[r], t_half(r), lim, t_full(r)) ? (1u << r) : 0u;
+                }
             }
             double supp[R], prod[R], snr_all[NP], pd_all[NP];
 #pragma unroll
@@ -509,7 +637,7 @@ __global__ void __launch_bounds__(256) agent_env_episode_scan_kernel(const DevTa
                 const bool is_jamming = (Tj >= 1) && (Tj <= 2 * R);
                 const int target = is_jamming ? ((Tj + 1) / 2 - 1) : 0;
                 const int jtype = Tj % 2;
-                const double pmin = tab.pmin[j], pmax = tab.pmax[j];
+                const double pmin = t_pmin(j), pmax = t_pmax(j);
                 const double power_range = pmax - pmin;
                 float Pc = Pcl[j][er];
                 Pc = Pc < 0.0f ? 0.0f : (Pc > 1.0f ? 1.0f : Pc);
@@ -518,20 +646,24 @@ __global__ void __launch_bounds__(256) agent_env_episode_scan_kernel(const DevTa
                 const double norm = (power_range > 1e-6) ? (double)((actual_f - (float)pmin) / (float)power_range) : 0.0;
                 r_p += tab.rp_max + (tab.rp_min - tab.rp_max) * norm;
                 // received jamming power (environment.py:280-302), receive gain by the jammer's bearing
-                const double denom = tab.denom[j * R + target];
-                const uint8_t fl = tab.flags[j * R + target];
+                double denom;   // (read in place: through an accessor the shared kernels' `live` mask is formed with swapped operands)
+                if constexpr (PE) denom = pt[(PR::DENOM + j * R + target) * 16 + er]; else denom = tab.denom[j * R + target];
+                const uint8_t fl = t_flags(j * R + target);
                 const bool recorded = is_jamming && (actual_d > 0.0) && (denom >= 0.0);
                 const bool live = recorded && denom > 1e-18;
                 const double dsafe = live ? denom : 1.0;
-                const double lim = (((s_bits >> target) & 1u) ? 0.0 : tab.sweep[target]) + tab.h2[target];
+                const double lim = (((s_bits >> target) & 1u) ? 0.0 : t_sweep(target)) + t_h2(target);
                 double grj;
-                if constexpr (PAT)
-                    grj = lv_gr[beam_level(tab.bj[j * R + target], s_az[target][er], tab.half[target], lim, tab.full[target] != 0,
-                                           lv_invw[target], pat_L) * R + target];
+                if constexpr (PAT && PE)
+                    grj = pp_row(PP_GR, beam_level(t_bj(j * R + target), s_az[target][er], t_half(target), lim, t_full(target),
+                                                   t_invw(target), pat_L), target);
+                else if constexpr (PAT)
+                    grj = lv_gr[beam_level(t_bj(j * R + target), s_az[target][er], t_half(target), lim, t_full(target),
+                                           t_invw(target), pat_L) * R + target];
                 else
-                    grj = in_main_lobe(tab.bj[j * R + target], s_az[target][er], tab.half[target], lim, tab.full[target] != 0)
-                              ? tab.gr[target] : tab.gr_side[target];
-                const float num = (actual_f * (float)tab.gj[j]) * (float)grj;
+                    grj = in_main_lobe(t_bj(j * R + target), s_az[target][er], t_half(target), lim, t_full(target))
+                              ? t_gr(target) : t_gr_side(target);
+                const float num = (actual_f * (float)t_gj(j)) * (float)grj;
                 const double q = (fl & MACJD_JR_WEAK_DENOM) ? (double)(num / (float)dsafe) : (double)num / dsafe;
                 const double prj = (live && q > 0.0) ? q : 0.0;
                 const bool is_sup = recorded && (jtype == 1);
@@ -541,18 +673,19 @@ __global__ void __launch_bounds__(256) agent_env_episode_scan_kernel(const DevTa
                 for (int r = 0; r < R; ++r) supp[r] = __builtin_fma(prj, (is_sup && target == r) ? 1.0 : 0.0, supp[r]);
                 dec_tgt[j] = is_dec ? target : -1;
                 // SNR of the false target (environment.py:410-422)
-                const double Pn_t = tab.Pn[target];
+                const double Pn_t = t_Pn(target);
                 const bool live_f = is_dec && Pn_t > 1e-18;
-                const double snr_f = (tab.D[target] * prj) / (live_f ? Pn_t : 1.0);
+                const double snr_f = (t_D(target) * prj) / (live_f ? Pn_t : 1.0);
                 snr_all[R + j] = (live_f && snr_f > 0.0) ? snr_f : 0.0;
             }
 #pragma unroll
             for (int r = 0; r < R; ++r) {   // SNR with jamming (environment.py:316-333)
-                const double den = tab.D[r] * supp[r] + tab.Pn[r];
+                const double den = t_D(r) * supp[r] + t_Pn(r);
                 const bool live = den > 1e-18;
                 double gaps;
-                if constexpr (PAT) gaps = lv_GaPs[(int)((lv_t >> (4 * r)) & 15u) * R + r];
-                else gaps = ((in_t >> r) & 1u) ? tab.GaPs[r] : tab.GaPs_side[r];
+                if constexpr (PAT && PE) gaps = pl_GaPs[r];
+                else if constexpr (PAT) gaps = lv_GaPs[(int)((lv_t >> (4 * r)) & 15u) * R + r];
+                else gaps = ((in_t >> r) & 1u) ? t_GaPs(r) : t_GaPs_side(r);
                 const double q = gaps / (live ? den : 1.0);
                 snr_all[r] = live ? q : 0.0;
             }
@@ -580,16 +713,17 @@ __global__ void __launch_bounds__(256) agent_env_episode_scan_kernel(const DevTa
                 const double pd = pd_all[r];
                 const bool detected = u32_mid(rw[r]) <= pd;
                 track_bits |= detected ? (1u << r) : 0u;
-                r_d += detected ? tab.rd_pen[r] : 0.0;
+                r_d += detected ? t_rd_pen(r) : 0.0;
                 double pd_no_r;
-                if constexpr (PAT) pd_no_r = lv_pd_no[(int)((lv_t >> (4 * r)) & 15u) * R + r];
-                else pd_no_r = ((in_t >> r) & 1u) ? tab.pd_no[r] : tab.pd_no_side[r];
+                if constexpr (PAT && PE) pd_no_r = pl_pd_no[r];
+                else if constexpr (PAT) pd_no_r = lv_pd_no[(int)((lv_t >> (4 * r)) & 15u) * R + r];
+                else pd_no_r = ((in_t >> r) & 1u) ? t_pd_no(r) : t_pd_no_side(r);
                 const double red = pd_no_r - pd;
                 r_j += ((supp_mask & (1u << r)) && red > 0.0) ? red : 0.0;
                 r_j_dec += (hit_mask & (1u << r)) ? 1.0 - prod[r] : 0.0;
-                double x = az[r] + tab.swm[r];
+                double x = az[r] + t_swm(r);
                 x = (x >= 360.0) ? x - 360.0 : x;
-                az[r] = detected ? tab.bt[r] : (((s_bits >> r) & 1u) ? az[r] : x);
+                az[r] = detected ? t_bt(r) : (((s_bits >> r) & 1u) ? az[r] : x);
             }
             r_j += r_j_dec;
             const double reward = r_d + r_p + r_j;
@@ -622,7 +756,21 @@ __global__ void __launch_bounds__(256) agent_env_episode_scan_kernel(const DevTa
             io.scan.theta_a[ee * io.scan.a_se + (int64_t)r * io.scan.a_sx] = az[r];
             io.track[ee * io.k_se + (int64_t)r * io.k_sx] = (s_bits >> r) & 1u;
             io.scan.state[ee * io.scan.st_se + col0 + r * colstep] = (float)az[r];
-            if constexpr (PAT) {
+            if constexpr (PE) {   // the env's own snr_no_lvl row of the last level / snr_no or snr_no_side row, by address
+                if (io.scan.snr_no) {
+                    double v;
+                    if constexpr (PAT) {
+                        v = pp_row(PP_SNR_NO, (int)((lv_last >> (4 * r)) & 15u), r);
+                    } else {
+                        const bool tiled = io.pe_tile > 0;
+                        const int64_t tl = tiled ? ee / io.pe_tile : 0;
+                        const int64_t sps = tiled ? (int64_t)io.pe_tile : io.sp_stride;
+                        const double* sp = io.sp_tables + tl * PR::NSP * sps + (tiled ? ee - tl * io.pe_tile : ee);
+                        v = sp[(int64_t)((((in_t_last >> r) & 1u) ? 6 : 7) * R + r) * sps];   // snr_no | snr_no_side
+                    }
+                    io.scan.snr_no[ee * io.scan.sn_se + (int64_t)r * io.scan.sn_sx] = (float)v;
+                }
+            } else if constexpr (PAT) {
                 if (io.scan.snr_no)
                     io.scan.snr_no[ee * io.scan.sn_se + (int64_t)r * io.scan.sn_sx] =
                         (float)tb->lv_snr_no[(int)((lv_last >> (4 * r)) & 15u) * R + r];
@@ -656,13 +804,16 @@ extern "C" int macjd_agent_env_episode_scan_supported(int32_t J, int32_t R, int3
     return (H == macjd::EP_H && ((J == 3 && R == 4 && A == 9) || (J == 2 && R == 2 && A == 5))) ? 1 : 0;
 }
 
-extern "C" int macjd_agent_env_episode_scan(const macjd_scenario* s, const macjd_agent_env_episode_scan_io* io, void* hip_stream) {
+// The argument checks both closed-loop entry points share (everything but the per-env blocks); `pe`: the caller is the
+// launch on per-env scenario tables, which needs io->pe_tables where the shared launch refuses them
+static int episode_scan_check(const macjd_scenario* s, const macjd_agent_env_episode_scan_io* io, const char* me, bool pe) {
     using namespace macjd;
-    const char* me = "macjd_agent_env_episode_scan";
     if (!s || !io) return set_err(MACJD_EINVAL, "%s: NULL scenario / io", me);
     if (!macjd_agent_env_episode_scan_supported(io->J, io->R, io->H, io->A) || io->actor_hidden != ES_AH)
         return set_err(MACJD_EUNSUPPORTED, "%s: unsupported J / R / H / A / actor width (see include/macjd_nets.h)", me);
-    if (io->pe_tables) return set_err(MACJD_EUNSUPPORTED, "%s: per-env scenario tables are not supported", me);
+    if (!pe && io->pe_tables) return set_err(MACJD_EUNSUPPORTED, "%s: per-env scenario tables are not supported", me);
+    if (pe && !io->pe_tables)
+        return set_err(MACJD_EINVAL, "%s: needs per-env scenario tables (base.pe_tables); macjd_agent_env_episode_scan takes the handle's", me);
     if (s->host.J != io->J || s->host.R != io->R) return set_err(MACJD_EINVAL, "%s: J / R differ from the scenario's", me);
     if (!s->host.scanning) return set_err(MACJD_EINVAL, "%s: the scenario has no scanning tables (macjd_scenario_set_scan)", me);
     if (io->S > 48) return set_err(MACJD_EUNSUPPORTED, "%s: state vectors wider than 48 are not supported", me);
@@ -678,10 +829,17 @@ extern "C" int macjd_agent_env_episode_scan(const macjd_scenario* s, const macjd
     if (io->w1_ld < io->H + io->A + 1) return set_err(MACJD_EINVAL, "%s: row stride smaller than the row", me);
     if (io->avail && io->avail_elem_size != 4 && io->avail_elem_size != 8)
         return set_err(MACJD_EINVAL, "%s: avail_elem_size must be 4 or 8", me);
+    if ((io->n_envs + 15) / 16 > 0x7fffffff) return set_err(MACJD_EINVAL, "%s: too many envs for one launch", me);
+    return MACJD_OK;
+}
+
+extern "C" int macjd_agent_env_episode_scan(const macjd_scenario* s, const macjd_agent_env_episode_scan_io* io, void* hip_stream) {
+    using namespace macjd;
+    const char* me = "macjd_agent_env_episode_scan";
+    const int rc = episode_scan_check(s, io, me, false);
+    if (rc != MACJD_OK) return rc;
     if (io->n_envs == 0) return MACJD_OK;
-    const int64_t wgs = (io->n_envs + 15) / 16;
-    if (wgs > 0x7fffffff) return set_err(MACJD_EINVAL, "%s: too many envs for one launch", me);
-    const dim3 grid((unsigned)wgs), block(256);
+    const dim3 grid((unsigned)((io->n_envs + 15) / 16)), block(256);
     hipStream_t st = (hipStream_t)hip_stream;
     if (s->host.pat_levels > 0) {   // stepped antenna pattern (macjd_scenario_set_scan_pattern)
         if (io->J == 3) hipLaunchKernelGGL((agent_env_episode_scan_kernel<3, 4, 9, 3, true>), grid, block, 0, st, s->dev, *io);
@@ -690,5 +848,48 @@ extern "C" int macjd_agent_env_episode_scan(const macjd_scenario* s, const macjd
     else hipLaunchKernelGGL((agent_env_episode_scan_kernel<2, 2, 5, 3, false>), grid, block, 0, st, s->dev, *io);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_agent_env_episode_scan: %s", hipGetErrorString(err));
+    return MACJD_OK;
+}
+
+extern "C" int macjd_agent_env_episode_scan_pe_supported(int32_t J, int32_t R, int32_t H, int32_t A) {
+    return macjd_agent_env_episode_scan_supported(J, R, H, A);
+}
+
+// The closed-loop launch on per-env scenario tables (include/macjd_nets.h, macjd_agent_env_episode_scan_pe_io); its argument
+// errors mirror macjd_env_step_scan_pe(_pattern)'s, and all of them return before any launch
+extern "C" int macjd_agent_env_episode_scan_pe(const macjd_scenario* s, const macjd_agent_env_episode_scan_pe_io* pio, void* hip_stream) {
+    using namespace macjd;
+    const char* me = "macjd_agent_env_episode_scan_pe";
+    const int rc = episode_scan_check(s, pio ? &pio->base : nullptr, me, true);
+    if (rc != MACJD_OK) return rc;
+    const macjd_agent_env_episode_scan_io* io = &pio->base;
+    const bool pat = pio->pattern.tables != nullptr;
+    if (!pio->pe_flags) return set_err(MACJD_EINVAL, "%s: NULL pe_flags", me);
+    if (!pio->scan_pe.tables) return set_err(MACJD_EINVAL, "%s: NULL per-env scan tables (scan_pe.tables)", me);
+    if (pio->pe_tile < 0) return set_err(MACJD_EINVAL, "%s: pe_tile must be >= 0", me);
+    if (pio->pe_tile == 0 && pio->pe_stride < io->n_envs) return set_err(MACJD_EINVAL, "%s: pe_stride must be >= n_envs (or pe_tile > 0)", me);
+    if (pio->pe_tile == 0 && pio->scan_pe.stride < io->n_envs)
+        return set_err(MACJD_EINVAL, "%s: scan_pe.stride must be >= n_envs (or pe_tile > 0)", me);
+    if (pat && pio->pe_tile == 0 && pio->pattern.stride < io->n_envs)
+        return set_err(MACJD_EINVAL, "%s: pattern.stride must be >= n_envs (or pe_tile > 0)", me);
+    if (pat && (pio->pattern.n_levels < 1 || pio->pattern.n_levels > MACJD_MAX_PATTERN_LEVELS))
+        return set_err(MACJD_EINVAL, "%s: pattern.n_levels outside 1..MACJD_MAX_PATTERN_LEVELS", me);
+    if (s->host.pat_levels > 0 && (!pat || s->host.pat_levels != pio->pattern.n_levels))
+        return set_err(MACJD_EUNSUPPORTED, "%s: the scenario handle carries pattern levels: accepted only with pattern.tables of the same n_levels", me);
+    if (io->n_envs == 0) return MACJD_OK;
+    EpScanPeIO k{};
+    static_cast<macjd_agent_env_episode_scan_io&>(k) = *io;
+    k.pe_flags = pio->pe_flags; k.pe_stride = pio->pe_stride; k.pe_tile = pio->pe_tile;
+    k.sp_tables = pio->scan_pe.tables; k.sp_stride = pio->scan_pe.stride;
+    k.pp_tables = pio->pattern.tables; k.pp_stride = pio->pattern.stride; k.pat_levels = pat ? pio->pattern.n_levels : 0;
+    const dim3 grid((unsigned)((io->n_envs + 15) / 16)), block(256);
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (pat) {
+        if (io->J == 3) hipLaunchKernelGGL((agent_env_episode_scan_kernel<3, 4, 9, 3, true, true, EpScanPeIO>), grid, block, 0, st, s->dev, k);
+        else hipLaunchKernelGGL((agent_env_episode_scan_kernel<2, 2, 5, 3, true, true, EpScanPeIO>), grid, block, 0, st, s->dev, k);
+    } else if (io->J == 3) hipLaunchKernelGGL((agent_env_episode_scan_kernel<3, 4, 9, 3, false, true, EpScanPeIO>), grid, block, 0, st, s->dev, k);
+    else hipLaunchKernelGGL((agent_env_episode_scan_kernel<2, 2, 5, 3, false, true, EpScanPeIO>), grid, block, 0, st, s->dev, k);
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_agent_env_episode_scan_pe: %s", hipGetErrorString(err));
     return MACJD_OK;
 }

@@ -355,16 +355,10 @@ def agent_env_episode_scan_supported(J: int, R: int, H: int, A: int) -> bool:
     return bool(_native.load().macjd_agent_env_episode_scan_supported(int(J), int(R), int(H), int(A)))
 
 
-def agent_env_episode_scan(agent, env_args: dict, n_envs: int, n_agents: int, T: int, avail, eps_sched, greedy_only: bool,
-                           seed: int, counter_base, stage: dict, rdpj_sum=None, h0=None, h_final=None):
-    """Closed-loop episode launch for scanning radars (csrc/macjd_episode_scan.h; include/macjd_nets.h,
-    macjd_agent_env_episode_scan_io): all T steps of agent AND environment of an episode batch in ONE launch.  ``agent`` is
-    the stock RNNAgent on the device, ``env_args`` what ``BatchedElectromagneticEnvironment.episode_scan_args()`` hands
-    over, ``stage`` the runner's time-major staging tensors (state, obs, hidden_state, actions_discrete,
-    actions_continuous, reward, terminated; the static columns of state / obs rows are the caller's).  ``eps_sched`` float32
-    [>= T] and ``counter_base`` int64 / uint64 [1] live on the device."""
-    lib = _native.load()
-    io = _native.AgentEnvEpisodeScanIO()
+def _fill_episode_scan_io(io, agent, env_args: dict, n_envs: int, n_agents: int, T: int, avail, eps_sched, greedy_only: bool,
+                          seed: int, counter_base, stage: dict, rdpj_sum, h0, h_final):
+    """Fill a ``macjd_agent_env_episode_scan_io`` block (the shared launch's own, or the ``base`` of the per-env launch's).
+    Returns the tensors that must outlive the launch call and the tensor whose device / stream the launch uses."""
     keep = []
 
     def f32(t):
@@ -430,9 +424,51 @@ def agent_env_episode_scan(agent, env_args: dict, n_envs: int, n_agents: int, T:
     if h_final is not None:
         assert h_final.is_contiguous() and h_final.dtype == torch.float32 and h_final.numel() == E * J * H
         io.h_final = h_final.data_ptr()
-    with torch.cuda.device(dev):
+    return keep, W1
+
+
+def agent_env_episode_scan(agent, env_args: dict, n_envs: int, n_agents: int, T: int, avail, eps_sched, greedy_only: bool,
+                           seed: int, counter_base, stage: dict, rdpj_sum=None, h0=None, h_final=None):
+    """Closed-loop episode launch for scanning radars (csrc/macjd_episode_scan.h; include/macjd_nets.h,
+    macjd_agent_env_episode_scan_io): all T steps of agent AND environment of an episode batch in ONE launch.  ``agent`` is
+    the stock RNNAgent on the device, ``env_args`` what ``BatchedElectromagneticEnvironment.episode_scan_args()`` hands
+    over, ``stage`` the runner's time-major staging tensors (state, obs, hidden_state, actions_discrete,
+    actions_continuous, reward, terminated; the static columns of state / obs rows are the caller's).  ``eps_sched`` float32
+    [>= T] and ``counter_base`` int64 / uint64 [1] live on the device."""
+    lib = _native.load()
+    io = _native.AgentEnvEpisodeScanIO()
+    keep, W1 = _fill_episode_scan_io(io, agent, env_args, n_envs, n_agents, T, avail, eps_sched, greedy_only, seed, counter_base,
+                                     stage, rdpj_sum, h0, h_final)
+    with torch.cuda.device(W1.device):
         _native.check(lib.macjd_agent_env_episode_scan(env_args["handle"], ctypes.byref(io), _stream(W1)),
                       "macjd_agent_env_episode_scan")
+    del keep
+
+
+def agent_env_episode_scan_pe_supported(J: int, R: int, H: int, A: int) -> bool:
+    return bool(_native.load().macjd_agent_env_episode_scan_pe_supported(int(J), int(R), int(H), int(A)))
+
+
+def agent_env_episode_scan_pe(agent, env_args: dict, n_envs: int, n_agents: int, T: int, avail, eps_sched, greedy_only: bool,
+                              seed: int, counter_base, stage: dict, rdpj_sum=None, h0=None, h_final=None):
+    """``agent_env_episode_scan`` on a per-env scanning scenario batch (include/macjd_nets.h,
+    macjd_agent_env_episode_scan_pe_io): the same launch with every table value read from the env's own columns.
+    ``env_args`` is what ``BatchedElectromagneticEnvironment.episode_scan_pe_args()`` hands over: the shared call's
+    entries plus the batch's scenario tables and flag bytes, their tile width, and the per-env scan / pattern blocks."""
+    lib = _native.load()
+    pio = _native.AgentEnvEpisodeScanPeIO()
+    keep, W1 = _fill_episode_scan_io(pio.base, agent, env_args, n_envs, n_agents, T, avail, eps_sched, greedy_only, seed,
+                                     counter_base, stage, rdpj_sum, h0, h_final)
+    pio.pe_flags, pio.pe_stride, pio.pe_tile = env_args["pe_flags"], int(env_args["n_envs"]), int(env_args["pe_tile"])
+    ctypes.memmove(ctypes.addressof(pio) + _native.AgentEnvEpisodeScanPeIO.scan_pe.offset, ctypes.addressof(env_args["scan_pe_io"]),
+                   ctypes.sizeof(_native.ScanPeIO))
+    if env_args.get("scan_pe_pattern_io") is not None:
+        ctypes.memmove(ctypes.addressof(pio) + _native.AgentEnvEpisodeScanPeIO.pattern.offset,
+                       ctypes.addressof(env_args["scan_pe_pattern_io"]), ctypes.sizeof(_native.ScanPePatternIO))
+    with torch.cuda.device(W1.device):
+        _native.check(lib.macjd_agent_env_episode_scan_pe(env_args["handle"], ctypes.byref(pio), _stream(W1)),
+                      "macjd_agent_env_episode_scan_pe")
+    del keep
 
 
 def gru_sequence_reference(gi: torch.Tensor, w_hh: torch.Tensor, b_hh: torch.Tensor,

@@ -33,6 +33,7 @@ for normal operation.
                                          first of them (four staging sets) / one launch per update, issued by the one before it
     MACJD_GRAPHED_ALLREDUCE   0 | 1      with ranks: RCCL all-reduce captured inside the update graph
     MACJD_CLOSED_LOOP_ROLLOUT 0 | 1      scanning radars: step-by-step rollout / agent and env of an episode batch in one launch
+                                         (shared scenario tables and per-env scanning scenario batches, pattern or not)
 """
 from __future__ import annotations
 

@@ -344,7 +344,7 @@ class BatchedEpisodeRunner:
         if device_schedule and self.fused_rollout_available():
             self._fused_launches(T)     # whole-episode launches (static observation): the same rows as the loop below
             return
-        if device_schedule and self.closed_loop_rollout and self.closed_loop_available():
+        if device_schedule and self.closed_loop_rollout and (self.closed_loop_available() or self.closed_loop_pe_available()):
             self._closed_loop_launch(T)   # scanning radars: agent and env of the whole batch in one launch
             return
         for t in range(T):
@@ -463,17 +463,34 @@ class BatchedEpisodeRunner:
     def closed_loop_available(self) -> bool:
         """The env's beams scan (dynamic observation, shared scenario tables), the MAC is the stock RNNAgent on a HIP
         device, and the closed-loop episode kernel covers the sizes (``ops.agent_env_episode_scan_supported``)."""
+        return self._closed_loop_conditions(per_env=False)
+
+    def closed_loop_pe_available(self) -> bool:
+        """``closed_loop_available`` for a per-env scanning scenario batch: the same conditions with the env bringing one
+        scenario per env (``episode_scan_pe_args``, ``ops.agent_env_episode_scan_pe_supported``)."""
+        return self._closed_loop_conditions(per_env=True)
+
+    def _closed_loop_conditions(self, per_env: bool) -> bool:
         env = self.env
-        if self.device.type != "cuda" or not hasattr(env, "episode_scan_args") or not getattr(env.scenario, "scanning", False):
+        args_name = "episode_scan_pe_args" if per_env else "episode_scan_args"
+        if self.device.type != "cuda" or not hasattr(env, args_name) or not getattr(env.scenario, "scanning", False):
             return False
-        if getattr(env, "scenario_batch", None) is not None or getattr(env, "kernel_flags", 0) != 0:
+        if (getattr(env, "scenario_batch", None) is not None) != per_env or getattr(env, "kernel_flags", 0) != 0:
             return False
         agent = getattr(self.mac, "agent", None)
         if agent is None or not hasattr(agent, "fc2_q_head") or not next(agent.parameters()).is_cuda:
             return False
         from .. import ops
+        supported = ops.agent_env_episode_scan_pe_supported if per_env else ops.agent_env_episode_scan_supported
         return (getattr(agent, "actor_hidden_dim", 0) == 128 and agent.input_shape == env.state_dim and env.state_dim <= 48
-                and ops.agent_env_episode_scan_supported(self.n_agents, env.num_radars, agent.rnn_hidden_dim, agent.n_actions))
+                and supported(self.n_agents, env.num_radars, agent.rnn_hidden_dim, agent.n_actions))
+
+    def rollout_closed_loop_pe(self, test_mode=False, n_steps=None):
+        """``rollout_closed_loop`` on a per-env scanning scenario batch (``ops.agent_env_episode_scan_pe``): one launch in
+        which every env reads its own tables; its env half is bit-identical to the per-env step kernels' all-float64 form."""
+        if not self.closed_loop_pe_available():
+            raise RuntimeError("rollout_closed_loop_pe: not available for this environment / agent (closed_loop_pe_available())")
+        self._rollout_closed_loop(test_mode, n_steps, "rollout_closed_loop_pe")
 
     def rollout_closed_loop(self, test_mode=False, n_steps=None):
         """One episode batch (or its first ``n_steps`` steps) of a scanning scenario in ONE launch
@@ -484,10 +501,13 @@ class BatchedEpisodeRunner:
         rewards by the all-float64 env form (<= (R + J) 6e-7), which can flip a choice only on a near-tie."""
         if not self.closed_loop_available():
             raise RuntimeError("rollout_closed_loop: not available for this environment / agent (closed_loop_available())")
+        self._rollout_closed_loop(test_mode, n_steps, "rollout_closed_loop")
+
+    def _rollout_closed_loop(self, test_mode, n_steps, what):
         T = self.episode_limit
         n = T if n_steps is None else int(n_steps)
         if not 1 <= n <= T:
-            raise ValueError(f"rollout_closed_loop: n_steps must be in 1..{T}, got {n_steps}")
+            raise ValueError(f"{what}: n_steps must be in 1..{T}, got {n_steps}")
         if getattr(self, "_eps_sched", None) is None:
             self._eps_sched = torch.zeros(T, dtype=torch.float32, device=self.device)
             self._ctr_base = torch.zeros(1, dtype=torch.int64, device=self.device)
@@ -504,10 +524,13 @@ class BatchedEpisodeRunner:
         of the state / obs staging rows; their static columns and the availability rows never change and are filled once."""
         from .. import ops
         if not self._static_filled:
-            self._fill_static()
-        ops.agent_env_episode_scan(self.mac.agent, self.env.episode_scan_args(), self.batch_envs, self.n_agents, n, self._avail,
-                                   self._eps_sched, bool(test_mode), self.mac.select_seed, self._ctr_base, self.stage,
-                                   rdpj_sum=self._rdpj_sum, h_final=self.mac.hidden_states)
+            self._fill_static()   # (a per-env batch: each env's own state row)
+        if getattr(self.env, "scenario_batch", None) is not None:   # per-env scenario batch: every env reads its own tables
+            launch, env_args = ops.agent_env_episode_scan_pe, self.env.episode_scan_pe_args()
+        else:
+            launch, env_args = ops.agent_env_episode_scan, self.env.episode_scan_args()
+        launch(self.mac.agent, env_args, self.batch_envs, self.n_agents, n, self._avail, self._eps_sched, bool(test_mode),
+               self.mac.select_seed, self._ctr_base, self.stage, rdpj_sum=self._rdpj_sum, h_final=self.mac.hidden_states)
 
     def run(self, test_mode=False, store=True, sync_stats=True):
         """One batch of E episodes.  Returns the reference's ``run_info`` keys as means over the E
@@ -518,6 +541,8 @@ class BatchedEpisodeRunner:
             self.rollout_fused(test_mode=test_mode)
         elif self.closed_loop_rollout and self.closed_loop_available():
             self.rollout_closed_loop(test_mode=test_mode)
+        elif self.closed_loop_rollout and self.closed_loop_pe_available():
+            self.rollout_closed_loop_pe(test_mode=test_mode)
         elif getattr(self, "_graph", None) is not None and not test_mode:
             self.rollout_graphed()
         else:

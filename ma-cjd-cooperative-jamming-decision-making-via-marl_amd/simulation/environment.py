@@ -431,6 +431,19 @@ class BatchedElectromagneticEnvironment:
                 "episode": self._episode, "seed": self.seed, "env_offset": self.env_offset, "n_radars": self.num_radars,
                 "pe_tables": None}
 
+    def episode_scan_pe_args(self) -> Dict[str, Any]:
+        """What the closed-loop episode launch on per-env tables (``ops.agent_env_episode_scan_pe``) needs from a per-env
+        scanning scenario batch: the entries of ``episode_scan_args`` plus the batch's scenario tables and flag bytes
+        with their tile width, ``n_envs`` (the plain layout's row stride), the per-env scan block and, under a stepped
+        pattern, the per-env level tables (else None)."""
+        if self._scan_pe_io is None:
+            raise RuntimeError("episode_scan_pe_args: needs a per-env scanning scenario batch (ScenarioBatch(..., scan=True)); "
+                               "episode_scan_args serves shared scenario tables")
+        return {"handle": self._handle.ptr, "scan_io": self._scan_io, "track": self._track, "step": self._step,
+                "episode": self._episode, "seed": self.seed, "env_offset": self.env_offset, "n_radars": self.num_radars,
+                "pe_tables": self._pe_tables.data_ptr(), "pe_flags": self._pe_flags.data_ptr(), "pe_tile": self._pe_tile,
+                "n_envs": self.batch_envs, "scan_pe_io": self._scan_pe_io, "scan_pe_pattern_io": self._scan_pe_pattern_io}
+
     def _refuse_scanning(self, what: str) -> None:
         # macjd_env_step_many rests on "a step's outcome depends on the past only through the step counter" (include/
         # macjd.h), which the beam azimuth breaks; the timing helper runs the non-scanning launch
