@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MACJD_ABI_VERSION 11
+#define MACJD_ABI_VERSION 12
 #define MACJD_PE_ROWS(R, J) (6 * (R) + 3 * (J) + (J) * (R))
 #define MACJD_PE_SCAN_ROWS(R, J) (10 * (R) + (J) * (R))
 #define MACJD_PE_SCAN_PATTERN_ROWS(R, L) ((R) + 4 * ((L) + 2) * (R))
@@ -62,7 +62,8 @@ extern "C" {
  * the sim-config YAML.  Replaces the per-step recomputation inside
  * ElectromagneticEnvironment.step (simulation/environment.py:316-333: echo power, SNR without
  * jamming; core/radar.py:35-60; utils/math_utils.py:40-42 distances) — all of it is static
- * because nothing in step() moves an entity (environment.py:237-238 is a TODO).
+ * because nothing in step() moves an entity (environment.py:237-238 is a TODO).  (Opt-in motion, macjd_motion_io below:
+ * one such set of tables per step of an episode; this handle then holds frame 0.)
  * All pointers are HOST pointers, copied by macjd_scenario_create.
  */
 typedef struct macjd_scenario_desc {
@@ -260,6 +261,43 @@ typedef struct macjd_scan_pe_pattern_io {
     int32_t reserved;
 } macjd_scan_pe_pattern_io;
 
+/*
+ * Moving entities (opt-in, sim-config `environment_params.motion`): target, radars and jammers move with constant
+ * velocities that do not depend on the actions, so every distance-dependent table is a pure function of the step counter.
+ * The host compiles one FRAME per step of an episode: frame k is the static scenario whose positions are, per axis,
+ * p0 + k (v dt) in float64 (dt = step_seconds), compiled like any other scenario (macjd_scenario_desc).  Device arrays:
+ *   frames       float64 [n_frames, MACJD_PE_ROWS(R,J)], frame-major: row t of frame f at frames[f * MACJD_PE_ROWS + t], rows
+ *                in the order of macjd_step_io.pe_tables (GaPs | Pn | D | pd_no | rd_pen | gr | pmin | pmax | gj | denom) —
+ *                the tiled per-env layout at tile width 1 with the frame index as the tile index: one env-step reads one
+ *                contiguous block;
+ *   frame_flags  uint8 [n_frames, J*R] (MACJD_JR_*), flag i of frame f at frame_flags[f * J*R + i];
+ *   frame_snr_no float64 [n_frames, R], optional (needed for snr_no): max(0, GaPs / Pn) of each frame as the host formed it;
+ *   positions    float32 [n_frames + 1, n_pos], n_pos = 2R + 2J: the position entries of frame k's state vector in state
+ *                order (per radar x, y; then per jammer x, y);
+ *   position_columns int32 [n_pos]: their columns in a state row.
+ * A step whose counter is k before it (for item t of a many-step launch: step[e] + t) runs macjd_env_step's arithmetic,
+ * order, RNG slots, Philox keying and stores on frame f = min(k, n_frames - 1) — the positions the agents saw when they
+ * chose the action.  The entities then move: the same launch copies positions[min(k + 1, n_frames)] into the env's state
+ * row at position_columns (plain stores; every other column is left alone) and, when snr_no is given, writes
+ * (float)frame_snr_no[f] to it.  Results are bit-identical to macjd_env_step on per-env tables (pe_tables) whose column for
+ * env e holds frame f_e, in the same (production or general all-float64) form.  The target is not part of the state
+ * vector: its motion acts through the tables only.  A step's outcome still depends on the past through the step counter
+ * alone, so the many-step launch stays legal (macjd_env_step_many_moving).  n_frames = the scenario's episode_limit.
+ */
+typedef struct macjd_motion_io {
+    const double*  frames;
+    const uint8_t* frame_flags;
+    const double*  frame_snr_no;      /* optional unless snr_no is given */
+    const float*   positions;
+    const int32_t* position_columns;
+    int32_t n_frames;                 /* F >= 1 */
+    int32_t n_pos;                    /* must equal 2R + 2J */
+    float*  state;    int64_t st_se;  /* [E,S] state rows, row stride in elements.  position_columns lives on the device, so
+                                         the library cannot check it: the CALLER guarantees 0 <= column < st_se for all
+                                         n_pos entries (a column outside the row is written out of bounds) */
+    float*  snr_no;   int64_t sn_se, sn_sx;   /* optional [E,R] SNR without jamming of the frame used; single steps only */
+} macjd_motion_io;
+
 /* library / device */
 int         macjd_abi_version(void);
 const char* macjd_last_error(void);
@@ -338,6 +376,21 @@ int macjd_env_step_scan_pe_pattern(const macjd_scenario* s, const macjd_step_io*
    configuration only (Philox uniforms, float32 actions); io->u, P64 and the float64 diagnostics must be NULL. */
 int macjd_env_step_many(const macjd_scenario* s, const macjd_step_io* io, int32_t n_steps, int64_t t_stride,
                         void* hip_stream);
+
+/* macjd_env_step for a moving scenario (see macjd_motion_io): the table column is chosen by the env's step counter.
+   io->pe_tables must be NULL; the handle supplies R, J, episode_limit, the r_p bounds and the Pd constants, every table
+   value comes from the frame.  One lane per env; compiled sizes 2j/2r, 3j/4r, 6j/8r have production and general variants,
+   every other size runs the generic-size kernel. */
+int macjd_env_step_moving(const macjd_scenario* s, const macjd_step_io* io, const macjd_motion_io* motion, void* hip_stream);
+/* macjd_env_step_many for a moving scenario: same contract and restrictions (production configuration, compiled sizes with
+   a production variant); item (t, e) runs frame min(step[e] + t, n_frames - 1); state rows end as after the last step;
+   motion->snr_no must be NULL. */
+int macjd_env_step_many_moving(const macjd_scenario* s, const macjd_step_io* io, const macjd_motion_io* motion,
+                               int32_t n_steps, int64_t t_stride, void* hip_stream);
+/* position part of a reset, issued next to macjd_env_reset with the same mask: frame-0 positions into the state rows of
+   the envs with mask != 0 (all when mask == NULL) */
+int macjd_env_reset_moving(const macjd_scenario* s, int64_t n_envs, const macjd_motion_io* motion, const uint8_t* mask,
+                           void* hip_stream);
 
 /* timing helper for bench.py: `iters` back-to-back env_step launches, replayed from one HIP graph on a private
    stream after the work queued on `hip_stream` has finished (as the benchmark's rollout replays them, so the

@@ -14,7 +14,7 @@ LIB_NAME = "libmacjd_hip.so"
 # MACJD_LIB points at another build of the same sources (kernel A/B runs); the default is the in-tree library
 LIB_PATH = os.environ.get("MACJD_LIB") or os.path.join(_PKG_DIR, LIB_NAME)
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 STEP_ARITH_F64 = 1
 STEP_LANE_KERNEL = 2
 STEP_SLOT_KERNEL = 4
@@ -40,6 +40,7 @@ EXPORTS = [
     "macjd_actor_gradient_supported", "macjd_actor_gradient",
     "macjd_linear_wgrad_many_norm", "macjd_linear_wgrad_many_norm_partials", "macjd_clip_adam_step_reduced",
     "macjd_prefetch_batches_supported", "macjd_prefetch_batches",
+    "macjd_env_step_moving", "macjd_env_step_many_moving", "macjd_env_reset_moving",
 ]
 
 
@@ -107,6 +108,18 @@ class ScanPePatternIO(ctypes.Structure):
     """ctypes mirror of ``macjd_scan_pe_pattern_io`` (include/macjd.h): the per-env pattern SoA,
     MACJD_PE_SCAN_PATTERN_ROWS(R, L) rows."""
     _fields_ = [("tables", ctypes.c_void_p), ("stride", ctypes.c_int64), ("n_levels", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class MotionIO(ctypes.Structure):
+    """ctypes mirror of ``macjd_motion_io`` (include/macjd.h): the per-step frame tables of a moving scenario and the
+    state rows whose position columns the step rewrites."""
+    _fields_ = [
+        ("frames", ctypes.c_void_p), ("frame_flags", ctypes.c_void_p), ("frame_snr_no", ctypes.c_void_p),
+        ("positions", ctypes.c_void_p), ("position_columns", ctypes.c_void_p),
+        ("n_frames", ctypes.c_int32), ("n_pos", ctypes.c_int32),
+        ("state", ctypes.c_void_p), ("st_se", ctypes.c_int64),
+        ("snr_no", ctypes.c_void_p), ("sn_se", ctypes.c_int64), ("sn_sx", ctypes.c_int64),
+    ]
 
 
 class QheadIO(ctypes.Structure):
@@ -469,6 +482,14 @@ def load() -> ctypes.CDLL:
     lib.macjd_env_reset_scan_pe.restype = ctypes.c_int
     lib.macjd_env_reset_scan_pe.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ScanIO), ctypes.POINTER(ScanPeIO),
                                             ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
+    lib.macjd_env_step_moving.restype = ctypes.c_int
+    lib.macjd_env_step_moving.argtypes = [ctypes.c_void_p, ctypes.POINTER(StepIO), ctypes.POINTER(MotionIO), ctypes.c_void_p]
+    lib.macjd_env_step_many_moving.restype = ctypes.c_int
+    lib.macjd_env_step_many_moving.argtypes = [ctypes.c_void_p, ctypes.POINTER(StepIO), ctypes.POINTER(MotionIO), ctypes.c_int32,
+                                               ctypes.c_int64, ctypes.c_void_p]
+    lib.macjd_env_reset_moving.restype = ctypes.c_int
+    lib.macjd_env_reset_moving.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(MotionIO), ctypes.c_void_p,
+                                           ctypes.c_void_p]
     lib.macjd_env_step.argtypes = [ctypes.c_void_p, ctypes.POINTER(StepIO), ctypes.c_void_p]
     lib.macjd_env_step_timed.restype = ctypes.c_int
     lib.macjd_env_step_timed.argtypes = [ctypes.c_void_p, ctypes.POINTER(StepIO), ctypes.c_int, ctypes.c_void_p,

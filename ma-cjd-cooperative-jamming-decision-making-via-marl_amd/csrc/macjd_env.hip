@@ -435,6 +435,16 @@ static void fill_scan(X& x, const macjd_scan_io* sc) {
     x.snr_no = sc->snr_no; x.sn_se = sc->sn_se; x.sn_sx = sc->sn_sx;
 }
 
+// ... and a MOVING launch's (include/macjd.h, macjd_motion_io)
+template <class X>
+static void fill_motion(X& x, const macjd_motion_io* mo) {
+    x.frames = mo->frames; x.frame_flags = mo->frame_flags; x.frame_snr_no = mo->frame_snr_no;
+    x.positions = mo->positions; x.position_columns = mo->position_columns;
+    x.state = mo->state; x.mv_st_se = mo->st_se;
+    x.mv_snr_no = mo->snr_no; x.mv_sn_se = mo->sn_se; x.mv_sn_sx = mo->sn_sx;
+    x.n_frames = mo->n_frames; x.n_pos = mo->n_pos;
+}
+
 template <int JT, int RT, bool PE, bool FAST, bool REG = false, bool PD32 = false, bool SCAN = false, bool PAT = false, class IO>
 static void launch_lanes(dim3 grid, dim3 block, hipStream_t stream, const macjd_scenario* s, const IO& io) {
     hipLaunchKernelGGL((macjd::env_step_kernel<JT, RT, PE, FAST, IO, REG, PD32, SCAN, PAT>), grid, block, 0, stream, s->dev, io);
@@ -951,6 +961,103 @@ int macjd_env_step_many(const macjd_scenario* s, const macjd_step_io* io, int32_
     hipLaunchKernelGGL(macjd::env_advance_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)hip_stream, io->n_envs,
                        n_steps, io->step, io->r_dpj, io->r_dpj_sum);
     return launch_status("macjd_env_step_many");
+}
+
+// ---- moving scenarios (include/macjd.h, macjd_motion_io; kernels in macjd_env_motion.hip) ----
+
+static int validate_motion(const macjd_scenario* s, const macjd_motion_io* mo, const char* what) {
+    if (!s || !mo) return set_err(MACJD_EINVAL, "%s: NULL scenario / motion io", what);
+    if (!mo->frames || !mo->frame_flags || !mo->positions || !mo->position_columns || !mo->state)
+        return set_err(MACJD_EINVAL, "%s: frames / frame_flags / positions / position_columns / state is NULL", what);
+    if (mo->n_frames < 1) return set_err(MACJD_EINVAL, "%s: n_frames < 1", what);
+    if (mo->n_frames != s->host.episode_limit)
+        return set_err(MACJD_EINVAL, "%s: n_frames must equal the scenario's episode_limit", what);
+    if (mo->n_pos != 2 * s->host.R + 2 * s->host.J) return set_err(MACJD_EINVAL, "%s: n_pos must equal 2R + 2J", what);
+    if (mo->st_se < mo->n_pos) return set_err(MACJD_EINVAL, "%s: state row stride smaller than the number of position columns", what);
+    if (mo->snr_no && (!mo->frame_snr_no || mo->sn_se < 0 || mo->sn_sx < 0 || (mo->sn_se == 0 && mo->sn_sx == 0)))
+        return set_err(MACJD_EINVAL, "%s: snr_no needs frame_snr_no and non-negative, non-zero strides", what);
+    return MACJD_OK;
+}
+
+// The production form's 32-bit offsets into the motion arrays: every state element of a row (the position columns lie below
+// the row stride; the caller's tables say which), the snr_no output
+static bool motion_spans_ok(const macjd_motion_io* mo, int64_t E, int R) {
+    return span_ok(E, mo->st_se, 1, 1, 4, mo->st_se - 1) && (!mo->snr_no || span_ok(E, mo->sn_se, mo->sn_sx, R, 4));
+}
+// MOVING launches: always the lane kernel on the frame tables (include/macjd.h, macjd_env_step_moving)
+static int launch_step_moving(const macjd_scenario* s, const macjd_step_io* io, const macjd_motion_io* mo, hipStream_t stream,
+                              int32_t many_T, int64_t t_stride, const char* who) {
+    const int64_t E = io->n_envs * (many_T > 0 ? many_T : 1);   // work items of the launch
+    const int J = s->host.J, R = s->host.R;
+    if (many_T > 65535) return set_err(MACJD_EINVAL, "%s: at most 65535 steps per launch", who);
+    const LaneGrid lg = lane_grid(E);
+    const dim3 gf((unsigned)(many_T > 0 ? (io->n_envs + lg.block - 1) / lg.block : lg.blocks), (unsigned)(many_T > 0 ? many_T : 1));
+    const dim3 g(lg.strided), b(lg.block);
+    const bool fast = macjd::motion_size_compiled(J, R) && production_io(io, J, R, lg.blocks, many_T, t_stride) &&
+                      motion_spans_ok(mo, io->n_envs, R);
+    if (fast) {
+        macjd::MotionStepIO<macjd::FastStepIO> f{};
+        fill_fast(f, io, many_T, t_stride);
+        fill_motion(f, mo);
+        (void)macjd::launch_motion_fast(J, R, gf, b, stream, s->dev, f);
+    } else {
+        if (many_T > 0)
+            return set_err(MACJD_EUNSUPPORTED, "%s: production configuration at a compiled size (2j/2r, 3j/4r, 6j/8r) only: Philox "
+                           "uniforms, float32 actions, no float64 diagnostics, offsets below 2^32 bytes", who);
+        macjd::MotionStepIO<macjd_step_io> w{};
+        static_cast<macjd_step_io&>(w) = *io;
+        fill_motion(w, mo);
+        macjd::launch_motion_general(J, R, g, b, stream, s->dev, w);
+    }
+    return launch_status(who);
+}
+
+int macjd_env_step_moving(const macjd_scenario* s, const macjd_step_io* io, const macjd_motion_io* motion, void* hip_stream) {
+    const char* me = "macjd_env_step_moving";
+    int rc = validate_io(s, io);
+    if (rc != MACJD_OK) return rc;
+    rc = validate_motion(s, motion, me);
+    if (rc != MACJD_OK) return rc;
+    if (io->pe_tables) return set_err(MACJD_EINVAL, "%s: io->pe_tables must be NULL (the frames are the tables)", me);
+    if (io->flags & MACJD_STEP_SLOT_KERNEL)
+        return set_err(MACJD_EUNSUPPORTED, "%s: the (env x slot) kernel has no moving variant (one lane per env only)", me);
+    if (io->n_envs == 0) return MACJD_OK;
+    return launch_step_moving(s, io, motion, (hipStream_t)hip_stream, 0, 0, me);
+}
+
+int macjd_env_step_many_moving(const macjd_scenario* s, const macjd_step_io* io, const macjd_motion_io* motion, int32_t n_steps,
+                               int64_t t_stride, void* hip_stream) {
+    const char* me = "macjd_env_step_many_moving";
+    int rc = validate_io(s, io);
+    if (rc != MACJD_OK) return rc;
+    rc = validate_motion(s, motion, me);
+    if (rc != MACJD_OK) return rc;
+    if (io->pe_tables) return set_err(MACJD_EINVAL, "%s: io->pe_tables must be NULL (the frames are the tables)", me);
+    if (n_steps < 1 || t_stride < 0) return set_err(MACJD_EINVAL, "%s: bad n_steps / t_stride", me);
+    if (io->pd || io->snr_with || motion->snr_no) return set_err(MACJD_EINVAL, "%s: pd / snr_with / snr_no are not written (pass NULL)", me);
+    if (io->r_dpj_sum && !io->r_dpj) return set_err(MACJD_EINVAL, "%s: r_dpj_sum needs the per-step r_dpj buffer", me);
+    if (io->n_envs == 0) return MACJD_OK;
+    rc = launch_step_moving(s, io, motion, (hipStream_t)hip_stream, n_steps, t_stride, me);
+    if (rc != MACJD_OK) return rc;
+    int64_t grid = (io->n_envs * 3 + 255) / 256;
+    if (grid > 4096) grid = 4096;
+    hipLaunchKernelGGL(macjd::env_advance_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)hip_stream, io->n_envs,
+                       n_steps, io->step, io->r_dpj, io->r_dpj_sum);
+    return launch_status(me);
+}
+
+int macjd_env_reset_moving(const macjd_scenario* s, int64_t n_envs, const macjd_motion_io* motion, const uint8_t* mask,
+                           void* hip_stream) {
+    const char* me = "macjd_env_reset_moving";
+    if (n_envs < 0) return set_err(MACJD_EINVAL, "%s: bad argument", me);
+    const int rc = validate_motion(s, motion, me);
+    if (rc != MACJD_OK) return rc;
+    if (n_envs == 0) return MACJD_OK;
+    int64_t grid = (n_envs + 255) / 256;
+    if (grid > 4096) grid = 4096;
+    macjd::launch_motion_reset(dim3((unsigned)grid), dim3(256), (hipStream_t)hip_stream, n_envs, motion->n_pos, motion->positions,
+                               motion->position_columns, motion->state, motion->st_se, mask);
+    return launch_status(me);
 }
 
 static int env_step_timed_impl(const macjd_scenario* s, const macjd_step_io* io, int iters, void* hip_stream,

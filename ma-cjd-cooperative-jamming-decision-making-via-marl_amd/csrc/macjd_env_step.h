@@ -118,6 +118,25 @@ struct ScanPePatStepIO : ScanPeStepIO<Base> {
     int32_t pat_levels, pp_reserved;
 };
 
+// Argument block of a MOVING launch (include/macjd.h, macjd_motion_io): the step's own block plus the per-step frame tables
+// and the state rows whose position columns the step rewrites.  The type switches the kernel (io_moves): the other
+// instantiations keep their argument block and code.  Offsets of the production form are 32-bit like FastStepIO's (the host
+// checks the spans).
+template <class Base>
+struct MotionStepIO : Base {
+    const double* frames;
+    const uint8_t* frame_flags;
+    const double* frame_snr_no;
+    const float* positions;
+    const int32_t* position_columns;
+    float* state;
+    float* mv_snr_no;
+    int64_t mv_st_se, mv_sn_se, mv_sn_sx;
+    int32_t n_frames, n_pos;
+};
+template <class IO> struct io_moves : std::false_type {};
+template <class Base> struct io_moves<MotionStepIO<Base>> : std::true_type {};
+
 // Per-lane pattern state of an env-step: the number of levels and the target's level at each radar, four bits per radar
 // in 64-bit words (word r >> 4; shifts only, so the per-lane index of the PD32 re-evaluation loop — compiled sizes,
 // R <= 16, one word — is no private-array index).  Empty without a pattern: those instantiations carry nothing.
@@ -182,6 +201,11 @@ __global__ void __launch_bounds__(256) env_step_kernel(const DevTables* __restri
     constexpr bool PSH = PAT && !PE;    // the pattern's level tables of the handle (LDS copies)
     static_assert(!SPP || !FAST || (JT && RT), "PAT on per-env tables: production variant at compiled sizes only");
     constexpr bool SSH = SCAN && !PE;   // ... on the shared tables (LDS copies of the gathered ones)
+    // MOV (IO = MotionStepIO<...>; include/macjd.h, macjd_motion_io): the per-env-table path with the table column chosen by
+    // the env's step counter instead of by its index, plus the position columns of the env's state row, rewritten with the
+    // next frame's positions.  Same arithmetic, order, RNG slots and stores as the PE kernel of the same form.
+    constexpr bool MOV = io_moves<IO>::value;
+    static_assert(!MOV || (PE && !SCAN), "MOV: the per-env-table path of the non-scanning step");
     constexpr int NJ = JT ? JT : MAXJ;
     constexpr int NR = RT ? RT : MAXR;
     const int J = JT ? JT : tb->J;
@@ -301,11 +325,22 @@ __global__ void __launch_bounds__(256) env_step_kernel(const DevTables* __restri
 
         // table accessors: this env's SoA column (PE) or the shared tables
         // this env's column of the per-env tables: plain SoA (row stride pe_stride) or tiled (row stride = tile width)
-        const int64_t ps = (PE && io.pe_tile > 0) ? (int64_t)io.pe_tile : io.pe_stride;
-        const int64_t pe_tile_idx = (PE && io.pe_tile > 0) ? e / io.pe_tile : 0;
-        const int64_t pe_col = (PE && io.pe_tile > 0) ? e - pe_tile_idx * io.pe_tile : e;
-        const double* __restrict__ pe = PE ? io.pe_tables + pe_tile_idx * (6 * R + 3 * J + J * R) * ps + pe_col : nullptr;
-        const uint8_t* __restrict__ pf = PE ? io.pe_flags + pe_tile_idx * (J * R) * ps + pe_col : nullptr;
+        // MOV: the column is frame f = min(step_before, n_frames - 1) of the frame-major tables — the tiled layout at tile
+        // width 1 with the frame index as the tile index (row stride 1: one contiguous block per env-step)
+        int32_t mv_frame = 0;
+        if constexpr (MOV) {
+            mv_frame = step_before < io.n_frames - 1 ? step_before : io.n_frames - 1;
+            mv_frame = mv_frame > 0 ? mv_frame : 0;
+        }
+        const int64_t ps = MOV ? (int64_t)1 : (PE && io.pe_tile > 0) ? (int64_t)io.pe_tile : io.pe_stride;
+        const int64_t pe_tile_idx = MOV ? (int64_t)mv_frame : (PE && io.pe_tile > 0) ? e / io.pe_tile : 0;
+        const int64_t pe_col = MOV ? (int64_t)0 : (PE && io.pe_tile > 0) ? e - pe_tile_idx * io.pe_tile : e;
+        const double* pe_base = nullptr;
+        const uint8_t* pf_base = nullptr;
+        if constexpr (MOV) { pe_base = io.frames; pf_base = io.frame_flags; }
+        else if constexpr (PE) { pe_base = io.pe_tables; pf_base = io.pe_flags; }
+        const double* __restrict__ pe = PE ? pe_base + pe_tile_idx * (6 * R + 3 * J + J * R) * ps + pe_col : nullptr;
+        const uint8_t* __restrict__ pf = PE ? pf_base + pe_tile_idx * (J * R) * ps + pe_col : nullptr;
         // PE, compile-time sizes: every table value this env-step can touch is requested up front so that all the
         // loads are in flight together — left at their use sites they sit behind branches and possibly-aliasing
         // stores and arrive one memory latency at a time.  Static-index rows (per radar / per jammer) directly; the
@@ -840,6 +875,29 @@ MACJD_ENV_UNROLL_SIZED(NR)
             io.out64[e * 4 + 2] = r_p;
             io.out64[e * 4 + 3] = r_j;
         }
+        if constexpr (MOV) {
+            // the entities move: frame min(step_count, n_frames)'s positions into this env's state row (the last item of a
+            // many-step launch only: rows end as after the last step); the columns are wave-uniform (scalar loads)
+            if (last_t) {
+                int32_t fn = step_count < io.n_frames ? step_count : io.n_frames;
+                fn = fn > 0 ? fn : 0;
+                const float* __restrict__ pos = io.positions + (int64_t)fn * io.n_pos;
+                constexpr int NPOS = 2 * (NR + NJ);
+                if constexpr (PRE) {
+#pragma unroll
+                    for (int i = 0; i < NPOS; ++i) at(io.state, e, io.mv_st_se, io.position_columns[i], 1) = pos[i];
+                } else {
+                    for (int i = 0; i < io.n_pos; ++i) at(io.state, e, io.mv_st_se, io.position_columns[i], 1) = pos[i];
+                }
+            }
+            if (io.mv_snr_no && !many) {
+MACJD_ENV_UNROLL_SIZED(NR)
+                for (int r = 0; r < NR; ++r) {
+                    if (!RT && r >= R) break;
+                    at(io.mv_snr_no, e, io.mv_sn_se, r, io.mv_sn_sx) = (float)io.frame_snr_no[(int64_t)mv_frame * R + r];
+                }
+            }
+        }
     };
     if constexpr (FAST) {
         // one env per lane, no grid-stride loop: inside a loop every argument and table constant is loop-invariant,
@@ -859,5 +917,17 @@ void launch_scan_pe_generic(dim3 grid, dim3 block, hipStream_t stream, const Dev
 // ... and its PAT form (ScanPePatStepIO), built there with the same unrolling
 void launch_scan_pe_pattern_generic(dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
                                     const ScanPePatStepIO<macjd_step_io>& io);
+
+
+// macjd_env_motion.hip: the MOV instantiations (moving scenarios), a translation unit of their own.  Compiled sizes 2j/2r,
+// 3j/4r, 6j/8r have a production and a general variant; launch_motion_fast returns false for every other size (no launch),
+// launch_motion_general runs those on the generic-size kernel.
+bool motion_size_compiled(int J, int R);
+bool launch_motion_fast(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
+                        const MotionStepIO<FastStepIO>& io);
+void launch_motion_general(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
+                           const MotionStepIO<macjd_step_io>& io);
+void launch_motion_reset(dim3 grid, dim3 block, hipStream_t stream, int64_t n_envs, int n_pos, const float* positions,
+                         const int32_t* position_columns, float* state, int64_t st_se, const uint8_t* mask);
 
 }  // namespace macjd

@@ -120,6 +120,9 @@ def build_components(args, sim_config_path):
             from .scenario import ScenarioBatch
             with open(sim_config_path) as f:
                 base = yaml.safe_load(f)
+            if ((base or {}).get("environment_params") or {}).get("motion") is not None:
+                raise ValueError(f"--randomize-scenarios is not supported with a moving scenario ({sim_config_path} has "
+                                 f"environment_params.motion): per-env scenario batches carry no frame tables")
             batch = ScenarioBatch.randomized(base, batch_envs, seed=args.seed, config=args, env_offset=off,
                                              azimuth_jitter=float(getattr(args, "randomize_azimuth_jitter", 0.0) or 0.0))
         env = BatchedElectromagneticEnvironment(args, sim_config_path, batch_envs=batch_envs, seed=args.seed,

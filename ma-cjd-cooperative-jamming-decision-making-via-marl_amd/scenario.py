@@ -8,6 +8,10 @@ module evaluates those quantities ONCE, on the host, with the same Python/NumPy 
 reference uses (so the table entries are bit-identical to what the reference computes per step) and
 hands them to the native library as a ``macjd_scenario_desc`` (include/macjd.h).
 
+Opt-in, ``environment_params.motion`` moves target, radars and jammers on straight lines that do not depend on the
+actions: the same compiler then runs once per step of an episode on the moved positions (``motion_frame_dict``) and the
+tables become per-step frames (``Scenario.motion_tables``; include/macjd.h, ``macjd_motion_io``).
+
 Validation and error behaviour follow environment.py:44-79 and :133-199 (same exception types and
 messages for the cases the reference checks).
 """
@@ -131,6 +135,80 @@ def _parse_scan_pattern(pat, source: str) -> Dict[str, Any]:
     return {"level_width": float(lw), "gain_db": [float(g) for g in gains]}
 
 
+_MOTION_KEYS = ("step_seconds", "target_velocity", "radar_velocity", "jammer_velocity")
+
+
+def parse_motion(env_params: dict, num_radars: Optional[int] = None, num_jammers: Optional[int] = None,
+                 source: str = "<dict>") -> Optional[Dict[str, Any]]:
+    """``environment_params.motion`` -> {'step_seconds', 'target_velocity': [vx, vy], 'radar_velocity': [[vx, vy]] * R,
+    'jammer_velocity': [[vx, vy]] * J} or None (absent / null: nothing moves).  Velocities are metres per second; a missing
+    list means zeros.  With ``num_radars`` / ``num_jammers`` (the entities the scenario uses) the lists must have exactly
+    that many pairs; without them (None) the lengths are taken as given."""
+    mo = env_params.get("motion")
+    if mo is None:
+        return None
+    if not isinstance(mo, dict):
+        raise ValueError(f"{source}: environment_params.motion must be a mapping or null")
+    unknown = set(mo) - set(_MOTION_KEYS)
+    if unknown:
+        raise ValueError(f"{source}: unknown motion key(s) {sorted(map(str, unknown))}")
+
+    def number(v):
+        return not isinstance(v, bool) and isinstance(v, (int, float)) and bool(np.isfinite(v))
+
+    def pair(v, what):
+        if not isinstance(v, (list, tuple)) or len(v) != 2 or not all(number(x) for x in v):
+            raise ValueError(f"{source}: motion.{what} must be a pair of finite numbers [vx, vy], got {v!r}")
+        return [float(v[0]), float(v[1])]
+
+    if "step_seconds" not in mo:
+        raise ValueError(f"{source}: motion is missing 'step_seconds'")
+    dt = mo["step_seconds"]
+    if not number(dt) or not dt > 0.0:
+        raise ValueError(f"{source}: motion.step_seconds must be a finite number > 0, got {dt!r}")
+    out: Dict[str, Any] = {"step_seconds": float(dt), "target_velocity": pair(mo.get("target_velocity", [0, 0]), "target_velocity")}
+    for key, n in (("radar_velocity", num_radars), ("jammer_velocity", num_jammers)):
+        v = mo.get(key)
+        if v is None:
+            out[key] = None if n is None else [[0.0, 0.0] for _ in range(n)]
+            continue
+        if not isinstance(v, (list, tuple)) or (n is not None and len(v) != n):
+            raise ValueError(f"{source}: motion.{key} must be a list of {'' if n is None else str(n) + ' '}[vx, vy] pairs "
+                             f"(one per {key.split('_')[0]} used), got {v!r}")
+        out[key] = [pair(x, f"{key}[{i}]") for i, x in enumerate(v)]
+    return out
+
+
+def motion_frame_dict(sim_config: dict, k: int) -> dict:
+    """Frame ``k`` of a moving scenario as an ordinary (static) sim-config dict: a deep copy of ``sim_config`` in which
+    every position is, per axis a and in Python floats, ``float(p0[a]) + float(k) * (float(v[a]) * dt)``, and from which
+    ``environment_params.motion`` is removed.  THE definition of a frame: the compiler (``Scenario.motion_tables``), the
+    tests and the fixture generator all go through it.  A config without ``motion`` comes back as a plain deep copy."""
+    import copy
+    d = copy.deepcopy(sim_config)
+    env_params = d.get("environment_params") or {}
+    mo = parse_motion(env_params)
+    if mo is None:
+        return d
+    del env_params["motion"]
+    dt = mo["step_seconds"]
+
+    def moved(p0, v):
+        p0 = np.array(p0).flatten()
+        return [float(p0[a]) + float(k) * (float(v[a]) * dt) for a in range(2)]
+
+    d["protected_target"]["position"] = moved(d["protected_target"]["position"], mo["target_velocity"])
+    for key, ents in (("radar_velocity", d.get("radars") or []), ("jammer_velocity", d.get("jammers") or [])):
+        vel = mo[key]
+        if vel is None:
+            vel = [[0.0, 0.0]] * len(ents)
+        if len(vel) > len(ents):
+            raise ValueError(f"motion.{key} has {len(vel)} pairs, but the scenario defines only {len(ents)} entities")
+        for ent, v in zip(ents, vel):
+            ent["position"] = moved(ent["position"], v)
+    return d
+
+
 class _Desc(ctypes.Structure):
     """ctypes mirror of ``macjd_scenario_desc`` (include/macjd.h)."""
     _fields_ = [
@@ -166,6 +244,20 @@ class Scenario:
     source: str = "<dict>"
     radar_scan: Optional[Dict[str, Any]] = None     # environment_params.radar_scan; None = static beams
     scan_tables: Dict[str, np.ndarray] = field(default_factory=dict)
+    motion: Optional[Dict[str, Any]] = None         # environment_params.motion; None = nothing moves
+    motion_tables: Dict[str, np.ndarray] = field(default_factory=dict)
+
+    @property
+    def moving(self) -> bool:
+        """Entities move (environment_params.motion given): the tables are per-step frames, the observation is dynamic."""
+        return self.motion is not None
+
+    @property
+    def position_columns(self) -> List[int]:
+        """Columns of the position entries in the state vector, in state order: per radar (x, y), then per jammer (x, y)."""
+        rfd, R = self.radar_feature_dim, self.num_radars
+        cols = [r * rfd + rfd - 2 + a for r in range(R) for a in range(2)]
+        return cols + [R * rfd + 2 * j + a for j in range(self.num_jammers) for a in range(2)]
 
     @property
     def scanning(self) -> bool:
@@ -254,6 +346,10 @@ class Scenario:
         if not (1 <= num_radars <= MAX_RADARS and 1 <= num_jammers <= MAX_JAMMERS):
             raise ValueError(f"Scenario size {num_jammers}j/{num_radars}r outside the supported range "
                              f"1..{MAX_JAMMERS} / 1..{MAX_RADARS}.")
+        motion = parse_motion(env_params, num_radars, num_jammers, source)
+        if motion is not None and radar_scan is not None:
+            raise ValueError(f"{source}: environment_params.motion together with radar_scan is not supported (the beams' "
+                             f"bearing tables would need frames too)")
 
         radars: List[Dict[str, Any]] = []
         for i, params in enumerate(radar_cfgs):  # :133-169
@@ -308,11 +404,37 @@ class Scenario:
         sc = cls(num_radars=num_radars, num_jammers=num_jammers, episode_limit=int(episode_limit),
                  max_radar_types=max_radar_types, rd_min=rd_min, rd_max=rd_max, rp_min=rp_min, rp_max=rp_max,
                  radars=radars, jammers=jammers, target_position=target_position, target_rcs=target_rcs,
-                 source=source, radar_scan=radar_scan)
+                 source=source, radar_scan=radar_scan, motion=motion)
         sc._compile()
         if radar_scan is not None:
             sc._compile_scan()
+        if motion is not None:
+            sc._compile_motion(sim_config, config)
         return sc
+
+    # ---- per-step frame tables of a moving scenario (include/macjd.h, macjd_motion_io) ----
+    def _compile_motion(self, sim_config: dict, config: Any) -> None:
+        """Frame f = the static scenario ``motion_frame_dict(sim_config, f)``, compiled by :meth:`from_dict` itself; its
+        arrays are COPIED into row f, so every value has the bits a static scenario of that frame would have (the
+        ``d <= 1e-6`` negative denominators and the weak-denominator flags included)."""
+        R, J, F = self.num_radars, self.num_jammers, self.episode_limit
+        if F < 1:
+            raise ValueError(f"{self.source}: a moving scenario needs episode_limit >= 1, got {F}")
+        cols = self.position_columns
+        frames = np.zeros((F, 6 * R + 3 * J + J * R), dtype=np.float64)
+        flags = np.zeros((F, J * R), dtype=np.uint8)
+        snr_no = np.zeros((F, R), dtype=np.float64)
+        positions = np.zeros((F + 1, len(cols)), dtype=np.float32)
+        for f in range(F + 1):
+            fr = Scenario.from_dict(motion_frame_dict(sim_config, f), config=config, source=f"{self.source}[frame {f}]")
+            positions[f] = fr.state_vector()[cols]
+            if f < F:
+                frames[f] = np.concatenate([np.asarray(fr.tables[key], dtype=np.float64).reshape(-1)
+                                            for key in _PE_RADAR_ROWS + _PE_JAMMER_ROWS + ("jr_denom",)])
+                flags[f] = fr.tables["jr_flags"].reshape(-1)
+                snr_no[f] = fr.tables["radar_snr_no"]
+        self.motion_tables = {"frames": frames, "flags": flags, "snr_no": snr_no, "positions": positions,
+                              "position_columns": np.asarray(cols, dtype=np.int32)}
 
     # ---- static tables ----
     def _compile(self) -> None:
@@ -615,6 +737,10 @@ class ScenarioBatch:
             i = next((k for k, sc in enumerate(scenarios) if sc.scan_pattern_levels), 0)
             raise ValueError(f"ScenarioBatch(pattern=True) needs scan=True (scenario {i}: the stepped antenna pattern belongs "
                              f"to scanning radars)")
+        for i, sc in enumerate(scenarios):
+            if sc.moving:
+                raise ValueError(f"ScenarioBatch: scenario {i} moves (environment_params.motion); moving scenarios are not "
+                                 f"supported in per-env scenario batches")
         s0 = scenarios[0]
         for i, sc in enumerate(scenarios):
             same = (sc.num_radars == s0.num_radars and sc.num_jammers == s0.num_jammers

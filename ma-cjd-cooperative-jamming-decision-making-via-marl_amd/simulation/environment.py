@@ -87,8 +87,11 @@ class BatchedElectromagneticEnvironment:
         if sc.scanning and scenario_batch is not None and not pe_scan:
             raise ValueError("scanning radars (environment_params.radar_scan) need a scanning per-env scenario batch "
                              "(ScenarioBatch(..., scan=True)); this batch carries no scan tables")
-        # scanning beams (environment_params.radar_scan): theta_a moves every step, so the observation does too
-        self.observation_is_static = not sc.scanning
+        if sc.moving and scenario_batch is not None:
+            raise ValueError("a moving scenario (environment_params.motion) is not supported with per-env scenario batches")
+        # scanning beams (environment_params.radar_scan): theta_a moves every step, so the observation does too; moving
+        # entities (environment_params.motion): the position columns do
+        self.observation_is_static = not sc.scanning and not sc.moving
         self.num_jammers, self.num_radars = sc.num_jammers, sc.num_radars
         self.episode_limit = sc.episode_limit
         self.state_dim = self.obs_dim = self.agent_obs_dim = sc.state_dim
@@ -180,6 +183,27 @@ class BatchedElectromagneticEnvironment:
             si.state, si.st_se = self._state_dyn.data_ptr(), self._state_dyn.stride(0)
             si.st_col0, si.st_col_step = sc.theta_a_col0, sc.theta_a_col_step
             si.snr_no, si.sn_se, si.sn_sx = self._snr_no_step.data_ptr(), 1, E
+        self._motion_io = self._motion_keep = None
+        if sc.moving:
+            # per-step frame tables (include/macjd.h, macjd_motion_io): f64 [F, rows], u8 [F, J*R], f64 [F, R], the
+            # positions f32 [F + 1, 2R + 2J] with their state columns; the per-env state rows f32 [E, S] start as frame 0
+            # (get_state / get_obs are views of them: one address for captured graphs) and the per-step SNR without
+            # jamming f32 [R, E] as frame 0's
+            mt = sc.motion_tables
+            keep = {k: torch.from_numpy(np.ascontiguousarray(mt[k])).to(dev)
+                    for k in ("frames", "flags", "snr_no", "positions", "position_columns")}
+            self._motion_keep = keep
+            self._pos_cols = keep["position_columns"].to(torch.int64)
+            st = torch.from_numpy(sc.state_vector()).to(dev)
+            self._state_dyn = st.view(1, -1).repeat(E, 1).contiguous()
+            self._state_dyn[:, self._pos_cols] = keep["positions"][0]
+            self._snr_no_step = keep["snr_no"][0].to(torch.float32).view(R, 1).repeat(1, E).contiguous()
+            mo = self._motion_io = _native.MotionIO()
+            mo.frames, mo.frame_flags, mo.frame_snr_no = keep["frames"].data_ptr(), keep["flags"].data_ptr(), keep["snr_no"].data_ptr()
+            mo.positions, mo.position_columns = keep["positions"].data_ptr(), keep["position_columns"].data_ptr()
+            mo.n_frames, mo.n_pos = int(mt["frames"].shape[0]), int(mt["positions"].shape[1])
+            mo.state, mo.st_se = self._state_dyn.data_ptr(), self._state_dyn.stride(0)
+            mo.snr_no, mo.sn_se, mo.sn_sx = self._snr_no_step.data_ptr(), 1, E
         self._io = _native.StepIO()
         self.kernel_flags = 0  # A/B hook: _native.STEP_LANE_KERNEL / STEP_SLOT_KERNEL force one kernel variant
         if verbose:
@@ -188,7 +212,7 @@ class BatchedElectromagneticEnvironment:
     # ---- reference-shaped getters, broadcast views (never materialised per env) ----
     def get_state(self) -> torch.Tensor:
         """f32 [E, S] expanded view of the static state vector (environment.py:479-510); with scanning beams the per-env
-        state rows, whose theta_a columns every step / reset rewrites in place."""
+        state rows, whose theta_a columns every step / reset rewrites in place (a moving scenario: its position columns)."""
         if self._state_dyn is not None:
             return self._state_dyn
         if self._state_vecs is not None:
@@ -223,6 +247,14 @@ class BatchedElectromagneticEnvironment:
         return self._theta_a.t()
 
     @property
+    def positions(self) -> torch.Tensor:
+        """f32 [E, 2R + 2J]: the current position columns of the state rows in state order (per radar x, y; then per jammer
+        x, y), gathered from them (moving scenarios only)."""
+        if self._motion_io is None:
+            raise AttributeError("positions: the scenario does not move (no environment_params.motion)")
+        return self._state_dyn[:, self._pos_cols]
+
+    @property
     def step_count(self) -> torch.Tensor:
         return self._step
 
@@ -251,6 +283,9 @@ class BatchedElectromagneticEnvironment:
             elif self._scan_io is not None:
                 _native.check(self._lib.macjd_env_reset_scan(self._handle.ptr, self.batch_envs, ctypes.byref(self._scan_io),
                                                              mptr, stream), "macjd_env_reset_scan")
+            elif self._motion_io is not None:
+                _native.check(self._lib.macjd_env_reset_moving(self._handle.ptr, self.batch_envs, ctypes.byref(self._motion_io),
+                                                               mptr, stream), "macjd_env_reset_moving")
         self._keep_mask = mask
         return self.get_state()
 
@@ -347,6 +382,11 @@ class BatchedElectromagneticEnvironment:
             elif self._scan_io is not None:
                 _native.check(self._lib.macjd_env_step_scan(self._handle.ptr, ctypes.byref(io), ctypes.byref(self._scan_io),
                                                             stream), "macjd_env_step_scan")
+            elif self._motion_io is not None:
+                mo = self._motion_io
+                mo.snr_no = self._snr_no_step.data_ptr() if want_info else None
+                _native.check(self._lib.macjd_env_step_moving(self._handle.ptr, ctypes.byref(io), ctypes.byref(mo), stream),
+                              "macjd_env_step_moving")
             else:
                 _native.check(self._lib.macjd_env_step(self._handle.ptr, ctypes.byref(io), stream), "macjd_env_step")
         rew = self._reward if out_reward is None else out_reward
@@ -384,8 +424,14 @@ class BatchedElectromagneticEnvironment:
         io.r_dpj = out_rdpj.data_ptr()
         stream = torch.cuda.current_stream(self.device).cuda_stream
         with torch.cuda.device(self.device):
-            _native.check(self._lib.macjd_env_step_many(self._handle.ptr, ctypes.byref(io), int(n), int(E * J), stream),
-                          "macjd_env_step_many")
+            if self._motion_io is not None:   # item (t, e) runs frame min(step[e] + t, F - 1); state rows end as after step n
+                mo = self._motion_io
+                mo.snr_no = None
+                _native.check(self._lib.macjd_env_step_many_moving(self._handle.ptr, ctypes.byref(io), ctypes.byref(mo), int(n),
+                                                                   int(E * J), stream), "macjd_env_step_many_moving")
+            else:
+                _native.check(self._lib.macjd_env_step_many(self._handle.ptr, ctypes.byref(io), int(n), int(E * J), stream),
+                              "macjd_env_step_many")
         io.r_dpj = self._r_dpj.data_ptr()
         self._keep = (actions_T, actions_P, out_reward, out_terminated, out_rdpj)
 
@@ -393,6 +439,7 @@ class BatchedElectromagneticEnvironment:
         """bench.py helper: average milliseconds per launch of the many-step kernel (n x E work items), ``iters``
         launches replayed from a HIP graph and bracketed by HIP events on the replay stream (macjd_env_step_many_timed)."""
         self._refuse_scanning("time_step_many_kernel")
+        self._refuse_moving("time_step_many_kernel")
         E, J = self.batch_envs, self.num_jammers
         n = actions_T.shape[0]
         io = self._fill_io(actions_T[0].view(E, J), actions_P[0].view(E, J), None, False, out_reward.view(-1)[:E],
@@ -411,6 +458,7 @@ class BatchedElectromagneticEnvironment:
         """bench.py helper: average milliseconds per env_step launch over ``iters`` back-to-back
         launches, measured with HIP events recorded on the launch stream (macjd_env_step_timed)."""
         self._refuse_scanning("time_step_kernel")
+        self._refuse_moving("time_step_kernel")
         io = self._fill_io(actions_T, actions_P, uniforms, False, None, None, want_info, None)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         ms = ctypes.c_float(0.0)
@@ -450,6 +498,11 @@ class BatchedElectromagneticEnvironment:
         if self._scan_io is not None:
             raise RuntimeError(f"{what}: not available with scanning radars (environment_params.radar_scan)")
 
+    def _refuse_moving(self, what: str) -> None:
+        # the timing helpers run the static launch on the handle's (frame-0) tables: not what a moving env steps with
+        if self._motion_io is not None:
+            raise RuntimeError(f"{what}: not available with a moving scenario (environment_params.motion)")
+
     @property
     def scenario_regular(self) -> bool:
         """The shared scenario's tables are regular (include/macjd.h, macjd_scenario_is_regular): the production lane
@@ -480,7 +533,8 @@ class ElectromagneticEnvironment:
         self.protected_target_config = {"position": sc.target_position, "rcs": sc.target_rcs}
         self._step_count = 0
         self._last_actions = np.zeros((self.num_jammers, 2))
-        self._state = sc.state_vector() if not sc.scanning else self._batched.get_state()[0].cpu().numpy().copy()
+        dynamic = sc.scanning or sc.moving
+        self._state = sc.state_vector() if not dynamic else self._batched.get_state()[0].cpu().numpy().copy()
         dev = self._batched.device
         R, J = self.num_radars, self.num_jammers
         self._diag = {"out64": torch.zeros((1, 4), dtype=torch.float64, device=dev),
@@ -500,7 +554,7 @@ class ElectromagneticEnvironment:
 
     def reset(self) -> np.ndarray:
         self._batched.reset()
-        if self._batched._scan_io is not None:
+        if self._batched._scan_io is not None or self._batched._motion_io is not None:
             self._state = self._batched.get_state()[0].cpu().numpy().copy()
         self._step_count = 0
         self._last_actions.fill(0)
@@ -517,6 +571,10 @@ class ElectromagneticEnvironment:
         powers: List[Any] = []
         n_dec = 0
         denom = sc.tables["jr_denom"].reshape(J, R)
+        if sc.moving:   # the frame this step runs on (self._step_count is already advanced: the counter before is one less)
+            mt = sc.motion_tables
+            f = min(self._step_count - 1, mt["frames"].shape[0] - 1)
+            denom = mt["frames"][f, 6 * R + 3 * J:].reshape(J, R)
         for i, (t_i, p_i) in enumerate(actions):
             t_i = int(t_i)
             p_c = np.clip(p_i, 0.0, 1.0)
@@ -578,6 +636,10 @@ class ElectromagneticEnvironment:
                 # stepped pattern: the matching level's value (equal gains give equal values: any of them will do)
                 for lvl in sc.scan_tables["pat_snr_no"][::-1]:
                     snr_no = np.where((lvl.astype(np.float32) == snr32) & (main.astype(np.float32) != snr32), lvl, snr_no)
+            self._state = b.get_state()[0].cpu().numpy().copy()
+        elif b._motion_io is not None:
+            mt = sc.motion_tables
+            snr_no = mt["snr_no"][min(self._step_count - 1, mt["snr_no"].shape[0] - 1)].copy()
             self._state = b.get_state()[0].cpu().numpy().copy()
         else:
             snr_no = sc.tables["radar_snr_no"].copy()
