@@ -229,7 +229,23 @@ typedef struct macjd_wgrad_io {
        one output per row, outer_w that layer's weight row.  Saves the launch that would materialise the product. */
     const float* outer_vec;               /* [K] */
     const float* outer_w;                 /* [M] */
+    /* optional, macjd_linear_wgrad_many_norm only (every other entry point returns MACJD_EUNSUPPORTED for kind != 0):
+       where the REDUCE launch takes the problem's terms from.  A problem of kind != 0 has no work item in the
+       partial-products launch; when no problem of a call has one, that launch is not issued.
+         MACJD_WGRAD_EXT_SLOTS     `workspace` already holds `ext_chunks` slots in the partial launch's layout — slot c at
+                                   workspace + c Mp Np (Mp / Np = M / N padded to 64, row stride Np), the bias rows behind
+                                   them at workspace + ext_chunks Mp Np + c Mp — written by an earlier launch
+                                   (macjd_mixer_wgrad_block).  gout / inp / K / outer_* are not read.  The contracted
+                                   problem: `ext_chunks` slots of [2][N] floats.
+         MACJD_WGRAD_ROW_PRODUCTS  no slots at all: output (m, n) = sum_k gout[k, m] * inp[k, n] and db[m] = sum_k gout[k, m]
+                                   straight from the operands (fmaf per term, the rounds / waves / tree of the slot sums
+                                   with term k in the place of slot k).  For short reductions (K of a few hundred rows).
+                                   `workspace` is not read; no outer_vec; not the contracted problem. */
+    int32_t kind, ext_chunks;
 } macjd_wgrad_io;
+#define MACJD_WGRAD_ORDINARY 0
+#define MACJD_WGRAD_EXT_SLOTS 1
+#define MACJD_WGRAD_ROW_PRODUCTS 2
 
 int64_t macjd_linear_wgrad_workspace_floats(int64_t K, int32_t M, int32_t N);
 int macjd_linear_wgrad(const macjd_wgrad_io* io, void* hip_stream);
@@ -266,6 +282,10 @@ typedef struct macjd_wgrad_norm_io {
 
 int32_t macjd_linear_wgrad_many_norm_partials(const macjd_wgrad_io* ios, int32_t n, int32_t ln_problem);   /* < 0: bad argument */
 int macjd_linear_wgrad_many_norm(const macjd_wgrad_io* ios, int32_t n, const macjd_wgrad_norm_io* norm, void* hip_stream);
+/* work items of that call's partial-products launch (0: the launch is not issued); < 0: bad argument */
+int64_t macjd_linear_wgrad_many_norm_work_items(const macjd_wgrad_io* ios, int32_t n, int32_t ln_problem);
+/* floats of `slots` external slots of an [M, N] problem with their bias rows (MACJD_WGRAD_EXT_SLOTS); < 0: bad argument */
+int64_t macjd_wgrad_slot_floats(int32_t M, int32_t N, int64_t slots);
 
 /* The optimiser step of macjd_clip_adam_step_sample as ONE launch behind macjd_linear_wgrad_many_norm: every workgroup sums
    io->partials[0 .. n_partials) itself (all 256 threads: loads first, then per thread in index order, across the wave,
@@ -624,6 +644,37 @@ typedef struct macjd_mixer_static_io {
 } macjd_mixer_static_io;
 int macjd_mixer_fused_train_static(const macjd_mixerf_io* eval, const macjd_mixerf_io* target, const macjd_tdloss_io* td,
                                    const float* tot_m, const macjd_mixer_static_io* st, void* hip_stream);
+/* macjd_mixer_fused_train_static whose workgroups also leave, behind everything above (which stays bit-identical), what the
+   weight-gradient REDUCE launch needs of the taken-action Q-head and of the LayerNorm — so that the update runs no
+   partial-products launch (macjd_wgrad_io.kind).  Workgroup `tile` = (b, k) forms gq for the mixer rows t = 16 k .. 16 k + 15
+   of episode b, i.e. for the 16 J agent rows n = (b T1 + 16 k) J .. of the Q-head grid (macjd_qhead_taken on M J rows):
+     * slot `tile` of the Q-head's first-layer problem, ws1 (M = H, N = H + A + 1: the [H x N] part of the padded
+       [Mp x Np] slot and the bias row, layout in macjd_wgrad_io.kind):
+           dW1_part = g_hid^T x,  db1_part = column sums of g_hid,  g_hid[r][m] = (act_q[r][m] > 0) ? gq[r] w2[m] : 0,
+           x[r] = [h[r], onehot(idx[r]), P[r]]  (an index outside [0, A) gives no one: macjd_qhead_taken's rule)
+       on exact-f32 MFMA, rows ascending; rows with t >= T1 are read from clamped addresses and count exact zeros;
+     * slot `tile` of its second-layer problem, ws2 (M = 1, N = H): dw2_part[m] = sum_r gq[r] act_q[r][m], db2_part = sum_r gq[r];
+     * the tile's LayerNorm slot ln_slots[tile][2][S]: [0][k] = xhat[tile][k] u[k], [1][k] = u[k] with
+       u[k] = sum_c W_first[c][k] gout1_sum[tile][c] (c ascending in eight runs of 48, combined as a fixed tree): the
+       contracted problem's terms, dgamma = sum_tiles xhat u, dbeta = sum_tiles u.
+   Fixed summation orders, no atomics; no workgroup reads what another one of the launch writes.  f32 operands only, H = 64,
+   1 <= A <= 15.  MACJD_EINVAL: a NULL member, act_q / h not 16-byte aligned or a row stride that is not a multiple of 4
+   or < H, idx_elem_size not 4 / 8, w_ld < S, a workspace smaller than n_tiles slots.  wg == NULL: the call above. */
+typedef struct macjd_mixer_wgrad_block {
+    const float* act_q; int64_t act_ld;    /* [M J, H] the Q-head's ReLU output (macjd_qtaken_io.act) */
+    const float* h;     int64_t h_ld;      /* [M J, H] */
+    const void* idx;    int32_t idx_elem_size, A;   /* [M J] int32 / int64 */
+    const float* P;                        /* [M J] */
+    const float* w2;                       /* [H] the Q-head's second layer */
+    int32_t H, reserved;
+    float* ws1; int64_t ws1_floats;        /* >= macjd_wgrad_slot_floats(H, H + A + 1, n_tiles) */
+    float* ws2; int64_t ws2_floats;        /* >= macjd_wgrad_slot_floats(1, H, n_tiles) */
+    float* ln_slots; int64_t ln_floats;    /* >= n_tiles * 2 * S */
+    const float* W_first; int64_t w_ld;    /* [2Hh+2Em, S] the merged first layer (= eval->W1 with its row stride) */
+} macjd_mixer_wgrad_block;
+int macjd_mixer_fused_train_static_wgrad(const macjd_mixerf_io* eval, const macjd_mixerf_io* target, const macjd_tdloss_io* td,
+                                         const float* tot_m, const macjd_mixer_static_io* st, const macjd_mixer_wgrad_block* wg,
+                                         void* hip_stream);
 
 /*
  * The agent side of a WHOLE episode batch in one launch: for t = 0 .. T-1 and every (env, agent) row

@@ -30,6 +30,7 @@ EXPORTS = [
     "macjd_agent_episode_supported", "macjd_agent_episode", "macjd_env_step_many", "macjd_env_step_many_timed",
     "macjd_qhead_double_q_supported", "macjd_qhead_double_q", "macjd_qhead_taken_supported", "macjd_qhead_taken",
     "macjd_qheads_pair", "macjd_mixer_fused_forward_pair", "macjd_mixer_fused_train", "macjd_mixer_fused_train_static",
+    "macjd_mixer_fused_train_static_wgrad",
     "macjd_scenario_set_scan", "macjd_env_step_scan", "macjd_env_reset_scan",
     "macjd_env_step_scan_pe", "macjd_env_reset_scan_pe", "macjd_env_step_scan_pe_pattern",
     "macjd_agent_env_episode_scan_supported", "macjd_agent_env_episode_scan",
@@ -39,6 +40,7 @@ EXPORTS = [
     "macjd_prefetch_batch_supported", "macjd_prefetch_batch",
     "macjd_actor_gradient_supported", "macjd_actor_gradient",
     "macjd_linear_wgrad_many_norm", "macjd_linear_wgrad_many_norm_partials", "macjd_clip_adam_step_reduced",
+    "macjd_linear_wgrad_many_norm_work_items", "macjd_wgrad_slot_floats",
     "macjd_prefetch_batches_supported", "macjd_prefetch_batches",
     "macjd_env_step_moving", "macjd_env_step_many_moving", "macjd_env_reset_moving",
 ]
@@ -218,6 +220,17 @@ class MixerStaticIO(ctypes.Structure):
         ("n_tiles", ctypes.c_int64), ("sn", ctypes.c_void_p), ("xhat", ctypes.c_void_p), ("act", ctypes.c_void_p),
         ("gout1_sum", ctypes.c_void_p), ("g_w1raw_sum", ctypes.c_void_p), ("g_wfraw_sum", ctypes.c_void_p),
         ("g_v_sum", ctypes.c_void_p),
+    ]
+
+
+class MixerWgradBlock(ctypes.Structure):
+    """ctypes mirror of ``macjd_mixer_wgrad_block`` (include/macjd_nets.h)."""
+    _fields_ = [
+        ("act_q", ctypes.c_void_p), ("act_ld", ctypes.c_int64), ("h", ctypes.c_void_p), ("h_ld", ctypes.c_int64),
+        ("idx", ctypes.c_void_p), ("idx_elem_size", ctypes.c_int32), ("A", ctypes.c_int32),
+        ("P", ctypes.c_void_p), ("w2", ctypes.c_void_p), ("H", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("ws1", ctypes.c_void_p), ("ws1_floats", ctypes.c_int64), ("ws2", ctypes.c_void_p), ("ws2_floats", ctypes.c_int64),
+        ("ln_slots", ctypes.c_void_p), ("ln_floats", ctypes.c_int64), ("W_first", ctypes.c_void_p), ("w_ld", ctypes.c_int64),
     ]
 
 
@@ -421,7 +434,11 @@ class WgradIO(ctypes.Structure):
         ("gout", ctypes.c_void_p), ("gout_ld", ctypes.c_int64), ("inp", ctypes.c_void_p), ("inp_ld", ctypes.c_int64),
         ("dW", ctypes.c_void_p), ("dw_ld", ctypes.c_int64), ("db", ctypes.c_void_p), ("workspace", ctypes.c_void_p),
         ("outer_vec", ctypes.c_void_p), ("outer_w", ctypes.c_void_p),
+        ("kind", ctypes.c_int32), ("ext_chunks", ctypes.c_int32),
     ]
+
+
+WGRAD_ORDINARY, WGRAD_EXT_SLOTS, WGRAD_ROW_PRODUCTS = 0, 1, 2   # macjd_wgrad_io.kind
 
 
 class WgradNormIO(ctypes.Structure):
@@ -543,6 +560,10 @@ def load() -> ctypes.CDLL:
     lib.macjd_mixer_fused_train_static.restype = ctypes.c_int
     lib.macjd_mixer_fused_train_static.argtypes = [ctypes.POINTER(MixerFusedIO), ctypes.POINTER(MixerFusedIO), ctypes.POINTER(TdLossIO),
                                                    ctypes.c_void_p, ctypes.POINTER(MixerStaticIO), ctypes.c_void_p]
+    lib.macjd_mixer_fused_train_static_wgrad.restype = ctypes.c_int
+    lib.macjd_mixer_fused_train_static_wgrad.argtypes = [ctypes.POINTER(MixerFusedIO), ctypes.POINTER(MixerFusedIO),
+                                                         ctypes.POINTER(TdLossIO), ctypes.c_void_p, ctypes.POINTER(MixerStaticIO),
+                                                         ctypes.POINTER(MixerWgradBlock), ctypes.c_void_p]
     lib.macjd_td_mask_sum.restype = ctypes.c_int
     lib.macjd_td_mask_sum.argtypes = [ctypes.POINTER(TdLossIO), ctypes.c_void_p, ctypes.c_void_p]
     lib.macjd_qhead_taken_supported.restype = ctypes.c_int
@@ -598,6 +619,10 @@ def load() -> ctypes.CDLL:
     lib.macjd_linear_wgrad_many_norm_partials.argtypes = [ctypes.POINTER(WgradIO), ctypes.c_int32, ctypes.c_int32]
     lib.macjd_clip_adam_step_reduced.restype = ctypes.c_int
     lib.macjd_clip_adam_step_reduced.argtypes = [ctypes.POINTER(AdamIO), ctypes.c_int32, ctypes.POINTER(SamplerIO), ctypes.c_void_p]
+    lib.macjd_linear_wgrad_many_norm_work_items.restype = ctypes.c_int64
+    lib.macjd_linear_wgrad_many_norm_work_items.argtypes = [ctypes.POINTER(WgradIO), ctypes.c_int32, ctypes.c_int32]
+    lib.macjd_wgrad_slot_floats.restype = ctypes.c_int64
+    lib.macjd_wgrad_slot_floats.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64]
     lib.macjd_linear_wgrad_many.restype = ctypes.c_int
     lib.macjd_linear_wgrad_many.argtypes = [ctypes.POINTER(WgradIO), ctypes.c_int32, ctypes.c_void_p]
     lib.macjd_linear_wgrad_workspace_floats.restype = ctypes.c_int64

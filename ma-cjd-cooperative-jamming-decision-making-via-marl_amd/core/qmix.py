@@ -556,6 +556,14 @@ class QMixLearner:
             mixer_static = (mixer_train and obs_static and bool(getattr(self, "_g_state_static", False))
                             and options.on("MIXER_STATIC_STATE"))
             self._g_mixer_static = mixer_static   # bookkeeping: what the (captured) update's mixer launch is
+            # ... whose workgroups then also leave the Q-head's weight-gradient partials and the LayerNorm contraction, so
+            # that the update runs no partial-products launch (ops.plan_wgrad_in_train): where the grouped launch pair
+            # serves the optimiser too (_norm_in_reduce) and every Q-head and mixer parameter takes its gradient from it
+            wgrad_in_train = (mixer_static and self._norm_in_reduce() and options.on("WGRAD_IN_TRAIN")
+                              and not self.eval_qmix_net.bf16_hyper and ops.wgrad_in_train_supported(H, A)
+                              and all(p.requires_grad for p in self.mac.agent.fc2_q_head.parameters())
+                              and all(p.requires_grad for p in self.eval_qmix_net.parameters()))
+            self._g_wgrad_in_train = wgrad_in_train
             train_gy = None
             try:   # (an argument block that a raising call leaves behind must not ride in a later, unrelated launch)
                 with torch.no_grad():
@@ -565,6 +573,8 @@ class QMixLearner:
                     for t_ in list(bases) + [p for p in params if p is not None]:
                         t_.record_stream(origin)
                     tq_agents = double_q(bases, params, paired=True)                            # launched with the next call
+                if wgrad_in_train:
+                    ops.plan_wgrad_in_train()           # (before the Q-head grid: it then writes no input rows)
                 q_taken = self.mac.agent.get_q_value_for_action(
                     st["hidden_state"].view(n, H), st["actions_discrete"].view(n, 1), st["actions_continuous"].view(n, 1),
                     validate=False).view(B, T1, J)                                              # qmix.py:138-147, 161-184

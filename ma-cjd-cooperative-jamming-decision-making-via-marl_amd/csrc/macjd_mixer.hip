@@ -631,241 +631,187 @@ struct MixerTrainLds {
     float ys[16], tqs[16];   // eval Q_tot of row m0 + i, target Q_tot of row m0 + 1 + i
 };
 
-template <int J, bool BF, bool NARROW, bool STATIC = false>
-__global__ void __launch_bounds__(512) mixer_fused_train_kernel(const macjd_mixerf_io io, const macjd_mixerf_io tio,
-                                                                 const macjd_tdloss_io td, const float* __restrict__ tot_m) {
-    constexpr int LDG = J * MX_EM + 8;
-    constexpr int LDF = MX_EM + 8;
-    constexpr int KQ1 = J * MX_EM / 16;
-    constexpr int KQF = MX_EM / 16;
-    __shared__ MixerTrainLds<J> L;
-    const int lane = threadIdx.x & 63;
-    const int wave8 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int wave = wave8 & 3;
-    const bool eval_half = wave8 < 4;
-    const int li = lane & 15, g = lane >> 4;
-    // rows of this workgroup: [m0, m0 + 16) below Mev (eval) and [m0 + 1, m0 + 17) below Mtg (target)
-    const int64_t tile = blockIdx.x;
-    int64_t m0 = tile * 16, Mev = io.M, Mtg = io.M;
-    if constexpr (STATIC) {   // tile k of episode b: rows t = 16 k .. 16 k + 15 of that episode only, the rest of the tile is dead
-        const int T1 = (int)td.gy_cols, tpe = (T1 + 15) / 16;
-        const int b = (int)blockIdx.x / tpe, k = (int)blockIdx.x - b * tpe;
-        m0 = (int64_t)b * T1 + 16 * k;
-        Mev = (int64_t)(b + 1) * T1;
-        Mtg = Mev + 1 < io.M ? Mev + 1 : io.M;
-    }
-    const float* Hs = L.ev.Hs;   // the eval mixer's first-layer output of the tile = `act`
+// mixer_fused_train_wgrad_kernel (STATIC, f32; macjd_mixer_fused_train_static_wgrad): behind all of the above the workgroup writes its slots of the
+// Q-head's two weight-gradient problems and of the LayerNorm contraction (`wb`, include/macjd_nets.h).  LDS that is dead by
+// then is reused — floats from the start of L.tg (dead since the first barrier): gs[384] a copy of the tile's gout1 sums,
+// up[8][64] the partial u, sX[16 J][80] the Q-head input rows, sQ[64] gq per agent row; from the start of L.ev (dead after
+// the column sums): sG[16 J][80] the masked outer product, sAq[16 J][64] the Q-head's ReLU output.
+constexpr int WGB_PITCH = 80;              // = 16 mod 32, as the weight-gradient kernel's chunks
+constexpr int WGB_GS = 0, WGB_UP = MX_N1, WGB_SX = MX_N1 + 8 * 64;
 
-    // the loss inputs of this lane's rows (4 g + r, and li for the V head), requested before the forward's loads
-    float rw[5], term[5], mk[5];
-    bool live[5];
-    if (eval_half) {
+// what a thread holds of the tile's R = 16 J agent rows between request and use: its float4 pieces of the Q-head's ReLU
+// output and of h (piece id = 512 it + thread: row id >> 4, columns 4 (id & 15) ..), and — thread r < R — row r's P and index
+template <int J>
+struct WgbLoads {
+    static constexpr int R = 16 * J;
+    static constexpr int NIT = (R * 16 + 511) / 512;
+    float4 a[NIT], h[NIT];
+    float p;
+    int idx;      // the taken action, -1 when outside [0, A)
+    int n_live;   // rows of the tile inside the episode (the others: clamped loads, exact zeros)
+    int A;
+};
+
+// every load from a clamped (valid) address, no branch around a load
+template <int J>
+__device__ __forceinline__ void wgb_load(const macjd_mixer_wgrad_block& wb, const int64_t n0, const int64_t n_end, WgbLoads<J>& out) {
+    constexpr int R = WgbLoads<J>::R, NIT = WgbLoads<J>::NIT;
+    const int tid = threadIdx.x;
+    out.n_live = (int)(n_end - n0 < R ? n_end - n0 : R);
+    out.A = wb.A;
 #pragma unroll
-        for (int r = 0; r < 5; ++r) {
-            const int row = r < 4 ? 4 * g + r : li;
-            const int64_t mc = (m0 + row < Mev) ? m0 + row : Mev - 1;
-            const int cols = (int)td.gy_cols;
-            const int b = (int)(mc / cols), t = (int)(mc - (int64_t)b * cols);
-            const int tc = t < td.Tm1 ? t : td.Tm1 - 1;
-            term[r] = td.terminated[b * td.t_sb + tc * td.t_st] ? 1.0f : 0.0f;
-            mk[r] = td.filled[b * td.f_sb + tc * td.f_st] ? 1.0f : 0.0f;
-            rw[r] = td.reward[b * td.r_sb + tc * td.r_st];
-            live[r] = t < td.Tm1;
-        }
+    for (int it = 0; it < NIT; ++it) {
+        const int id = it * 512 + tid;
+        const int r = (id >> 4) < R ? (id >> 4) : R - 1, c4 = (id & 15) * 4;
+        const int64_t n = n0 + r < n_end ? n0 + r : n_end - 1;
+        out.a[it] = *reinterpret_cast<const float4*>(wb.act_q + n * wb.act_ld + c4);
+        out.h[it] = *reinterpret_cast<const float4*>(wb.h + n * wb.h_ld + c4);
     }
+}
 
-    MixerKeep<J> K;
-    f32x4 D1[KQ1], Df[KQF];
-    if (eval_half) {
-        if constexpr (STATIC) {
-            macjd_mixerf_io eio = io;
-            eio.M = Mev;
-            mixer_fused_forward_body<J, J, true, true, true, BF, NARROW, true>(eio, m0, wave, L.ev, &K, tile);
-        } else {
-            mixer_fused_forward_body<J, J, true, true, true, BF, NARROW>(io, m0, wave, L.ev, &K);
+// ... and thread r's (r < R; the others repeat row R - 1) index and P
+template <int J>
+__device__ __forceinline__ void wgb_load_row(const macjd_mixer_wgrad_block& wb, const int64_t n0, const int64_t n_end, WgbLoads<J>& out) {
+    constexpr int R = WgbLoads<J>::R;
+    const int tid = threadIdx.x;
+    const int r = tid < R ? tid : R - 1;
+    const int64_t n = n0 + r < n_end ? n0 + r : n_end - 1;
+    out.p = wb.P[n];
+    int64_t v;
+    if (wb.idx_elem_size == 8) v = reinterpret_cast<const int64_t*>(wb.idx)[n];   // (uniform)
+    else v = reinterpret_cast<const int32_t*>(wb.idx)[n];
+    out.idx = (v >= 0 && v < wb.A) ? (int)v : -1;
+}
+
+// sX[r][0 .. 80) = [h[r], onehot(idx[r]), P[r], zeros]; dead rows all zero
+template <int J>
+__device__ __forceinline__ void wgb_stage_x(const WgbLoads<J>& l, float* __restrict__ sX) {
+    constexpr int R = WgbLoads<J>::R, NIT = WgbLoads<J>::NIT;
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+        const int id = it * 512 + tid;
+        const int r = id >> 4, c4 = (id & 15) * 4;
+        if (id < R * 16) {
+            const bool live = r < l.n_live;
+            float4 v = l.h[it];
+            v.x = live ? v.x : 0.0f; v.y = live ? v.y : 0.0f; v.z = live ? v.z : 0.0f; v.w = live ? v.w : 0.0f;
+            *reinterpret_cast<float4*>(sX + r * WGB_PITCH + c4) = v;
         }
-        if (wave == 0 && g == 0) L.ys[li] = K.y;
-    } else {
-        MixerKeep<J> Kt;
-        if constexpr (STATIC) {
-            macjd_mixerf_io etio = tio;
-            etio.M = Mtg;
-            mixer_fused_forward_body<J, J, false, true, true, BF, NARROW>(etio, m0 + 1, wave, L.tg, &Kt);
-        } else {
-            mixer_fused_forward_body<J, J, false, true, true, BF, NARROW>(tio, m0 + 1, wave, L.tg, &Kt);
-        }
-        if (wave == 0 && g == 0) L.tqs[li] = Kt.y;
     }
-    // transposed second-layer fragments of this wave's gout1 column tile n = 16 wave8 + li (B[k][n] = W2[k][n], k = 16 Q +
-    // 4 g + jj), requested while the tail gradients run
+    if (tid < R) {
+        const bool live = tid < l.n_live;
+#pragma unroll
+        for (int a = 0; a < 16; ++a)
+            sX[tid * WGB_PITCH + 64 + a] = !live ? 0.0f : a == l.idx ? 1.0f : a == l.A ? l.p : 0.0f;
+    }
+}
+
+// the tile's slots (macjd_mixer_wgrad_block).  Called by all 512 threads behind the column sums; two barriers inside.
+template <int J>
+__device__ __forceinline__ void wgb_finish(const macjd_mixer_wgrad_block& wb, const WgbLoads<J>& l, const float* xhat, const int S,
+                                           const int64_t tile, const int64_t n_tiles, const float (*gq_part)[16][J],
+                                           float* __restrict__ tg, float* __restrict__ ev) {
+    constexpr int R = WgbLoads<J>::R, NIT = WgbLoads<J>::NIT;
+    const int tid = threadIdx.x, lane = tid & 63, wave8 = tid >> 6, li = lane & 15, g = lane >> 4;
+    const float* gs = tg + WGB_GS;
+    float* up = tg + WGB_UP;
+    const float* sX = tg + WGB_SX;
+    float* sQ = tg + WGB_SX + R * WGB_PITCH;
+    float* sG = ev;
+    float* sAq = ev + R * WGB_PITCH;
+    // u's weights (wave w: rows 48 w .. 48 w + 47 of W_first, lane = column, clamped) and this thread's four of w2
+    constexpr int RUN = MX_N1 / 8;
+    const int kc = lane < S ? lane : S - 1;
+    float wv[RUN], w2v[4];
+#pragma unroll
+    for (int i = 0; i < RUN; ++i) wv[i] = wb.W_first[(int64_t)(RUN * wave8 + i) * wb.w_ld + kc];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) w2v[e] = wb.w2[(tid & 15) * 4 + e];
+    wgb_stage_x<J>(l, tg + WGB_SX);   // (L.tg: free already)
+    __syncthreads();   // the column sums are done: L.ev is dead, gs and sX are complete
     {
-        const int n = 16 * wave8 + li;
+        float u = 0.0f;
 #pragma unroll
-        for (int Q = 0; Q < KQ1; ++Q)
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) D1[Q][jj] = io.W2[(int64_t)(BF ? mx_kq<KQ1>(Q, g) + jj : 16 * Q + 4 * g + jj) * MX_HH + n];
-#pragma unroll
-        for (int Q = 0; Q < KQF; ++Q)
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) Df[Q][jj] = io.Wf2[(int64_t)(BF ? mx_kq<KQF>(Q, g) + jj : 16 * Q + 4 * g + jj) * MX_HH + n];
+        for (int i = 0; i < RUN; ++i) u = fmaf(wv[i], gs[RUN * wave8 + i], u);
+        up[wave8 * 64 + lane] = u;
     }
-    float wvo[2];
 #pragma unroll
-    for (int i = 0; i < 2; ++i) wvo[i] = io.wV2[(threadIdx.x + 512 * i) & (MX_EM - 1)];
-    __syncthreads();   // ys / tqs of the tile
-
-    if (eval_half) {
-        const float scale = 2.0f / tot_m[0];
-        float gyv[5];
-#pragma unroll
-        for (int r = 0; r < 5; ++r) {
-            const int row = r < 4 ? 4 * g + r : li;
-            const float target = rw[r] + td.gamma * (1.0f - term[r]) * L.tqs[row];
-            const float gv = scale * mk[r] * (L.ys[row] - target);
-            gyv[r] = live[r] ? gv : 0.0f;
-        }
-        const int e = 16 * wave + li;
-        float gb1_sum = 0.0f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = 4 * g + r;
-            const int64_t m = m0 + row;
-            const float b1r = Hs[row * MX_LDH + MX_RELU + e];
-            float hid = mx_clamp(b1r, -5.0f, 5.0f);
-            float w1r[J];
-#pragma unroll
-            for (int j = 0; j < J; ++j) {
-                w1r[j] = K.acc2[j][r] + K.b2e[j];
-                hid = fmaf(K.qv[r][j], mx_clamp(w1r[j], 0.0f, 5.0f), hid);
-            }
-            const float h = hid > 0.0f ? hid : expm1f(hid);
-            const float wfr = K.accf[r] + K.bfe;
-            const float ghid = gyv[r] * mx_clamp(wfr, 0.0f, 5.0f) * (hid > 0.0f ? 1.0f : h + 1.0f);
-            const float gwf = (wfr >= 0.0f && wfr <= 5.0f) ? gyv[r] * h : 0.0f;
-            const float gb1 = (b1r >= -5.0f && b1r <= 5.0f) ? ghid : 0.0f;
-            L.Gf[row * LDF + e] = gwf;
-            if constexpr (STATIC) {
-                gb1_sum = r == 0 ? gb1 : gb1_sum + gb1;
-            } else if (m < Mev) {
-                io.g_wfraw[m * MX_EM + e] = gwf;
-                io.gout1[m * MX_N1 + MX_RELU + e] = gb1;
-            }
-#pragma unroll
-            for (int j = 0; j < J; ++j) {
-                const float gw = (w1r[j] >= 0.0f && w1r[j] <= 5.0f) ? ghid * K.qv[r][j] : 0.0f;
-                L.G1[row * LDG + j * MX_EM + e] = gw;
-                if (!STATIC && m < Mev) io.g_w1raw[m * (J * MX_EM) + j * MX_EM + e] = gw;
-                const float t = mx_sum16(ghid * mx_clamp(w1r[j], 0.0f, 5.0f));
-                if (li == 0) L.gq_part[wave][row][j] = t;
-            }
-        }
-        if constexpr (STATIC) {   // the b1 block of gout1: this lane's four rows above, then the four lane groups
-            gb1_sum += __shfl_xor(gb1_sum, 16, 64);
-            gb1_sum += __shfl_xor(gb1_sum, 32, 64);
-            if (g == 0) io.gout1[tile * MX_N1 + MX_RELU + e] = gb1_sum;
-        }
-        if (wave == 0 && g == 0) {   // v = clamp(v_raw, -5, 5): row li
-            const int64_t m = m0 + li;
-            const float gv = (K.v_raw >= -5.0f && K.v_raw <= 5.0f) ? gyv[4] : 0.0f;
-            L.gv_s[li] = gv;
-            if (!STATIC && m < Mev) io.g_v[m] = gv;
+    for (int it = 0; it < NIT; ++it) {
+        const int id = it * 512 + tid;
+        const int r = id >> 4, c4 = (id & 15) * 4;
+        if (id < R * 16) {
+            const int row = r / J, j = r - row * J;
+            const bool live = r < l.n_live;
+            const float gq = (gq_part[0][row][j] + gq_part[1][row][j]) + (gq_part[2][row][j] + gq_part[3][row][j]);
+            const float4 a = l.a[it];
+            float4 gh, aq;
+            gh.x = (live && a.x > 0.0f) ? gq * w2v[0] : 0.0f; aq.x = live ? a.x : 0.0f;
+            gh.y = (live && a.y > 0.0f) ? gq * w2v[1] : 0.0f; aq.y = live ? a.y : 0.0f;
+            gh.z = (live && a.z > 0.0f) ? gq * w2v[2] : 0.0f; aq.z = live ? a.z : 0.0f;
+            gh.w = (live && a.w > 0.0f) ? gq * w2v[3] : 0.0f; aq.w = live ? a.w : 0.0f;
+            *reinterpret_cast<float4*>(sG + r * WGB_PITCH + c4) = gh;
+            *reinterpret_cast<float4*>(sAq + r * 64 + c4) = aq;
+            if ((id & 15) == 0) sQ[r] = live ? gq : 0.0f;
         }
     }
     __syncthreads();
-    // dL/dq: the four embed blocks' partial sums in fixed order
-    if (threadIdx.x < 16 * J) {
-        const int row = threadIdx.x / J, j = threadIdx.x - row * J;
-        if (m0 + row < Mev)
-            io.gq[(m0 + row) * J + j] = (L.gq_part[0][row][j] + L.gq_part[1][row][j]) + (L.gq_part[2][row][j] + L.gq_part[3][row][j]);
-    }
-    // input gradients of the second layers, masked by the first layer's ReLU: column tile n of [0, Hh) and of [Hh, 2 Hh)
-    {
-        f32x4 a1 = f32x4{0.f, 0.f, 0.f, 0.f}, af = f32x4{0.f, 0.f, 0.f, 0.f};
-        if constexpr (BF) {
+    const int N1 = 64 + l.A + 1, Np1 = (N1 + 63) / 64 * 64;
+    // Q-head first layer: 4 x 5 tiles of 16 x 16 over the eight waves, rows ascending
+    for (int t = wave8; t < 20; t += 8) {
+        const int mt = t & 3, nt = t >> 2;
+        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+        const float* pa = sG + g * WGB_PITCH + 16 * mt + li;
+        const float* pb = sX + g * WGB_PITCH + 16 * nt + li;
 #pragma unroll
-            for (int P = 0; P < KQ1 / 2; ++P) a1 = mx_mfma_bf16(mx_a_bf16<KQ1>(L.G1 + li * LDG, P, g), mx_b_bf16<KQ1>(D1, P), a1);
+        for (int kk = 0; kk < R / 4; ++kk)
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(pa[kk * 4 * WGB_PITCH], pb[kk * 4 * WGB_PITCH], acc, 0, 0, 0);
+        const int n = 16 * nt + li;
+        if (n < N1) {
 #pragma unroll
-            for (int P = 0; P < KQF / 2; ++P) af = mx_mfma_bf16(mx_a_bf16<KQF>(L.Gf + li * LDF, P, g), mx_b_bf16<KQF>(Df, P), af);
-        } else {
-            const float* gp = L.G1 + li * LDG + 4 * g;
-            const float* fp = L.Gf + li * LDF + 4 * g;
-#pragma unroll
-            for (int Q = 0; Q < KQ1; ++Q) {
-                const f32x4 a = *reinterpret_cast<const f32x4*>(gp + 16 * Q);
-#pragma unroll
-                for (int jj = 0; jj < 4; ++jj) a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[jj], D1[Q][jj], a1, 0, 0, 0);
-            }
-#pragma unroll
-            for (int Q = 0; Q < KQF; ++Q) {
-                const f32x4 a = *reinterpret_cast<const f32x4*>(fp + 16 * Q);
-#pragma unroll
-                for (int jj = 0; jj < 4; ++jj) af = __builtin_amdgcn_mfma_f32_16x16x4f32(a[jj], Df[Q][jj], af, 0, 0, 0);
-            }
-        }
-        const int n = 16 * wave8 + li;
-        float s1 = 0.0f, sf = 0.0f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = 4 * g + r;
-            const int64_t m = m0 + row;
-            const float v1 = (Hs[row * MX_LDH + n] > 0.0f) ? a1[r] : 0.0f;
-            const float vf = (Hs[row * MX_LDH + MX_HH + n] > 0.0f) ? af[r] : 0.0f;
-            if constexpr (STATIC) {
-                s1 = r == 0 ? v1 : s1 + v1;
-                sf = r == 0 ? vf : sf + vf;
-            } else if (m < Mev) {
-                io.gout1[m * MX_N1 + n] = v1;
-                io.gout1[m * MX_N1 + MX_HH + n] = vf;
-            }
-        }
-        if constexpr (STATIC) {   // this lane's four rows above, then the four lane groups
-            s1 += __shfl_xor(s1, 16, 64);
-            s1 += __shfl_xor(s1, 32, 64);
-            sf += __shfl_xor(sf, 16, 64);
-            sf += __shfl_xor(sf, 32, 64);
-            if (g == 0) {
-                io.gout1[tile * MX_N1 + n] = s1;
-                io.gout1[tile * MX_N1 + MX_HH + n] = sf;
-            }
+            for (int r = 0; r < 4; ++r) wb.ws1[(tile * 64 + 16 * mt + 4 * g + r) * Np1 + n] = acc[r];
         }
     }
-    if constexpr (STATIC) {
-        // column sums over the tile's LDS rows, row 0 first: g_w1raw / g_wfraw (threads 0 .. J Em + Em - 1), the V block of
-        // gout1 (threads 256 .. 256 + Em - 1, each row under its own ReLU mask) and g_v (thread 256 + Em)
-        const int c = threadIdx.x;
-        if (c < J * MX_EM) {
-            float s = L.G1[c];
-#pragma unroll
-            for (int row = 1; row < 16; ++row) s += L.G1[row * LDG + c];
-            io.g_w1raw[tile * (J * MX_EM) + c] = s;
-        } else if (c < J * MX_EM + MX_EM) {
-            const int cf = c - J * MX_EM;
-            float s = L.Gf[cf];
-#pragma unroll
-            for (int row = 1; row < 16; ++row) s += L.Gf[row * LDF + cf];
-            io.g_wfraw[tile * MX_EM + cf] = s;
-        } else if (c >= 256 && c < 256 + MX_EM) {
-            const int k = c - 256;   // wvo[0] = wV2[k]
-            float s = (Hs[2 * MX_HH + k] > 0.0f) ? L.gv_s[0] * wvo[0] : 0.0f;
-#pragma unroll
-            for (int row = 1; row < 16; ++row) s += (Hs[row * MX_LDH + 2 * MX_HH + k] > 0.0f) ? L.gv_s[row] * wvo[0] : 0.0f;
-            io.gout1[tile * MX_N1 + 2 * MX_HH + k] = s;
-        } else if (c == 256 + MX_EM) {
-            float s = L.gv_s[0];
-#pragma unroll
-            for (int row = 1; row < 16; ++row) s += L.gv_s[row];
-            io.g_v[tile] = s;
+    if (wave8 == 0) {          // the LayerNorm slot: the eight runs of u as a fixed tree
+        if (lane < S) {
+            const float u = ((up[lane] + up[64 + lane]) + (up[128 + lane] + up[192 + lane])) +
+                            ((up[256 + lane] + up[320 + lane]) + (up[384 + lane] + up[448 + lane]));
+            wb.ln_slots[(tile * 2) * S + lane] = xhat[tile * S + lane] * u;
+            wb.ln_slots[(tile * 2 + 1) * S + lane] = u;
         }
-        return;
+    } else if (wave8 == 1) {   // db1: column sums of g_hid, rows ascending
+        float s = sG[lane];
+#pragma unroll 8
+        for (int r = 1; r < R; ++r) s += sG[r * WGB_PITCH + lane];
+        wb.ws1[n_tiles * 64 * Np1 + tile * 64 + lane] = s;
+    } else if (wave8 == 2) {   // dw2[m] = sum_r gq[r] act_q[r][m]
+        float s = 0.0f;
+#pragma unroll 8
+        for (int r = 0; r < R; ++r) s = fmaf(sQ[r], sAq[r * 64 + lane], s);
+        wb.ws2[tile * 64 * 64 + lane] = s;
+    } else if (wave8 == 3 && lane == 0) {   // db2 = sum_r gq[r]
+        float s = sQ[0];
+        for (int r = 1; r < R; ++r) s += sQ[r];
+        wb.ws2[n_tiles * 64 * 64 + tile * 64] = s;
     }
-    // the V head's one-output second layer: outer product g_v wV2, masked: columns [2 Hh, 2 Hh + Em)
-#pragma unroll
-    for (int i = 0; i < 16 * MX_EM / 512; ++i) {
-        const int idx = threadIdx.x + 512 * i;
-        const int row = idx / MX_EM, k = idx - row * MX_EM;
-        if (m0 + row < Mev)
-            io.gout1[(m0 + row) * MX_N1 + 2 * MX_HH + k] = (Hs[row * MX_LDH + 2 * MX_HH + k] > 0.0f) ? L.gv_s[row] * wvo[i] : 0.0f;
-    }
+}
+
+template <int J, bool BF, bool NARROW, bool STATIC = false>
+__global__ void __launch_bounds__(512) mixer_fused_train_kernel(const macjd_mixerf_io io, const macjd_mixerf_io tio,
+                                                                 const macjd_tdloss_io td, const float* __restrict__ tot_m) {
+#define MX_TRAIN_WG 0
+#include "macjd_mixer_train_body.h"
+#undef MX_TRAIN_WG
+}
+
+template <int J, bool NARROW>
+__global__ void __launch_bounds__(512) mixer_fused_train_wgrad_kernel(const macjd_mixerf_io io, const macjd_mixerf_io tio,
+                                                                       const macjd_tdloss_io td, const float* __restrict__ tot_m,
+                                                                       const macjd_mixer_wgrad_block wb) {
+    constexpr bool BF = false, STATIC = true;
+#define MX_TRAIN_WG 1
+#include "macjd_mixer_train_body.h"
+#undef MX_TRAIN_WG
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1421,6 +1367,19 @@ static void mixerf_launch_train_static(const macjd_mixerf_io* eval, const macjd_
     else hipLaunchKernelGGL((mixer_fused_train_kernel<3, BF, NARROW, true>), grid, block, 0, s, *eval, *target, *td, tot_m);
 }
 
+// floats of `slots` slots of an [M, N] weight-gradient problem with their bias rows (= macjd_wgrad_slot_floats: tiles of 64)
+static int64_t mixerf_wgrad_slot_floats(int64_t M, int64_t N, int64_t slots) {
+    const int64_t Mp = (M + 63) / 64 * 64, Np = (N + 63) / 64 * 64;
+    return slots * Mp * Np + slots * Mp;
+}
+
+template <bool NARROW>
+static void mixerf_launch_train_wgrad(const macjd_mixerf_io* eval, const macjd_mixerf_io* target, const macjd_tdloss_io* td,
+                                      const float* tot_m, const macjd_mixer_wgrad_block* wg, dim3 grid, dim3 block, hipStream_t s) {
+    if (eval->J == 2) hipLaunchKernelGGL((mixer_fused_train_wgrad_kernel<2, NARROW>), grid, block, 0, s, *eval, *target, *td, tot_m, *wg);
+    else hipLaunchKernelGGL((mixer_fused_train_wgrad_kernel<3, NARROW>), grid, block, 0, s, *eval, *target, *td, tot_m, *wg);
+}
+
 // the argument checks the two training entry points share (`eval` with the output pointers its kernel writes through)
 static int mixerf_train_check(const char* fn, const macjd_mixerf_io* eval, const macjd_mixerf_io* target, const macjd_tdloss_io* td,
                               const float* tot_m) {
@@ -1543,8 +1502,14 @@ extern "C" int macjd_mixer_fused_train(const macjd_mixerf_io* eval, const macjd_
 
 extern "C" int macjd_mixer_fused_train_static(const macjd_mixerf_io* eval, const macjd_mixerf_io* target, const macjd_tdloss_io* td,
                                               const float* tot_m, const macjd_mixer_static_io* st, void* hip_stream) {
+    return macjd_mixer_fused_train_static_wgrad(eval, target, td, tot_m, st, nullptr, hip_stream);
+}
+
+extern "C" int macjd_mixer_fused_train_static_wgrad(const macjd_mixerf_io* eval, const macjd_mixerf_io* target,
+                                                    const macjd_tdloss_io* td, const float* tot_m, const macjd_mixer_static_io* st,
+                                                    const macjd_mixer_wgrad_block* wg, void* hip_stream) {
     using namespace macjd;
-    const char* fn = "macjd_mixer_fused_train_static";
+    const char* fn = wg ? "macjd_mixer_fused_train_static_wgrad" : "macjd_mixer_fused_train_static";
     if (!eval || !st) return set_err(MACJD_EINVAL, "%s: NULL argument", fn);
     if (!st->sn || !st->xhat || !st->act || !st->gout1_sum || !st->g_w1raw_sum || !st->g_wfraw_sum || !st->g_v_sum)
         return set_err(MACJD_EINVAL, "%s: NULL compact output", fn);
@@ -1560,10 +1525,23 @@ extern "C" int macjd_mixer_fused_train_static(const macjd_mixerf_io* eval, const
     const int64_t n_tiles = (int64_t)td->B * ((td->gy_cols + 15) / 16);
     if (st->n_tiles != n_tiles || n_tiles > 0x7fffffff)
         return set_err(MACJD_EINVAL, "%s: n_tiles must be B x ceil(gy_cols / 16)", fn);
+    if (wg) {
+        if (ev.operand_dtype) return set_err(MACJD_EUNSUPPORTED, "%s: f32 operands only", fn);
+        if (!wg->act_q || !wg->h || !wg->idx || !wg->P || !wg->w2 || !wg->ws1 || !wg->ws2 || !wg->ln_slots || !wg->W_first)
+            return set_err(MACJD_EINVAL, "%s: NULL member of the weight-gradient block", fn);
+        if (wg->H != 64 || wg->A < 1 || wg->A > 15) return set_err(MACJD_EUNSUPPORTED, "%s: H = 64 and 1 <= A <= 15", fn);
+        if ((((uintptr_t)wg->act_q) & 15) || (((uintptr_t)wg->h) & 15) || (wg->act_ld & 3) || (wg->h_ld & 3) || wg->act_ld < wg->H ||
+            wg->h_ld < wg->H || (wg->idx_elem_size != 4 && wg->idx_elem_size != 8) || wg->w_ld < ev.S)
+            return set_err(MACJD_EINVAL, "%s: bad stride, alignment or index size in the weight-gradient block", fn);
+        if (wg->ws1_floats < mixerf_wgrad_slot_floats(wg->H, wg->H + wg->A + 1, n_tiles) ||
+            wg->ws2_floats < mixerf_wgrad_slot_floats(1, wg->H, n_tiles) || wg->ln_floats < n_tiles * 2 * ev.S)
+            return set_err(MACJD_EINVAL, "%s: a workspace of the weight-gradient block is smaller than n_tiles slots", fn);
+    }
     const dim3 grid((unsigned)n_tiles), block(512);
     hipStream_t s = (hipStream_t)hip_stream;
     const bool narrow = mixerf_narrow(&ev);
-    if (ev.operand_dtype) mixerf_launch_train_static<true, false>(&ev, target, td, tot_m, grid, block, s);
+    if (wg) narrow ? mixerf_launch_train_wgrad<true>(&ev, target, td, tot_m, wg, grid, block, s) : mixerf_launch_train_wgrad<false>(&ev, target, td, tot_m, wg, grid, block, s);
+    else if (ev.operand_dtype) mixerf_launch_train_static<true, false>(&ev, target, td, tot_m, grid, block, s);
     else narrow ? mixerf_launch_train_static<false, true>(&ev, target, td, tot_m, grid, block, s) : mixerf_launch_train_static<false, false>(&ev, target, td, tot_m, grid, block, s);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_mixer_fused_train_static: %s", hipGetErrorString(err));

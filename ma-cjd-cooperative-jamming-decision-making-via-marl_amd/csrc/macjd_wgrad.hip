@@ -44,6 +44,27 @@ constexpr int WG_ROWS = WG_KC * WG_SUB;   // rows of the reduction per work item
 
 __host__ __device__ inline int64_t wg_pad(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
+// One problem as the kernels take it: macjd_wgrad_io without the fields only the host reads (kind, ext_chunks), so the
+// argument blocks — and the code — of the launches that know no kinds are what they were before the kinds existed.
+struct WgradDevIO {
+    int64_t K;
+    int32_t M, N;
+    const float* gout; int64_t gout_ld;
+    const float* inp;  int64_t inp_ld;
+    float* dW;         int64_t dw_ld;
+    float* db;
+    float* workspace;
+    const float* outer_vec;
+    const float* outer_w;
+};
+
+inline WgradDevIO wg_dev(const macjd_wgrad_io& io) {
+    WgradDevIO d;
+    d.K = io.K; d.M = io.M; d.N = io.N; d.gout = io.gout; d.gout_ld = io.gout_ld; d.inp = io.inp; d.inp_ld = io.inp_ld;
+    d.dW = io.dW; d.dw_ld = io.dw_ld; d.db = io.db; d.workspace = io.workspace; d.outer_vec = io.outer_vec; d.outer_w = io.outer_w;
+    return d;
+}
+
 // fields of one problem as the partial-products body needs them (selected with compile-time indices from a batch)
 struct WgradProb {
     int64_t K, gout_ld, inp_ld;
@@ -286,7 +307,7 @@ __device__ __forceinline__ float wgrad_wave_sum(float x) {
     return x;
 }
 
-__global__ void __launch_bounds__(256) wgrad_partial_kernel(const macjd_wgrad_io io, const int Mp, const int Np) {
+__global__ void __launch_bounds__(256) wgrad_partial_kernel(const WgradDevIO io, const int Mp, const int Np) {
     __shared__ float sA[WG_KC * WG_PITCH];   // gout chunk  [k][m]
     __shared__ float sB[WG_KC * WG_PITCH];   // inp chunk   [k][n]
     WgradProb p;
@@ -330,7 +351,7 @@ __device__ __forceinline__ float wgrad_meet(float (*part)[WG_RED], const float m
     return out;
 }
 
-__global__ void __launch_bounds__(256) wgrad_reduce_kernel(const macjd_wgrad_io io, const int Mp, const int Np,
+__global__ void __launch_bounds__(256) wgrad_reduce_kernel(const WgradDevIO io, const int Mp, const int Np,
                                                            const int n_chunks) {
     __shared__ float part[4][WG_RED];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -354,7 +375,7 @@ __global__ void __launch_bounds__(256) wgrad_reduce_kernel(const macjd_wgrad_io 
 
 // ---- several problems in one launch pair (the backward pass of the learner defers its weight gradients) ----
 struct WgradBatch {
-    macjd_wgrad_io io[MACJD_WGRAD_MAX_BATCH];
+    WgradDevIO io[MACJD_WGRAD_MAX_BATCH];
     int Mp[MACJD_WGRAD_MAX_BATCH], Np[MACJD_WGRAD_MAX_BATCH], chunks[MACJD_WGRAD_MAX_BATCH];
     int tiles_n[MACJD_WGRAD_MAX_BATCH], tiles_m[MACJD_WGRAD_MAX_BATCH];
     int64_t wg_start[MACJD_WGRAD_MAX_BATCH + 1];    // prefix of workgroups (tile x chunk work items) per problem
@@ -454,7 +475,32 @@ __global__ void __launch_bounds__(256) wgrad_partial_many_norm_kernel(const Wgra
 // wgrad_reduce_many_kernel with (1) the contracted problem's 2 N outputs (item i = which * N + n sums element i of its
 // `slots` slots of 2 N floats), (2) partials[workgroup] = sum of the squares of what the workgroup stored: per lane of
 // wave 0 in item order, then wgrad_wave_sum, (3) the step counter.
-__global__ void __launch_bounds__(256) wgrad_reduce_many_norm_kernel(const WgradBatch b, const WgradNorm ln) {
+//
+// ROWS (wgrad_reduce_many_rows_kernel): problems whose bit is set in `rows_mask` are ROW PRODUCTS — term k of output (m, n)
+// is gout[k, m] * inp[k, n] (bias output: gout[k, m]) read from the operands, b.chunks[] = K terms.  Every lane loads two
+// values per term, (slot value, itself) or (gout, inp), and adds fmaf(first, second-or-1, acc): for a slot value that is
+// acc + value, the very sum of the other instantiation.
+__device__ __forceinline__ float wgrad_sum_rounds_rows(const float* __restrict__ pa, const int64_t sa, const float* __restrict__ pb,
+                                                       const int64_t sb, const bool two, const int n_terms, const int wave) {
+    float a[8];
+#pragma unroll
+    for (int s8 = 0; s8 < 8; ++s8) a[s8] = 0.0f;
+    for (int c = 8 * wave; c < n_terms; c += 32) {
+        float v[8], x[8];
+#pragma unroll
+        for (int s8 = 0; s8 < 8; ++s8) {   // (no branch around a load: past the last term the last term is read and dropped)
+            const int cc = c + s8 < n_terms ? c + s8 : n_terms - 1;
+            v[s8] = pa[(int64_t)cc * sa];
+            x[s8] = pb[(int64_t)cc * sb];
+        }
+#pragma unroll
+        for (int s8 = 0; s8 < 8; ++s8) a[s8] = fmaf((c + s8 < n_terms) ? v[s8] : 0.0f, two ? x[s8] : 1.0f, a[s8]);
+    }
+    return ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+}
+
+template <bool ROWS>
+__device__ __forceinline__ void wgrad_reduce_norm_body(const WgradBatch& b, const WgradNorm& ln, const unsigned rows_mask) {
     __shared__ float part[4][WG_RED];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t total_all = b.out_start[b.n];
@@ -481,7 +527,24 @@ __global__ void __launch_bounds__(256) wgrad_reduce_many_norm_kernel(const Wgrad
         const int n = is_w ? (int)(i - (int64_t)m * N) : 0;
         const float* src = is_ln ? workspace + i : is_w ? workspace + (int64_t)m * Np + n : workspace + (int64_t)n_chunks * Mp * Np + m;
         const int64_t stride = is_ln ? (int64_t)2 * N : is_w ? (int64_t)Mp * Np : (int64_t)Mp;
-        const float v = wgrad_meet(part, wgrad_sum_rounds(src, stride, is_ln ? ln.slots : n_chunks, wave), wave, lane);
+        float mine;
+        if constexpr (ROWS) {
+            const float* gout = b.io[0].gout;
+            const float* inp = b.io[0].inp;
+            int64_t gout_ld = b.io[0].gout_ld, inp_ld = b.io[0].inp_ld;
+#pragma unroll
+            for (int q = 1; q < MACJD_WGRAD_MAX_BATCH; ++q) {
+                if (q == prob) { gout = b.io[q].gout; inp = b.io[q].inp; gout_ld = b.io[q].gout_ld; inp_ld = b.io[q].inp_ld; }
+            }
+            const bool rows = ((rows_mask >> prob) & 1u) != 0;   // (never the contracted problem)
+            const bool two = rows && is_w;
+            const float* pa = rows ? gout + m : src;
+            const int64_t sa = rows ? gout_ld : stride;
+            mine = wgrad_sum_rounds_rows(pa, sa, two ? inp + n : pa, two ? inp_ld : sa, two, is_ln ? ln.slots : n_chunks, wave);
+        } else {
+            mine = wgrad_sum_rounds(src, stride, is_ln ? ln.slots : n_chunks, wave);
+        }
+        const float v = wgrad_meet(part, mine, wave, lane);
         if (wave == 0 && g0 + lane < total_all) {
             // (a problem without a bias output still owns M items behind its M N: summed, dropped, and not counted)
             float* dst = is_ln ? (i < N ? ln.dgamma + i : ln.dbeta + (i - N)) : is_w ? dW + (int64_t)m * dw_ld + n : db ? db + m : nullptr;
@@ -500,6 +563,14 @@ __global__ void __launch_bounds__(256) wgrad_reduce_many_norm_kernel(const Wgrad
     }
 }
 
+__global__ void __launch_bounds__(256) wgrad_reduce_many_norm_kernel(const WgradBatch b, const WgradNorm ln) {
+    wgrad_reduce_norm_body<false>(b, ln, 0u);
+}
+
+__global__ void __launch_bounds__(256) wgrad_reduce_many_rows_kernel(const WgradBatch b, const WgradNorm ln, const unsigned rows_mask) {
+    wgrad_reduce_norm_body<true>(b, ln, rows_mask);
+}
+
 }  // namespace macjd
 
 extern "C" int64_t macjd_linear_wgrad_workspace_floats(int64_t K, int32_t M, int32_t N) {
@@ -511,6 +582,8 @@ extern "C" int64_t macjd_linear_wgrad_workspace_floats(int64_t K, int32_t M, int
 
 extern "C" int macjd_linear_wgrad(const macjd_wgrad_io* io, void* hip_stream) {
     using namespace macjd;
+    if (io && io->kind != MACJD_WGRAD_ORDINARY)
+        return set_err(MACJD_EUNSUPPORTED, "%s", "macjd_linear_wgrad: problem kinds are macjd_linear_wgrad_many_norm's");
     if (!io || io->K < 1 || io->M < 1 || io->N < 1 || !io->gout || !io->inp || !io->dW || !io->workspace)
         return set_err(MACJD_EINVAL, "%s", "macjd_linear_wgrad: bad argument");
     if (io->gout_ld < io->M || io->inp_ld < io->N || io->dw_ld < io->N)
@@ -521,10 +594,10 @@ extern "C" int macjd_linear_wgrad(const macjd_wgrad_io* io, void* hip_stream) {
     const int64_t chunks = (io->K + WG_ROWS - 1) / WG_ROWS;
     if (chunks > 65535) return set_err(MACJD_EUNSUPPORTED, "%s", "macjd_linear_wgrad: K too large");
     hipStream_t s = (hipStream_t)hip_stream;
-    hipLaunchKernelGGL(wgrad_partial_kernel, dim3(Np / WG_BN, Mp / WG_BM, (unsigned)chunks), dim3(256), 0, s, *io, Mp, Np);
+    hipLaunchKernelGGL(wgrad_partial_kernel, dim3(Np / WG_BN, Mp / WG_BM, (unsigned)chunks), dim3(256), 0, s, wg_dev(*io), Mp, Np);
     const int64_t total = (int64_t)io->M * io->N + io->M;   // WG_RED output elements per workgroup
     const unsigned rblocks = (unsigned)((total + WG_RED - 1) / WG_RED < 8192 ? (total + WG_RED - 1) / WG_RED : 8192);
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(rblocks), dim3(256), 0, s, *io, Mp, Np, (int)chunks);
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(rblocks), dim3(256), 0, s, wg_dev(*io), Mp, Np, (int)chunks);
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_linear_wgrad: %s", hipGetErrorString(err));
     return MACJD_OK;
@@ -538,13 +611,15 @@ extern "C" int macjd_linear_wgrad_many(const macjd_wgrad_io* ios, int32_t n, voi
     b.n = n;
     for (int p = 0; p < n; ++p) {
         const macjd_wgrad_io* io = &ios[p];
+        if (io->kind != MACJD_WGRAD_ORDINARY)
+            return set_err(MACJD_EUNSUPPORTED, "%s", "macjd_linear_wgrad_many: problem kinds are macjd_linear_wgrad_many_norm's");
         if (io->K < 1 || io->M < 1 || io->N < 1 || !io->gout || !io->inp || !io->dW || !io->workspace)
             return set_err(MACJD_EINVAL, "%s", "macjd_linear_wgrad_many: bad argument");
         if (io->gout_ld < io->M || io->inp_ld < io->N || io->dw_ld < io->N)
             return set_err(MACJD_EINVAL, "%s", "macjd_linear_wgrad_many: bad leading dimension");
         if ((io->outer_vec == nullptr) != (io->outer_w == nullptr))
             return set_err(MACJD_EINVAL, "%s", "macjd_linear_wgrad_many: outer_vec and outer_w go together");
-        b.io[p] = *io;
+        b.io[p] = wg_dev(*io);
         b.Mp[p] = (int)wg_pad(io->M, WG_BM);
         b.Np[p] = (int)wg_pad(io->N, WG_BN);
         b.chunks[p] = (int)((io->K + WG_ROWS - 1) / WG_ROWS);
@@ -570,32 +645,46 @@ extern "C" int macjd_linear_wgrad_many(const macjd_wgrad_io* ios, int32_t n, voi
 }
 
 // validation and tables of the grouped launches that know a contracted problem; returns MACJD_OK or the error set
-static int wgrad_norm_batch(const macjd_wgrad_io* ios, int32_t n, int32_t ln_problem, macjd::WgradBatch* out, const char* who) {
+static int wgrad_norm_batch(const macjd_wgrad_io* ios, int32_t n, int32_t ln_problem, macjd::WgradBatch* out, const char* who,
+                            unsigned* rows_mask = nullptr) {
     using namespace macjd;
     if (!ios || n < 1 || n > MACJD_WGRAD_MAX_BATCH || ln_problem < -1 || ln_problem >= n)
         return set_err(MACJD_EINVAL, "%s: 1..MACJD_WGRAD_MAX_BATCH problems, ln_problem -1 or one of them", who);
     WgradBatch& b = *out;
     b = WgradBatch{};
     b.n = n;
+    unsigned rows = 0;
     for (int p = 0; p < n; ++p) {
         const macjd_wgrad_io* io = &ios[p];
         const bool is_ln = p == ln_problem;
-        if (io->K < 1 || io->M < 1 || io->N < 1 || !io->gout || !io->inp || (!io->dW && !is_ln) || !io->workspace)
-            return set_err(MACJD_EINVAL, "%s: bad argument", who);
-        if (io->gout_ld < io->M || io->inp_ld < io->N || (!is_ln && io->dw_ld < io->N))
-            return set_err(MACJD_EINVAL, "%s: bad leading dimension", who);
-        if ((io->outer_vec == nullptr) != (io->outer_w == nullptr))
-            return set_err(MACJD_EINVAL, "%s: outer_vec and outer_w go together", who);
+        const bool ext = io->kind == MACJD_WGRAD_EXT_SLOTS, rowp = io->kind == MACJD_WGRAD_ROW_PRODUCTS;
+        if (io->kind != MACJD_WGRAD_ORDINARY && !ext && !rowp) return set_err(MACJD_EINVAL, "%s: unknown problem kind", who);
+        if (io->M < 1 || io->N < 1 || (!io->dW && !is_ln)) return set_err(MACJD_EINVAL, "%s: bad argument", who);
+        if (!rowp && !io->workspace) return set_err(MACJD_EINVAL, "%s: bad argument", who);
+        if (ext) {   // the slots are there: the operands are not read
+            if (io->ext_chunks < 1) return set_err(MACJD_EINVAL, "%s: ext_chunks must be >= 1", who);
+        } else {
+            if (io->K < 1 || !io->gout || !io->inp) return set_err(MACJD_EINVAL, "%s: bad argument", who);
+            if (io->gout_ld < io->M || io->inp_ld < io->N) return set_err(MACJD_EINVAL, "%s: bad leading dimension", who);
+            if ((io->outer_vec == nullptr) != (io->outer_w == nullptr))
+                return set_err(MACJD_EINVAL, "%s: outer_vec and outer_w go together", who);
+        }
+        if (!is_ln && io->dw_ld < io->N) return set_err(MACJD_EINVAL, "%s: bad leading dimension", who);
+        if (rowp && (is_ln || io->outer_vec || io->K > 0x7fffffff))
+            return set_err(MACJD_EUNSUPPORTED, "%s: a row-products problem is not contracted and has no outer_vec", who);
         if (is_ln && (io->N > WG_BN || io->db))
             return set_err(MACJD_EUNSUPPORTED, "%s: the contracted problem has N <= 64 and no bias output", who);
-        b.io[p] = *io;
+        b.io[p] = wg_dev(*io);
         b.Mp[p] = (int)wg_pad(io->M, WG_BM);
         b.Np[p] = (int)wg_pad(io->N, WG_BN);
-        b.chunks[p] = (int)((io->K + WG_ROWS - 1) / WG_ROWS);
+        // terms of an output in the reduce launch: partial tiles, the slots that are there already, or the rows themselves
+        b.chunks[p] = ext ? io->ext_chunks : rowp ? (int)io->K : (int)((io->K + WG_ROWS - 1) / WG_ROWS);
         b.tiles_n[p] = b.Np[p] / WG_BN;
         b.tiles_m[p] = b.Mp[p] / WG_BM;
-        b.wg_start[p + 1] = b.wg_start[p] + (int64_t)b.tiles_n[p] * b.tiles_m[p] * b.chunks[p];
+        // (a problem of kind != 0 has no work item in the partial-products launch)
+        b.wg_start[p + 1] = b.wg_start[p] + ((ext || rowp) ? 0 : (int64_t)b.tiles_n[p] * b.tiles_m[p] * b.chunks[p]);
         b.out_start[p + 1] = b.out_start[p] + (is_ln ? (int64_t)2 * io->N : (int64_t)io->M * io->N + io->M);
+        if (rowp) rows |= 1u << p;
     }
     for (int p = n; p < MACJD_WGRAD_MAX_BATCH; ++p) {
         b.wg_start[p + 1] = b.wg_start[n];
@@ -603,6 +692,7 @@ static int wgrad_norm_batch(const macjd_wgrad_io* ios, int32_t n, int32_t ln_pro
         b.tiles_n[p] = b.tiles_m[p] = 1;
     }
     if (b.wg_start[n] > 0x7fffffff) return set_err(MACJD_EUNSUPPORTED, "%s: too many work items", who);
+    if (rows_mask) *rows_mask = rows;
     return MACJD_OK;
 }
 
@@ -617,27 +707,44 @@ extern "C" int32_t macjd_linear_wgrad_many_norm_partials(const macjd_wgrad_io* i
     return (int32_t)wgrad_reduce_blocks(b.out_start[n]);
 }
 
+extern "C" int64_t macjd_linear_wgrad_many_norm_work_items(const macjd_wgrad_io* ios, int32_t n, int32_t ln_problem) {
+    macjd::WgradBatch b;
+    if (wgrad_norm_batch(ios, n, ln_problem, &b, "macjd_linear_wgrad_many_norm_work_items") != MACJD_OK) return -1;
+    return b.wg_start[n];
+}
+
+extern "C" int64_t macjd_wgrad_slot_floats(int32_t M, int32_t N, int64_t slots) {
+    using namespace macjd;
+    if (M < 1 || N < 1 || slots < 1) return -1;
+    const int64_t Mp = wg_pad(M, WG_BM), Np = wg_pad(N, WG_BN);
+    return slots * Mp * Np + slots * Mp;
+}
+
 extern "C" int macjd_linear_wgrad_many_norm(const macjd_wgrad_io* ios, int32_t n, const macjd_wgrad_norm_io* norm, void* hip_stream) {
     using namespace macjd;
     const char* who = "macjd_linear_wgrad_many_norm";
     if (!norm || !norm->partials || !norm->step) return set_err(MACJD_EINVAL, "%s: bad argument", who);
     WgradBatch b;
-    const int rc = wgrad_norm_batch(ios, n, norm->ln_problem, &b, who);
+    unsigned rows_mask = 0;
+    const int rc = wgrad_norm_batch(ios, n, norm->ln_problem, &b, who, &rows_mask);
     if (rc != MACJD_OK) return rc;
     WgradNorm ln{};
     ln.problem = norm->ln_problem;
     ln.partials = norm->partials; ln.step = norm->step;
     if (ln.problem >= 0) {
-        if (!norm->W || !norm->dgamma || !norm->dbeta || norm->w_ld < ios[ln.problem].N)
+        const bool ext_ln = ios[ln.problem].kind == MACJD_WGRAD_EXT_SLOTS;   // (slots contracted already: W is not read)
+        if (!norm->dgamma || !norm->dbeta || (!ext_ln && (!norm->W || norm->w_ld < ios[ln.problem].N)))
             return set_err(MACJD_EINVAL, "%s: bad LayerNorm argument", who);
         ln.W = norm->W; ln.w_ld = norm->w_ld; ln.dgamma = norm->dgamma; ln.dbeta = norm->dbeta;
-        ln.slots = b.tiles_m[ln.problem] * b.chunks[ln.problem];
+        ln.slots = ios[ln.problem].kind == MACJD_WGRAD_EXT_SLOTS ? b.chunks[ln.problem] : b.tiles_m[ln.problem] * b.chunks[ln.problem];
     }
     const unsigned rblocks = wgrad_reduce_blocks(b.out_start[n]);
     if ((int64_t)rblocks > (int64_t)norm->partials_cap) return set_err(MACJD_EINVAL, "%s: partials_cap too small", who);
     hipStream_t s = (hipStream_t)hip_stream;
-    hipLaunchKernelGGL(wgrad_partial_many_norm_kernel, dim3((unsigned)b.wg_start[n]), dim3(256), 0, s, b, ln);
-    hipLaunchKernelGGL(wgrad_reduce_many_norm_kernel, dim3(rblocks), dim3(256), 0, s, b, ln);
+    if (b.wg_start[n] > 0)   // (no problem of kind 0: nothing to multiply)
+        hipLaunchKernelGGL(wgrad_partial_many_norm_kernel, dim3((unsigned)b.wg_start[n]), dim3(256), 0, s, b, ln);
+    if (rows_mask) hipLaunchKernelGGL(wgrad_reduce_many_rows_kernel, dim3(rblocks), dim3(256), 0, s, b, ln, rows_mask);
+    else hipLaunchKernelGGL(wgrad_reduce_many_norm_kernel, dim3(rblocks), dim3(256), 0, s, b, ln);
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_linear_wgrad_many_norm: %s", hipGetErrorString(err));
     return MACJD_OK;

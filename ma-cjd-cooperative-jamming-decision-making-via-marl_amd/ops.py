@@ -214,16 +214,41 @@ def pair_mixer_train_with_next_fused(q, s, params, reward, terminated, filled, g
     return y, placeholder
 
 
+# The update without a partial-products launch (MACJD_WGRAD_IN_TRAIN, include/macjd_nets.h macjd_mixer_wgrad_block): a
+# caller that knows the whole chain — Q-head grid, static mixer training launch, weight gradients through
+# ``deferred_wgrad(norm=...)`` — announces it BEFORE the Q-head grid goes out.  The plan is a dict that travels with the
+# chain: ``_QheadTaken.forward`` writes no input rows and leaves its operands in it, ``_mixer_train`` passes them to the
+# training launch with the slot workspaces it allocates (inside the capture, like every workspace), and the two backward
+# passes record problems whose terms the reduce launch finds in those slots or forms itself.
+_WGRAD_IN_TRAIN = None
+wgrad_partial_launches = 0   # partial-products launches issued by ``deferred_wgrad`` (bookkeeping; the tests read it)
+
+
+def wgrad_in_train_supported(H: int, A: int) -> bool:
+    """Sizes macjd_mixer_fused_train_static_wgrad takes for the Q-head: H = 64 hidden units, 1 .. 15 actions."""
+    return int(H) == 64 and 1 <= int(A) <= 15
+
+
+def plan_wgrad_in_train():
+    """Announce the chain above: the next ``qhead_taken`` forward and the next static mixer training launch take the plan.
+    The caller vouches for what the kernels cannot see: every Q-head and mixer parameter gets its gradient from this
+    chain, and the backward runs inside ``deferred_wgrad(norm=...)`` with a plan ``norm_in_reduce_plan`` accepts (it raises
+    otherwise: there is no other way to these gradients once the Q-head grid has run without its input rows)."""
+    global _WGRAD_IN_TRAIN
+    assert _WGRAD_IN_TRAIN is None, "a weight-gradient plan is already waiting"
+    _WGRAD_IN_TRAIN = {}
+
+
 def clear_pending_pairs():
     """Drop every argument block handed to ``pair_*`` and not launched (a forward that raised before taking it)."""
-    global _PAIRED_DQ, _PAIRED_MIXER, _PAIRED_TRAIN
-    _PAIRED_DQ = _PAIRED_MIXER = _PAIRED_TRAIN = None
+    global _PAIRED_DQ, _PAIRED_MIXER, _PAIRED_TRAIN, _WGRAD_IN_TRAIN
+    _PAIRED_DQ = _PAIRED_MIXER = _PAIRED_TRAIN = _WGRAD_IN_TRAIN = None
 
 
 def assert_pairs_launched():
     """Every launch handed to ``pair_*`` has gone out (it has not if the autograd call took another code path)."""
-    left = [n for n, v in (("Double-DQN", _PAIRED_DQ), ("mixer", _PAIRED_MIXER), ("mixer training", _PAIRED_TRAIN))
-            if v is not None]
+    left = [n for n, v in (("Double-DQN", _PAIRED_DQ), ("mixer", _PAIRED_MIXER), ("mixer training", _PAIRED_TRAIN),
+                           ("weight-gradient plan", _WGRAD_IN_TRAIN)) if v is not None]
     clear_pending_pairs()
     if left:
         raise RuntimeError("paired launch not taken by the autograd forward it was meant for: " + ", ".join(left))
@@ -849,9 +874,15 @@ class _FusedMixer(torch.autograd.Function):
         params = _mixerf_params(ln_w, ln_b, eps, w_cat, b_cat, W2, b2, Wf2, bf2, wV2, bV2, bf16=bf16)
         global _PAIRED_TRAIN
         train, _PAIRED_TRAIN = _PAIRED_TRAIN, None
-        ctx.train = None
+        ctx.train = ctx.wg_plan = None
         if train is not None:   # target mixer, loss gradient and this mixer's backward in one launch (see _mixer_train)
-            y, qc, (sn, xhat, act), ctx.train = _mixer_train(q, s, params, train)
+            global _WGRAD_IN_TRAIN
+            plan = _WGRAD_IN_TRAIN
+            try:
+                y, qc, (sn, xhat, act), ctx.train = _mixer_train(q, s, params, train)
+            finally:
+                _WGRAD_IN_TRAIN = None
+            ctx.wg_plan = plan   # (filled by _mixer_train: the slots this launch wrote)
         else:
             y, qc, (sn, xhat, act) = mixer_fused_forward(q, s, params, save=True)
         ctx.save_for_backward(qc, sn, xhat, act, w_cat, W2, Wf2, wV2, ln_w, ln_b, b2, bf2, bV2)
@@ -901,12 +932,19 @@ class _FusedMixer(torch.autograd.Function):
         dev = q.device
         nd = ctx.needs_input_grad
         # weight / bias gradients: split-K products of the matrices the kernel wrote (recorded inside deferred_wgrad)
-        gW1, gb1 = linear_wgrad(gout1, sn, want_bias=True, w_key=grad_key(w_cat), b_key=ctx.keys["b_cat"])
-        G, _ = linear_wgrad(gout1, xhat, want_bias=False)
-        gW2, gb2 = linear_wgrad(g_w1, act[:, :Hh], want_bias=True, w_key=grad_key(W2), b_key=ctx.keys["b2"], need=(nd[7], nd[8]))
-        gWf, gbf = linear_wgrad(g_wf, act[:, Hh:2 * Hh], want_bias=True, w_key=grad_key(Wf2), b_key=ctx.keys["bf2"], need=(nd[9], nd[10]))
+        # wg_plan: the operands are the compact per-tile rows and the training launch left the LayerNorm slots — the
+        # reduce launch forms the five products from the rows themselves (macjd_wgrad_io.kind)
+        plan = getattr(ctx, "wg_plan", None)
+        kind = None if plan is None else _native.WGRAD_ROW_PRODUCTS
+        gW1, gb1 = linear_wgrad(gout1, sn, want_bias=True, w_key=grad_key(w_cat), b_key=ctx.keys["b_cat"], kind=kind)
+        G, _ = linear_wgrad(gout1, xhat, want_bias=False,
+                            kind=None if plan is None else (_native.WGRAD_EXT_SLOTS, plan["ln_slots"], plan["n_tiles"]))
+        gW2, gb2 = linear_wgrad(g_w1, act[:, :Hh], want_bias=True, w_key=grad_key(W2), b_key=ctx.keys["b2"], need=(nd[7], nd[8]),
+                                kind=kind)
+        gWf, gbf = linear_wgrad(g_wf, act[:, Hh:2 * Hh], want_bias=True, w_key=grad_key(Wf2), b_key=ctx.keys["bf2"], need=(nd[9], nd[10]),
+                                kind=kind)
         gWv, gbv = linear_wgrad(g_v, act[:, 2 * Hh:2 * Hh + Em], want_bias=True, w_key=grad_key(wV2), b_key=ctx.keys["bV2"],
-                                need=(nd[11], nd[12]))
+                                need=(nd[11], nd[12]), kind=kind)
         # LayerNorm parameter gradients from (W_cat, G, gb1), one small launch after the grouped products
         K = w_cat.shape[1]
         dgamma, dbeta = _grad_dst(ctx.keys["ln_w"], (K,)), _grad_dst(ctx.keys["ln_b"], (K,))
@@ -959,10 +997,33 @@ def _mixer_train(q, s, params, train):
     io.y, io.save, io.gq = y.data_ptr(), 1, gq.data_ptr()
     td.y = y.data_ptr()
     tot_m = keep[6]
+    if _WGRAD_IN_TRAIN is not None and (not static_rows or params.get("bf16") or "qhead" not in _WGRAD_IN_TRAIN):
+        raise _native.NativeLibraryError("weight-gradient plan: needs the static f32 mixer training launch behind a qhead_taken grid")
     if static_rows:
         st = _native.MixerStaticIO()
         st.n_tiles, st.sn, st.xhat, st.act = R, sn.data_ptr(), xhat.data_ptr(), act.data_ptr()
         st.gout1_sum, st.g_w1raw_sum, st.g_wfraw_sum, st.g_v_sum = gout1.data_ptr(), g_w1.data_ptr(), g_wf.data_ptr(), g_v.data_ptr()
+        plan = _WGRAD_IN_TRAIN
+        if plan is not None:
+            # the Q-head's two problems and the LayerNorm contraction leave this launch as per-tile slots
+            act_q, hq, iq, Pq, w2q, Hq, Aq = plan["qhead"]
+            assert act_q.shape[0] == M * J, "weight-gradient plan: the Q-head grid's rows are not this mixer's agent rows"
+            w1m = params["W1"]
+            new = lambda n_: torch.empty(int(n_), dtype=torch.float32, device=dev)
+            ws1 = new(lib.macjd_wgrad_slot_floats(Hq, Hq + Aq + 1, R))
+            ws2 = new(lib.macjd_wgrad_slot_floats(1, Hq, R))
+            ln_slots = new(R * 2 * S)
+            wb = _native.MixerWgradBlock()
+            wb.act_q, wb.act_ld, wb.h, wb.h_ld = act_q.data_ptr(), act_q.stride(0), hq.data_ptr(), hq.stride(0)
+            wb.idx, wb.idx_elem_size, wb.A, wb.P, wb.w2, wb.H = iq.data_ptr(), iq.element_size(), Aq, Pq.data_ptr(), w2q.data_ptr(), Hq
+            wb.ws1, wb.ws1_floats, wb.ws2, wb.ws2_floats = ws1.data_ptr(), ws1.numel(), ws2.data_ptr(), ws2.numel()
+            wb.ln_slots, wb.ln_floats, wb.W_first, wb.w_ld = ln_slots.data_ptr(), ln_slots.numel(), w1m.data_ptr(), w1m.stride(0)
+            with torch.cuda.device(dev):
+                _native.check(lib.macjd_mixer_fused_train_static_wgrad(ctypes.byref(io), ctypes.byref(tio), ctypes.byref(td),
+                                                                       tot_m.data_ptr(), ctypes.byref(st), ctypes.byref(wb),
+                                                                       _stream(q)), "macjd_mixer_fused_train_static_wgrad")
+            plan.update(ws1=ws1, ws2=ws2, ln_slots=ln_slots, n_tiles=R, keep=(act_q, hq, iq, Pq, w2q, w1m))
+            return y, q, (sn, xhat, act), (placeholder, (gq, gout1, g_w1, g_wf, g_v))
         with torch.cuda.device(dev):
             _native.check(lib.macjd_mixer_fused_train_static(ctypes.byref(io), ctypes.byref(tio), ctypes.byref(td), tot_m.data_ptr(),
                                                              ctypes.byref(st), _stream(q)), "macjd_mixer_fused_train_static")
@@ -1471,6 +1532,10 @@ class deferred_wgrad:
             if q is not None:
                 self.norm_partials = self._flush_norm(pending, q, lns[0], partials, step)
                 return False
+        if exc[0] is None and any(io.kind != _native.WGRAD_ORDINARY for io, _ in pending):
+            # (no quiet way out: these problems' terms exist only as slots / rows for macjd_linear_wgrad_many_norm's reduce)
+            raise _native.NativeLibraryError("deferred_wgrad: problems recorded for the training launch's slots, but "
+                                             "norm_in_reduce_plan refuses the update")
         self._flush(exc, pending)
         if exc[0] is None:
             for fn in post:      # launches that consume the flushed products (e.g. LayerNorm parameter gradients)
@@ -1491,6 +1556,8 @@ class deferred_wgrad:
                 with torch.cuda.device(dev):
                     _native.check(lib.macjd_linear_wgrad_many(arr, len(part), _stream(part[0][1][0])),
                                   "macjd_linear_wgrad_many")
+                global wgrad_partial_launches
+                wgrad_partial_launches += 1
 
     @staticmethod
     def _flush_norm(pending, q, lio, partials, step):
@@ -1509,6 +1576,9 @@ class deferred_wgrad:
         with torch.cuda.device(t0.device):
             _native.check(lib.macjd_linear_wgrad_many_norm(arr, len(pending), ctypes.byref(nio), _stream(t0)),
                           "macjd_linear_wgrad_many_norm")
+        if int(lib.macjd_linear_wgrad_many_norm_work_items(arr, len(pending), q)) > 0:   # (0: only the reduce went out)
+            global wgrad_partial_launches
+            wgrad_partial_launches += 1
         return n_partials
 
 
@@ -1521,15 +1591,29 @@ def norm_in_reduce_plan(ios, lns, cover):
       * that launch's G is the (bias-less, N <= 64) output of one of the problems, its gb the bias output of another one
         with the SAME [K, M] operand (so the contracted problem's own column sums are gb), its W has G's shape;
       * every range of ``cover`` is written by the pair: by contiguous dW / db outputs of the other problems or by
-        dgamma / dbeta — then the squares it counts are the whole norm."""
+        dgamma / dbeta — then the squares it counts are the whole norm;
+      * every problem's kind (macjd_wgrad_io.kind) is one the reduce launch serves: ordinary; external slots (a workspace
+        and ext_chunks >= 1; the contracted problem may be one); row products (K rows that fit an int, no outer_vec, not
+        the contracted problem)."""
     if not ios or len(ios) > 8 or len(lns) != 1:
         return None
+    for io in ios:
+        if io.kind == _native.WGRAD_EXT_SLOTS:
+            if io.ext_chunks < 1 or not io.workspace:
+                return None
+        elif io.kind == _native.WGRAD_ROW_PRODUCTS:
+            if io.outer_vec or io.outer_w or not (1 <= io.K <= 0x7fffffff):
+                return None
+        elif io.kind != _native.WGRAD_ORDINARY:
+            return None
     ln = lns[0]
     qs = [k for k, io in enumerate(ios) if io.dW == ln.G and not io.db]
     if len(qs) != 1:
         return None
     q = qs[0]
     g = ios[q]
+    if g.kind == _native.WGRAD_ROW_PRODUCTS:
+        return None
     if g.N > 64 or g.M != ln.C or g.N != ln.K or g.dw_ld != ln.g_ld or not ln.W or ln.w_ld < ln.K:
         return None
     same_operand = [io for k, io in enumerate(ios) if k != q and io.db and io.db == ln.gb and
@@ -1556,12 +1640,14 @@ def norm_in_reduce_plan(ios, lns, cover):
     return q
 
 
-def linear_wgrad(gout, inp, want_bias=True, w_key=None, b_key=None, need=(True, True), outer=None):
+def linear_wgrad(gout, inp, want_bias=True, w_key=None, b_key=None, need=(True, True), outer=None, kind=None):
     """dW [M,N] = gout[K,M]^T inp[K,N], db [M] = column sums of gout (HIP device, float32, row-strided inputs).
     ``w_key`` / ``b_key`` = grad_key of the parameters these are the gradients of: when the active ``deferred_wgrad``
     context maps them to destinations, the results are written there.  ``need`` = which of (dW, db) the caller hands
     to autograd for a tensor that requires grad; a result autograd will drop is kept alive until the deferred launch
-    has written it (its memory must not be reused before)."""
+    has written it (its memory must not be reused before).  ``kind`` (inside ``deferred_wgrad(norm=...)`` only):
+    WGRAD_ROW_PRODUCTS — no workspace, the reduce launch forms the products from the rows — or (WGRAD_EXT_SLOTS, slots
+    tensor, n_slots): an earlier launch left the problem's partial slots there (macjd_wgrad_io.kind)."""
     lib = _native.load()
     gout, inp = _f32c(gout), _f32c(inp)
     K, M = gout.shape
@@ -1579,11 +1665,19 @@ def linear_wgrad(gout, inp, want_bias=True, w_key=None, b_key=None, need=(True, 
         db = _grad_dst(b_key, (M,))
         if db is None:
             db = torch.empty((M,), dtype=torch.float32, device=gout.device)
-    ws = torch.empty(int(lib.macjd_linear_wgrad_workspace_floats(K, M, N)), dtype=torch.float32, device=gout.device)
     io = _native.WgradIO()
+    if kind is None:
+        ws = torch.empty(int(lib.macjd_linear_wgrad_workspace_floats(K, M, N)), dtype=torch.float32, device=gout.device)
+    elif kind == _native.WGRAD_ROW_PRODUCTS:
+        ws, io.kind = None, kind
+    else:
+        io.kind, ws, io.ext_chunks = kind[0], kind[1], int(kind[2])
+    if kind is not None and (_DEFERRED_WGRAD is None or any(k is not None and k in _DEFERRED_SEEN for k in (w_key, b_key))):
+        raise _native.NativeLibraryError("linear_wgrad: a problem kind needs a deferred_wgrad context and a parameter used once")
     io.K, io.M, io.N = K, M, N
     io.gout, io.gout_ld, io.inp, io.inp_ld = gout.data_ptr(), gout.stride(0), inp.data_ptr(), inp.stride(0)
-    io.dW, io.dw_ld, io.db, io.workspace = dW.data_ptr(), dW.stride(0), (db.data_ptr() if want_bias else None), ws.data_ptr()
+    io.dW, io.dw_ld, io.db = dW.data_ptr(), dW.stride(0), (db.data_ptr() if want_bias else None)
+    io.workspace = None if ws is None else ws.data_ptr()
     if outer is not None:
         io.outer_vec, io.outer_w = o_vec.data_ptr(), o_w.data_ptr()
     if _DEFERRED_WGRAD is not None and any(k is not None and k in _DEFERRED_SEEN for k in (w_key, b_key)):
@@ -1600,10 +1694,36 @@ def linear_wgrad(gout, inp, want_bias=True, w_key=None, b_key=None, need=(True, 
         # AccumulateGrad only adopts a gradient tensor it is the sole owner of — with a second reference it would
         # clone the still unfilled buffer into .grad right away (the flush would then fill a tensor nobody reads)
         unowned = tuple(t for t, n in ((dW, need[0]), (db, need[1])) if t is not None and not n)
-        _DEFERRED_WGRAD.append((io, (ws, gout, inp) + unowned + ((o_vec, o_w) if outer is not None else ())))
+        _DEFERRED_WGRAD.append((io, (gout, inp, ws) + unowned + ((o_vec, o_w) if outer is not None else ())))
         return dW, db
     with torch.cuda.device(gout.device):
         _native.check(lib.macjd_linear_wgrad(ctypes.byref(io), _stream(gout)), "macjd_linear_wgrad")
+    global wgrad_partial_launches
+    wgrad_partial_launches += 1
+    return dW, db
+
+
+def _wgrad_from_slots(M, N, slots, n_slots, want_bias, w_key, b_key, need, keep):
+    """Record (dW [M, N], db [M]) as a problem whose ``n_slots`` partial slots an earlier launch has left in ``slots``
+    (MACJD_WGRAD_EXT_SLOTS): only the reduce launch of the active ``deferred_wgrad(norm=...)`` context touches it.
+    Destinations and ownership as in ``linear_wgrad``; ``keep``: what that launch read (alive until the flush)."""
+    if _DEFERRED_WGRAD is None or any(k is not None and k in _DEFERRED_SEEN for k in (w_key, b_key)):
+        raise _native.NativeLibraryError("a weight gradient from slots needs a deferred_wgrad context and a parameter used once")
+    M, N = int(M), int(N)
+    dW = _grad_dst(w_key, (M, N))
+    if dW is None:
+        dW = torch.empty((M, N), dtype=torch.float32, device=slots.device)
+    db = None
+    if want_bias:
+        db = _grad_dst(b_key, (M,))
+        if db is None:
+            db = torch.empty((M,), dtype=torch.float32, device=slots.device)
+    io = _native.WgradIO()
+    io.K, io.M, io.N, io.kind, io.ext_chunks = 1, M, N, _native.WGRAD_EXT_SLOTS, int(n_slots)
+    io.dW, io.dw_ld, io.db, io.workspace = dW.data_ptr(), dW.stride(0), (db.data_ptr() if want_bias else None), slots.data_ptr()
+    _DEFERRED_SEEN.update(k for k in (w_key, b_key) if k is not None)
+    unowned = tuple(t for t, n in ((dW, need[0]), (db, need[1])) if t is not None and not n)
+    _DEFERRED_WGRAD.append((io, (slots,) + tuple(keep) + unowned))
     return dW, db
 
 
@@ -2001,7 +2121,9 @@ class _QheadTaken(torch.autograd.Function):
             ic = ic.to(torch.int64)
         ic = ic.contiguous()
         w1c, b1c, w2c = _f32c(w1.detach()), _f32c(b1.detach()), _f32c(w2.detach()).reshape(-1)
-        x = torch.empty((n, H + n_actions + 1), dtype=torch.float32, device=h.device)
+        # (a waiting weight-gradient plan: the training launch rebuilds the rows it needs from h / idx / P — none is written)
+        plan = _WGRAD_IN_TRAIN
+        x = None if plan is not None else torch.empty((n, H + n_actions + 1), dtype=torch.float32, device=h.device)
         act = torch.empty((n, H), dtype=torch.float32, device=h.device)
         q = torch.empty((n, 1), dtype=torch.float32, device=h.device)
         io = _native.QtakenIO()
@@ -2009,7 +2131,14 @@ class _QheadTaken(torch.autograd.Function):
         io.h, io.h_ld, io.idx, io.idx_elem_size, io.P = hc.data_ptr(), hc.stride(0), ic.data_ptr(), ic.element_size(), Pc.data_ptr()
         io.W1, io.w1_ld, io.b1, io.w2 = w1c.data_ptr(), w1c.stride(0), b1c.data_ptr(), w2c.data_ptr()
         io.b2 = _f32c(b2.detach()).data_ptr() if b2 is not None else None
-        io.x, io.x_ld, io.act, io.act_ld, io.q = x.data_ptr(), x.stride(0), act.data_ptr(), act.stride(0), q.data_ptr()
+        if x is not None:
+            io.x, io.x_ld = x.data_ptr(), x.stride(0)
+        io.act, io.act_ld, io.q = act.data_ptr(), act.stride(0), q.data_ptr()
+        if plan is not None:
+            if not wgrad_in_train_supported(H, n_actions) or not (w1.requires_grad and b1.requires_grad and w2.requires_grad):
+                raise _native.NativeLibraryError("weight-gradient plan: Q-head outside H = 64, 1 <= A <= 15 or with frozen parameters")
+            plan["qhead"] = (act, hc, ic, Pc, w2c, int(H), int(n_actions))
+        ctx.wg_plan = plan
         global _PAIRED_DQ
         pair, _PAIRED_DQ = _PAIRED_DQ, None
         with torch.cuda.device(h.device):
@@ -2026,6 +2155,17 @@ class _QheadTaken(torch.autograd.Function):
         x, w1, y, w2 = ctx.saved_tensors
         nd = ctx.needs_input_grad
         gW1 = gb1 = gW2 = gb2 = None
+        if ctx.wg_plan is not None:
+            # the mixer training launch has left both problems as one slot per tile: only the reduce launch is needed
+            plan = ctx.wg_plan
+            if "ws1" not in plan:
+                raise _native.NativeLibraryError("weight-gradient plan: the mixer training launch did not take it")
+            keep = tuple(plan["keep"])
+            gW1, gb1 = _wgrad_from_slots(w1.shape[0], w1.shape[1], plan["ws1"], plan["n_tiles"], True, grad_key(w1), ctx.b1_key,
+                                         (nd[3], nd[4]), keep)
+            gW2, gb2 = _wgrad_from_slots(1, w2.numel(), plan["ws2"], plan["n_tiles"], ctx.has_b2, grad_key(w2), ctx.b2_key,
+                                         (nd[5], ctx.has_b2 and nd[6]), keep)
+            return None, None, None, gW1, gb1, gW2, (gb2 if ctx.has_b2 else None), None
         if nd[3] or nd[4]:   # the first layer's operand gq w2 masked by the ReLU is formed inside the weight-gradient kernel
             gW1, gb1 = linear_wgrad(y, x, want_bias=True, w_key=grad_key(w1), b_key=ctx.b1_key, need=(nd[3], nd[4]),
                                     outer=(gq, w2))
