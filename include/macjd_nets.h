@@ -727,6 +727,30 @@ int macjd_agent_episode_supported(int32_t J, int32_t H, int32_t A);
 int macjd_agent_episode(const macjd_agent_episode_io* io, void* hip_stream);
 
 /*
+ * macjd_agent_episode with PER-STEP inputs: gi and P_all carry a leading time dimension and step t reads
+ *   gi    + t * gi_lt + n * base.gi_ld + c * H + u      ([T, rows or 1, 3H])
+ *   P_all + t * p_lt  + n * base.p_ld  + a              ([T, rows or 1, A])
+ * For a MOVING scenario (macjd_motion_io): its observation shows frame min(k, F) for every env whatever the agents did,
+ * so gi / P are functions of the step counter alone — one row per frame (base.gi_ld = base.p_ld = 0, gi_lt = 3H,
+ * p_lt = A), computed by one launch for the whole episode — and, as in the static case, nothing the agent computes
+ * depends on the environment's outputs (the env steps of the episode run as macjd_env_step_many_moving).
+ * Everything else is macjd_agent_episode: step t of this launch computes what a T = 1 launch of macjd_agent_episode on
+ * (gi[t], P_all[t], h0 = h_{t-1}, eps + t, *counter_base + t) computes, bit for bit.
+ *   base.gi_ld / base.p_ld   as in macjd_agent_episode (0 = one row for all rows of a step)
+ *   gi_lt >= 3H, p_lt >= A   time strides in elements; or 0: the step reads row block 0 (both 0: the launch equals
+ *                            macjd_agent_episode).  MACJD_EINVAL for 0 < gi_lt < 3H or 0 < p_lt < A.
+ * Supported: the one-tile-per-agent forms — H = 64 with (J, A) in {(2, 5), (3, 9), (6, 17)}, H = 128 with (J, A) in
+ * {(2, 5), (3, 9)}; MACJD_EUNSUPPORTED otherwise (no four-tile form).
+ */
+typedef struct macjd_agent_episode_seq_io {
+    macjd_agent_episode_io base;
+    int64_t gi_lt, p_lt;
+} macjd_agent_episode_seq_io;
+
+int macjd_agent_episode_seq_supported(int32_t J, int32_t H, int32_t A);
+int macjd_agent_episode_seq(const macjd_agent_episode_seq_io* io, void* hip_stream);
+
+/*
  * Closed-loop episode launch for scanning radars (macjd_scan_desc): agent AND environment of a whole episode batch in
  * ONE launch.  With scanning beams the observation's theta_a columns change every step and depend, through the FSM, on
  * what the agents did, so macjd_agent_episode + macjd_env_step_many do not apply; environments are still independent of

@@ -43,6 +43,7 @@ EXPORTS = [
     "macjd_linear_wgrad_many_norm_work_items", "macjd_wgrad_slot_floats",
     "macjd_prefetch_batches_supported", "macjd_prefetch_batches",
     "macjd_env_step_moving", "macjd_env_step_many_moving", "macjd_env_reset_moving",
+    "macjd_agent_episode_seq_supported", "macjd_agent_episode_seq",
 ]
 
 
@@ -247,6 +248,11 @@ class AgentEpisodeIO(ctypes.Structure):
         ("eps", ctypes.c_void_p), ("seed", ctypes.c_uint64), ("counter_base", ctypes.c_void_p),
         ("hidden", ctypes.c_void_p), ("T_out", ctypes.c_void_p), ("P_out", ctypes.c_void_p), ("h_final", ctypes.c_void_p),
     ]
+
+
+class AgentEpisodeSeqIO(ctypes.Structure):
+    """ctypes mirror of ``macjd_agent_episode_seq_io`` (include/macjd_nets.h): the static block, then the two time strides."""
+    _fields_ = [("base", AgentEpisodeIO), ("gi_lt", ctypes.c_int64), ("p_lt", ctypes.c_int64)]
 
 
 class AgentEnvEpisodeScanIO(ctypes.Structure):
@@ -534,6 +540,10 @@ def load() -> ctypes.CDLL:
     lib.macjd_agent_episode_supported.argtypes = [ctypes.c_int32] * 3
     lib.macjd_agent_episode.restype = ctypes.c_int
     lib.macjd_agent_episode.argtypes = [ctypes.POINTER(AgentEpisodeIO), ctypes.c_void_p]
+    lib.macjd_agent_episode_seq_supported.restype = ctypes.c_int
+    lib.macjd_agent_episode_seq_supported.argtypes = [ctypes.c_int32] * 3
+    lib.macjd_agent_episode_seq.restype = ctypes.c_int
+    lib.macjd_agent_episode_seq.argtypes = [ctypes.POINTER(AgentEpisodeSeqIO), ctypes.c_void_p]
     lib.macjd_agent_env_episode_scan_supported.restype = ctypes.c_int
     lib.macjd_agent_env_episode_scan_supported.argtypes = [ctypes.c_int32] * 4
     lib.macjd_agent_env_episode_scan.restype = ctypes.c_int

@@ -48,6 +48,9 @@ class BasicMAC:
         # (params_all [N, A], gi [N, 3H]) of observations that do not change during an episode, set by
         # prepare_static_obs(); while set, select_actions skips the actor and the fc1 -> W_ih chains
         self.static_inputs = None
+        # (params [T, A], gi [T, 3H]) of a moving scenario's frames (one observation row per step counter, the same for
+        # every env and agent), set by prepare_frame_obs(); read by the batched runner's moving whole-episode rollout only
+        self.frame_inputs = None
 
     def prepare_static_obs(self, obs_batch):
         """The environment's observation is constant within an episode (the batched runner asks the env:
@@ -86,6 +89,33 @@ class BasicMAC:
         callers that change the agent body in a way the version counters of the key do not see (writes through
         ``p.data`` views: the learner's fused optimiser step with ``train_agent_body`` / ``train_actor``)."""
         self._static_key = None
+        self._frame_key = None
+
+    def prepare_frame_obs(self, frame_rows, n_steps=None):
+        """A moving scenario's observation is a function of the step counter alone (every env and agent sees frame
+        min(k, F), whatever the agents did): the actor output and the GRU input transform of ALL steps of an episode are
+        then one row per frame, computed here by ONE launch — ``agent.static_step_inputs(frame_rows[:T])`` — and kept as
+        ``frame_inputs = (params [T, A], gi [T, 3H])``.  ``frame_rows`` [>= T, S] (``env.frame_states()``), T =
+        ``n_steps`` or all rows; None forgets them.  Cached and recomputed like ``prepare_static_obs``: the same rows and
+        an unchanged agent body launch nothing, a captured rollout recomputes at every replay, and
+        ``invalidate_static_inputs`` forgets the key."""
+        if frame_rows is None:
+            self.frame_inputs, self._frame_key = None, None
+            return
+        device = next(self.agent.parameters()).device
+        rows = frame_rows.to(device) if frame_rows.device != device else frame_rows
+        T = rows.shape[0] if n_steps is None else int(n_steps)
+        if not 1 <= T <= rows.shape[0]:
+            raise ValueError(f"prepare_frame_obs: n_steps must be in 1..{rows.shape[0]}, got {n_steps}")
+        key = (rows.data_ptr(), rows._version, tuple(rows.shape), tuple(rows.stride()), T,
+               tuple((p.data_ptr(), p._version) for n_, p in self.agent.named_parameters() if not n_.startswith("fc2_q_head")))
+        capturing = rows.is_cuda and torch.cuda.is_current_stream_capturing()
+        if self.frame_inputs is not None and getattr(self, "_frame_key", None) == key and not capturing:
+            return
+        self._frame_key = None if capturing else key
+        with torch.no_grad():
+            params, gi = self.agent.static_step_inputs(rows[:T])
+        self.frame_inputs = (params, gi)
 
     def select_actions(self, obs_batch, avail_actions_batch, t_env, test_mode=False):
         device = next(self.agent.parameters()).device

@@ -30,6 +30,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/macjd.h"
 #include "../../include/macjd_nets.h"
 #include "macjd_err.h"
@@ -58,8 +60,21 @@ constexpr int EP_KQ = EP_H / 16;  // quads of a K = 64 product
 // wave = agent tile, lane = (row, quarter of the units) = 32 units per lane: the waves without a tile do not wait there
 // (no barrier closes a step) but run ahead into the next step's gh products, so the matrix pipe works on step t + 1
 // while waves 0 .. J-1 evaluate the heads of step t on the vector pipe.
-template <int EP_H, int J, int A, bool FLAT = false>
-__global__ void __launch_bounds__(EP_H * 4) agent_episode_kernel(const macjd_agent_episode_io io) {
+//
+// SEQ (moving scenarios, macjd_agent_episode_seq): gi and P_all are one row block PER STEP — the observation of a moving
+// scenario shows frame min(k, F) whatever the agents did, so the argument above holds with "constant" replaced by "a
+// function of the step counter".  The lane's giv / pv values are then loaded at the top of every iteration, in front of
+// phase (1): the gates need giv only in phase (2) and the heads pv only in phase (4), so the recurrent product covers
+// the latency (H = 128: pv behind the barrier after (2), see PV_LATE below).  The loads write registers only: no barrier
+// is added and the note at the end of the step stays true.
+__device__ __forceinline__ const macjd_agent_episode_io& episode_base(const macjd_agent_episode_io& a) { return a; }
+__device__ __forceinline__ const macjd_agent_episode_io& episode_base(const macjd_agent_episode_seq_io& a) { return a.base; }
+
+template <int EP_H, int J, int A, bool FLAT = false, bool SEQ = false>
+__global__ void __launch_bounds__(EP_H * 4)
+agent_episode_kernel(const typename std::conditional<SEQ, macjd_agent_episode_seq_io, macjd_agent_episode_io>::type arg) {
+    static_assert(!(SEQ && FLAT), "per-step inputs: one tile per agent only");
+    const macjd_agent_episode_io& io = episode_base(arg);
     static_assert(EP_H == 64 || EP_H == 128, "hidden size");
     constexpr int EP_LD = EP_H + 8;    // LDS pitch (= 8 mod 16 floats: conflict-free ds_read_b128 fragments)
     constexpr int EP_KQ = EP_H / 16;   // quads of a K = H product
@@ -126,7 +141,8 @@ __global__ void __launch_bounds__(EP_H * 4) agent_episode_kernel(const macjd_age
             bool live;
             const int64_t n = row_of(j, 4 * g + r, live);           // clamped: rows past the end are computed, never stored
 #pragma unroll
-            for (int c = 0; c < 3; ++c) giv[j][r][c] = io.gi[n * io.gi_ld + c * EP_H + u];
+            for (int c = 0; c < 3; ++c)
+                if constexpr (!SEQ) giv[j][r][c] = io.gi[n * io.gi_ld + c * EP_H + u];
             const float hinit = io.h0 ? io.h0[n * EP_H + u] : 0.0f;
             if constexpr (H_REG) hreg[j][r] = hinit;
             Hl[0][j][(4 * g + r) * EP_LD + u] = hinit;
@@ -151,7 +167,7 @@ __global__ void __launch_bounds__(EP_H * 4) agent_episode_kernel(const macjd_age
         n_avail[pass] = 0;
 #pragma unroll
         for (int a = 0; a < A; ++a) {
-            pv[pass][a] = io.P_all[n * io.p_ld + a];
+            if constexpr (!SEQ) pv[pass][a] = io.P_all[n * io.p_ld + a];
             bool av = true;
             if (io.avail) {
                 const int64_t off = ec * io.av_se + jc * io.av_sj + (int64_t)a * io.av_sa;
@@ -162,10 +178,45 @@ __global__ void __launch_bounds__(EP_H * 4) agent_episode_kernel(const macjd_age
         }
     }
     const uint64_t ctr_base = io.counter_base ? io.counter_base[0] : 0ull;
+    int64_t gi_lt = 0, p_lt = 0;   // SEQ: time strides of gi / P_all
+    if constexpr (SEQ) {
+        gi_lt = arg.gi_lt;
+        p_lt = arg.p_lt;
+    }
     __syncthreads();
 
+    // SEQ: the P row of step t for this lane's Q-head row (same clamped row as the static load).  H = 128 at J = 3 has no
+    // register to spare in phases (1) / (2) (256 VGPRs without it), so there the loads are issued behind the barrier that
+    // follows (2): phase (3)'s MFMA chain and the barrier behind it cover them.
+    constexpr bool PV_LATE = SEQ && EP_H > 64;
+    auto load_pv = [&](int t) {
+        const float* p_t = io.P_all + (int64_t)t * p_lt;
+#pragma unroll
+        for (int pass = 0; pass < (J + NW - 1) / NW; ++pass) {
+            const int j = wave + NW * pass;
+            bool live_q;
+            const int64_t n = row_of(j < J ? j : 0, qr, live_q);
+#pragma unroll
+            for (int a = 0; a < A; ++a) pv[pass][a] = p_t[n * io.p_ld + a];
+        }
+    };
     for (int t = 0; t < T; ++t) {
         const int cur = t & 1, nxt = cur ^ 1;
+        if constexpr (SEQ) {
+            // ---- (0) this step's gi / P rows (same clamped rows as the static loads) ----
+            const float* gi_t = io.gi + (int64_t)t * gi_lt;
+            // (row n = e * J + j of the clamped env e: one per-lane address per r, the agent's offset j * gi_ld is uniform)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int64_t e = (e0 + 4 * g + r < E) ? e0 + 4 * g + r : E - 1;
+                const float* gi_e = gi_t + e * (J * io.gi_ld) + u;
+#pragma unroll
+                for (int j = 0; j < J; ++j)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) giv[j][r][c] = gi_e[j * io.gi_ld + c * EP_H];
+            }
+            if constexpr (!PV_LATE) load_pv(t);
+        }
         // ---- (1) gh = W_hh h_{t-1} for this wave's units, all gates, all agent tiles ----
         f32x4 acc[J][3];
 #pragma unroll
@@ -206,6 +257,7 @@ __global__ void __launch_bounds__(EP_H * 4) agent_episode_kernel(const macjd_age
                 if (live) io.hidden[((int64_t)t * N + n) * EP_H + u] = hnew;   // staging row t: post-update h_t
             }
         __syncthreads();
+        if constexpr (PV_LATE) load_pv(t);
         // ---- (3) Q-head base = W1[:, :H] h_t + b1 for this wave's 16 units ----
         {
             f32x4 ab[J];
@@ -697,19 +749,27 @@ extern "C" int macjd_agent_episode_supported(int32_t J, int32_t H, int32_t A) {
     return (H == 64) && J >= 1 && (A == 5 || A == 9 || A == 17 || A == 33);
 }
 
+// the argument checks the static launch and the one with per-step inputs share (behind their own size check)
+static int agent_episode_check(const macjd_agent_episode_io* io, const char* who) {
+    using namespace macjd;
+    if (io->n_envs < 0 || io->T < 1 || !io->gi || !io->P_all || !io->w_hh || !io->b_hh || !io->W1 || !io->b1 || !io->w2 ||
+        !io->b2 || !io->hidden || !io->T_out || !io->P_out || (!io->greedy_only && !io->eps))
+        return set_err(MACJD_EINVAL, "%s: bad n_envs / T or NULL pointer", who);
+    if ((io->gi_ld != 0 && io->gi_ld < 3 * io->H) || (io->p_ld != 0 && io->p_ld < io->A) || io->w1_ld < io->H + io->A + 1)
+        return set_err(MACJD_EINVAL, "%s: row stride smaller than the row", who);
+    if (io->avail && io->avail_elem_size != 4 && io->avail_elem_size != 8)
+        return set_err(MACJD_EINVAL, "%s: avail_elem_size must be 4 or 8", who);
+    if (((uintptr_t)io->w_hh) & 15) return set_err(MACJD_EINVAL, "%s: w_hh must be 16-byte aligned", who);
+    return MACJD_OK;
+}
+
 extern "C" int macjd_agent_episode(const macjd_agent_episode_io* io, void* hip_stream) {
     using namespace macjd;
     if (!io) return set_err(MACJD_EINVAL, "%s", "macjd_agent_episode: NULL io");
     if (!macjd_agent_episode_supported(io->J, io->H, io->A))
         return set_err(MACJD_EUNSUPPORTED, "%s", "macjd_agent_episode: unsupported J / H / A (see include/macjd_nets.h)");
-    if (io->n_envs < 0 || io->T < 1 || !io->gi || !io->P_all || !io->w_hh || !io->b_hh || !io->W1 || !io->b1 || !io->w2 ||
-        !io->b2 || !io->hidden || !io->T_out || !io->P_out || (!io->greedy_only && !io->eps))
-        return set_err(MACJD_EINVAL, "%s", "macjd_agent_episode: bad n_envs / T or NULL pointer");
-    if ((io->gi_ld != 0 && io->gi_ld < 3 * io->H) || (io->p_ld != 0 && io->p_ld < io->A) || io->w1_ld < io->H + io->A + 1)
-        return set_err(MACJD_EINVAL, "%s", "macjd_agent_episode: row stride smaller than the row");
-    if (io->avail && io->avail_elem_size != 4 && io->avail_elem_size != 8)
-        return set_err(MACJD_EINVAL, "%s", "macjd_agent_episode: avail_elem_size must be 4 or 8");
-    if (((uintptr_t)io->w_hh) & 15) return set_err(MACJD_EINVAL, "%s", "macjd_agent_episode: w_hh must be 16-byte aligned");
+    const int rc = agent_episode_check(io, "macjd_agent_episode");
+    if (rc != MACJD_OK) return rc;
     if (io->n_envs == 0) return MACJD_OK;
     if (io->H == 128) {   // eight waves; rows of w_hh are 128 floats, so the 16-byte check above covers every fragment
         const int64_t wgs128 = (io->n_envs + 15) / 16;
@@ -755,6 +815,40 @@ extern "C" int macjd_agent_episode(const macjd_agent_episode_io* io, void* hip_s
 #undef MACJD_EP
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_agent_episode: %s", hipGetErrorString(err));
+    return MACJD_OK;
+}
+
+extern "C" int macjd_agent_episode_seq_supported(int32_t J, int32_t H, int32_t A) {
+    // the one-tile-per-agent forms the moving many-step env launch pairs with; no four-tile (FLAT) form
+    if (H == 128) return ((J == 2 && A == 5) || (J == 3 && A == 9)) ? 1 : 0;
+    return (H == 64 && ((J == 2 && A == 5) || (J == 3 && A == 9) || (J == 6 && A == 17))) ? 1 : 0;
+}
+
+extern "C" int macjd_agent_episode_seq(const macjd_agent_episode_seq_io* sio, void* hip_stream) {
+    using namespace macjd;
+    if (!sio) return set_err(MACJD_EINVAL, "%s", "macjd_agent_episode_seq: NULL io");
+    const macjd_agent_episode_io* io = &sio->base;
+    if (!macjd_agent_episode_seq_supported(io->J, io->H, io->A))
+        return set_err(MACJD_EUNSUPPORTED, "%s", "macjd_agent_episode_seq: unsupported J / H / A (see include/macjd_nets.h)");
+    const int rc = agent_episode_check(io, "macjd_agent_episode_seq");
+    if (rc != MACJD_OK) return rc;
+    if ((sio->gi_lt != 0 && sio->gi_lt < 3 * io->H) || (sio->p_lt != 0 && sio->p_lt < io->A))
+        return set_err(MACJD_EINVAL, "%s", "macjd_agent_episode_seq: time stride gi_lt / p_lt neither 0 nor >= the row (3H / A)");
+    if (io->n_envs == 0) return MACJD_OK;
+    const int64_t wgs = (io->n_envs + 15) / 16;
+    if (wgs > 0x7fffffff) return set_err(MACJD_EINVAL, "%s", "macjd_agent_episode_seq: too many rows for one launch");
+    const dim3 grid((unsigned)wgs), block(io->H == 128 ? 512 : 256);
+    hipStream_t s = (hipStream_t)hip_stream;
+#define MACJD_EP_SEQ(H_, J_, A_) hipLaunchKernelGGL((agent_episode_kernel<H_, J_, A_, false, true>), grid, block, 0, s, *sio)
+    if (io->H == 128) {
+        if (io->J == 2) MACJD_EP_SEQ(128, 2, 5);
+        else MACJD_EP_SEQ(128, 3, 9);
+    } else if (io->J == 2) MACJD_EP_SEQ(64, 2, 5);
+    else if (io->J == 3) MACJD_EP_SEQ(64, 3, 9);
+    else MACJD_EP_SEQ(64, 6, 17);
+#undef MACJD_EP_SEQ
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_agent_episode_seq: %s", hipGetErrorString(err));
     return MACJD_OK;
 }
 

@@ -325,9 +325,19 @@ def agent_episode(gi, P_all, h0, w_hh, b_hh, W1, b1, w2, b2, n_envs: int, n_agen
     the static actor output ``P_all`` [E*J or 1, A], mask, epsilon-greedy (``eps_sched`` float32 [>= T] on the device,
     ``counter_base`` uint64 / int64 [1] on the device), gather.  Writes the staging rows ``hidden_out`` [>= T, E, J, H],
     ``T_out`` int32 [T, E, J(,1)], ``P_out`` float32 [T, E, J(,1)] (all contiguous) and ``h_final`` [E*J, H]."""
-    lib = _native.load()
-    H, A = w_hh.shape[1], P_all.shape[-1]
     io = _native.AgentEpisodeIO()
+    keep = _fill_agent_episode_io(io, 0, gi, P_all, h0, w_hh, b_hh, W1, b1, w2, b2, n_envs, n_agents, T, avail, eps_sched,
+                                  greedy_only, seed, counter_base, hidden_out, T_out, P_out, h_final)
+    with torch.cuda.device(keep[0].device):
+        _native.check(_native.load().macjd_agent_episode(ctypes.byref(io), _stream(keep[0])), "macjd_agent_episode")
+
+
+def _fill_agent_episode_io(io, row_dim: int, gi, P_all, h0, w_hh, b_hh, W1, b1, w2, b2, n_envs, n_agents, T, avail, eps_sched,
+                           greedy_only, seed, counter_base, hidden_out, T_out, P_out, h_final):
+    """Marshal the arguments of ``agent_episode`` / ``agent_episode_seq`` into a ``macjd_agent_episode_io``; ``row_dim`` is
+    the row dimension of ``gi`` / ``P_all`` (0, or 1 behind a leading time dimension).  Returns the tensors the block points
+    at, the float32 ``gi`` and ``P_all`` first."""
+    H, A = w_hh.shape[1], P_all.shape[-1]
     io.n_envs, io.T, io.J, io.H, io.A = int(n_envs), int(T), int(n_agents), H, A
     io.greedy_only = 1 if greedy_only else 0
     keep = []
@@ -339,8 +349,8 @@ def agent_episode(gi, P_all, h0, w_hh, b_hh, W1, b1, w2, b2, n_envs: int, n_agen
         return t
 
     gi, P_all = f32(gi), f32(P_all)
-    io.gi, io.gi_ld = gi.data_ptr(), gi.stride(0)
-    io.P_all, io.p_ld = P_all.data_ptr(), P_all.stride(0)
+    io.gi, io.gi_ld = gi.data_ptr(), gi.stride(row_dim)
+    io.P_all, io.p_ld = P_all.data_ptr(), P_all.stride(row_dim)
     if h0 is not None:
         h0 = f32(h0).contiguous()
         keep.append(h0)
@@ -372,8 +382,33 @@ def agent_episode(gi, P_all, h0, w_hh, b_hh, W1, b1, w2, b2, n_envs: int, n_agen
     if h_final is not None:
         assert h_final.is_contiguous() and h_final.dtype == torch.float32 and h_final.numel() == n_envs * n_agents * H
         io.h_final = h_final.data_ptr()
+    return keep
+
+
+def agent_episode_seq_supported(J: int, H: int, A: int) -> bool:
+    return bool(_native.load().macjd_agent_episode_seq_supported(int(J), int(H), int(A)))
+
+
+def agent_episode_seq(gi, P_all, h0, w_hh, b_hh, W1, b1, w2, b2, n_envs: int, n_agents: int, T: int, avail, eps_sched,
+                      greedy_only: bool, seed: int, counter_base, hidden_out, T_out, P_out, h_final=None):
+    """``agent_episode`` with per-step inputs (moving scenarios; include/macjd_nets.h, macjd_agent_episode_seq_io): ``gi``
+    [>= T, E*J or 1, 3H] and ``P_all`` [>= T, E*J or 1, A] carry a leading time dimension and step t reads row block t.  The
+    strides are the tensors' own: a row dimension of size 1 (or stride 0) is one row for all rows of a step, a time stride
+    of 0 (an expanded tensor) the same block at every step.  Everything else as ``agent_episode``."""
+    N = int(n_envs) * int(n_agents)
+    for name, t_, w in (("gi", gi, 3 * w_hh.shape[1]), ("P_all", P_all, P_all.shape[-1])):
+        assert t_.dim() == 3 and t_.shape[0] >= T and t_.shape[1] in (1, N) and t_.shape[2] == w, (name, tuple(t_.shape))
+    sio = _native.AgentEpisodeSeqIO()
+    keep = _fill_agent_episode_io(sio.base, 1, gi, P_all, h0, w_hh, b_hh, W1, b1, w2, b2, n_envs, n_agents, T, avail, eps_sched,
+                                  greedy_only, seed, counter_base, hidden_out, T_out, P_out, h_final)
+    gi, P_all = keep[0], keep[1]
+    if gi.shape[1] == 1:
+        sio.base.gi_ld = 0
+    if P_all.shape[1] == 1:
+        sio.base.p_ld = 0
+    sio.gi_lt, sio.p_lt = gi.stride(0), P_all.stride(0)
     with torch.cuda.device(gi.device):
-        _native.check(lib.macjd_agent_episode(ctypes.byref(io), _stream(gi)), "macjd_agent_episode")
+        _native.check(_native.load().macjd_agent_episode_seq(ctypes.byref(sio), _stream(gi)), "macjd_agent_episode_seq")
 
 
 def agent_env_episode_scan_supported(J: int, R: int, H: int, A: int) -> bool:

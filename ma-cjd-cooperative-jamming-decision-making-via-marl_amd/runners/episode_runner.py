@@ -322,7 +322,8 @@ class BatchedEpisodeRunner:
         # the graph's lifetime, and the MAC's recurrent state is pointed back at the captured one after each replay
         if getattr(self, "_graph_keep", None) is None:
             self._graph_keep = {}
-        self._graph_keep[n] = (self.mac.hidden_states, getattr(self.mac, "static_inputs", None), self._avail, self._obs)
+        self._graph_keep[n] = (self.mac.hidden_states, getattr(self.mac, "static_inputs", None), self._avail, self._obs,
+                               getattr(self.mac, "frame_inputs", None))
         if n == T:
             self._graph = graph
         if env_ep0 is not None:
@@ -346,6 +347,9 @@ class BatchedEpisodeRunner:
             return
         if device_schedule and self.closed_loop_rollout and (self.closed_loop_available() or self.closed_loop_pe_available()):
             self._closed_loop_launch(T)   # scanning radars: agent and env of the whole batch in one launch
+            return
+        if device_schedule and self.moving_episode_rollout and self.moving_rollout_available():
+            self._moving_launches(T)      # moving scenario: per-frame inputs, the agent's steps, the env's steps
             return
         for t in range(T):
             if device_schedule:
@@ -532,6 +536,79 @@ class BatchedEpisodeRunner:
         launch(self.mac.agent, env_args, self.batch_envs, self.n_agents, n, self._avail, self._eps_sched, bool(test_mode),
                self.mac.select_seed, self._ctr_base, self.stage, rdpj_sum=self._rdpj_sum, h_final=self.mac.hidden_states)
 
+    # ---- moving scenarios: the agent's T steps on per-frame inputs as one launch, the env's T steps as another ----
+    moving_episode_rollout = _OptionSwitch("MOVING_EPISODE_ROLLOUT")   # default off (MACJD_MOVING_EPISODE_ROLLOUT=1 turns it on)
+
+    def moving_rollout_available(self) -> bool:
+        """The env moves on shared frame tables (no scenario batch) and its many-step launch has a production form at this
+        size, the MAC is the stock RNNAgent on a HIP device, and the episode kernel takes per-step inputs at this size
+        (``ops.agent_episode_seq_supported``).  The observation of a moving scenario is a function of the step counter
+        alone, so — as with a static observation — nothing the agent computes depends on the env's outputs."""
+        env = self.env
+        if self.device.type != "cuda" or not getattr(env.scenario, "moving", False) or not hasattr(env, "frame_states"):
+            return False
+        if getattr(env, "scenario_batch", None) is not None or getattr(env, "kernel_flags", 0) != 0:
+            return False
+        if not (hasattr(env, "step_many_has_production_form") and env.step_many_has_production_form()):
+            return False
+        agent = getattr(self.mac, "agent", None)
+        if agent is None or not hasattr(self.mac, "prepare_frame_obs") or not hasattr(agent, "fc2_q_head") \
+                or not next(agent.parameters()).is_cuda:
+            return False
+        from .. import ops
+        return ops.agent_episode_seq_supported(self.n_agents, agent.rnn_hidden_dim, agent.n_actions)
+
+    def rollout_moving(self, test_mode=False, n_steps=None):
+        """One episode batch (or its first ``n_steps`` steps) of a moving scenario in THREE launches (+ the counter
+        update): ``mac.prepare_frame_obs`` (actor output and GRU input transform of every frame, one row per step),
+        ``ops.agent_episode_seq`` (the agent's steps, step t on frame t's row) and ``env.step_many`` (the moving many-step
+        launch).  Same staging rows, exploration draws (row, episode * (T + 1) + t + 1) and Monte-Carlo streams as the
+        step-by-step path; hidden states / Q-values differ from it by the summation order of two matrix products (~1e-7),
+        which can flip an arg-max only on a near-tie."""
+        if not self.moving_rollout_available():
+            raise RuntimeError("rollout_moving: not available for this environment / agent (moving_rollout_available())")
+        T = self.episode_limit
+        n = T if n_steps is None else int(n_steps)
+        if not 1 <= n <= T:
+            raise ValueError(f"rollout_moving: n_steps must be in 1..{T}, got {n_steps}")
+        if getattr(self, "_eps_sched", None) is None:
+            self._eps_sched = torch.zeros(T, dtype=torch.float32, device=self.device)
+            self._ctr_base = torch.zeros(1, dtype=torch.int64, device=self.device)
+        if not test_mode and n in (getattr(self, "_graphs", None) or {}):
+            return self.rollout_graphed(n)
+        self._upload_eps_schedule(self._eps_schedule(n, test_mode))
+        self.begin_episodes()                       # episode index, zero hidden state, env reset (frame-0 positions)
+        self._ctr_base.fill_(self._ep * (T + 1))
+        self._moving_launches(n, test_mode=test_mode)
+        self.t_env += n
+
+    def _moving_launches(self, n, test_mode=False):
+        """The launches of ``rollout_moving`` for the first ``n`` steps (behind ``begin_episodes``).  Every episode shows the
+        same frames: state / obs row t is frame t's row for every env and agent and the availability rows are constant, so
+        the staging rows are filled once (rows below the largest ``n`` so far)."""
+        from .. import ops
+        st, mac, env = self.stage, self.mac, self.env
+        E, J, T = self.batch_envs, self.n_agents, self.episode_limit
+        frames = env.frame_states()                 # [F + 1, S]
+        done = getattr(self, "_frames_filled", 0)
+        if n > done:
+            st["state"][done:n] = frames[done:n].unsqueeze(1)
+            st["obs"][done:n] = frames[done:n].view(n - done, 1, 1, -1)
+            st["avail_actions"][done:n] = env.get_avail_actions()
+            self._frames_filled = n
+        if getattr(self, "_rdpj_steps", None) is None:
+            self._rdpj_steps = torch.zeros((T, E, 3), dtype=torch.float32, device=self.device)
+        mac.prepare_frame_obs(frames, T)            # one launch for all frames (nothing when rows and body are unchanged)
+        params, gi = mac.frame_inputs
+        a = mac.agent
+        l1, l2 = a.fc2_q_head[0], a.fc2_q_head[2]
+        ops.agent_episode_seq(gi.unsqueeze(1), params.unsqueeze(1), None, a.rnn.weight_hh, a.rnn.bias_hh, l1.weight, l1.bias,
+                              l2.weight, l2.bias, E, J, n, self._avail, self._eps_sched, bool(test_mode), mac.select_seed,
+                              self._ctr_base, st["hidden_state"], st["actions_discrete"], st["actions_continuous"],
+                              h_final=mac.hidden_states)
+        env.step_many(st["actions_discrete"][:n], st["actions_continuous"][:n], st["reward"][:n], st["terminated"][:n],
+                      self._rdpj_steps[:n], rdpj_sum=self._rdpj_sum)
+
     def run(self, test_mode=False, store=True, sync_stats=True):
         """One batch of E episodes.  Returns the reference's ``run_info`` keys as means over the E
         episodes (one host sync at the very end; pass ``sync_stats=False`` to get 0-dim tensors)."""
@@ -543,6 +620,8 @@ class BatchedEpisodeRunner:
             self.rollout_closed_loop(test_mode=test_mode)
         elif self.closed_loop_rollout and self.closed_loop_pe_available():
             self.rollout_closed_loop_pe(test_mode=test_mode)
+        elif self.moving_episode_rollout and self.moving_rollout_available():
+            self.rollout_moving(test_mode=test_mode)
         elif getattr(self, "_graph", None) is not None and not test_mode:
             self.rollout_graphed()
         else:

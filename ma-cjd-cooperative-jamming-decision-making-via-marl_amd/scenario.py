@@ -623,6 +623,17 @@ class Scenario:
             feats.extend(np.array(p["position"]).flatten())
         return np.array(feats, dtype=np.float32)
 
+    def frame_state_rows(self) -> np.ndarray:
+        """f32[F + 1, S] of a moving scenario: row k is ``state_vector()`` with ``position_columns`` replaced by
+        ``motion_tables["positions"][k]`` — the state row every env shows at step counter k (the bits the moving step
+        writes), equal to the state vector of the static scenario of frame k (``motion_frame_dict``)."""
+        if not self.moving:
+            raise AttributeError("frame_state_rows: the scenario does not move (no environment_params.motion)")
+        pos = self.motion_tables["positions"]
+        rows = np.repeat(self.state_vector()[None, :], pos.shape[0], axis=0)
+        rows[:, self.motion_tables["position_columns"]] = pos
+        return np.ascontiguousarray(rows, dtype=np.float32)
+
     def env_info(self) -> Dict[str, int]:
         """environment.py:553-565."""
         return {"state_shape": self.state_dim, "obs_shape": self.state_dim, "n_actions": self.n_actions,

@@ -254,6 +254,16 @@ class BatchedElectromagneticEnvironment:
             raise AttributeError("positions: the scenario does not move (no environment_params.motion)")
         return self._state_dyn[:, self._pos_cols]
 
+    def frame_states(self) -> torch.Tensor:
+        """f32 [F + 1, S] on the device (moving scenarios only): row k is the state row every env shows at step counter k —
+        the scenario's state vector with the position columns of frame k (``Scenario.frame_state_rows``), i.e. the bits
+        the moving step writes.  Built once."""
+        if self._motion_io is None:
+            raise AttributeError("frame_states: the scenario does not move (no environment_params.motion)")
+        if getattr(self, "_frame_states", None) is None:
+            self._frame_states = torch.from_numpy(self.scenario.frame_state_rows()).to(self.device)
+        return self._frame_states
+
     @property
     def step_count(self) -> torch.Tensor:
         return self._step
@@ -491,6 +501,13 @@ class BatchedElectromagneticEnvironment:
                 "episode": self._episode, "seed": self.seed, "env_offset": self.env_offset, "n_radars": self.num_radars,
                 "pe_tables": self._pe_tables.data_ptr(), "pe_flags": self._pe_flags.data_ptr(), "pe_tile": self._pe_tile,
                 "n_envs": self.batch_envs, "scan_pe_io": self._scan_pe_io, "scan_pe_pattern_io": self._scan_pe_pattern_io}
+
+    MANY_STEP_MOVING_SIZES = ((2, 2), (3, 4), (6, 8))   # (J, R) of csrc/macjd_env_motion.hip, motion_size_compiled
+
+    def step_many_has_production_form(self) -> bool:
+        """A moving env's ``step_many`` exists in the production form only (the lane kernel at a compiled size; any other
+        size is refused by the launch): True when this env moves and its size is one of them."""
+        return self._motion_io is not None and (self.num_jammers, self.num_radars) in self.MANY_STEP_MOVING_SIZES
 
     def _refuse_scanning(self, what: str) -> None:
         # macjd_env_step_many rests on "a step's outcome depends on the past only through the step counter" (include/
