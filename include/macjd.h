@@ -298,6 +298,21 @@ typedef struct macjd_motion_io {
     float*  snr_no;   int64_t sn_se, sn_sx;   /* optional [E,R] SNR without jamming of the frame used; single steps only */
 } macjd_motion_io;
 
+/*
+ * Moving entities WITH scanning beams (sim-config `environment_params.motion` and `radar_scan` on one clock: both
+ * `step_seconds` equal, one env step is one dt for the beams and for the entities).  Frame k is the static SCANNING scenario
+ * at positions p0 + k (v dt), so the beams' tables are per-step frames too.  Device arrays:
+ *   scan_frames    float64 [n_frames, MACJD_PE_SCAN_ROWS(R,J)], frame-major, rows in the order of macjd_scan_pe_io.tables;
+ *   pattern_frames float64 [n_frames, MACJD_PE_SCAN_PATTERN_ROWS(R,L)], frame-major, rows in the order of
+ *                  macjd_scan_pe_pattern_io.tables; given exactly when n_levels > 0 (a stepped antenna pattern).
+ * Row f of each holds the bits of the per-env column of frame f's compiled scenario.  n_frames is macjd_motion_io's.
+ */
+typedef struct macjd_motion_scan_io {
+    const double* scan_frames;      /* [n_frames, MACJD_PE_SCAN_ROWS(R,J)], frame-major */
+    const double* pattern_frames;   /* optional [n_frames, MACJD_PE_SCAN_PATTERN_ROWS(R,L)] */
+    int32_t n_levels, reserved;     /* L, 0 without pattern_frames */
+} macjd_motion_scan_io;
+
 /* library / device */
 int         macjd_abi_version(void);
 const char* macjd_last_error(void);
@@ -391,6 +406,23 @@ int macjd_env_step_many_moving(const macjd_scenario* s, const macjd_step_io* io,
    the envs with mask != 0 (all when mask == NULL) */
 int macjd_env_reset_moving(const macjd_scenario* s, int64_t n_envs, const macjd_motion_io* motion, const uint8_t* mask,
                            void* hip_stream);
+
+/* The env step of a moving scenario with scanning beams (see macjd_motion_scan_io); needs a scanning handle
+   (macjd_scenario_set_scan).  A step whose counter is k before it runs the arithmetic, order, RNG slots and Philox keying of
+   macjd_env_step_scan_pe (macjd_env_step_scan_pe_pattern when pattern_frames is given) on frame f = min(k, n_frames - 1):
+   the step's own rows from motion->frames / frame_flags, every scan row from scan_frames, the level rows from
+   pattern_frames; the handle supplies R, J, episode_limit, the r_p bounds and the Pd constants (pattern levels of the handle
+   are accepted only if their L equals n_levels, and are never read).  The beams advance as macjd_scan_desc says, with
+   bear_tgt of frame f: a beam that keeps detecting follows a moving target one frame behind.  The same launch then writes
+   (float)theta_a' into scan->state's theta_a columns (when given), positions[min(k + 1, n_frames)] into the position
+   columns of motion->state, and the per-step SNR without jamming into scan->snr_no (when given).  io->pe_tables and
+   motion->snr_no must be NULL; scan->state, when given, must equal motion->state.  Results are bit-identical to
+   macjd_env_step_scan_pe(_pattern) on per-env tables whose column for env e holds frame f_e, in the same (production or
+   general all-float64) form.  The outcome depends on the past through theta_a, so there is no many-step form; the reset is
+   macjd_env_reset + macjd_env_reset_scan + macjd_env_reset_moving with one mask (az0 does not depend on the frame).
+   One lane per env; sizes and variants as macjd_env_step_moving. */
+int macjd_env_step_moving_scan(const macjd_scenario* s, const macjd_step_io* io, const macjd_motion_io* motion,
+                               const macjd_scan_io* scan, const macjd_motion_scan_io* motion_scan, void* hip_stream);
 
 /* timing helper for bench.py: `iters` back-to-back env_step launches, replayed from one HIP graph on a private
    stream after the work queued on `hip_stream` has finished (as the benchmark's rollout replays them, so the

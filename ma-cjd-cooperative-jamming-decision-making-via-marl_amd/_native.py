@@ -42,7 +42,7 @@ EXPORTS = [
     "macjd_linear_wgrad_many_norm", "macjd_linear_wgrad_many_norm_partials", "macjd_clip_adam_step_reduced",
     "macjd_linear_wgrad_many_norm_work_items", "macjd_wgrad_slot_floats",
     "macjd_prefetch_batches_supported", "macjd_prefetch_batches",
-    "macjd_env_step_moving", "macjd_env_step_many_moving", "macjd_env_reset_moving",
+    "macjd_env_step_moving", "macjd_env_step_many_moving", "macjd_env_reset_moving", "macjd_env_step_moving_scan",
     "macjd_agent_episode_seq_supported", "macjd_agent_episode_seq",
 ]
 
@@ -123,6 +123,13 @@ class MotionIO(ctypes.Structure):
         ("state", ctypes.c_void_p), ("st_se", ctypes.c_int64),
         ("snr_no", ctypes.c_void_p), ("sn_se", ctypes.c_int64), ("sn_sx", ctypes.c_int64),
     ]
+
+
+class MotionScanIO(ctypes.Structure):
+    """ctypes mirror of ``macjd_motion_scan_io`` (include/macjd.h): the per-frame scan and pattern tables of a moving scenario
+    with scanning beams."""
+    _fields_ = [("scan_frames", ctypes.c_void_p), ("pattern_frames", ctypes.c_void_p),
+                ("n_levels", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 class QheadIO(ctypes.Structure):
@@ -513,6 +520,9 @@ def load() -> ctypes.CDLL:
     lib.macjd_env_reset_moving.restype = ctypes.c_int
     lib.macjd_env_reset_moving.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(MotionIO), ctypes.c_void_p,
                                            ctypes.c_void_p]
+    lib.macjd_env_step_moving_scan.restype = ctypes.c_int
+    lib.macjd_env_step_moving_scan.argtypes = [ctypes.c_void_p, ctypes.POINTER(StepIO), ctypes.POINTER(MotionIO),
+                                               ctypes.POINTER(ScanIO), ctypes.POINTER(MotionScanIO), ctypes.c_void_p]
     lib.macjd_env_step.argtypes = [ctypes.c_void_p, ctypes.POINTER(StepIO), ctypes.c_void_p]
     lib.macjd_env_step_timed.restype = ctypes.c_int
     lib.macjd_env_step_timed.argtypes = [ctypes.c_void_p, ctypes.POINTER(StepIO), ctypes.c_int, ctypes.c_void_p,

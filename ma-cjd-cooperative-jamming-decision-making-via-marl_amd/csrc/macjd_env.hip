@@ -445,6 +445,21 @@ static void fill_motion(X& x, const macjd_motion_io* mo) {
     x.n_frames = mo->n_frames; x.n_pos = mo->n_pos;
 }
 
+// ... and a MOVING SCANNING launch's (include/macjd.h, macjd_motion_scan_io)
+template <class X>
+static void fill_motion_scan(X& x, const macjd_motion_io* mo, const macjd_scan_io* sc, const macjd_motion_scan_io* ms) {
+    fill_scan(x, sc);
+    x.sp_tables = ms->scan_frames; x.sp_stride = 0;   // frame-major: the strides are not read
+    x.frames = mo->frames; x.frame_flags = mo->frame_flags;
+    x.positions = mo->positions; x.position_columns = mo->position_columns;
+    x.mv_state = mo->state; x.mv_st_se = mo->st_se;
+    x.n_frames = mo->n_frames; x.n_pos = mo->n_pos;
+}
+template <class X>
+static void fill_motion_scan_pattern(X& x, const macjd_motion_scan_io* ms) {
+    x.pp_tables = ms->pattern_frames; x.pp_stride = 0; x.pat_levels = ms->n_levels;
+}
+
 template <int JT, int RT, bool PE, bool FAST, bool REG = false, bool PD32 = false, bool SCAN = false, bool PAT = false, class IO>
 static void launch_lanes(dim3 grid, dim3 block, hipStream_t stream, const macjd_scenario* s, const IO& io) {
     hipLaunchKernelGGL((macjd::env_step_kernel<JT, RT, PE, FAST, IO, REG, PD32, SCAN, PAT>), grid, block, 0, stream, s->dev, io);
@@ -1058,6 +1073,75 @@ int macjd_env_reset_moving(const macjd_scenario* s, int64_t n_envs, const macjd_
     macjd::launch_motion_reset(dim3((unsigned)grid), dim3(256), (hipStream_t)hip_stream, n_envs, motion->n_pos, motion->positions,
                                motion->position_columns, motion->state, motion->st_se, mask);
     return launch_status(me);
+}
+
+// ---- moving scenarios with scanning beams (include/macjd.h, macjd_motion_scan_io; kernels in macjd_env_motion_scan.hip) ----
+
+// Always the lane kernel on the frame tables: the production variant or the general one at the compiled sizes, the
+// generic-size kernel for the others
+static int launch_step_moving_scan(const macjd_scenario* s, const macjd_step_io* io, const macjd_motion_io* mo, const macjd_scan_io* sc,
+                                   const macjd_motion_scan_io* ms, hipStream_t stream, const char* who) {
+    const int64_t E = io->n_envs;
+    const int J = s->host.J, R = s->host.R;
+    const LaneGrid lg = lane_grid(E);
+    const dim3 gf((unsigned)lg.blocks), g(lg.strided), b(lg.block);
+    const bool fast = macjd::motion_size_compiled(J, R) && production_io(io, J, R, lg.blocks, 0, 0) && scan_spans_ok(sc, E, R) &&
+                      motion_spans_ok(mo, E, R);
+    if (ms->pattern_frames) {
+        if (fast) {
+            macjd::MotionScanStepIO<macjd::ScanPePatStepIO<macjd::FastStepIO>> f{};
+            fill_fast(f, io, 0, 0);
+            fill_motion_scan(f, mo, sc, ms);
+            fill_motion_scan_pattern(f, ms);
+            (void)macjd::launch_motion_scan_pattern_fast(J, R, gf, b, stream, s->dev, f);
+        } else {
+            macjd::MotionScanStepIO<macjd::ScanPePatStepIO<macjd_step_io>> w{};
+            static_cast<macjd_step_io&>(w) = *io;
+            fill_motion_scan(w, mo, sc, ms);
+            fill_motion_scan_pattern(w, ms);
+            macjd::launch_motion_scan_pattern_general(J, R, g, b, stream, s->dev, w);
+        }
+    } else if (fast) {
+        macjd::MotionScanStepIO<macjd::ScanPeStepIO<macjd::FastStepIO>> f{};
+        fill_fast(f, io, 0, 0);
+        fill_motion_scan(f, mo, sc, ms);
+        (void)macjd::launch_motion_scan_fast(J, R, gf, b, stream, s->dev, f);
+    } else {
+        macjd::MotionScanStepIO<macjd::ScanPeStepIO<macjd_step_io>> w{};
+        static_cast<macjd_step_io&>(w) = *io;
+        fill_motion_scan(w, mo, sc, ms);
+        macjd::launch_motion_scan_general(J, R, g, b, stream, s->dev, w);
+    }
+    return launch_status(who);
+}
+
+int macjd_env_step_moving_scan(const macjd_scenario* s, const macjd_step_io* io, const macjd_motion_io* motion,
+                               const macjd_scan_io* scan, const macjd_motion_scan_io* motion_scan, void* hip_stream) {
+    const char* me = "macjd_env_step_moving_scan";
+    int rc = validate_io(s, io);
+    if (rc != MACJD_OK) return rc;
+    rc = validate_motion(s, motion, me);
+    if (rc != MACJD_OK) return rc;
+    rc = validate_scan(s, scan, me);   // (refuses a handle that is not a scanning handle)
+    if (rc != MACJD_OK) return rc;
+    if (!motion_scan || !motion_scan->scan_frames) return set_err(MACJD_EINVAL, "%s: NULL motion scan io / scan_frames", me);
+    if (io->pe_tables) return set_err(MACJD_EINVAL, "%s: io->pe_tables must be NULL (the frames are the tables)", me);
+    if (motion->snr_no)
+        return set_err(MACJD_EINVAL, "%s: motion->snr_no must be NULL (the per-step value travels in scan->snr_no)", me);
+    if (motion_scan->n_levels < 0 || motion_scan->n_levels > MACJD_MAX_PATTERN_LEVELS)
+        return set_err(MACJD_EINVAL, "%s: n_levels outside 0..MACJD_MAX_PATTERN_LEVELS", me);
+    if (s->host.pat_levels > 0 && s->host.pat_levels != motion_scan->n_levels)
+        return set_err(MACJD_EINVAL, "%s: n_levels differs from the pattern levels of the scenario handle", me);
+    if ((motion_scan->pattern_frames != nullptr) != (motion_scan->n_levels > 0))
+        return set_err(MACJD_EINVAL, "%s: pattern_frames and n_levels > 0 go together (both or neither)", me);
+    if (scan->state && scan->state != motion->state)
+        return set_err(MACJD_EINVAL, "%s: scan->state and motion->state must be the same rows", me);
+    if (scan->state && scan->st_se != motion->st_se)
+        return set_err(MACJD_EINVAL, "%s: scan->st_se and motion->st_se must be the same row stride", me);
+    if (io->flags & MACJD_STEP_SLOT_KERNEL)
+        return set_err(MACJD_EUNSUPPORTED, "%s: the (env x slot) kernel has no moving variant (one lane per env only)", me);
+    if (io->n_envs == 0) return MACJD_OK;
+    return launch_step_moving_scan(s, io, motion, scan, motion_scan, (hipStream_t)hip_stream, me);
 }
 
 static int env_step_timed_impl(const macjd_scenario* s, const macjd_step_io* io, int iters, void* hip_stream,

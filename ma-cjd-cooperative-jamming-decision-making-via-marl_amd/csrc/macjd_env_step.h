@@ -1,5 +1,6 @@
 // The one-lane-per-env step kernel (env_step_kernel) with its argument blocks: a header, so that a second translation unit
-// (macjd_env_scan_pe.hip) can instantiate it with another unrolling directive on its size-bounded loops.
+// (macjd_env_scan_pe.hip, macjd_env_motion_scan.hip) can instantiate it with another unrolling directive on its size-bounded
+// loops.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -134,8 +135,28 @@ struct MotionStepIO : Base {
     int64_t mv_st_se, mv_sn_se, mv_sn_sx;
     int32_t n_frames, n_pos;
 };
+// Argument block of a MOVING SCANNING launch (include/macjd.h, macjd_motion_scan_io): ScanBase = ScanPeStepIO<...> or, under a
+// stepped antenna pattern, ScanPePatStepIO<...>, whose sp_tables / pp_tables point at the per-frame scan / pattern tables
+// (frame-major like `frames`; the strides are not read), plus the frame tables and positions of MotionStepIO.  The beam
+// block's `state` (theta_a columns, optional) and `snr_no` keep their names; the rows whose position columns the step
+// rewrites are `mv_state`, and the moving step's own snr_no output does not exist here (the scan block's carries the
+// per-step value): compile-time constants, its code folds away.
+template <class ScanBase>
+struct MotionScanStepIO : ScanBase {
+    const double* frames;
+    const uint8_t* frame_flags;
+    const float* positions;
+    const int32_t* position_columns;
+    float* mv_state;
+    int64_t mv_st_se;
+    int32_t n_frames, n_pos;
+    static constexpr const double* frame_snr_no = nullptr;
+    static constexpr float* mv_snr_no = nullptr;
+    static constexpr int64_t mv_sn_se = 0, mv_sn_sx = 0;
+};
 template <class IO> struct io_moves : std::false_type {};
 template <class Base> struct io_moves<MotionStepIO<Base>> : std::true_type {};
+template <class ScanBase> struct io_moves<MotionScanStepIO<ScanBase>> : std::true_type {};
 
 // Per-lane pattern state of an env-step: the number of levels and the target's level at each radar, four bits per radar
 // in 64-bit words (word r >> 4; shifts only, so the per-lane index of the PD32 re-evaluation loop — compiled sizes,
@@ -205,7 +226,10 @@ __global__ void __launch_bounds__(256) env_step_kernel(const DevTables* __restri
     // the env's step counter instead of by its index, plus the position columns of the env's state row, rewritten with the
     // next frame's positions.  Same arithmetic, order, RNG slots and stores as the PE kernel of the same form.
     constexpr bool MOV = io_moves<IO>::value;
-    static_assert(!MOV || (PE && !SCAN), "MOV: the per-env-table path of the non-scanning step");
+    // MOV && SCAN (IO = MotionScanStepIO<...>; include/macjd.h, macjd_motion_scan_io): the scan rows, and under PAT the
+    // pattern rows, come from frame f of per-frame tables in the same way; the tail writes the theta_a columns and the
+    // position columns of the env's state row.
+    static_assert(!MOV || PE, "MOV: the per-env-table path of the step");
     constexpr int NJ = JT ? JT : MAXJ;
     constexpr int NR = RT ? RT : MAXR;
     const int J = JT ? JT : tb->J;
@@ -375,7 +399,8 @@ __global__ void __launch_bounds__(256) env_step_kernel(const DevTables* __restri
         const double* __restrict__ sp = nullptr;
         int64_t sps = 0;
         if constexpr (SPE) {
-            sps = io.pe_tile > 0 ? (int64_t)io.pe_tile : io.sp_stride;
+            if constexpr (MOV) sps = 1;   // frame-major: one contiguous block per frame
+            else sps = io.pe_tile > 0 ? (int64_t)io.pe_tile : io.sp_stride;
             sp = io.sp_tables + pe_tile_idx * (10 * R + J * R) * sps + pe_col;
         }
         constexpr bool SHOIST = SPE && HOIST;
@@ -388,7 +413,8 @@ __global__ void __launch_bounds__(256) env_step_kernel(const DevTables* __restri
         const double* __restrict__ pp = nullptr;
         int64_t pps = 0, pp_lv = 0;   // pp_lv = (L + 2) R: rows of one level table
         if constexpr (SPP) {
-            pps = io.pe_tile > 0 ? (int64_t)io.pe_tile : io.pp_stride;
+            if constexpr (MOV) pps = 1;
+            else pps = io.pe_tile > 0 ? (int64_t)io.pe_tile : io.pp_stride;
             pp_lv = (int64_t)(io.pat_levels + 2) * R;
             pp = io.pp_tables + pe_tile_idx * (R + 4 * pp_lv) * pps + pe_col;
         }
@@ -882,12 +908,14 @@ MACJD_ENV_UNROLL_SIZED(NR)
                 int32_t fn = step_count < io.n_frames ? step_count : io.n_frames;
                 fn = fn > 0 ? fn : 0;
                 const float* __restrict__ pos = io.positions + (int64_t)fn * io.n_pos;
+                float* mv_rows;   // (a scanning launch's `state` is the beam block's: optional, theta_a columns)
+                if constexpr (SCAN) mv_rows = io.mv_state; else mv_rows = io.state;
                 constexpr int NPOS = 2 * (NR + NJ);
                 if constexpr (PRE) {
 #pragma unroll
-                    for (int i = 0; i < NPOS; ++i) at(io.state, e, io.mv_st_se, io.position_columns[i], 1) = pos[i];
+                    for (int i = 0; i < NPOS; ++i) at(mv_rows, e, io.mv_st_se, io.position_columns[i], 1) = pos[i];
                 } else {
-                    for (int i = 0; i < io.n_pos; ++i) at(io.state, e, io.mv_st_se, io.position_columns[i], 1) = pos[i];
+                    for (int i = 0; i < io.n_pos; ++i) at(mv_rows, e, io.mv_st_se, io.position_columns[i], 1) = pos[i];
                 }
             }
             if (io.mv_snr_no && !many) {
@@ -929,5 +957,16 @@ void launch_motion_general(int J, int R, dim3 grid, dim3 block, hipStream_t stre
                            const MotionStepIO<macjd_step_io>& io);
 void launch_motion_reset(dim3 grid, dim3 block, hipStream_t stream, int64_t n_envs, int n_pos, const float* positions,
                          const int32_t* position_columns, float* state, int64_t st_se, const uint8_t* mask);
+
+// macjd_env_motion_scan.hip: the MOV && SCAN instantiations (moving scenarios with scanning beams), with and without PAT, a
+// translation unit of their own.  Same sizes and return convention as the launchers of macjd_env_motion.hip.
+bool launch_motion_scan_fast(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
+                             const MotionScanStepIO<ScanPeStepIO<FastStepIO>>& io);
+void launch_motion_scan_general(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
+                                const MotionScanStepIO<ScanPeStepIO<macjd_step_io>>& io);
+bool launch_motion_scan_pattern_fast(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
+                                     const MotionScanStepIO<ScanPePatStepIO<FastStepIO>>& io);
+void launch_motion_scan_pattern_general(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
+                                        const MotionScanStepIO<ScanPePatStepIO<macjd_step_io>>& io);
 
 }  // namespace macjd

@@ -479,6 +479,8 @@ class BatchedEpisodeRunner:
         args_name = "episode_scan_pe_args" if per_env else "episode_scan_args"
         if self.device.type != "cuda" or not hasattr(env, args_name) or not getattr(env.scenario, "scanning", False):
             return False
+        if getattr(env.scenario, "moving", False):   # moving entities under scanning beams: the step loop only
+            return False
         if (getattr(env, "scenario_batch", None) is not None) != per_env or getattr(env, "kernel_flags", 0) != 0:
             return False
         agent = getattr(self.mac, "agent", None)
@@ -546,6 +548,8 @@ class BatchedEpisodeRunner:
         alone, so — as with a static observation — nothing the agent computes depends on the env's outputs."""
         env = self.env
         if self.device.type != "cuda" or not getattr(env.scenario, "moving", False) or not hasattr(env, "frame_states"):
+            return False
+        if getattr(env.scenario, "scanning", False):   # the state rows depend on detections (theta_a): the step loop only
             return False
         if getattr(env, "scenario_batch", None) is not None or getattr(env, "kernel_flags", 0) != 0:
             return False

@@ -10,7 +10,9 @@ hands them to the native library as a ``macjd_scenario_desc`` (include/macjd.h).
 
 Opt-in, ``environment_params.motion`` moves target, radars and jammers on straight lines that do not depend on the
 actions: the same compiler then runs once per step of an episode on the moved positions (``motion_frame_dict``) and the
-tables become per-step frames (``Scenario.motion_tables``; include/macjd.h, ``macjd_motion_io``).
+tables become per-step frames (``Scenario.motion_tables``; include/macjd.h, ``macjd_motion_io``).  Together with
+``radar_scan`` on one clock (equal ``step_seconds``) the beams' scan and pattern tables become frames as well
+(``motion_tables["scan_frames"]`` / ``["pattern_frames"]``; ``macjd_motion_scan_io``).
 
 Validation and error behaviour follow environment.py:44-79 and :133-199 (same exception types and
 messages for the cases the reference checks).
@@ -347,9 +349,11 @@ class Scenario:
             raise ValueError(f"Scenario size {num_jammers}j/{num_radars}r outside the supported range "
                              f"1..{MAX_JAMMERS} / 1..{MAX_RADARS}.")
         motion = parse_motion(env_params, num_radars, num_jammers, source)
-        if motion is not None and radar_scan is not None:
-            raise ValueError(f"{source}: environment_params.motion together with radar_scan is not supported (the beams' "
-                             f"bearing tables would need frames too)")
+        if motion is not None and radar_scan is not None and float(motion["step_seconds"]) != float(radar_scan["step_seconds"]):
+            # one env step is one dt for the beams and for the entities: the scan tables become per-step frames too
+            raise ValueError(f"{source}: environment_params.motion together with radar_scan is not supported unless both run "
+                             f"on one clock: motion.step_seconds ({motion['step_seconds']!r}) and radar_scan.step_seconds "
+                             f"({radar_scan['step_seconds']!r}) must be equal")
 
         radars: List[Dict[str, Any]] = []
         for i, params in enumerate(radar_cfgs):  # :133-169
@@ -425,16 +429,22 @@ class Scenario:
         flags = np.zeros((F, J * R), dtype=np.uint8)
         snr_no = np.zeros((F, R), dtype=np.float64)
         positions = np.zeros((F + 1, len(cols)), dtype=np.float32)
+        scan_frs = []   # the frames' compiled scenarios (scanning: their scan / pattern columns are copied below)
         for f in range(F + 1):
             fr = Scenario.from_dict(motion_frame_dict(sim_config, f), config=config, source=f"{self.source}[frame {f}]")
             positions[f] = fr.state_vector()[cols]
             if f < F:
+                scan_frs.append(fr)
                 frames[f] = np.concatenate([np.asarray(fr.tables[key], dtype=np.float64).reshape(-1)
                                             for key in _PE_RADAR_ROWS + _PE_JAMMER_ROWS + ("jr_denom",)])
                 flags[f] = fr.tables["jr_flags"].reshape(-1)
                 snr_no[f] = fr.tables["radar_snr_no"]
         self.motion_tables = {"frames": frames, "flags": flags, "snr_no": snr_no, "positions": positions,
                               "position_columns": np.asarray(cols, dtype=np.int32)}
+        if self.scanning:   # the beams' tables per frame too (include/macjd.h, macjd_motion_scan_io)
+            self.motion_tables["scan_frames"] = np.stack([_scan_column(fr) for fr in scan_frs])
+            if self.scan_pattern_levels:
+                self.motion_tables["pattern_frames"] = np.stack([_pattern_column(fr) for fr in scan_frs])
 
     # ---- static tables ----
     def _compile(self) -> None:
@@ -689,6 +699,12 @@ def pe_scan_pattern_rows(n_radars: int, n_levels: int) -> int:
     return n_radars + 4 * (n_levels + 2) * n_radars
 
 
+def _scan_column(sc: "Scenario") -> np.ndarray:
+    """Scenario ``sc``'s own arrays in the row order ``PE_SCAN_ROWS``, as one float64 vector (copied, not recomputed)."""
+    return np.concatenate([np.asarray(sc.tables["radar_snr_no"] if key == "snr_no" else sc.scan_tables[key],
+                                      dtype=np.float64).reshape(-1) for key in PE_SCAN_ROWS])
+
+
 def _pattern_column(sc: "Scenario") -> np.ndarray:
     """Scenario ``sc``'s own arrays in the row order ``PE_SCAN_PATTERN_ROWS``, as one float64 vector (copied, not recomputed)."""
     parts = [sc.scan_tables["pat_inv_width"]]
@@ -792,11 +808,7 @@ class ScenarioBatch:
         assert self.tables.shape == (6 * R + 3 * J + J * R, self.n_envs)
         self.scan_tables = None
         if scan:
-            def scan_row(sc, key):
-                return sc.tables["radar_snr_no"] if key == "snr_no" else sc.scan_tables[key]
-            self.scan_tables = np.ascontiguousarray(np.concatenate(
-                [np.stack([np.asarray(scan_row(sc, key), dtype=np.float64).reshape(-1) for sc in scenarios], axis=1)
-                 for key in PE_SCAN_ROWS], axis=0))                                           # [10R + JR, E]
+            self.scan_tables = np.ascontiguousarray(np.stack([_scan_column(sc) for sc in scenarios], axis=1))   # [10R + JR, E]
             assert self.scan_tables.shape == (pe_scan_rows(R, J), self.n_envs)
         self.pattern_tables = None
         if pattern:

@@ -183,27 +183,38 @@ class BatchedElectromagneticEnvironment:
             si.state, si.st_se = self._state_dyn.data_ptr(), self._state_dyn.stride(0)
             si.st_col0, si.st_col_step = sc.theta_a_col0, sc.theta_a_col_step
             si.snr_no, si.sn_se, si.sn_sx = self._snr_no_step.data_ptr(), 1, E
-        self._motion_io = self._motion_keep = None
+        self._motion_io = self._motion_keep = self._motion_scan_io = None
         if sc.moving:
             # per-step frame tables (include/macjd.h, macjd_motion_io): f64 [F, rows], u8 [F, J*R], f64 [F, R], the
             # positions f32 [F + 1, 2R + 2J] with their state columns; the per-env state rows f32 [E, S] start as frame 0
             # (get_state / get_obs are views of them: one address for captured graphs) and the per-step SNR without
             # jamming f32 [R, E] as frame 0's
             mt = sc.motion_tables
+            # With scanning beams (one clock, include/macjd.h, macjd_motion_scan_io) the state rows, beams and per-step SNR
+            # set up above serve both: the step rewrites their theta_a AND position columns, and the per-frame scan tables
+            # f64 [F, 10R + JR] (under a stepped pattern also the level tables f64 [F, R + 4(L+2)R]) are uploaded too.
             keep = {k: torch.from_numpy(np.ascontiguousarray(mt[k])).to(dev)
-                    for k in ("frames", "flags", "snr_no", "positions", "position_columns")}
+                    for k in ("frames", "flags", "snr_no", "positions", "position_columns", "scan_frames", "pattern_frames")
+                    if k in mt}
             self._motion_keep = keep
             self._pos_cols = keep["position_columns"].to(torch.int64)
-            st = torch.from_numpy(sc.state_vector()).to(dev)
-            self._state_dyn = st.view(1, -1).repeat(E, 1).contiguous()
+            if self._state_dyn is None:
+                st = torch.from_numpy(sc.state_vector()).to(dev)
+                self._state_dyn = st.view(1, -1).repeat(E, 1).contiguous()
+                self._snr_no_step = keep["snr_no"][0].to(torch.float32).view(R, 1).repeat(1, E).contiguous()
             self._state_dyn[:, self._pos_cols] = keep["positions"][0]
-            self._snr_no_step = keep["snr_no"][0].to(torch.float32).view(R, 1).repeat(1, E).contiguous()
             mo = self._motion_io = _native.MotionIO()
             mo.frames, mo.frame_flags, mo.frame_snr_no = keep["frames"].data_ptr(), keep["flags"].data_ptr(), keep["snr_no"].data_ptr()
             mo.positions, mo.position_columns = keep["positions"].data_ptr(), keep["position_columns"].data_ptr()
             mo.n_frames, mo.n_pos = int(mt["frames"].shape[0]), int(mt["positions"].shape[1])
             mo.state, mo.st_se = self._state_dyn.data_ptr(), self._state_dyn.stride(0)
             mo.snr_no, mo.sn_se, mo.sn_sx = self._snr_no_step.data_ptr(), 1, E
+            if sc.scanning:
+                mo.snr_no = None   # the per-step value travels in the beam block's snr_no
+                ms = self._motion_scan_io = _native.MotionScanIO()
+                ms.scan_frames = keep["scan_frames"].data_ptr()
+                ms.pattern_frames = keep["pattern_frames"].data_ptr() if "pattern_frames" in keep else None
+                ms.n_levels = sc.scan_pattern_levels if "pattern_frames" in keep else 0
         self._io = _native.StepIO()
         self.kernel_flags = 0  # A/B hook: _native.STEP_LANE_KERNEL / STEP_SLOT_KERNEL force one kernel variant
         if verbose:
@@ -260,6 +271,9 @@ class BatchedElectromagneticEnvironment:
         the moving step writes.  Built once."""
         if self._motion_io is None:
             raise AttributeError("frame_states: the scenario does not move (no environment_params.motion)")
+        if self._motion_scan_io is not None:   # the theta_a columns depend on the detections, not on the counter alone
+            raise RuntimeError("frame_states: not available with scanning radars (environment_params.radar_scan): the state "
+                               "rows of a moving scanning scenario depend on the detections")
         if getattr(self, "_frame_states", None) is None:
             self._frame_states = torch.from_numpy(self.scenario.frame_state_rows()).to(self.device)
         return self._frame_states
@@ -293,7 +307,7 @@ class BatchedElectromagneticEnvironment:
             elif self._scan_io is not None:
                 _native.check(self._lib.macjd_env_reset_scan(self._handle.ptr, self.batch_envs, ctypes.byref(self._scan_io),
                                                              mptr, stream), "macjd_env_reset_scan")
-            elif self._motion_io is not None:
+            if self._motion_io is not None:   # (next to the beam reset when the scenario also scans)
                 _native.check(self._lib.macjd_env_reset_moving(self._handle.ptr, self.batch_envs, ctypes.byref(self._motion_io),
                                                                mptr, stream), "macjd_env_reset_moving")
         self._keep_mask = mask
@@ -382,7 +396,13 @@ class BatchedElectromagneticEnvironment:
                            rdpj_sum)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         with torch.cuda.device(self.device):
-            if self._scan_pe_pattern_io is not None:
+            if self._motion_scan_io is not None:
+                si = self._scan_io
+                si.snr_no = self._snr_no_step.data_ptr() if want_info else None
+                _native.check(self._lib.macjd_env_step_moving_scan(
+                    self._handle.ptr, ctypes.byref(io), ctypes.byref(self._motion_io), ctypes.byref(si),
+                    ctypes.byref(self._motion_scan_io), stream), "macjd_env_step_moving_scan")
+            elif self._scan_pe_pattern_io is not None:
                 _native.check(self._lib.macjd_env_step_scan_pe_pattern(
                     self._handle.ptr, ctypes.byref(io), ctypes.byref(self._scan_io), ctypes.byref(self._scan_pe_io),
                     ctypes.byref(self._scan_pe_pattern_io), stream), "macjd_env_step_scan_pe_pattern")
@@ -485,6 +505,9 @@ class BatchedElectromagneticEnvironment:
             raise RuntimeError("episode_scan_args: the scenario's beams do not scan (no environment_params.radar_scan)")
         if self._pe_tables is not None:
             raise RuntimeError("episode_scan_args: per-env scenario tables are not supported with scanning radars")
+        if self._motion_io is not None:
+            raise RuntimeError("episode_scan_args: not available with a moving scenario (environment_params.motion): the "
+                               "closed-loop launch reads the handle's frame-0 tables")
         return {"handle": self._handle.ptr, "scan_io": self._scan_io, "track": self._track, "step": self._step,
                 "episode": self._episode, "seed": self.seed, "env_offset": self.env_offset, "n_radars": self.num_radars,
                 "pe_tables": None}
@@ -507,7 +530,8 @@ class BatchedElectromagneticEnvironment:
     def step_many_has_production_form(self) -> bool:
         """A moving env's ``step_many`` exists in the production form only (the lane kernel at a compiled size; any other
         size is refused by the launch): True when this env moves and its size is one of them."""
-        return self._motion_io is not None and (self.num_jammers, self.num_radars) in self.MANY_STEP_MOVING_SIZES
+        return (self._motion_io is not None and self._motion_scan_io is None
+                and (self.num_jammers, self.num_radars) in self.MANY_STEP_MOVING_SIZES)
 
     def _refuse_scanning(self, what: str) -> None:
         # macjd_env_step_many rests on "a step's outcome depends on the past only through the step counter" (include/
@@ -647,11 +671,18 @@ class ElectromagneticEnvironment:
         if b._scan_io is not None:
             # the kernel reports which lobe's no-jamming SNR applied (float32); hand out that table's float64 value
             snr32 = b._snr_no_step.t().cpu().numpy()[0]
-            main = sc.tables["radar_snr_no"]
-            snr_no = np.where(main.astype(np.float32) == snr32, main, sc.scan_tables["snr_no_side"]).astype(np.float64)
+            main, side = sc.tables["radar_snr_no"], sc.scan_tables["snr_no_side"]
+            levels = sc.scan_tables["pat_snr_no"] if sc.scan_pattern_levels else None
+            if b._motion_scan_io is not None:   # a moving scenario: the tables of the frame this step ran on
+                mt, L = sc.motion_tables, sc.scan_pattern_levels
+                f = min(self._step_count - 1, mt["scan_frames"].shape[0] - 1)
+                main, side = mt["scan_frames"][f, 6 * R:7 * R], mt["scan_frames"][f, 7 * R:8 * R]
+                if L:   # snr_no_lvl block of the pattern row: [L + 2, R] behind inv_width and GaPs_lvl
+                    levels = mt["pattern_frames"][f, R + (L + 2) * R:R + 2 * (L + 2) * R].reshape(L + 2, R)[1:L + 1]
+            snr_no = np.where(main.astype(np.float32) == snr32, main, side).astype(np.float64)
             if sc.scan_pattern_levels:
                 # stepped pattern: the matching level's value (equal gains give equal values: any of them will do)
-                for lvl in sc.scan_tables["pat_snr_no"][::-1]:
+                for lvl in levels[::-1]:
                     snr_no = np.where((lvl.astype(np.float32) == snr32) & (main.astype(np.float32) != snr32), lvl, snr_no)
             self._state = b.get_state()[0].cpu().numpy().copy()
         elif b._motion_io is not None:
