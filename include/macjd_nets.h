@@ -840,6 +840,41 @@ int macjd_agent_env_episode_scan_pe_supported(int32_t J, int32_t R, int32_t H, i
 int macjd_agent_env_episode_scan_pe(const macjd_scenario* scenario, const macjd_agent_env_episode_scan_pe_io* io, void* hip_stream);
 
 /*
+ * macjd_agent_env_episode_scan for a MOVING scenario under scanning radars (macjd_motion_io + macjd_motion_scan_io, with
+ * or without a stepped antenna pattern): the same launch and outputs, with the env's tables taken from the frame of the
+ * step.  Env e runs step t on frame f = min(step0[e] + t, n_frames - 1), step0[e] = base.step[e] at entry (step counters
+ * are per env: one workgroup may hold envs on different frames): the step's own rows from motion.frames[f] /
+ * frame_flags[f], every scan row from motion_scan.scan_frames[f], under a pattern inv_width and the level rows from
+ * motion_scan.pattern_frames[f].
+ *   base         the shared call's block; base.pe_tables must be NULL (the frames are the tables)
+ *   motion       frames, frame_flags, positions, position_columns, n_frames, n_pos and state (= base.scan.state) are
+ *                read; snr_no must be NULL (the per-step value travels in base.scan.snr_no); frame_snr_no is not read
+ *   motion_scan  scan_frames; pattern_frames together with n_levels = L, or neither
+ * The observation of step t shows positions[min(step0[e] + t, n_frames)] at position_columns: besides the theta_a columns
+ * the kernel writes these n_pos = 2R + 2J columns of the staging rows t < T (st_state, st_obs); every other column is the
+ * caller's.  At exit theta_a, track, step, rdpj_sum, h_final, the theta_a columns and the position columns
+ * (positions[min(step0[e] + T, n_frames)]) of the env's state rows hold what T single macjd_env_step_moving_scan steps
+ * would have left, and scan.snr_no the last step's value of its frame: the snr_no / snr_no_side row of scan_frames, or
+ * under a pattern the snr_no_lvl row of the last level in pattern_frames.  The env half is bit-identical to T single
+ * macjd_env_step_moving_scan steps in their general all-float64 form on the actions the agent half chose.
+ * The handle is the scenario's scanning handle (R, J, episode_limit, the r_p bounds, the Pd constants).  MACJD_EINVAL: NULL
+ * frames / frame_flags / positions / position_columns / scan_frames, n_frames < 1 or not the handle's episode_limit,
+ * n_pos != 2R + 2J, motion.snr_no != NULL, motion.state != base.scan.state (or another row stride), pattern_frames without
+ * n_levels in 1..MACJD_MAX_PATTERN_LEVELS or n_levels without pattern_frames, a handle whose pattern L differs from
+ * n_levels, a handle without scan tables, base.pe_tables != NULL; MACJD_EUNSUPPORTED: sizes other than those of
+ * macjd_agent_env_episode_scan.  Every check returns before any launch.
+ */
+typedef struct macjd_agent_env_episode_moving_scan_io {
+    macjd_agent_env_episode_scan_io base;   /* base.pe_tables must be NULL */
+    macjd_motion_io       motion;
+    macjd_motion_scan_io  motion_scan;
+} macjd_agent_env_episode_moving_scan_io;
+
+int macjd_agent_env_episode_moving_scan_supported(int32_t J, int32_t R, int32_t H, int32_t A);
+int macjd_agent_env_episode_moving_scan(const macjd_scenario* scenario, const macjd_agent_env_episode_moving_scan_io* io,
+                                        void* hip_stream);
+
+/*
  * Double-DQN target values straight from the unrolled hidden states (reference core/qmix.py:138-147): for every row n
  *   a* = argmax_a Q_eval(h_e[n], a, P_e[n,a])   (no availability mask there, qmix.py:141-142)
  *   out[n] = Q_target(h_t[n], a*, P_t[n,a*])

@@ -35,6 +35,7 @@ EXPORTS = [
     "macjd_env_step_scan_pe", "macjd_env_reset_scan_pe", "macjd_env_step_scan_pe_pattern",
     "macjd_agent_env_episode_scan_supported", "macjd_agent_env_episode_scan",
     "macjd_agent_env_episode_scan_pe_supported", "macjd_agent_env_episode_scan_pe",
+    "macjd_agent_env_episode_moving_scan_supported", "macjd_agent_env_episode_moving_scan",
     "macjd_scenario_set_scan_pattern",
     "macjd_gru_sequence_backward_supported", "macjd_gru_sequence_backward",
     "macjd_prefetch_batch_supported", "macjd_prefetch_batch",
@@ -292,6 +293,11 @@ class AgentEnvEpisodeScanPeIO(ctypes.Structure):
         ("pe_flags", ctypes.c_void_p), ("pe_stride", ctypes.c_int64), ("pe_tile", ctypes.c_int32), ("reserved", ctypes.c_int32),
         ("scan_pe", ScanPeIO), ("pattern", ScanPePatternIO),
     ]
+
+
+class AgentEnvEpisodeMovingScanIO(ctypes.Structure):
+    """ctypes mirror of ``macjd_agent_env_episode_moving_scan_io`` (include/macjd_nets.h)."""
+    _fields_ = [("base", AgentEnvEpisodeScanIO), ("motion", MotionIO), ("motion_scan", MotionScanIO)]
 
 
 class DoubleQIO(ctypes.Structure):
@@ -562,6 +568,10 @@ def load() -> ctypes.CDLL:
     lib.macjd_agent_env_episode_scan_pe_supported.argtypes = [ctypes.c_int32] * 4
     lib.macjd_agent_env_episode_scan_pe.restype = ctypes.c_int
     lib.macjd_agent_env_episode_scan_pe.argtypes = [ctypes.c_void_p, ctypes.POINTER(AgentEnvEpisodeScanPeIO), ctypes.c_void_p]
+    lib.macjd_agent_env_episode_moving_scan_supported.restype = ctypes.c_int
+    lib.macjd_agent_env_episode_moving_scan_supported.argtypes = [ctypes.c_int32] * 4
+    lib.macjd_agent_env_episode_moving_scan.restype = ctypes.c_int
+    lib.macjd_agent_env_episode_moving_scan.argtypes = [ctypes.c_void_p, ctypes.POINTER(AgentEnvEpisodeMovingScanIO), ctypes.c_void_p]
     lib.macjd_env_step_many.restype = ctypes.c_int
     lib.macjd_env_step_many.argtypes = [ctypes.c_void_p, ctypes.POINTER(StepIO), ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p]
     lib.macjd_env_step_many_timed.restype = ctypes.c_int

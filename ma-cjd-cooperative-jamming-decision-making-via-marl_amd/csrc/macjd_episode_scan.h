@@ -37,6 +37,11 @@
 // Per-env scenario batches (include/macjd_nets.h, macjd_agent_env_episode_scan_pe_io): PE, the next template parameter,
 // with the argument block EpScanPeIO — the same kernel with every table read taken from the env's own column (see the
 // comment on the kernel).  Again only the names of the existing variants change, profiles/r18_episode_isa_check.txt.
+//
+// Moving scenarios under scanning radars (include/macjd_nets.h, macjd_agent_env_episode_moving_scan_io): the PE variant
+// launched with the argument block EpScanMovIO (MOV below, deduced from the block's type so that the existing variants keep
+// their names) — the env's column is frame f = min(step counter, F - 1) of the frame tables, staged again every step, and
+// the observation's position columns follow positions[min(step counter, F)] (see the comment on the kernel).
 #pragma once
 
 #include <type_traits>
@@ -79,6 +84,19 @@ struct EpScanPeIO : macjd_agent_env_episode_scan_io {
     int32_t pe_tile, pat_levels;
 };
 
+// Argument block of the launch on a moving scanning scenario (include/macjd_nets.h, macjd_agent_env_episode_moving_scan_io):
+// the shared launch's block plus the frame tables of macjd_motion_io / macjd_motion_scan_io (frame-major: the tiled per-env
+// layout at tile width 1 with the frame index as the tile index).
+struct EpScanMovIO : macjd_agent_env_episode_scan_io {
+    const double* frames;
+    const uint8_t* frame_flags;
+    const double* scan_frames;
+    const double* pattern_frames;
+    const float* positions;
+    const int32_t* position_columns;
+    int32_t n_frames, pat_levels;
+};
+
 // Rows of the per-env LDS block [row][16] of the PE variants (lane er reads [row * 16 + er]): the env's pe_tables rows in
 // their own order, then the scan rows the step reads, then (PAT) inv_width.
 template <int J, int R>
@@ -105,10 +123,22 @@ struct EpScanPeRows {
 // HBM (96 rows at L = 6 do not fit beside the rest): the one row an object's level selects is loaded from the env's
 // column by address, 2R + J loads per lane and step, as env_step_kernel<.., PAT && PE> does.  The handle supplies only the
 // r_p bounds, the Pd constants and episode_limit.  The agent half (S1-S4), keying and barriers are the shared kernel's.
+//
+// MOV (IO = EpScanMovIO, PE = true): env e runs step t on frame f = min(step0[e] + t, F - 1), step0 = io.step[e] at entry, so
+// one workgroup may hold envs on different frames.  The [row][16] block and the flag bytes are rewritten in place by all
+// 256 threads at the top of every step (thread -> column tid & 15, whose step0 the thread holds already): the block is
+// read only in S5 by wave 0, the barrier that closes S5 of step t - 1 precedes the writes and the barriers of S1 - S4
+// precede the reads, so the step keeps its five barriers.  The level rows under a pattern and the hand-over's snr_no row
+// are loaded by address from frame f's row of pattern_frames / scan_frames.  The observation's n_pos = 2R + 2J position
+// columns: waves 1 - 3, idle during S5, copy positions[min(step0 + t + 1, F)] into the LDS observation tile for step t + 1
+// (wave 0 writes the theta_a columns there: disjoint columns), S1 copies them from the tile into the staging rows next to
+// the theta_a columns, and the env lane leaves positions[min(step0 + T, F)] in the env's state row at exit.
 template <int J, int R, int A, int SQ, bool PAT, bool PE = false, class IO = macjd_agent_env_episode_scan_io>
 __global__ void __launch_bounds__(256) agent_env_episode_scan_kernel(const DevTables* __restrict__ tb, const IO io) {
     static_assert(J <= 4, "one wave per agent tile in the Q-head phase");
-    static_assert(PE == std::is_same_v<IO, EpScanPeIO>, "PE: the argument block with the per-env tables");
+    constexpr bool MOV = std::is_same_v<IO, EpScanMovIO>;
+    static_assert(PE == (std::is_same_v<IO, EpScanPeIO> || MOV), "PE: the argument block with the per-env tables");
+    constexpr int NPOS = 2 * R + 2 * J;   // MOV: position columns of a state row
     static_assert(!PAT || R <= 8, "PAT: the target's levels are packed four bits per radar into 32 bits");
     static_assert(16 * A <= 256, "actor layer 3: one thread per (env, action)");
     constexpr int OLD = 16 * SQ + 8;   // LDS pitch of the observation tile (S <= 16 SQ columns, zero-padded)
@@ -131,6 +161,7 @@ __global__ void __launch_bounds__(256) agent_env_episode_scan_kernel(const DevTa
     constexpr int PTN = PR::INVW + (PAT ? R : 0);
     __shared__ double pt[PE ? PTN * 16 : 1];
     __shared__ uint8_t pfl[PE ? J * R * 16 : 1];
+    __shared__ int pcol[MOV ? NPOS : 1];   // MOV: the position columns' indices in a state row
     // PAT: level tables [L + 2, R] packed [k * R + r] (row 0 main, 1..L the pattern's levels, L + 1 side lobe), 1 / width
     constexpr int LVN = (PAT && !PE) ? MAXLV * R : 1;
     __shared__ double lv_GaPs[LVN], lv_pd_no[LVN], lv_gr[LVN], lv_invw[(PAT && !PE) ? R : 1];
@@ -232,7 +263,13 @@ __global__ void __launch_bounds__(256) agent_env_episode_scan_kernel(const DevTa
     }
     const float b2 = io.b2[0];
     // env tables -> LDS
-    if constexpr (PE) {
+    if constexpr (MOV) {   // (the frame's rows are staged at the top of every step)
+        if (tid < NPOS) pcol[tid] = io.position_columns[tid];
+        if (tid == 0) {
+            tab.rp_min = tb->rp_min; tab.rp_max = tb->rp_max; tab.pd_A = tb->pd_A; tab.pd_c1 = tb->pd_c1;
+            tab.pd_denB = tb->pd_denB; tab.episode_limit = tb->episode_limit;
+        }
+    } else if constexpr (PE) {
         // thread -> (column tid & 15 = env of the workgroup, rows tid >> 4, + 16, ...): one env column per thread, so the
         // tile arithmetic is done once; sixteen consecutive envs of a row are 128 contiguous bytes (a tile boundary aside)
         const int c = tid & 15;
@@ -321,6 +358,7 @@ __global__ void __launch_bounds__(256) agent_env_episode_scan_kernel(const DevTa
         s_bits |= (io.track[ee * io.k_se + (int64_t)r * io.k_sx] != 0) ? (1u << r) : 0u;
     }
     int32_t step_ctr = io.step[ee];
+    const int32_t step0 = step_ctr;   // MOV: env (lane & 15)'s counter at entry, in every wave
     const uint32_t episode = io.episode ? (uint32_t)io.episode[ee] : 0u;
     float rsum[3] = {0.0f, 0.0f, 0.0f};
     if (io.rdpj_sum) {
@@ -335,6 +373,11 @@ __global__ void __launch_bounds__(256) agent_env_episode_scan_kernel(const DevTa
         }
     }
     __syncthreads();
+    if constexpr (MOV) {   // the first step's position columns of the observation tile, from the table like every later step's
+        const int k = step0 < io.n_frames ? step0 : io.n_frames;
+        for (int i = tid; i < 16 * NPOS; i += 256) Ol[er * OLD + pcol[i >> 4]] = io.positions[(int64_t)k * NPOS + (i >> 4)];
+        __syncthreads();
+    }
     const PdConsts pdk = pd_consts(tab.pd_A, tab.pd_c1, tab.pd_denB);
     // table reads of the env half: the shared LDS struct, or (PE) this lane's column er of the per-env block
 #define ES_TAB(name, ROW, member)                                     \
@@ -365,16 +408,33 @@ __global__ void __launch_bounds__(256) agent_env_episode_scan_kernel(const DevTa
     enum { PP_GAPS = 0, PP_SNR_NO, PP_PD_NO, PP_GR };
     const double* __restrict__ pp_lane = nullptr;
     int64_t pps = 0;
-    if constexpr (PAT && PE) {
+    const double* mv_pp = nullptr;   // MOV: frame f's row of pattern_frames (set in S5)
+    if constexpr (PAT && PE && !MOV) {
         const bool tiled = io.pe_tile > 0;
         const int64_t tl = tiled ? ee / io.pe_tile : 0;
         pps = tiled ? (int64_t)io.pe_tile : io.pp_stride;
         pp_lane = io.pp_tables + tl * (R + 4 * (int64_t)(pat_L + 2) * R) * pps + (tiled ? ee - tl * io.pe_tile : ee);
     }
-    auto pp_row = [&](int lt, int k, int r) -> double { return pp_lane[(int64_t)(R + (lt * (pat_L + 2) + k) * R + r) * pps]; };
+    auto pp_row = [&](int lt, int k, int r) -> double {
+        if constexpr (MOV) return mv_pp[R + (lt * (pat_L + 2) + k) * R + r];
+        else return pp_lane[(int64_t)(R + (lt * (pat_L + 2) + k) * R + r) * pps];
+    };
 
     for (int t = 0; t < T; ++t) {
         const int cur = t & 1, nxt = cur ^ 1;
+        if constexpr (MOV) {
+            // frame f of env column (tid & 15) -> the [row][16] block and the flag bytes, in place (read next in S5)
+            const int64_t f = (step0 + t < io.n_frames ? step0 + t : io.n_frames - 1);
+            const double* __restrict__ pe = io.frames + f * PR::NPE;
+            const double* __restrict__ sp = io.scan_frames + f * PR::NSP;
+            for (int row = tid >> 4; row < PR::INVW; row += 16)
+                pt[row * 16 + er] = row < PR::NPE ? pe[row] : sp[PR::sp_src(row - PR::NPE)];
+            if ((tid >> 4) < J * R) pfl[(tid >> 4) * 16 + er] = io.frame_flags[f * (J * R) + (tid >> 4)];
+            if constexpr (PAT) {   // inv_width: the first R rows of the frame's pattern row
+                if (tid < 16 * R)
+                    pt[(PR::INVW + (tid >> 4)) * 16 + er] = io.pattern_frames[f * (R + 4 * (int64_t)(pat_L + 2) * R) + (tid >> 4)];
+            }
+        }
         // ---- (S1) this step's observation: theta_a columns of the staging rows; first layers ----
         for (int i = tid; i < 16 * R * (J + 1); i += 256) {
             const int row = i & 15, rest = i >> 4;
@@ -386,6 +446,20 @@ __global__ void __launch_bounds__(256) agent_env_episode_scan_kernel(const DevTa
             if (live) {
                 if (jj == J) io.st_state[((int64_t)t * E + e) * S + c] = v;
                 else io.st_obs[(((int64_t)t * E + e) * J + jj) * S + c] = v;
+            }
+        }
+        if constexpr (MOV) {   // position columns of this step's staging rows, from the observation tile
+            for (int i = tid; i < 16 * NPOS * (J + 1); i += 256) {
+                const int row = i & 15, rest = i >> 4;
+                const int p = rest % NPOS, jj = rest / NPOS;      // jj == J: the state row
+                bool live;
+                const int64_t e = env_of(row, live);
+                const int c = pcol[p];
+                const float v = Ol[row * OLD + c];
+                if (live) {
+                    if (jj == J) io.st_state[((int64_t)t * E + e) * S + c] = v;
+                    else io.st_obs[(((int64_t)t * E + e) * J + jj) * S + c] = v;
+                }
             }
         }
         {
@@ -600,6 +674,8 @@ __global__ void __launch_bounds__(256) agent_env_episode_scan_kernel(const DevTa
         if (wave == 0) {
             constexpr int NP = R + J, NBLK = (NP + 3) / 4;
             const uint32_t step_before = (uint32_t)step_ctr;
+            if constexpr (MOV && PAT)   // the level rows of this step's frame (wave 0's counter is step0 + t here)
+                mv_pp = io.pattern_frames + (int64_t)(step_ctr < io.n_frames ? step_ctr : io.n_frames - 1) * (R + 4 * (int64_t)(pat_L + 2) * R);
             uint32_t rw[NBLK * 4];
 #pragma unroll
             for (int b = 0; b < NBLK; ++b) {
@@ -746,6 +822,10 @@ __global__ void __launch_bounds__(256) agent_env_episode_scan_kernel(const DevTa
                     io.terminated[(int64_t)t * E + ee] = (step_ctr >= tab.episode_limit) ? 1 : 0;
                 }
             }
+        } else if constexpr (MOV) {
+            // waves 1 - 3: the position columns of step t + 1's observation (row = tid & 15: the env whose step0 the thread holds)
+            const int k = step0 + t + 1 < io.n_frames ? step0 + t + 1 : io.n_frames;
+            for (int i = tid - 64; i < 16 * NPOS; i += 192) Ol[er * OLD + pcol[i >> 4]] = io.positions[(int64_t)k * NPOS + (i >> 4)];
         }
         __syncthreads();
     }
@@ -761,6 +841,9 @@ __global__ void __launch_bounds__(256) agent_env_episode_scan_kernel(const DevTa
                     double v;
                     if constexpr (PAT) {
                         v = pp_row(PP_SNR_NO, (int)((lv_last >> (4 * r)) & 15u), r);
+                    } else if constexpr (MOV) {   // the last step's frame: its snr_no | snr_no_side row
+                        const int64_t fl = step_ctr - 1 < io.n_frames ? step_ctr - 1 : io.n_frames - 1;
+                        v = io.scan_frames[fl * PR::NSP + (((in_t_last >> r) & 1u) ? 6 : 7) * R + r];
                     } else {
                         const bool tiled = io.pe_tile > 0;
                         const int64_t tl = tiled ? ee / io.pe_tile : 0;
@@ -779,6 +862,11 @@ __global__ void __launch_bounds__(256) agent_env_episode_scan_kernel(const DevTa
                     io.scan.snr_no[ee * io.scan.sn_se + (int64_t)r * io.scan.sn_sx] =
                         (float)(((in_t_last >> r) & 1u) ? tab.snr_no[r] : tab.snr_no_side[r]);
             }
+        }
+        if constexpr (MOV) {   // the positions the next step's agents see
+            const int k = step_ctr < io.n_frames ? step_ctr : io.n_frames;
+#pragma unroll
+            for (int p = 0; p < NPOS; ++p) io.scan.state[ee * io.scan.st_se + pcol[p]] = io.positions[(int64_t)k * NPOS + p];
         }
         io.step[ee] = step_ctr;
         if (io.rdpj_sum) {
@@ -891,5 +979,56 @@ extern "C" int macjd_agent_env_episode_scan_pe(const macjd_scenario* s, const ma
     else hipLaunchKernelGGL((agent_env_episode_scan_kernel<2, 2, 5, 3, false, true, EpScanPeIO>), grid, block, 0, st, s->dev, k);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_agent_env_episode_scan_pe: %s", hipGetErrorString(err));
+    return MACJD_OK;
+}
+
+extern "C" int macjd_agent_env_episode_moving_scan_supported(int32_t J, int32_t R, int32_t H, int32_t A) {
+    return macjd_agent_env_episode_scan_supported(J, R, H, A);
+}
+
+// The closed-loop launch on a moving scanning scenario's frame tables (include/macjd_nets.h,
+// macjd_agent_env_episode_moving_scan_io); its argument errors mirror macjd_env_step_moving_scan's, and all of them return
+// before any launch
+extern "C" int macjd_agent_env_episode_moving_scan(const macjd_scenario* s, const macjd_agent_env_episode_moving_scan_io* mio,
+                                                   void* hip_stream) {
+    using namespace macjd;
+    const char* me = "macjd_agent_env_episode_moving_scan";
+    if (mio && mio->base.pe_tables) return set_err(MACJD_EINVAL, "%s: base.pe_tables must be NULL (the frames are the tables)", me);
+    const int rc = episode_scan_check(s, mio ? &mio->base : nullptr, me, false);
+    if (rc != MACJD_OK) return rc;
+    const macjd_agent_env_episode_scan_io* io = &mio->base;
+    const macjd_motion_io* mo = &mio->motion;
+    const macjd_motion_scan_io* ms = &mio->motion_scan;
+    if (!mo->frames || !mo->frame_flags || !mo->positions || !mo->position_columns || !mo->state)
+        return set_err(MACJD_EINVAL, "%s: frames / frame_flags / positions / position_columns / state is NULL", me);
+    if (!ms->scan_frames) return set_err(MACJD_EINVAL, "%s: NULL scan_frames", me);
+    if (mo->n_frames < 1) return set_err(MACJD_EINVAL, "%s: n_frames < 1", me);
+    if (mo->n_frames != s->host.episode_limit) return set_err(MACJD_EINVAL, "%s: n_frames must equal the scenario's episode_limit", me);
+    if (mo->n_pos != 2 * io->R + 2 * io->J) return set_err(MACJD_EINVAL, "%s: n_pos must equal 2R + 2J", me);
+    if (mo->snr_no) return set_err(MACJD_EINVAL, "%s: motion.snr_no must be NULL (the per-step value travels in base.scan.snr_no)", me);
+    if (mo->state != io->scan.state || mo->st_se != io->scan.st_se)
+        return set_err(MACJD_EINVAL, "%s: base.scan.state and motion.state must be the same rows with the same row stride", me);
+    if (ms->n_levels < 0 || ms->n_levels > MACJD_MAX_PATTERN_LEVELS)
+        return set_err(MACJD_EINVAL, "%s: n_levels outside 0..MACJD_MAX_PATTERN_LEVELS", me);
+    if (s->host.pat_levels > 0 && s->host.pat_levels != ms->n_levels)
+        return set_err(MACJD_EINVAL, "%s: n_levels differs from the pattern levels of the scenario handle", me);
+    if ((ms->pattern_frames != nullptr) != (ms->n_levels > 0))
+        return set_err(MACJD_EINVAL, "%s: pattern_frames and n_levels > 0 go together (both or neither)", me);
+    if (io->n_envs == 0) return MACJD_OK;
+    const bool pat = ms->pattern_frames != nullptr;
+    EpScanMovIO k{};
+    static_cast<macjd_agent_env_episode_scan_io&>(k) = *io;
+    k.frames = mo->frames; k.frame_flags = mo->frame_flags; k.scan_frames = ms->scan_frames; k.pattern_frames = ms->pattern_frames;
+    k.positions = mo->positions; k.position_columns = mo->position_columns;
+    k.n_frames = mo->n_frames; k.pat_levels = pat ? ms->n_levels : 0;
+    const dim3 grid((unsigned)((io->n_envs + 15) / 16)), block(256);
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (pat) {
+        if (io->J == 3) hipLaunchKernelGGL((agent_env_episode_scan_kernel<3, 4, 9, 3, true, true, EpScanMovIO>), grid, block, 0, st, s->dev, k);
+        else hipLaunchKernelGGL((agent_env_episode_scan_kernel<2, 2, 5, 3, true, true, EpScanMovIO>), grid, block, 0, st, s->dev, k);
+    } else if (io->J == 3) hipLaunchKernelGGL((agent_env_episode_scan_kernel<3, 4, 9, 3, false, true, EpScanMovIO>), grid, block, 0, st, s->dev, k);
+    else hipLaunchKernelGGL((agent_env_episode_scan_kernel<2, 2, 5, 3, false, true, EpScanMovIO>), grid, block, 0, st, s->dev, k);
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_agent_env_episode_moving_scan: %s", hipGetErrorString(err));
     return MACJD_OK;
 }

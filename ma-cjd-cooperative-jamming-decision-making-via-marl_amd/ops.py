@@ -531,6 +531,32 @@ def agent_env_episode_scan_pe(agent, env_args: dict, n_envs: int, n_agents: int,
     del keep
 
 
+def agent_env_episode_moving_scan_supported(J: int, R: int, H: int, A: int) -> bool:
+    return bool(_native.load().macjd_agent_env_episode_moving_scan_supported(int(J), int(R), int(H), int(A)))
+
+
+def agent_env_episode_moving_scan(agent, env_args: dict, n_envs: int, n_agents: int, T: int, avail, eps_sched, greedy_only: bool,
+                                  seed: int, counter_base, stage: dict, rdpj_sum=None, h0=None, h_final=None):
+    """``agent_env_episode_scan`` on a moving scenario under scanning radars (include/macjd_nets.h,
+    macjd_agent_env_episode_moving_scan_io): the same launch with env e's step t on frame min(step[e] + t, F - 1) of the frame
+    tables and the observation's position columns following the frames.  ``env_args`` is what
+    ``BatchedElectromagneticEnvironment.episode_moving_scan_args()`` hands over: the shared call's entries plus the motion
+    and motion-scan blocks."""
+    lib = _native.load()
+    mio = _native.AgentEnvEpisodeMovingScanIO()
+    keep, W1 = _fill_episode_scan_io(mio.base, agent, env_args, n_envs, n_agents, T, avail, eps_sched, greedy_only, seed,
+                                     counter_base, stage, rdpj_sum, h0, h_final)
+    ctypes.memmove(ctypes.addressof(mio) + _native.AgentEnvEpisodeMovingScanIO.motion.offset, ctypes.addressof(env_args["motion_io"]),
+                   ctypes.sizeof(_native.MotionIO))
+    ctypes.memmove(ctypes.addressof(mio) + _native.AgentEnvEpisodeMovingScanIO.motion_scan.offset,
+                   ctypes.addressof(env_args["motion_scan_io"]), ctypes.sizeof(_native.MotionScanIO))
+    mio.motion.snr_no = None   # the per-step value travels in the beam block's snr_no
+    with torch.cuda.device(W1.device):
+        _native.check(lib.macjd_agent_env_episode_moving_scan(env_args["handle"], ctypes.byref(mio), _stream(W1)),
+                      "macjd_agent_env_episode_moving_scan")
+    del keep
+
+
 def gru_sequence_reference(gi: torch.Tensor, w_hh: torch.Tensor, b_hh: torch.Tensor,
                            h0: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Step-by-step GRU recurrence with stock torch ops (host tensors / numerics tests).

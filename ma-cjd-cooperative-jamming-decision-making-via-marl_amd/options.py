@@ -40,6 +40,8 @@ for normal operation.
                                          (shared scenario tables and per-env scanning scenario batches, pattern or not)
     MACJD_MOVING_EPISODE_ROLLOUT 0 | 1   moving scenarios: step-by-step rollout / one launch for the per-frame agent inputs, the
                                          agent's steps of an episode batch as one launch, the env's steps as another
+    MACJD_CLOSED_LOOP_MOVING_ROLLOUT 0 | 1   moving scenarios under scanning radars: step-by-step rollout / agent and env of an
+                                         episode batch in one launch on the frame tables
 """
 from __future__ import annotations
 
@@ -50,7 +52,7 @@ _DEFAULTS = {
     "LEARNER_STATIC_OBS": "1", "ACTOR_IN_SCAN": "1", "DEVICE_SAMPLER": "1", "LN_IN_SQNORM": "1", "NORM_IN_REDUCE": "1", "WGRAD_OUTER": "1",
     "QHEAD_TAKEN": "1", "QHEAD_DOUBLE_Q": "1", "QHEAD_DOUBLE_Q_H128": "0", "PAIRED_HEADS": "1", "MIXER_TRAIN": "1", "MIXER_STATIC_STATE": "1", "WGRAD_IN_TRAIN": "1", "GRAPHED_ALLREDUCE": "0",
     "PREFETCH_LAUNCH": "1", "PREFETCH_AHEAD": "2",
-    "CLOSED_LOOP_ROLLOUT": "0", "MOVING_EPISODE_ROLLOUT": "0",
+    "CLOSED_LOOP_ROLLOUT": "0", "MOVING_EPISODE_ROLLOUT": "0", "CLOSED_LOOP_MOVING_ROLLOUT": "0",
 }
 _values = None
 

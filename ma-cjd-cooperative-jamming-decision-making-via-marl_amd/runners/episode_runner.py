@@ -351,6 +351,9 @@ class BatchedEpisodeRunner:
         if device_schedule and self.moving_episode_rollout and self.moving_rollout_available():
             self._moving_launches(T)      # moving scenario: per-frame inputs, the agent's steps, the env's steps
             return
+        if device_schedule and self.closed_loop_moving_rollout and self.closed_loop_moving_available():
+            self._closed_loop_launch(T)   # moving scenario under scanning radars: one launch on the frame tables
+            return
         for t in range(T):
             if device_schedule:
                 self.mac.device_schedule = (self._eps_sched[t:t + 1], self._ctr_base, t + 1)
@@ -474,12 +477,18 @@ class BatchedEpisodeRunner:
         scenario per env (``episode_scan_pe_args``, ``ops.agent_env_episode_scan_pe_supported``)."""
         return self._closed_loop_conditions(per_env=True)
 
-    def _closed_loop_conditions(self, per_env: bool) -> bool:
+    def closed_loop_moving_available(self) -> bool:
+        """``closed_loop_available`` for a moving scenario under scanning radars: the env both moves and scans on shared
+        frame tables (no scenario batch), ``kernel_flags == 0``, the stock RNNAgent on a HIP device at a size the closed-loop
+        kernel covers (``episode_moving_scan_args``, ``ops.agent_env_episode_moving_scan_supported``)."""
+        return self._closed_loop_conditions(per_env=False, moving=True)
+
+    def _closed_loop_conditions(self, per_env: bool, moving: bool = False) -> bool:
         env = self.env
-        args_name = "episode_scan_pe_args" if per_env else "episode_scan_args"
+        args_name = "episode_moving_scan_args" if moving else ("episode_scan_pe_args" if per_env else "episode_scan_args")
         if self.device.type != "cuda" or not hasattr(env, args_name) or not getattr(env.scenario, "scanning", False):
             return False
-        if getattr(env.scenario, "moving", False):   # moving entities under scanning beams: the step loop only
+        if bool(getattr(env.scenario, "moving", False)) != moving:   # moving entities under scanning beams: their own launch
             return False
         if (getattr(env, "scenario_batch", None) is not None) != per_env or getattr(env, "kernel_flags", 0) != 0:
             return False
@@ -488,6 +497,8 @@ class BatchedEpisodeRunner:
             return False
         from .. import ops
         supported = ops.agent_env_episode_scan_pe_supported if per_env else ops.agent_env_episode_scan_supported
+        if moving:
+            supported = ops.agent_env_episode_moving_scan_supported
         return (getattr(agent, "actor_hidden_dim", 0) == 128 and agent.input_shape == env.state_dim and env.state_dim <= 48
                 and supported(self.n_agents, env.num_radars, agent.rnn_hidden_dim, agent.n_actions))
 
@@ -497,6 +508,17 @@ class BatchedEpisodeRunner:
         if not self.closed_loop_pe_available():
             raise RuntimeError("rollout_closed_loop_pe: not available for this environment / agent (closed_loop_pe_available())")
         self._rollout_closed_loop(test_mode, n_steps, "rollout_closed_loop_pe")
+
+    closed_loop_moving_rollout = _OptionSwitch("CLOSED_LOOP_MOVING_ROLLOUT")   # default off (MACJD_CLOSED_LOOP_MOVING_ROLLOUT=1)
+
+    def rollout_closed_loop_moving(self, test_mode=False, n_steps=None):
+        """``rollout_closed_loop`` on a moving scenario under scanning radars (``ops.agent_env_episode_moving_scan``): one
+        launch in which env e runs step t on frame min(step[e] + t, F - 1) and the observation's position columns follow the
+        frames; its env half is bit-identical to the moving scanning step kernels' all-float64 form."""
+        if not self.closed_loop_moving_available():
+            raise RuntimeError("rollout_closed_loop_moving: not available for this environment / agent "
+                               "(closed_loop_moving_available())")
+        self._rollout_closed_loop(test_mode, n_steps, "rollout_closed_loop_moving")
 
     def rollout_closed_loop(self, test_mode=False, n_steps=None):
         """One episode batch (or its first ``n_steps`` steps) of a scanning scenario in ONE launch
@@ -527,11 +549,14 @@ class BatchedEpisodeRunner:
 
     def _closed_loop_launch(self, n, test_mode=False):
         """The launch of ``rollout_closed_loop`` (behind ``begin_episodes``).  The kernel writes only the theta_a columns
-        of the state / obs staging rows; their static columns and the availability rows never change and are filled once."""
+        (a moving scenario: and the position columns) of the state / obs staging rows; their other columns and the
+        availability rows never change and are filled once."""
         from .. import ops
         if not self._static_filled:
             self._fill_static()   # (a per-env batch: each env's own state row)
-        if getattr(self.env, "scenario_batch", None) is not None:   # per-env scenario batch: every env reads its own tables
+        if getattr(self.env.scenario, "moving", False):   # moving under scanning radars: the frame tables
+            launch, env_args = ops.agent_env_episode_moving_scan, self.env.episode_moving_scan_args()
+        elif getattr(self.env, "scenario_batch", None) is not None:   # per-env scenario batch: every env reads its own tables
             launch, env_args = ops.agent_env_episode_scan_pe, self.env.episode_scan_pe_args()
         else:
             launch, env_args = ops.agent_env_episode_scan, self.env.episode_scan_args()
@@ -626,6 +651,8 @@ class BatchedEpisodeRunner:
             self.rollout_closed_loop_pe(test_mode=test_mode)
         elif self.moving_episode_rollout and self.moving_rollout_available():
             self.rollout_moving(test_mode=test_mode)
+        elif self.closed_loop_moving_rollout and self.closed_loop_moving_available():
+            self.rollout_closed_loop_moving(test_mode=test_mode)
         elif getattr(self, "_graph", None) is not None and not test_mode:
             self.rollout_graphed()
         else:

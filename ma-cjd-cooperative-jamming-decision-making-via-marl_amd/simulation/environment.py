@@ -525,6 +525,18 @@ class BatchedElectromagneticEnvironment:
                 "pe_tables": self._pe_tables.data_ptr(), "pe_flags": self._pe_flags.data_ptr(), "pe_tile": self._pe_tile,
                 "n_envs": self.batch_envs, "scan_pe_io": self._scan_pe_io, "scan_pe_pattern_io": self._scan_pe_pattern_io}
 
+    def episode_moving_scan_args(self) -> Dict[str, Any]:
+        """What the closed-loop episode launch on a moving scanning scenario (``ops.agent_env_episode_moving_scan``) needs:
+        the entries of ``episode_scan_args`` plus the motion block (frame tables, positions and their state columns) and the
+        motion-scan block (per-frame beam tables, under a stepped pattern the per-frame level tables)."""
+        if self._motion_io is None or self._motion_scan_io is None:
+            raise RuntimeError("episode_moving_scan_args: needs a scenario that both moves and scans (environment_params.motion "
+                               "and environment_params.radar_scan); episode_scan_args serves a static scanning scenario")
+        self._scan_io.snr_no = self._snr_no_step.data_ptr()   # (a step with want_info=False clears it)
+        return {"handle": self._handle.ptr, "scan_io": self._scan_io, "motion_io": self._motion_io,
+                "motion_scan_io": self._motion_scan_io, "track": self._track, "step": self._step, "episode": self._episode,
+                "seed": self.seed, "env_offset": self.env_offset, "n_radars": self.num_radars, "pe_tables": None}
+
     MANY_STEP_MOVING_SIZES = ((2, 2), (3, 4), (6, 8))   # (J, R) of csrc/macjd_env_motion.hip, motion_size_compiled
 
     def step_many_has_production_form(self) -> bool:
