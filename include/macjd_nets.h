@@ -893,7 +893,9 @@ typedef struct macjd_doubleq_io {
     float* out;              /* [n] */
     int64_t* argmax_out;     /* optional [n] */
     /* optional row map of P_e / P_t: p_group > 0 -> row n reads P row (n / p_group) * p_inner + n % p_inner (one actor
-       row per SEQUENCE (b, j) for rows n = (b, t, j): p_group = T * J, p_inner = J) */
+       row per SEQUENCE (b, j) for rows n = (b, t, j): p_group = T * J, p_inner = J).  p_group = 0: no map, p_inner is
+       not read.  MACJD_EINVAL, before any launch, for p_group < 0 and for p_group > 0 with p_inner < 1 or
+       p_inner > p_group (macjd_qhead_double_q and macjd_qheads_pair alike). */
     int64_t p_group, p_inner;
 } macjd_doubleq_io;
 

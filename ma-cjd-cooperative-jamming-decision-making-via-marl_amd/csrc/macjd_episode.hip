@@ -697,6 +697,9 @@ static int doubleq_check(const macjd_doubleq_io* io) {
     if (io->he_ld < io->H || io->ht_ld < io->H || io->pe_ld < io->A || io->pt_ld < io->A || io->w1e_ld < io->H + io->A + 1 ||
         io->w1t_ld < io->H + io->A + 1)
         return set_err(MACJD_EINVAL, "%s", "macjd_qhead_double_q: row stride smaller than the row");
+    // the row map divides by p_group and takes the remainder by p_inner on the device: both checked here
+    if (io->p_group < 0 || (io->p_group > 0 && (io->p_inner < 1 || io->p_inner > io->p_group)))
+        return set_err(MACJD_EINVAL, "%s", "macjd_qhead_double_q: row map needs 1 <= p_inner <= p_group");
     return MACJD_OK;
 }
 
