@@ -313,6 +313,72 @@ typedef struct macjd_motion_scan_io {
     int32_t n_levels, reserved;     /* L, 0 without pattern_frames */
 } macjd_motion_scan_io;
 
+/*
+ * PER-ENV moving scenarios (opt-in): macjd_motion_io with every table per env — each env has its own trajectory, so its
+ * frame f is its own static scenario at p0_e + f (v_e dt).  The tables are the per-env tiled layout (macjd_step_io.pe_tile)
+ * with the frame index between tile and row; envs are grouped in tiles of `tile` consecutive envs, the last tile padded:
+ *   frames       float64 [n_tiles, F, MACJD_PE_ROWS(R,J), tile]: row t of frame f of env e at
+ *                frames[(((e / tile) * F + f) * MACJD_PE_ROWS + t) * tile + e % tile], rows in the order of pe_tables;
+ *   frame_flags  uint8   [n_tiles, F, J*R, tile]   (MACJD_JR_*), likewise;
+ *   frame_snr_no float64 [n_tiles, F, R, tile], optional (needed for snr_no), likewise;
+ *   positions    float32 [n_tiles, F + 1, n_pos, tile], likewise with F + 1 frames per tile.
+ * A wave whose envs are on one frame reads whole contiguous row pieces; envs on different frames (after individual resets)
+ * still read their own columns.  position_columns, n_frames, n_pos, state / st_se, snr_no and the clamps are macjd_motion_io's:
+ * the step runs on frame min(k, F - 1), positions come from frame min(k + 1, F).
+ */
+typedef struct macjd_motion_pe_io {
+    const double*  frames;
+    const uint8_t* frame_flags;
+    const double*  frame_snr_no;      /* optional unless snr_no is given */
+    const float*   positions;
+    const int32_t* position_columns;  /* int32 [n_pos], shared by the batch */
+    int32_t n_frames;                 /* F >= 1 */
+    int32_t n_pos;                    /* must equal 2R + 2J */
+    int32_t tile;                     /* >= 1: envs per tile */
+    int32_t reserved;
+    float*  state;    int64_t st_se;  /* as macjd_motion_io: the CALLER guarantees 0 <= column < st_se */
+    float*  snr_no;   int64_t sn_se, sn_sx;   /* optional [E,R]; single steps only */
+} macjd_motion_pe_io;
+
+/*
+ * The device frame compiler of per-env moving scenarios (macjd_motion_pe_compile): ONE launch, item (e, f) for f in 0..F
+ * writes frame f of env e into the four tables of macjd_motion_pe_io (f = F: the positions only).  Its input is one column
+ * per env, float64 [n_tiles, MACJD_MOTION_PE_IN_ROWS(R,J), tile] in the same tiled layout (row t of env e at
+ * in_tables[((e / tile) * MACJD_MOTION_PE_IN_ROWS + t) * tile + e % tile]), rows in the order
+ *   Pn[R] | D[R] | rd_pen[R] | gr[R] | echo_num[R] | r_loss[R] | r_latm[R] | Ga[R] |
+ *   pmin[J] | pmax[J] | gj[J] | j_loss[J] | j_latm[J] | bj_eff[J] |
+ *   tgt_p0[2] | tgt_vdt[2] | radar_p0[2R] | radar_vdt[2R] | jam_p0[2J] | jam_vdt[2J]      (x, y per entity)
+ * Pn, D, rd_pen, gr, pmin, pmax, gj are the env's distance-independent pe_tables rows and are copied through unchanged;
+ * echo_num = pt gt gr lambda^2 rcs as the host's scenario compiler forms it, r_loss / r_latm / Ga the radar's linear loss
+ * factors and pulse-compression gain; j_loss / j_latm the jammer's, bj_eff = max(1e-9, bj); p0 the float64 position at frame
+ * 0 and vdt the host's float(v[a]) * dt per axis.  in_weak is uint8 [n_tiles, J, tile]: 1 when the product
+ * 1e-9 * j_loss * j_latm * bj_eff is a Python float on the host (MACJD_JR_WEAK_DENOM's rule, which then depends on the
+ * distance only).  Arithmetic of an item, plain IEEE float64 in this order (no fused multiply-add), fd = (double)f:
+ *   position per axis  p = p0 + fd * vdt;  the positions table gets (float)p in state order (radars, then jammers);
+ *   radar r:  dx, dy to the target;  d = sqrt(dx*dx + dy*dy);  sd = max(d, 1e-6);  d4 = (sd*sd)*(sd*sd);
+ *             den = ((c0*d4)*r_loss)*r_latm, c0 = four_pi_cubed;  Ps = den <= 1e-18 ? 0 : echo_num/den;  GaPs = Ga*Ps;
+ *             snr_no = max(0, Pn > 1e-18 ? GaPs/Pn : 0);  pd_no = the all-float64 detection probability of the step
+ *             kernels (|denB| < 1e-9 -> 0, B > 700 -> 1, B < -700 -> 0 included);
+ *   jammer j, radar r:  d likewise;  !(d > 1e-6): denom = -1.0, flag = 0;  otherwise d2 = d*d, dsq = d2 > 1e-9 ? d2 : 1e-9,
+ *             denom = ((dsq*j_loss)*j_latm)*bj_eff, flag bit 0 = !(d2 > 1e-9) && in_weak[j].
+ * Lanes of the last tile's padding and bytes outside the tables are not written.
+ */
+#define MACJD_MOTION_PE_IN_ROWS(R, J) (12 * (R) + 10 * (J) + 4)
+typedef struct macjd_motion_pe_compile_desc {
+    int64_t n_envs;                /* E */
+    int32_t n_radars, n_jammers;   /* R, J */
+    int32_t n_frames;              /* F, 1..65534 */
+    int32_t tile;                  /* >= 1 */
+    double  four_pi_cubed;         /* (4 pi)^3 as the host evaluates it */
+    double  pd_A, pd_c1, pd_denB;  /* the Pd constants of macjd_scenario_desc */
+    const double*  in_tables;
+    const uint8_t* in_weak;
+    double*  frames;
+    uint8_t* frame_flags;
+    double*  frame_snr_no;         /* optional */
+    float*   positions;
+} macjd_motion_pe_compile_desc;
+
 /* library / device */
 int         macjd_abi_version(void);
 const char* macjd_last_error(void);
@@ -406,6 +472,21 @@ int macjd_env_step_many_moving(const macjd_scenario* s, const macjd_step_io* io,
    the envs with mask != 0 (all when mask == NULL) */
 int macjd_env_reset_moving(const macjd_scenario* s, int64_t n_envs, const macjd_motion_io* motion, const uint8_t* mask,
                            void* hip_stream);
+
+/* macjd_env_step_moving on PER-ENV frame tables (see macjd_motion_pe_io): env e runs frame f_e = min(step[e], F - 1) of its
+   OWN tables.  io->pe_tables must be NULL; the handle supplies R, J, episode_limit, the r_p bounds and the Pd constants.
+   Bit-identical to macjd_env_step on pe_tables whose column for env e holds env e's frame f_e, in the same (production or
+   general all-float64) form.  Sizes and variants as macjd_env_step_moving. */
+int macjd_env_step_moving_pe(const macjd_scenario* s, const macjd_step_io* io, const macjd_motion_pe_io* motion_pe,
+                             void* hip_stream);
+/* macjd_env_step_many_moving on per-env frame tables: same contract and restrictions; motion_pe->snr_no must be NULL. */
+int macjd_env_step_many_moving_pe(const macjd_scenario* s, const macjd_step_io* io, const macjd_motion_pe_io* motion_pe,
+                                  int32_t n_steps, int64_t t_stride, void* hip_stream);
+/* macjd_env_reset_moving on per-env frame tables: each masked env's own frame-0 positions into its state row */
+int macjd_env_reset_moving_pe(const macjd_scenario* s, int64_t n_envs, const macjd_motion_pe_io* motion_pe, const uint8_t* mask,
+                              void* hip_stream);
+/* the device frame compiler of per-env moving scenarios (see macjd_motion_pe_compile_desc): one launch, no handle */
+int macjd_motion_pe_compile(const macjd_motion_pe_compile_desc* desc, void* hip_stream);
 
 /* The env step of a moving scenario with scanning beams (see macjd_motion_scan_io); needs a scanning handle
    (macjd_scenario_set_scan).  A step whose counter is k before it runs the arithmetic, order, RNG slots and Philox keying of

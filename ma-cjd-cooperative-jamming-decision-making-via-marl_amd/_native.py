@@ -45,6 +45,7 @@ EXPORTS = [
     "macjd_prefetch_batches_supported", "macjd_prefetch_batches",
     "macjd_env_step_moving", "macjd_env_step_many_moving", "macjd_env_reset_moving", "macjd_env_step_moving_scan",
     "macjd_agent_episode_seq_supported", "macjd_agent_episode_seq",
+    "macjd_env_step_moving_pe", "macjd_env_step_many_moving_pe", "macjd_env_reset_moving_pe", "macjd_motion_pe_compile",
 ]
 
 
@@ -123,6 +124,30 @@ class MotionIO(ctypes.Structure):
         ("n_frames", ctypes.c_int32), ("n_pos", ctypes.c_int32),
         ("state", ctypes.c_void_p), ("st_se", ctypes.c_int64),
         ("snr_no", ctypes.c_void_p), ("sn_se", ctypes.c_int64), ("sn_sx", ctypes.c_int64),
+    ]
+
+
+class MotionPeIO(ctypes.Structure):
+    """ctypes mirror of ``macjd_motion_pe_io`` (include/macjd.h): the frame tables of a per-env moving scenario batch in the
+    tiled per-env layout (frame index between tile and row) and the state rows whose position columns the step rewrites."""
+    _fields_ = [
+        ("frames", ctypes.c_void_p), ("frame_flags", ctypes.c_void_p), ("frame_snr_no", ctypes.c_void_p),
+        ("positions", ctypes.c_void_p), ("position_columns", ctypes.c_void_p),
+        ("n_frames", ctypes.c_int32), ("n_pos", ctypes.c_int32), ("tile", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("state", ctypes.c_void_p), ("st_se", ctypes.c_int64),
+        ("snr_no", ctypes.c_void_p), ("sn_se", ctypes.c_int64), ("sn_sx", ctypes.c_int64),
+    ]
+
+
+class MotionPeCompileDesc(ctypes.Structure):
+    """ctypes mirror of ``macjd_motion_pe_compile_desc`` (include/macjd.h): the device frame compiler's arguments."""
+    _fields_ = [
+        ("n_envs", ctypes.c_int64), ("n_radars", ctypes.c_int32), ("n_jammers", ctypes.c_int32),
+        ("n_frames", ctypes.c_int32), ("tile", ctypes.c_int32),
+        ("four_pi_cubed", ctypes.c_double), ("pd_A", ctypes.c_double), ("pd_c1", ctypes.c_double), ("pd_denB", ctypes.c_double),
+        ("in_tables", ctypes.c_void_p), ("in_weak", ctypes.c_void_p),
+        ("frames", ctypes.c_void_p), ("frame_flags", ctypes.c_void_p), ("frame_snr_no", ctypes.c_void_p),
+        ("positions", ctypes.c_void_p),
     ]
 
 
@@ -526,6 +551,16 @@ def load() -> ctypes.CDLL:
     lib.macjd_env_reset_moving.restype = ctypes.c_int
     lib.macjd_env_reset_moving.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(MotionIO), ctypes.c_void_p,
                                            ctypes.c_void_p]
+    lib.macjd_env_step_moving_pe.restype = ctypes.c_int
+    lib.macjd_env_step_moving_pe.argtypes = [ctypes.c_void_p, ctypes.POINTER(StepIO), ctypes.POINTER(MotionPeIO), ctypes.c_void_p]
+    lib.macjd_env_step_many_moving_pe.restype = ctypes.c_int
+    lib.macjd_env_step_many_moving_pe.argtypes = [ctypes.c_void_p, ctypes.POINTER(StepIO), ctypes.POINTER(MotionPeIO),
+                                                  ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p]
+    lib.macjd_env_reset_moving_pe.restype = ctypes.c_int
+    lib.macjd_env_reset_moving_pe.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(MotionPeIO), ctypes.c_void_p,
+                                              ctypes.c_void_p]
+    lib.macjd_motion_pe_compile.restype = ctypes.c_int
+    lib.macjd_motion_pe_compile.argtypes = [ctypes.POINTER(MotionPeCompileDesc), ctypes.c_void_p]
     lib.macjd_env_step_moving_scan.restype = ctypes.c_int
     lib.macjd_env_step_moving_scan.argtypes = [ctypes.c_void_p, ctypes.POINTER(StepIO), ctypes.POINTER(MotionIO),
                                                ctypes.POINTER(ScanIO), ctypes.POINTER(MotionScanIO), ctypes.c_void_p]

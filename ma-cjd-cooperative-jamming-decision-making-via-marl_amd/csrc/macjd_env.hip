@@ -1075,6 +1075,109 @@ int macjd_env_reset_moving(const macjd_scenario* s, int64_t n_envs, const macjd_
     return launch_status(me);
 }
 
+// ---- per-env moving scenarios (include/macjd.h, macjd_motion_pe_io; kernels in macjd_env_motion_pe.hip) ----
+
+// The shared-frame block with the same members: validation, span checks and fill_motion serve both
+static macjd_motion_io motion_pe_as_motion(const macjd_motion_pe_io* mp) {
+    macjd_motion_io mo{};
+    mo.frames = mp->frames; mo.frame_flags = mp->frame_flags; mo.frame_snr_no = mp->frame_snr_no;
+    mo.positions = mp->positions; mo.position_columns = mp->position_columns;
+    mo.n_frames = mp->n_frames; mo.n_pos = mp->n_pos;
+    mo.state = mp->state; mo.st_se = mp->st_se;
+    mo.snr_no = mp->snr_no; mo.sn_se = mp->sn_se; mo.sn_sx = mp->sn_sx;
+    return mo;
+}
+
+static int validate_motion_pe(const macjd_scenario* s, const macjd_motion_pe_io* mp, macjd_motion_io* mo, const char* what) {
+    if (!s || !mp) return set_err(MACJD_EINVAL, "%s: NULL scenario / motion io", what);
+    *mo = motion_pe_as_motion(mp);
+    const int rc = validate_motion(s, mo, what);
+    if (rc != MACJD_OK) return rc;
+    if (mp->tile < 1) return set_err(MACJD_EINVAL, "%s: tile < 1", what);
+    return MACJD_OK;
+}
+
+// MOVING launches on per-env frame tables: always the lane kernel (include/macjd.h, macjd_env_step_moving_pe)
+static int launch_step_moving_pe(const macjd_scenario* s, const macjd_step_io* io, const macjd_motion_io* mo, int32_t tile,
+                                 hipStream_t stream, int32_t many_T, int64_t t_stride, const char* who) {
+    const int64_t E = io->n_envs * (many_T > 0 ? many_T : 1);   // work items of the launch
+    const int J = s->host.J, R = s->host.R;
+    if (many_T > 65535) return set_err(MACJD_EINVAL, "%s: at most 65535 steps per launch", who);
+    const LaneGrid lg = lane_grid(E);
+    const dim3 gf((unsigned)(many_T > 0 ? (io->n_envs + lg.block - 1) / lg.block : lg.blocks), (unsigned)(many_T > 0 ? many_T : 1));
+    const dim3 g(lg.strided), b(lg.block);
+    const bool fast = macjd::motion_size_compiled(J, R) && production_io(io, J, R, lg.blocks, many_T, t_stride) &&
+                      motion_spans_ok(mo, io->n_envs, R) && io->n_envs < ((int64_t)1 << 31);
+    if (fast) {
+        macjd::MotionPeStepIO<macjd::FastStepIO> f{};
+        fill_fast(f, io, many_T, t_stride);
+        fill_motion(f, mo);
+        f.mv_tile = tile;
+        (void)macjd::launch_motion_pe_fast(J, R, gf, b, stream, s->dev, f);
+    } else {
+        if (many_T > 0)
+            return set_err(MACJD_EUNSUPPORTED, "%s: production configuration at a compiled size (2j/2r, 3j/4r, 6j/8r) only: Philox "
+                           "uniforms, float32 actions, no float64 diagnostics, offsets below 2^32 bytes", who);
+        macjd::MotionPeStepIO<macjd_step_io> w{};
+        static_cast<macjd_step_io&>(w) = *io;
+        fill_motion(w, mo);
+        w.mv_tile = tile;
+        macjd::launch_motion_pe_general(J, R, g, b, stream, s->dev, w);
+    }
+    return launch_status(who);
+}
+
+int macjd_env_step_moving_pe(const macjd_scenario* s, const macjd_step_io* io, const macjd_motion_pe_io* motion_pe, void* hip_stream) {
+    const char* me = "macjd_env_step_moving_pe";
+    int rc = validate_io(s, io);
+    if (rc != MACJD_OK) return rc;
+    macjd_motion_io mo;
+    rc = validate_motion_pe(s, motion_pe, &mo, me);
+    if (rc != MACJD_OK) return rc;
+    if (io->pe_tables) return set_err(MACJD_EINVAL, "%s: io->pe_tables must be NULL (the frames are the tables)", me);
+    if (io->flags & MACJD_STEP_SLOT_KERNEL)
+        return set_err(MACJD_EUNSUPPORTED, "%s: the (env x slot) kernel has no moving variant (one lane per env only)", me);
+    if (io->n_envs == 0) return MACJD_OK;
+    return launch_step_moving_pe(s, io, &mo, motion_pe->tile, (hipStream_t)hip_stream, 0, 0, me);
+}
+
+int macjd_env_step_many_moving_pe(const macjd_scenario* s, const macjd_step_io* io, const macjd_motion_pe_io* motion_pe,
+                                  int32_t n_steps, int64_t t_stride, void* hip_stream) {
+    const char* me = "macjd_env_step_many_moving_pe";
+    int rc = validate_io(s, io);
+    if (rc != MACJD_OK) return rc;
+    macjd_motion_io mo;
+    rc = validate_motion_pe(s, motion_pe, &mo, me);
+    if (rc != MACJD_OK) return rc;
+    if (io->pe_tables) return set_err(MACJD_EINVAL, "%s: io->pe_tables must be NULL (the frames are the tables)", me);
+    if (n_steps < 1 || t_stride < 0) return set_err(MACJD_EINVAL, "%s: bad n_steps / t_stride", me);
+    if (io->pd || io->snr_with || mo.snr_no) return set_err(MACJD_EINVAL, "%s: pd / snr_with / snr_no are not written (pass NULL)", me);
+    if (io->r_dpj_sum && !io->r_dpj) return set_err(MACJD_EINVAL, "%s: r_dpj_sum needs the per-step r_dpj buffer", me);
+    if (io->n_envs == 0) return MACJD_OK;
+    rc = launch_step_moving_pe(s, io, &mo, motion_pe->tile, (hipStream_t)hip_stream, n_steps, t_stride, me);
+    if (rc != MACJD_OK) return rc;
+    int64_t grid = (io->n_envs * 3 + 255) / 256;
+    if (grid > 4096) grid = 4096;
+    hipLaunchKernelGGL(macjd::env_advance_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)hip_stream, io->n_envs,
+                       n_steps, io->step, io->r_dpj, io->r_dpj_sum);
+    return launch_status(me);
+}
+
+int macjd_env_reset_moving_pe(const macjd_scenario* s, int64_t n_envs, const macjd_motion_pe_io* motion_pe, const uint8_t* mask,
+                              void* hip_stream) {
+    const char* me = "macjd_env_reset_moving_pe";
+    if (n_envs < 0) return set_err(MACJD_EINVAL, "%s: bad argument", me);
+    macjd_motion_io mo;
+    const int rc = validate_motion_pe(s, motion_pe, &mo, me);
+    if (rc != MACJD_OK) return rc;
+    if (n_envs == 0) return MACJD_OK;
+    int64_t grid = (n_envs + 255) / 256;
+    if (grid > 4096) grid = 4096;
+    macjd::launch_motion_pe_reset(dim3((unsigned)grid), dim3(256), (hipStream_t)hip_stream, n_envs, mo.n_pos, mo.n_frames,
+                                  motion_pe->tile, mo.positions, mo.position_columns, mo.state, mo.st_se, mask);
+    return launch_status(me);
+}
+
 // ---- moving scenarios with scanning beams (include/macjd.h, macjd_motion_scan_io; kernels in macjd_env_motion_scan.hip) ----
 
 // Always the lane kernel on the frame tables: the production variant or the general one at the compiled sizes, the

@@ -1,5 +1,5 @@
 // The one-lane-per-env step kernel (env_step_kernel) with its argument blocks: a header, so that a second translation unit
-// (macjd_env_scan_pe.hip, macjd_env_motion_scan.hip) can instantiate it with another unrolling directive on its size-bounded
+// (macjd_env_scan_pe.hip, macjd_env_motion.hip, macjd_env_motion_pe.hip, macjd_env_motion_scan.hip) can instantiate it with another unrolling directive on its size-bounded
 // loops.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -154,8 +154,18 @@ struct MotionScanStepIO : ScanBase {
     static constexpr float* mv_snr_no = nullptr;
     static constexpr int64_t mv_sn_se = 0, mv_sn_sx = 0;
 };
+// Argument block of a MOVING launch on PER-ENV frame tables (include/macjd.h, macjd_motion_pe_io): MotionStepIO's members with
+// every table in the tiled per-env layout, the frame index between tile and row; mv_tile = envs per tile.  A type of its own:
+// the shared-frame instantiations keep their argument block and code.
+template <class Base>
+struct MotionPeStepIO : MotionStepIO<Base> {
+    int32_t mv_tile, mv_reserved;
+};
 template <class IO> struct io_moves : std::false_type {};
 template <class Base> struct io_moves<MotionStepIO<Base>> : std::true_type {};
+template <class Base> struct io_moves<MotionPeStepIO<Base>> : std::true_type {};
+template <class IO> struct io_moves_pe : std::false_type {};
+template <class Base> struct io_moves_pe<MotionPeStepIO<Base>> : std::true_type {};
 template <class ScanBase> struct io_moves<MotionScanStepIO<ScanBase>> : std::true_type {};
 
 // Per-lane pattern state of an env-step: the number of levels and the target's level at each radar, four bits per radar
@@ -230,6 +240,9 @@ __global__ void __launch_bounds__(256) env_step_kernel(const DevTables* __restri
     // pattern rows, come from frame f of per-frame tables in the same way; the tail writes the theta_a columns and the
     // position columns of the env's state row.
     static_assert(!MOV || PE, "MOV: the per-env-table path of the step");
+    // MOV on per-env frame tables (IO = MotionPeStepIO<...>; include/macjd.h, macjd_motion_pe_io): the same path with MotionStepIO
+    // generalised by an env tile — row stride = tile, tile index (e / tile) * F + f, column e % tile.
+    constexpr bool MVPE = io_moves_pe<IO>::value;
     constexpr int NJ = JT ? JT : MAXJ;
     constexpr int NR = RT ? RT : MAXR;
     const int J = JT ? JT : tb->J;
@@ -356,9 +369,19 @@ __global__ void __launch_bounds__(256) env_step_kernel(const DevTables* __restri
             mv_frame = step_before < io.n_frames - 1 ? step_before : io.n_frames - 1;
             mv_frame = mv_frame > 0 ? mv_frame : 0;
         }
-        const int64_t ps = MOV ? (int64_t)1 : (PE && io.pe_tile > 0) ? (int64_t)io.pe_tile : io.pe_stride;
-        const int64_t pe_tile_idx = MOV ? (int64_t)mv_frame : (PE && io.pe_tile > 0) ? e / io.pe_tile : 0;
-        const int64_t pe_col = MOV ? (int64_t)0 : (PE && io.pe_tile > 0) ? e - pe_tile_idx * io.pe_tile : e;
+        // MVPE: this env's tile and column of the per-env frame tables (production form: 32-bit division, the host checks
+        // that every env index fits); the shared-frame form is tile width 1 with the frame as the tile: constants
+        int64_t mv_ps = 1, mv_tile_idx = mv_frame, mv_col = 0, mv_env_tile = 0;
+        if constexpr (MVPE) {
+            if constexpr (FAST) mv_env_tile = (int64_t)((uint32_t)e / (uint32_t)io.mv_tile);
+            else mv_env_tile = e / io.mv_tile;
+            mv_ps = io.mv_tile;
+            mv_col = e - mv_env_tile * io.mv_tile;
+            mv_tile_idx = mv_env_tile * io.n_frames + mv_frame;
+        }
+        const int64_t ps = MOV ? mv_ps : (PE && io.pe_tile > 0) ? (int64_t)io.pe_tile : io.pe_stride;
+        const int64_t pe_tile_idx = MOV ? mv_tile_idx : (PE && io.pe_tile > 0) ? e / io.pe_tile : 0;
+        const int64_t pe_col = MOV ? mv_col : (PE && io.pe_tile > 0) ? e - pe_tile_idx * io.pe_tile : e;
         const double* pe_base = nullptr;
         const uint8_t* pf_base = nullptr;
         if constexpr (MOV) { pe_base = io.frames; pf_base = io.frame_flags; }
@@ -907,22 +930,27 @@ MACJD_ENV_UNROLL_SIZED(NR)
             if (last_t) {
                 int32_t fn = step_count < io.n_frames ? step_count : io.n_frames;
                 fn = fn > 0 ? fn : 0;
-                const float* __restrict__ pos = io.positions + (int64_t)fn * io.n_pos;
+                const float* __restrict__ pos;
+                if constexpr (MVPE) pos = io.positions + ((mv_env_tile * (io.n_frames + 1) + fn) * io.n_pos) * mv_ps + mv_col;
+                else pos = io.positions + (int64_t)fn * io.n_pos;
                 float* mv_rows;   // (a scanning launch's `state` is the beam block's: optional, theta_a columns)
                 if constexpr (SCAN) mv_rows = io.mv_state; else mv_rows = io.state;
                 constexpr int NPOS = 2 * (NR + NJ);
                 if constexpr (PRE) {
 #pragma unroll
-                    for (int i = 0; i < NPOS; ++i) at(mv_rows, e, io.mv_st_se, io.position_columns[i], 1) = pos[i];
+                    for (int i = 0; i < NPOS; ++i) at(mv_rows, e, io.mv_st_se, io.position_columns[i], 1) = pos[MVPE ? i * mv_ps : i];
                 } else {
-                    for (int i = 0; i < io.n_pos; ++i) at(mv_rows, e, io.mv_st_se, io.position_columns[i], 1) = pos[i];
+                    for (int i = 0; i < io.n_pos; ++i) at(mv_rows, e, io.mv_st_se, io.position_columns[i], 1) = pos[MVPE ? i * mv_ps : i];
                 }
             }
             if (io.mv_snr_no && !many) {
 MACJD_ENV_UNROLL_SIZED(NR)
                 for (int r = 0; r < NR; ++r) {
                     if (!RT && r >= R) break;
-                    at(io.mv_snr_no, e, io.mv_sn_se, r, io.mv_sn_sx) = (float)io.frame_snr_no[(int64_t)mv_frame * R + r];
+                    if constexpr (MVPE)
+                        at(io.mv_snr_no, e, io.mv_sn_se, r, io.mv_sn_sx) = (float)io.frame_snr_no[(mv_tile_idx * R + r) * mv_ps + mv_col];
+                    else
+                        at(io.mv_snr_no, e, io.mv_sn_se, r, io.mv_sn_sx) = (float)io.frame_snr_no[(int64_t)mv_frame * R + r];
                 }
             }
         }
@@ -957,6 +985,16 @@ void launch_motion_general(int J, int R, dim3 grid, dim3 block, hipStream_t stre
                            const MotionStepIO<macjd_step_io>& io);
 void launch_motion_reset(dim3 grid, dim3 block, hipStream_t stream, int64_t n_envs, int n_pos, const float* positions,
                          const int32_t* position_columns, float* state, int64_t st_se, const uint8_t* mask);
+
+// macjd_env_motion_pe.hip: the MOV instantiations on per-env frame tables (include/macjd.h, macjd_motion_pe_io) and the
+// position part of their reset.  Same sizes and return convention as the launchers of macjd_env_motion.hip.
+bool launch_motion_pe_fast(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
+                           const MotionPeStepIO<FastStepIO>& io);
+void launch_motion_pe_general(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
+                              const MotionPeStepIO<macjd_step_io>& io);
+void launch_motion_pe_reset(dim3 grid, dim3 block, hipStream_t stream, int64_t n_envs, int n_pos, int n_frames, int tile,
+                            const float* positions, const int32_t* position_columns, float* state, int64_t st_se,
+                            const uint8_t* mask);
 
 // macjd_env_motion_scan.hip: the MOV && SCAN instantiations (moving scenarios with scanning beams), with and without PAT, a
 // translation unit of their own.  Same sizes and return convention as the launchers of macjd_env_motion.hip.

@@ -23,6 +23,11 @@ What is added (build flags, all optional):
                   of the scenario file (positions, threat levels, powers; ``scenario.ScenarioBatch``), scanning
                   radars and their stepped antenna pattern included; ``randomize_azimuth_jitter`` (degrees, default 0) also moves every radar's
                   initial beam azimuth.
+  ``randomize_moving_scenarios`` / ``--randomize-moving-scenarios`` (batched runs on a ``motion`` sim-config without
+                  ``radar_scan``): every env gets its own random variation of the MOVING scenario — start positions,
+                  threat levels, powers and, with ``randomize_velocity_jitter`` / ``--randomize-velocity-jitter X``
+                  (m/s, default 0), velocities; its frame tables are compiled on the device
+                  (``scenario.MovingScenarioBatch``).
   ``--resume DIR`` restores agent, mixer, optimiser and ``trainer_state.json`` (env steps, episodes, epsilon
                   clock, learner step counters, and the positions of the three random streams: exploration counter,
                   replay sampler, per-env Monte-Carlo episode index) — the reference saves the optimiser but never
@@ -114,7 +119,26 @@ def build_components(args, sim_config_path):
     if batch_envs > 1:
         from .simulation.environment import BatchedElectromagneticEnvironment
         off = int(getattr(args, "env_offset", 0))
-        batch = None
+        batch = moving_batch = None
+        if getattr(args, "randomize_moving_scenarios", False):   # every env its own variation of the MOVING scenario
+            import yaml
+            from .scenario import MovingScenarioBatch
+            if getattr(args, "randomize_scenarios", False):
+                raise ValueError("--randomize-moving-scenarios and --randomize-scenarios are exclusive")
+            with open(sim_config_path) as f:
+                base = yaml.safe_load(f)
+            env_params = (base or {}).get("environment_params") or {}
+            if env_params.get("motion") is None:
+                raise ValueError(f"--randomize-moving-scenarios needs a moving scenario ({sim_config_path} has no "
+                                 f"environment_params.motion); --randomize-scenarios takes static ones")
+            if env_params.get("radar_scan") is not None:
+                raise ValueError(f"--randomize-moving-scenarios is not supported with scanning radars ({sim_config_path} has "
+                                 f"environment_params.radar_scan)")
+            moving_batch = MovingScenarioBatch.randomized(
+                base, batch_envs, seed=args.seed, config=args, env_offset=off,
+                velocity_jitter=float(getattr(args, "randomize_velocity_jitter", 0.0) or 0.0), compile="device")
+        elif float(getattr(args, "randomize_velocity_jitter", 0.0) or 0.0) != 0.0:
+            raise ValueError("--randomize-velocity-jitter needs --randomize-moving-scenarios")
         if getattr(args, "randomize_scenarios", False):   # every env its own variation of the scenario file
             import yaml
             from .scenario import ScenarioBatch
@@ -122,12 +146,16 @@ def build_components(args, sim_config_path):
                 base = yaml.safe_load(f)
             if ((base or {}).get("environment_params") or {}).get("motion") is not None:
                 raise ValueError(f"--randomize-scenarios is not supported with a moving scenario ({sim_config_path} has "
-                                 f"environment_params.motion): per-env scenario batches carry no frame tables")
+                                 f"environment_params.motion): per-env scenario batches carry no frame tables "
+                                 f"(--randomize-moving-scenarios builds a per-env moving batch)")
             batch = ScenarioBatch.randomized(base, batch_envs, seed=args.seed, config=args, env_offset=off,
                                              azimuth_jitter=float(getattr(args, "randomize_azimuth_jitter", 0.0) or 0.0))
         env = BatchedElectromagneticEnvironment(args, sim_config_path, batch_envs=batch_envs, seed=args.seed,
-                                                env_offset=off, verbose=True, scenario_batch=batch)
+                                                env_offset=off, verbose=True, scenario_batch=batch, moving_batch=moving_batch)
     else:
+        if getattr(args, "randomize_moving_scenarios", False) or float(getattr(args, "randomize_velocity_jitter", 0.0) or 0.0):
+            raise ValueError("--randomize-moving-scenarios needs a batched run (batch_envs > 1): the single-env facade "
+                             "takes no per-env moving batch")
         from .simulation.environment import ElectromagneticEnvironment
         env = ElectromagneticEnvironment(config=args, sim_config_path=sim_config_path)
     env_info = env.get_env_info()
@@ -388,6 +416,11 @@ def main(argv=None):
     parser.add_argument("--resume", type=str, default=None)
     parser.add_argument("--randomize-scenarios", action="store_true",
                         help="batched runs: every env gets its own random variation of the scenario (per-env tables)")
+    parser.add_argument("--randomize-moving-scenarios", action="store_true",
+                        help="batched runs on a moving scenario (environment_params.motion, no radar_scan): every env gets its "
+                             "own random variation; the per-env frame tables are compiled on the device")
+    parser.add_argument("--randomize-velocity-jitter", type=float, default=0.0, metavar="X",
+                        help="with --randomize-moving-scenarios: N(0, X) m/s per axis on every velocity (default 0)")
     parser.add_argument("--train-agent-body", action="store_true",
                         help="also train fc1 and the GRU of the agent (back-propagation through the unrolled episode); "
                              "eager updates, the actor stays frozen unless --train-actor is given")
@@ -405,6 +438,10 @@ def main(argv=None):
     config.resume = a.resume
     if a.randomize_scenarios:
         config.randomize_scenarios = True
+    if a.randomize_moving_scenarios:
+        config.randomize_moving_scenarios = True
+    if a.randomize_velocity_jitter:
+        config.randomize_velocity_jitter = a.randomize_velocity_jitter
     if a.train_agent_body:
         config.train_agent_body = True
     if a.train_actor:

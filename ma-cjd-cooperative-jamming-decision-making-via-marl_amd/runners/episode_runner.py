@@ -578,6 +578,8 @@ class BatchedEpisodeRunner:
             return False
         if getattr(env, "scenario_batch", None) is not None or getattr(env, "kernel_flags", 0) != 0:
             return False
+        if getattr(env, "moving_batch", None) is not None:   # per-env frames: no one state row per step; the step loop only
+            return False
         if not (hasattr(env, "step_many_has_production_form") and env.step_many_has_production_form()):
             return False
         agent = getattr(self.mac, "agent", None)

@@ -13,6 +13,9 @@ actions: the same compiler then runs once per step of an episode on the moved po
 tables become per-step frames (``Scenario.motion_tables``; include/macjd.h, ``macjd_motion_io``).  Together with
 ``radar_scan`` on one clock (equal ``step_seconds``) the beams' scan and pattern tables become frames as well
 (``motion_tables["scan_frames"]`` / ``["pattern_frames"]``; ``macjd_motion_scan_io``).
+``MovingScenarioBatch`` is the per-env batch of moving scenarios (``macjd_motion_pe_io``): every env's own frame tables,
+stacked from host compiles or written by the device frame compiler from one input column per env
+(``Scenario.motion_compile_inputs``; ``macjd_motion_pe_compile``).
 
 Validation and error behaviour follow environment.py:44-79 and :133-199 (same exception types and
 messages for the cases the reference checks).
@@ -446,6 +449,14 @@ class Scenario:
             if self.scan_pattern_levels:
                 self.motion_tables["pattern_frames"] = np.stack([_pattern_column(fr) for fr in scan_frs])
 
+    def motion_compile_inputs(self) -> Dict[str, np.ndarray]:
+        """Input column of the device frame compiler (include/macjd.h, macjd_motion_pe_compile_desc) for this moving
+        scenario: ``{"column": float64 [MACJD_MOTION_PE_IN_ROWS(R, J)], "weak": uint8 [J]}``.  Needs only the static compile
+        at the start positions (``self.tables``, frame 0) and the parsed ``motion`` block: no frame is compiled."""
+        if not self.moving:
+            raise AttributeError("motion_compile_inputs: the scenario does not move (no environment_params.motion)")
+        return _motion_compile_inputs(self, self.motion)
+
     # ---- static tables ----
     def _compile(self) -> None:
         R, J = self.num_radars, self.num_jammers
@@ -712,6 +723,222 @@ def _pattern_column(sc: "Scenario") -> np.ndarray:
         main, levels, side = _PE_PATTERN_LEVEL_SOURCES[key]
         parts += [sc.tables[main], sc.scan_tables[levels], sc.scan_tables[side]]
     return np.concatenate([np.asarray(a, dtype=np.float64).reshape(-1) for a in parts])
+
+
+def motion_pe_in_rows(n_radars: int, n_jammers: int) -> int:
+    """MACJD_MOTION_PE_IN_ROWS(R, J) of include/macjd.h."""
+    return 12 * n_radars + 10 * n_jammers + 4
+
+
+FOUR_PI_CUBED = float((4 * np.pi) ** 3)   # as Scenario._compile evaluates it (radar.py:35-60)
+
+
+def _motion_compile_inputs(sc: "Scenario", motion: Dict[str, Any]) -> Dict[str, np.ndarray]:
+    """The device frame compiler's input column from ``sc`` — a scenario compiled at the START positions (a moving scenario's
+    own static tables, or the static scenario of frame 0) — and the parsed motion block.  Row order of include/macjd.h,
+    macjd_motion_pe_compile_desc; every per-entity factor is formed with the expressions of ``Scenario._compile``."""
+    R, J = sc.num_radars, sc.num_jammers
+    t = sc.tables
+    dt = motion["step_seconds"]
+    num = np.zeros(R); rloss = np.zeros(R); rlatm = np.zeros(R); ga = np.zeros(R)
+    for r, p in enumerate(sc.radars):
+        pt = float(p["pt"])
+        gt = db_to_linear(p["gt"])
+        gr = db_to_linear(p["gr"])
+        lam = p["wavelength"]
+        num[r] = pt * gt * gr * (lam ** 2) * sc.target_rcs
+        rloss[r] = db_to_linear(p["loss"])
+        rlatm[r] = db_to_linear(p["latm"])
+        ga[r] = p["pulse_compression_gain"]
+    jloss = np.zeros(J); jlatm = np.zeros(J); bj_eff = np.zeros(J); weak = np.zeros(J, dtype=np.uint8)
+    for j, p in enumerate(sc.jammers):
+        loss = db_to_linear(p["loss"])
+        latm = db_to_linear(p["latm"])
+        effective_bj = max(1e-9, p["bj"])
+        jloss[j], jlatm[j], bj_eff[j] = loss, latm, effective_bj
+        # the host's denominator max(1e-9, d^2) * loss * latm * bj is a Python float exactly when d^2 <= 1e-9 (the max
+        # then returns its Python-float argument) and these three factors are Python floats too
+        weak[j] = 0 if isinstance(1e-9 * loss * latm * effective_bj, np.floating) else 1
+
+    def p0(pos):
+        q = np.array(pos).flatten()
+        return [float(q[0]), float(q[1])]
+
+    def vdt(v):
+        return [float(v[0]) * dt, float(v[1]) * dt]
+
+    pos_rows = p0(sc.target_position) + vdt(motion["target_velocity"])
+    pos_rows += [x for p in sc.radars for x in p0(p["position"])]
+    pos_rows += [x for v in motion["radar_velocity"] for x in vdt(v)]
+    pos_rows += [x for p in sc.jammers for x in p0(p["position"])]
+    pos_rows += [x for v in motion["jammer_velocity"] for x in vdt(v)]
+    col = np.concatenate([np.asarray(a, dtype=np.float64).reshape(-1) for a in (
+        t["radar_Pn"], t["radar_D"], t["radar_rd_pen"], t["radar_gr"], num, rloss, rlatm, ga,
+        t["jam_pmin"], t["jam_pmax"], t["jam_gj"], jloss, jlatm, bj_eff, pos_rows)])
+    assert col.shape == (motion_pe_in_rows(R, J),)
+    return {"column": col, "weak": weak}
+
+
+def tile_envs(a: np.ndarray, tile: int) -> np.ndarray:
+    """[E, ...] -> [n_tiles, ..., tile]: the tiled per-env layout with the env index split into (tile, column) and the
+    column innermost; the last tile is zero-padded."""
+    E = a.shape[0]
+    n_tiles = (E + tile - 1) // tile
+    padded = np.zeros((n_tiles * tile,) + a.shape[1:], dtype=a.dtype)
+    padded[:E] = a
+    padded = padded.reshape((n_tiles, tile) + a.shape[1:])
+    return np.ascontiguousarray(np.moveaxis(padded, 1, -1))
+
+
+def randomized_moving_scenario_dict(base: dict, rng: np.random.Generator, velocity_jitter: float = 0.0,
+                                    num_radars: Optional[int] = None, num_jammers: Optional[int] = None, **jitter) -> dict:
+    """``randomized_scenario_dict`` plus N(0, velocity_jitter) metres per second per axis on every velocity of the
+    ``motion`` block (target, then radars, then jammers; a missing list counts as zeros for the ``num_radars`` /
+    ``num_jammers`` entities used, default all defined).  The velocity draws come after all the others and only when the
+    jitter is > 0: without it the dict and the generator's state afterwards are ``randomized_scenario_dict``'s."""
+    d = randomized_scenario_dict(base, rng, **jitter)
+    if velocity_jitter > 0:
+        env_params = d.get("environment_params") or {}
+        nr = len(d["radars"]) if num_radars is None else int(num_radars)
+        nj = len(d["jammers"]) if num_jammers is None else int(num_jammers)
+        mo = parse_motion(env_params, nr, nj)
+        if mo is None:
+            raise ValueError("randomized_moving_scenario_dict: the scenario does not move (no environment_params.motion)")
+        draw = lambda v: [v[0] + float(rng.normal(0.0, velocity_jitter)), v[1] + float(rng.normal(0.0, velocity_jitter))]
+        mo["target_velocity"] = draw(mo["target_velocity"])
+        mo["radar_velocity"] = [draw(v) for v in mo["radar_velocity"]]
+        mo["jammer_velocity"] = [draw(v) for v in mo["jammer_velocity"]]
+        env_params["motion"] = mo
+    return d
+
+
+class MovingScenarioBatch:
+    """E MOVING, non-scanning scenarios of one shape (same R, J, episode limit F, r_p bounds, Pd constants and
+    ``motion.step_seconds``): every env has its own trajectory and so its own frame tables (include/macjd.h,
+    macjd_motion_pe_io).  ``ScenarioBatch`` keeps refusing moving scenarios; this class is their per-env batch.
+
+    Host path (``MovingScenarioBatch(scenarios)``): every scenario's own ``motion_tables`` stacked, bit for bit —
+    ``frames`` f64 [E, F, rows], ``flags`` u8 [E, F, J*R], ``snr_no`` f64 [E, F, R], ``positions`` f32 [E, F + 1, n_pos];
+    ``tiled(tile)`` gives them in the device layout.  Device path (``randomized(..., compile="device")``): only the input
+    columns of the device frame compiler exist (``compile_inputs`` f64 [E, in_rows], ``compile_weak`` u8 [E, J]) and
+    ``frames`` is None; the environment runs macjd_motion_pe_compile."""
+
+    def __init__(self, scenarios: List[Scenario]):
+        if not scenarios:
+            raise ValueError("MovingScenarioBatch needs at least one scenario")
+        for i, sc in enumerate(scenarios):
+            if not sc.moving:
+                raise ValueError(f"MovingScenarioBatch: scenario {i} does not move (no environment_params.motion); "
+                                 f"ScenarioBatch takes static scenarios")
+            if sc.scanning:
+                raise ValueError(f"MovingScenarioBatch: scenario {i} has scanning radars (environment_params.radar_scan); "
+                                 f"motion together with scanning is not supported on per-env batches")
+        self._check_shared(scenarios, [sc.motion["step_seconds"] for sc in scenarios])
+        self._init_common(scenarios[0], len(scenarios), np.stack([sc.state_vector() for sc in scenarios]))
+        self.scenarios = list(scenarios)
+        mt = [sc.motion_tables for sc in scenarios]
+        self.frames = np.ascontiguousarray(np.stack([m["frames"] for m in mt]), dtype=np.float64)
+        self.flags = np.ascontiguousarray(np.stack([m["flags"] for m in mt]), dtype=np.uint8)
+        self.snr_no = np.ascontiguousarray(np.stack([m["snr_no"] for m in mt]), dtype=np.float64)
+        self.positions = np.ascontiguousarray(np.stack([m["positions"] for m in mt]), dtype=np.float32)
+        self.state_vectors[:, self.position_columns] = self.positions[:, 0]
+        self.compile_inputs = self.compile_weak = None
+
+    @staticmethod
+    def _check_shared(scenarios: List[Scenario], step_seconds: List[float]) -> None:
+        s0 = scenarios[0]
+        for i, sc in enumerate(scenarios):
+            same = (sc.num_radars == s0.num_radars and sc.num_jammers == s0.num_jammers
+                    and sc.episode_limit == s0.episode_limit and sc.max_radar_types == s0.max_radar_types
+                    and sc.rp_min == s0.rp_min and sc.rp_max == s0.rp_max and sc.pd_consts == s0.pd_consts)
+            if not same:
+                raise ValueError(f"MovingScenarioBatch: scenario {i} differs from scenario 0 in shape / episode limit / "
+                                 f"r_p bounds / Pd constants (these are shared by the whole batch)")
+            if step_seconds[i] != step_seconds[0]:
+                raise ValueError(f"MovingScenarioBatch: scenario {i}'s motion.step_seconds ({step_seconds[i]!r}) differs from "
+                                 f"scenario 0's ({step_seconds[0]!r}) (it is shared by the whole batch)")
+
+    def _init_common(self, base: Scenario, n_envs: int, state_vectors: np.ndarray) -> None:
+        self.base = base
+        self.n_envs = int(n_envs)
+        self.n_frames = int(base.episode_limit)
+        if self.n_frames < 1:
+            raise ValueError(f"MovingScenarioBatch: a moving scenario needs episode_limit >= 1, got {self.n_frames}")
+        self.position_columns = np.asarray(base.position_columns, dtype=np.int32)
+        self.state_vectors = np.ascontiguousarray(state_vectors, dtype=np.float32)
+
+    @property
+    def host_compiled(self) -> bool:
+        """The frame tables exist on the host (built from scenarios' own ``motion_tables``)."""
+        return self.frames is not None
+
+    def tiled(self, tile: int) -> Dict[str, np.ndarray]:
+        """The four tables in the device layout of include/macjd.h, macjd_motion_pe_io: ``frames`` [n_tiles, F, rows, tile],
+        ``flags`` [n_tiles, F, J*R, tile], ``snr_no`` [n_tiles, F, R, tile], ``positions`` [n_tiles, F + 1, n_pos, tile]; the
+        last tile is zero-padded.  Host-compiled batches only."""
+        if not self.host_compiled:
+            raise RuntimeError("MovingScenarioBatch.tiled: this batch was made for the device frame compiler "
+                               "(compile='device'): no host frames exist")
+        return {"frames": tile_envs(self.frames, tile), "flags": tile_envs(self.flags, tile),
+                "snr_no": tile_envs(self.snr_no, tile), "positions": tile_envs(self.positions, tile)}
+
+    def tiled_compile_inputs(self, tile: int) -> Dict[str, np.ndarray]:
+        """The device frame compiler's input in its layout: ``in_tables`` f64 [n_tiles, in_rows, tile], ``in_weak`` u8
+        [n_tiles, J, tile]."""
+        if self.compile_inputs is None:
+            raise RuntimeError("MovingScenarioBatch.tiled_compile_inputs: this batch carries no compiler inputs")
+        return {"in_tables": tile_envs(self.compile_inputs, tile), "in_weak": tile_envs(self.compile_weak, tile)}
+
+    def table_bytes(self, tile: int) -> int:
+        """Bytes of the four device tables at env tile ``tile`` (the padded last tile included)."""
+        R, J, F = self.base.num_radars, self.base.num_jammers, self.n_frames
+        n_pad = ((self.n_envs + tile - 1) // tile) * tile
+        return n_pad * (F * ((6 * R + 3 * J + J * R) * 8 + J * R + R * 8) + (F + 1) * (2 * R + 2 * J) * 4)
+
+    @classmethod
+    def randomized(cls, base_dict: dict, n_envs: int, seed: int = 0, config: Any = None, env_offset: int = 0,
+                   velocity_jitter: float = 0.0, compile: str = "device", **jitter) -> "MovingScenarioBatch":
+        """``n_envs`` random variations of the moving ``base_dict`` (``randomized_moving_scenario_dict``); env e of the batch
+        is variation number ``env_offset + e`` of the stream keyed by ``seed`` (shard-invariant like
+        ``ScenarioBatch.randomized``).  ``compile="host"`` compiles every frame of every env on the host (the yardstick, and
+        fine for small batches); ``compile="device"`` compiles only each env's start positions and carries the device frame
+        compiler's input columns: no host frames exist."""
+        if compile not in ("device", "host"):
+            raise ValueError(f"MovingScenarioBatch.randomized: compile must be 'device' or 'host', got {compile!r}")
+        env_params = (base_dict or {}).get("environment_params") or {}
+        if parse_motion(env_params) is None:
+            raise ValueError("MovingScenarioBatch.randomized: the base scenario does not move (no environment_params.motion); "
+                             "ScenarioBatch.randomized takes static scenarios")
+        if parse_radar_scan(env_params) is not None:
+            raise ValueError("MovingScenarioBatch.randomized: the base scenario has scanning radars "
+                             "(environment_params.radar_scan); motion together with scanning is not supported on per-env batches")
+        nr = getattr(config, "num_radars", None)
+        nj = getattr(config, "num_jammers", None)
+        dicts = []
+        for e in range(n_envs):
+            rng = np.random.default_rng([int(seed), int(env_offset) + e])
+            dicts.append(randomized_moving_scenario_dict(base_dict, rng, velocity_jitter=velocity_jitter, num_radars=nr,
+                                                         num_jammers=nj, **jitter))
+        if compile == "host":
+            return cls([Scenario.from_dict(d, config=config, source=f"<randomized moving {seed}:{env_offset + e}>")
+                        for e, d in enumerate(dicts)])
+        # device: the static scenario of frame 0 (the start positions) + the parsed motion block per env
+        starts, motions = [], []
+        for e, d in enumerate(dicts):
+            sc0 = Scenario.from_dict(motion_frame_dict(d, 0), config=config, source=f"<randomized moving {seed}:{env_offset + e}>[frame 0]")
+            starts.append(sc0)
+            motions.append(parse_motion(d["environment_params"], sc0.num_radars, sc0.num_jammers))
+        cls._check_shared(starts, [m["step_seconds"] for m in motions])
+        out = object.__new__(cls)
+        # the shared handle and shape come from a moving Scenario of env 0 (its own frames: one scenario's host compile)
+        base = Scenario.from_dict(dicts[0], config=config, source=f"<randomized moving {seed}:{env_offset}>")
+        out._init_common(base, n_envs, np.stack([sc0.state_vector() for sc0 in starts]))
+        out.scenarios = None
+        out.frames = out.flags = out.snr_no = out.positions = None
+        ins = [_motion_compile_inputs(sc0, m) for sc0, m in zip(starts, motions)]
+        out.compile_inputs = np.ascontiguousarray(np.stack([i["column"] for i in ins]))
+        out.compile_weak = np.ascontiguousarray(np.stack([i["weak"] for i in ins]))
+        return out
 
 
 def randomized_scenario_dict(base: dict, rng: np.random.Generator, position_jitter: float = 60.0,

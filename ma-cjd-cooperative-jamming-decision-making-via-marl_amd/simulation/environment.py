@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from .. import _native
-from ..scenario import DEFAULT_SIM_CONFIG_PATH, Scenario, ScenarioBatch
+from ..scenario import DEFAULT_SIM_CONFIG_PATH, FOUR_PI_CUBED, MovingScenarioBatch, Scenario, ScenarioBatch
 
 RADAR_STATE_SEARCH = "SEARCH"  # core/radar.py:5-7
 RADAR_STATE_TRACK = "TRACK"
@@ -63,17 +63,34 @@ class BatchedElectromagneticEnvironment:
     observation_is_static = True
     PE_TILE = 256            # envs per tile of the per-env tables (= the lane kernel's workgroup at streaming sizes)
     pe_tiled = True          # A/B hook: False keeps the plain [rows, E] SoA on the device
+    moving_batch = None      # the per-env moving scenario batch (moving_batch=...), None otherwise
+    _motion_pe_io = None     # ... and its argument block (include/macjd.h, macjd_motion_pe_io)
 
     def __init__(self, config: Any = None, sim_config_path: str = DEFAULT_SIM_CONFIG_PATH,
                  batch_envs: Optional[int] = None, device=None, seed: Optional[int] = None,
                  env_offset: int = 0, scenario: Optional[Scenario] = None, verbose: bool = False,
-                 scenario_batch: Optional[ScenarioBatch] = None):
-        """``scenario_batch``: one scenario PER ENV (radar / jammer positions, threat levels, powers differing
+                 scenario_batch: Optional[ScenarioBatch] = None, moving_batch: Optional[MovingScenarioBatch] = None):
+        """``moving_batch``: one MOVING scenario per env (``MovingScenarioBatch``; exclusive with ``scenario_batch``): every
+        env steps on its own frame tables (include/macjd.h, macjd_motion_pe_io), uploaded from the batch's host frames or
+        compiled on the device from its input columns (macjd_motion_pe_compile).
+
+        ``scenario_batch``: one scenario PER ENV (radar / jammer positions, threat levels, powers differing
         between envs — SURVEY.md 8f-3); its tables live in HBM as an SoA that every step streams, and the
         observation becomes a per-env [E, S] tensor (still constant in time).  A scanning batch
         (``ScenarioBatch(..., scan=True)``) also streams each env's scan tables; its theta_a columns move.  With
         ``pattern=True`` each env's stepped antenna pattern tables are streamed too (macjd_env_step_scan_pe_pattern)."""
         self.scenario_batch = scenario_batch
+        self.moving_batch = moving_batch
+        if moving_batch is not None:
+            if scenario_batch is not None:
+                raise ValueError("moving_batch and scenario_batch are exclusive (a per-env batch is either static or moving)")
+            if scenario is not None and scenario is not moving_batch.base:
+                raise ValueError("moving_batch brings its own scenario (MovingScenarioBatch.base): do not pass `scenario` too")
+            scenario = moving_batch.base
+            if batch_envs is None:
+                batch_envs = moving_batch.n_envs
+            if int(batch_envs) != moving_batch.n_envs:
+                raise ValueError(f"batch_envs ({batch_envs}) != scenarios in the moving batch ({moving_batch.n_envs})")
         if scenario_batch is not None:
             scenario = scenario_batch.base
             if batch_envs is None:
@@ -184,7 +201,10 @@ class BatchedElectromagneticEnvironment:
             si.st_col0, si.st_col_step = sc.theta_a_col0, sc.theta_a_col_step
             si.snr_no, si.sn_se, si.sn_sx = self._snr_no_step.data_ptr(), 1, E
         self._motion_io = self._motion_keep = self._motion_scan_io = None
-        if sc.moving:
+        self._motion_pe_io = None
+        if moving_batch is not None:
+            self._init_moving_batch(moving_batch)
+        elif sc.moving:
             # per-step frame tables (include/macjd.h, macjd_motion_io): f64 [F, rows], u8 [F, J*R], f64 [F, R], the
             # positions f32 [F + 1, 2R + 2J] with their state columns; the per-env state rows f32 [E, S] start as frame 0
             # (get_state / get_obs are views of them: one address for captured graphs) and the per-step SNR without
@@ -219,6 +239,65 @@ class BatchedElectromagneticEnvironment:
         self.kernel_flags = 0  # A/B hook: _native.STEP_LANE_KERNEL / STEP_SLOT_KERNEL force one kernel variant
         if verbose:
             print(f"Batched environment: {E} envs x {J} jammers / {R} radars on {dev} (from {sc.source})")
+
+    def _init_moving_batch(self, mb: MovingScenarioBatch) -> None:
+        """Per-env frame tables on the device (include/macjd.h, macjd_motion_pe_io) at env tile PE_TILE: uploaded from the
+        batch's host frames, or written by ONE launch of the device frame compiler from its input columns; the per-env state
+        rows f32 [E, S] start as each env's frame 0 and the per-step SNR without jamming f32 [R, E] as frame 0's."""
+        E, R, J, dev = self.batch_envs, self.num_radars, self.num_jammers, self.device
+        w = int(self.PE_TILE)
+        F, n_pos = mb.n_frames, 2 * R + 2 * J
+        n_tiles = (E + w - 1) // w
+        rows = 6 * R + 3 * J + J * R
+        keep = {"position_columns": torch.from_numpy(np.ascontiguousarray(mb.position_columns, dtype=np.int32)).to(dev)}
+        if mb.host_compiled:
+            for k, a in mb.tiled(w).items():
+                keep[k] = torch.from_numpy(a).to(dev)
+        else:
+            ins = mb.tiled_compile_inputs(w)
+            keep["in_tables"] = torch.from_numpy(ins["in_tables"]).to(dev)
+            keep["in_weak"] = torch.from_numpy(ins["in_weak"]).to(dev)
+            keep["frames"] = torch.zeros((n_tiles, F, rows, w), dtype=torch.float64, device=dev)
+            keep["flags"] = torch.zeros((n_tiles, F, J * R, w), dtype=torch.uint8, device=dev)
+            keep["snr_no"] = torch.zeros((n_tiles, F, R, w), dtype=torch.float64, device=dev)
+            keep["positions"] = torch.zeros((n_tiles, F + 1, n_pos, w), dtype=torch.float32, device=dev)
+            d = _native.MotionPeCompileDesc()
+            d.n_envs, d.n_radars, d.n_jammers, d.n_frames, d.tile = E, R, J, F, w
+            d.four_pi_cubed = FOUR_PI_CUBED
+            d.pd_A, d.pd_c1, d.pd_denB = self.scenario.pd_consts
+            d.in_tables, d.in_weak = keep["in_tables"].data_ptr(), keep["in_weak"].data_ptr()
+            d.frames, d.frame_flags = keep["frames"].data_ptr(), keep["flags"].data_ptr()
+            d.frame_snr_no, d.positions = keep["snr_no"].data_ptr(), keep["positions"].data_ptr()
+            with torch.cuda.device(dev):
+                _native.check(self._lib.macjd_motion_pe_compile(ctypes.byref(d), torch.cuda.current_stream(dev).cuda_stream),
+                              "macjd_motion_pe_compile")
+        assert tuple(keep["frames"].shape) == (n_tiles, F, rows, w) and tuple(keep["positions"].shape) == (n_tiles, F + 1, n_pos, w)
+        self._motion_keep = keep
+        self._pe_tile = w
+        self._pos_cols = keep["position_columns"].to(torch.int64)
+        untile = lambda t: t.permute(0, 2, 1).reshape(n_tiles * w, -1)[:E]      # [n_tiles, k, w] -> [E, k]
+        self._state_vecs = torch.from_numpy(mb.state_vectors).to(dev)
+        self._state_dyn = self._state_vecs.clone()
+        self._state_dyn[:, self._pos_cols] = untile(keep["positions"][:, 0])
+        self._snr_no_step = untile(keep["snr_no"][:, 0]).to(torch.float32).t().contiguous()   # f32 [R, E]
+        mp = self._motion_pe_io = _native.MotionPeIO()
+        mp.frames, mp.frame_flags, mp.frame_snr_no = keep["frames"].data_ptr(), keep["flags"].data_ptr(), keep["snr_no"].data_ptr()
+        mp.positions, mp.position_columns = keep["positions"].data_ptr(), keep["position_columns"].data_ptr()
+        mp.n_frames, mp.n_pos, mp.tile = F, n_pos, w
+        mp.state, mp.st_se = self._state_dyn.data_ptr(), self._state_dyn.stride(0)
+        mp.snr_no, mp.sn_se, mp.sn_sx = self._snr_no_step.data_ptr(), 1, E
+
+    @property
+    def table_bytes(self) -> int:
+        """Bytes of the per-env frame tables on the device (per-env moving batches only)."""
+        if self._motion_pe_io is None:
+            raise AttributeError("table_bytes: not a per-env moving batch (moving_batch=...)")
+        return int(sum(self._motion_keep[k].numel() * self._motion_keep[k].element_size()
+                       for k in ("frames", "flags", "snr_no", "positions")))
+
+    def _refuse_moving_batch(self, what: str) -> None:
+        if self._motion_pe_io is not None:
+            raise RuntimeError(f"{what}: not available on a per-env moving scenario batch (moving_batch=...)")
 
     # ---- reference-shaped getters, broadcast views (never materialised per env) ----
     def get_state(self) -> torch.Tensor:
@@ -261,7 +340,7 @@ class BatchedElectromagneticEnvironment:
     def positions(self) -> torch.Tensor:
         """f32 [E, 2R + 2J]: the current position columns of the state rows in state order (per radar x, y; then per jammer
         x, y), gathered from them (moving scenarios only)."""
-        if self._motion_io is None:
+        if self._motion_io is None and self._motion_pe_io is None:
             raise AttributeError("positions: the scenario does not move (no environment_params.motion)")
         return self._state_dyn[:, self._pos_cols]
 
@@ -269,6 +348,7 @@ class BatchedElectromagneticEnvironment:
         """f32 [F + 1, S] on the device (moving scenarios only): row k is the state row every env shows at step counter k —
         the scenario's state vector with the position columns of frame k (``Scenario.frame_state_rows``), i.e. the bits
         the moving step writes.  Built once."""
+        self._refuse_moving_batch("frame_states")   # every env has its own frames
         if self._motion_io is None:
             raise AttributeError("frame_states: the scenario does not move (no environment_params.motion)")
         if self._motion_scan_io is not None:   # the theta_a columns depend on the detections, not on the counter alone
@@ -307,6 +387,10 @@ class BatchedElectromagneticEnvironment:
             elif self._scan_io is not None:
                 _native.check(self._lib.macjd_env_reset_scan(self._handle.ptr, self.batch_envs, ctypes.byref(self._scan_io),
                                                              mptr, stream), "macjd_env_reset_scan")
+            if self._motion_pe_io is not None:
+                _native.check(self._lib.macjd_env_reset_moving_pe(self._handle.ptr, self.batch_envs,
+                                                                  ctypes.byref(self._motion_pe_io), mptr, stream),
+                              "macjd_env_reset_moving_pe")
             if self._motion_io is not None:   # (next to the beam reset when the scenario also scans)
                 _native.check(self._lib.macjd_env_reset_moving(self._handle.ptr, self.batch_envs, ctypes.byref(self._motion_io),
                                                                mptr, stream), "macjd_env_reset_moving")
@@ -412,6 +496,11 @@ class BatchedElectromagneticEnvironment:
             elif self._scan_io is not None:
                 _native.check(self._lib.macjd_env_step_scan(self._handle.ptr, ctypes.byref(io), ctypes.byref(self._scan_io),
                                                             stream), "macjd_env_step_scan")
+            elif self._motion_pe_io is not None:
+                mp = self._motion_pe_io
+                mp.snr_no = self._snr_no_step.data_ptr() if want_info else None
+                _native.check(self._lib.macjd_env_step_moving_pe(self._handle.ptr, ctypes.byref(io), ctypes.byref(mp), stream),
+                              "macjd_env_step_moving_pe")
             elif self._motion_io is not None:
                 mo = self._motion_io
                 mo.snr_no = self._snr_no_step.data_ptr() if want_info else None
@@ -454,7 +543,12 @@ class BatchedElectromagneticEnvironment:
         io.r_dpj = out_rdpj.data_ptr()
         stream = torch.cuda.current_stream(self.device).cuda_stream
         with torch.cuda.device(self.device):
-            if self._motion_io is not None:   # item (t, e) runs frame min(step[e] + t, F - 1); state rows end as after step n
+            if self._motion_pe_io is not None:   # the same on each env's own frames
+                mp = self._motion_pe_io
+                mp.snr_no = None
+                _native.check(self._lib.macjd_env_step_many_moving_pe(self._handle.ptr, ctypes.byref(io), ctypes.byref(mp), int(n),
+                                                                      int(E * J), stream), "macjd_env_step_many_moving_pe")
+            elif self._motion_io is not None:   # item (t, e) runs frame min(step[e] + t, F - 1); state rows end as after step n
                 mo = self._motion_io
                 mo.snr_no = None
                 _native.check(self._lib.macjd_env_step_many_moving(self._handle.ptr, ctypes.byref(io), ctypes.byref(mo), int(n),
@@ -470,6 +564,7 @@ class BatchedElectromagneticEnvironment:
         launches replayed from a HIP graph and bracketed by HIP events on the replay stream (macjd_env_step_many_timed)."""
         self._refuse_scanning("time_step_many_kernel")
         self._refuse_moving("time_step_many_kernel")
+        self._refuse_moving_batch("time_step_many_kernel")
         E, J = self.batch_envs, self.num_jammers
         n = actions_T.shape[0]
         io = self._fill_io(actions_T[0].view(E, J), actions_P[0].view(E, J), None, False, out_reward.view(-1)[:E],
@@ -489,6 +584,7 @@ class BatchedElectromagneticEnvironment:
         launches, measured with HIP events recorded on the launch stream (macjd_env_step_timed)."""
         self._refuse_scanning("time_step_kernel")
         self._refuse_moving("time_step_kernel")
+        self._refuse_moving_batch("time_step_kernel")
         io = self._fill_io(actions_T, actions_P, uniforms, False, None, None, want_info, None)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         ms = ctypes.c_float(0.0)
@@ -501,6 +597,7 @@ class BatchedElectromagneticEnvironment:
         """What the closed-loop episode launch (``ops.agent_env_episode_scan``) needs from a scanning environment: the
         scenario handle, the beam / state-row block, the FSM bits, step counters and episode indices it reads and leaves
         as T single steps would, and the Monte-Carlo stream's seed and env offset."""
+        self._refuse_moving_batch("episode_scan_args")
         if self._scan_io is None:
             raise RuntimeError("episode_scan_args: the scenario's beams do not scan (no environment_params.radar_scan)")
         if self._pe_tables is not None:
@@ -517,6 +614,7 @@ class BatchedElectromagneticEnvironment:
         scanning scenario batch: the entries of ``episode_scan_args`` plus the batch's scenario tables and flag bytes
         with their tile width, ``n_envs`` (the plain layout's row stride), the per-env scan block and, under a stepped
         pattern, the per-env level tables (else None)."""
+        self._refuse_moving_batch("episode_scan_pe_args")
         if self._scan_pe_io is None:
             raise RuntimeError("episode_scan_pe_args: needs a per-env scanning scenario batch (ScenarioBatch(..., scan=True)); "
                                "episode_scan_args serves shared scenario tables")
@@ -529,6 +627,7 @@ class BatchedElectromagneticEnvironment:
         """What the closed-loop episode launch on a moving scanning scenario (``ops.agent_env_episode_moving_scan``) needs:
         the entries of ``episode_scan_args`` plus the motion block (frame tables, positions and their state columns) and the
         motion-scan block (per-frame beam tables, under a stepped pattern the per-frame level tables)."""
+        self._refuse_moving_batch("episode_moving_scan_args")
         if self._motion_io is None or self._motion_scan_io is None:
             raise RuntimeError("episode_moving_scan_args: needs a scenario that both moves and scans (environment_params.motion "
                                "and environment_params.radar_scan); episode_scan_args serves a static scanning scenario")
