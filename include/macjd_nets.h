@@ -438,7 +438,9 @@ int macjd_layernorm_param_grad(const macjd_lnparam_io* io, void* hip_stream);
 /* macjd_clip_adam_step_sample whose FIRST launch also evaluates the LayerNorm parameter gradients (this struct) — they are
    part of the clipped vector, at elements gamma_off / beta_off of io->grad (ln->dgamma / ln->dbeta must point there), so
    the squared-norm launch computes them in K extra workgroups and counts their squares itself; the other workgroups skip
-   those two ranges.  One launch less behind the weight-gradient reduce.  io->partials: >= 256 + ln->K floats. */
+   those two ranges.  One launch less behind the weight-gradient reduce.  io->partials: >= 256 + ln->K floats.
+   The two ranges [gamma_off, gamma_off + K) and [beta_off, beta_off + K) lie inside [0, io->n) and must not overlap
+   (|gamma_off - beta_off| >= K; adjacent ranges are fine): MACJD_EINVAL before any launch otherwise.  ln->K <= 1024. */
 int macjd_clip_adam_step_ln(const macjd_adam_io* io, const macjd_sampler_io* next, const macjd_lnparam_io* ln,
                             int64_t gamma_off, int64_t beta_off, void* hip_stream);
 

@@ -1202,6 +1202,9 @@ extern "C" int macjd_clip_adam_step_ln(const macjd_adam_io* io, const macjd_samp
     if (gamma_off < 0 || beta_off < 0 || gamma_off + ln->K > io->n || beta_off + ln->K > io->n ||
         ln->dgamma != io->grad + gamma_off || ln->dbeta != io->grad + beta_off)
         return set_nets_err(MACJD_EINVAL, "macjd_clip_adam_step_ln: dgamma / dbeta must be the named ranges of the gradient vector");
+    // overlapping ranges: workgroups nb + k and nb + k' would store dgamma[k] and dbeta[k'] to one element in no defined order
+    if ((gamma_off <= beta_off ? beta_off - gamma_off : gamma_off - beta_off) < ln->K)
+        return set_nets_err(MACJD_EINVAL, "macjd_clip_adam_step_ln: the dgamma and dbeta ranges overlap");
     hipStream_t s = (hipStream_t)hip_stream;
     int blocks = (int)((io->n + 255) / 256);
     if (blocks > ADAM_BLOCKS) blocks = ADAM_BLOCKS;
