@@ -82,12 +82,14 @@ typedef struct macjd_gru_io {
     int32_t n_nets, B, T, J, H, reserved;   /* n_nets = 1 or 2; reserved != 0 ("gi_static"): gi is [B,1,J,3H], the
                                                same input transform at every step (static observation) */
     const float* gi[2];    /* [B,T,J,3H] */
-    const float* w_hh[2];  /* rnn.weight_hh [3H,H] row-major */
+    const float* w_hh[2];  /* rnn.weight_hh [3H,H] row-major, 16-byte aligned (its rows are read as float4;
+                              MACJD_EINVAL otherwise) */
     const float* b_hh[2];  /* rnn.bias_hh [3H] */
     const float* h0[2];    /* optional initial state [B,J,H]; NULL = zeros (mac.init_hidden) */
     float* h_out[2];       /* [B,T,J,H] */
     int64_t h0_sb[2];      /* element stride between batch entries of h0 (0 = J*H, contiguous): lets the caller pass
-                              step 0 of a stored [B,T+1,J,H] hidden-state tensor without copying it */
+                              step 0 of a stored [B,T+1,J,H] hidden-state tensor without copying it.  0 never means
+                              "one [J,H] block for every batch entry": such an h0 has to be materialised as [B,J,H] */
     /* Static observation, input transform computed IN the kernel (gi[] may then be NULL): sequence (b, j) reads its
        observation row obs + row(b) * obs_sb + j * obs_sj (row(b) = obs_index[b] if obs_index else b — e.g. the sampled
        episodes' step-0 rows straight out of the replay ring, no gather in front of the scan) and evaluates
@@ -348,7 +350,10 @@ int macjd_prefetch_batch(const macjd_prefetch_io* io, void* hip_stream);
  * and seed, the mask geometry and gather_blocks: ios[i] must equal ios[0] in everything but
  *     sampler.reserved (the counter offset), no_draw, sampler.idx_out,
  *     gather.dst[] / gather.dst_row_bytes[], gru.h_out[0], gru.p_out[0], tot_m,
- * and no two batches may share one of these outputs (MACJD_EINVAL otherwise).  The launch only reads the counter.
+ * and no two batches may share one of these outputs (MACJD_EINVAL otherwise): the byte ranges that two batches write —
+ * h_out [B,T,J,H], p_out [B,J,A], tot_m, idx_out [B] unless no_draw, dst[k] (B - 1 row pitches + one row) — must not
+ * overlap, whichever outputs they belong to; an idx_out that is only read (no_draw) may be shared between such batches
+ * but not overlap anything another batch writes.  The launch only reads the counter.
  */
 #define MACJD_PREFETCH_MAX_BATCHES 4
 int macjd_prefetch_batches_supported(int32_t n_nets, int32_t H, int32_t B, int32_t n);   /* 1 / 0 */

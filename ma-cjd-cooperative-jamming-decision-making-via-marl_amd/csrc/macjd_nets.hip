@@ -631,6 +631,9 @@ extern "C" int macjd_gru_sequence(const macjd_gru_io* io, void* hip_stream) {
     for (int n = 0; n < io->n_nets; ++n) {
         if ((!io->gi[n] && !io->obs) || !io->w_hh[n] || !io->b_hh[n] || !io->h_out[n])
             return set_nets_err(MACJD_EINVAL, "macjd_gru_sequence: NULL pointer");
+        // both scan forms read the rows of w_hh as float4 (H is a multiple of 4, so an aligned base aligns every row)
+        if (((uintptr_t)io->w_hh[n]) & 15)
+            return set_nets_err(MACJD_EINVAL, "macjd_gru_sequence: w_hh must be 16-byte aligned");
         if (io->obs && (!io->fc1_w[n] || !io->fc1_b[n] || !io->w_ih[n] || !io->b_ih[n]))
             return set_nets_err(MACJD_EINVAL, "macjd_gru_sequence: in-kernel input transform needs fc1 / W_ih");
     }
@@ -1266,11 +1269,30 @@ static int prefetch_shares_with_first(const macjd_prefetch_io* first, const macj
 }
 
 // the per-batch outputs of two batches of one launch must be different tensors (their workgroups run side by side)
+// — compared as BYTE RANGES: a batch whose output starts inside another batch's buffer races just as one that shares its base.
+// idx_out of a batch with no_draw is only read: two such batches may share it, but nothing may be written into it.
+struct PrefetchRange { uintptr_t lo, hi; bool written; };
+static int prefetch_ranges(const macjd_prefetch_io* io, PrefetchRange* r) {
+    const macjd_gru_io& g = io->gru;
+    const uintptr_t BJ = (uintptr_t)g.B * (uintptr_t)g.J;
+    int n = 0;
+    auto add = [&](const void* p, uintptr_t bytes, bool written) { r[n++] = PrefetchRange{(uintptr_t)p, (uintptr_t)p + bytes, written}; };
+    add(g.h_out[0], BJ * (uintptr_t)g.T * (uintptr_t)g.H * sizeof(float), true);
+    add(g.p_out[0], BJ * (uintptr_t)g.A * sizeof(float), true);
+    add(io->tot_m, sizeof(float), true);
+    add(io->sampler.idx_out, (uintptr_t)g.B * sizeof(int64_t), io->no_draw == 0);
+    for (int k = 0; k < io->gather.n_tensors; ++k) {
+        const int64_t pitch = io->gather.dst_row_bytes[k] ? io->gather.dst_row_bytes[k] : io->gather.row_bytes[k];
+        add(io->gather.dst[k], (uintptr_t)(g.B - 1) * (uintptr_t)pitch + (uintptr_t)io->gather.row_bytes[k], true);
+    }
+    return n;
+}
 static int prefetch_outputs_distinct(const macjd_prefetch_io* x, const macjd_prefetch_io* y) {
-    if (x->gru.h_out[0] == y->gru.h_out[0] || x->gru.p_out[0] == y->gru.p_out[0] || x->tot_m == y->tot_m) return 0;
-    if (x->sampler.idx_out == y->sampler.idx_out && !(x->no_draw && y->no_draw)) return 0;
-    for (int k = 0; k < x->gather.n_tensors; ++k)
-        if (x->gather.dst[k] == y->gather.dst[k]) return 0;
+    PrefetchRange rx[12], ry[12];
+    const int nx = prefetch_ranges(x, rx), ny = prefetch_ranges(y, ry);
+    for (int i = 0; i < nx; ++i)
+        for (int j = 0; j < ny; ++j)
+            if ((rx[i].written || ry[j].written) && rx[i].lo < ry[j].hi && ry[j].lo < rx[i].hi) return 0;
     return 1;
 }
 
@@ -1282,6 +1304,7 @@ static int prefetch_one_ok(const macjd_prefetch_io* io) {
     if (g.T < 1 || g.J < 1 || !g.obs || g.S < 1 || g.S > 256 || !g.w_hh[0] || !g.b_hh[0] || !g.h_out[0] || !g.fc1_w[0] ||
         !g.fc1_b[0] || !g.w_ih[0] || !g.b_ih[0])
         return set_nets_err(MACJD_EINVAL, "macjd_prefetch_batch: bad scan argument");
+    if (((uintptr_t)g.w_hh[0]) & 15) return set_nets_err(MACJD_EINVAL, "macjd_prefetch_batch: w_hh must be 16-byte aligned");
     if (!g.p_out[0] || g.Ah < 1 || g.Ah > 256 || g.A < 1 || g.A > 64)
         return set_nets_err(MACJD_EINVAL, "macjd_prefetch_batch: needs the in-kernel actor (Ah <= 256, A <= 64)");
     for (int l = 0; l < 3; ++l)

@@ -29,6 +29,12 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
     return t if t.stride(-1) == 1 else t.contiguous()
 
 
+def _aligned16(t: torch.Tensor) -> torch.Tensor:
+    """t itself, or a copy when its first element is not 16-byte aligned (a view into a flat parameter vector): the GRU
+    scan reads the rows of w_hh as float4 and refuses a misaligned pointer."""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 def _qhead_fill(io: _native.QheadIO, base, P_all, W1, w2, b2, H: int, A: int, n_agents: int):
     io.n_rows, io.H, io.A, io.n_agents = base.shape[0], H, A, n_agents
     io.base, io.base_ld = base.data_ptr(), base.stride(0)
@@ -707,7 +713,7 @@ def _gru_from_obs_io(obs, obs_index, part, B: int, J: int, n_steps: int, with_ac
     for k, a in enumerate(part):
         ts = [t.detach().float().contiguous() for t in (a.rnn.weight_hh, a.rnn.bias_hh, a.fc1.weight, a.fc1.bias,
                                                         a.rnn.weight_ih, a.rnn.bias_ih)]
-        keep += ts
+        keep += ts   # (w_hh in place, 16-byte aligned or refused: a captured launch must read the live parameter)
         io.w_hh[k], io.b_hh[k], io.fc1_w[k], io.fc1_b[k], io.w_ih[k], io.b_ih[k] = [t.data_ptr() for t in ts]
         o = torch.empty((B, n_steps, J, H), dtype=torch.float32, device=obs.device)
         io.h_out[k] = o.data_ptr()
@@ -753,13 +759,14 @@ def gru_sequence_multi(gis, w_hhs, b_hhs, h0s=None, n_steps=None):
         io.reserved = 1 if static else 0
         for k in range(cnt):
             g = gis[start + k].detach().float().contiguous()
-            w = w_hhs[start + k].detach().float().contiguous()
+            w = _aligned16(w_hhs[start + k].detach().float().contiguous())
             bb = b_hhs[start + k].detach().float().contiguous()
             h0 = h0s[start + k]
             if h0 is not None:
                 # [B, J, H] with any batch stride (e.g. step 0 of a stored [B, T+1, J, H] tensor): no copy
                 h0 = h0.detach().float().reshape(B, J, H) if h0.dim() != 3 else h0.detach().float()
-                if h0.stride(2) != 1 or h0.stride(1) != H:
+                # (h0_sb = 0 means "contiguous" to the kernel: an h0 expanded over the batch is materialised)
+                if h0.stride(2) != 1 or h0.stride(1) != H or (h0.stride(0) == 0 and B > 1):
                     h0 = h0.contiguous()
                 io.h0_sb[k] = h0.stride(0)
             o = torch.empty((B, T, J, H), dtype=torch.float32, device=g.device)
