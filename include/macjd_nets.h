@@ -34,6 +34,17 @@ extern "C" {
  * action column W1[:, H+a] and the rank-1 power term W1[:, H+A] * P_a, applies ReLU and the second
  * layer (w2, b2), for all a, without materialising [N, A, H].
  * Row n of base / P_all / Q is (env e, agent j) with n = e * n_agents + j.
+ *
+ * Selection of row n (T_out32 / T_out64 / P_out):
+ *   greedy    the FIRST maximum of Q over the available actions (unavailable ones count as -inf; the lower index wins a
+ *             tie).  A row with NO available action takes action 0.
+ *   explore   unless greedy_only or epsilon <= 0: (v0, v1, ., .) = Philox4x32-10(counter words (n lo, n hi, c lo, c hi),
+ *             key (seed lo, seed hi)) with c = counter + *counter_dev.  The row explores iff (v0 >> 8) 2^-24 < epsilon
+ *             (compared in float32; the left side is exact).  Then pool = number of available actions, or A if none is
+ *             available, k = (v1 * pool) >> 32, and the choice is the k-th available action in index order — with no
+ *             available action the k-th of all A: uniform over all of them.
+ *   P_out = P_all[n, chosen], bit for bit.
+ * q_gather_out[n] is 0 for a gather_idx[n] outside [0, A).
  */
 typedef struct macjd_qhead_io {
     int64_t n_rows;          /* N = E * n_agents */
