@@ -893,6 +893,64 @@ int macjd_agent_env_episode_moving_scan(const macjd_scenario* scenario, const ma
                                         void* hip_stream);
 
 /*
+ * The agent side of a whole episode batch on PER-ENV moving frames (macjd_motion_pe_io) in ONE launch.  The observation
+ * of env e at step t is its own state row with the position columns taken from its own frame min(step0[e] + t, F),
+ * whatever the agents did, so — as for macjd_agent_episode_seq — nothing the agent computes depends on the environment's
+ * outputs, and the env's T steps run as macjd_env_step_many_moving_pe.  Per-step gi / P rows would be [T, E J, 3H + A], so
+ * the observation-only work is done in the kernel, once per ENV (every agent of an env sees the same observation), as in
+ * macjd_agent_env_episode_scan.  Step t, row n = e J + j:
+ *   obs = state[e, :S] with column position_columns[p] replaced by
+ *         positions[(((e / tile) * (F + 1) + min(step0[e] + t, F)) * n_pos + p) * tile + e % tile],  p = 0 .. n_pos - 1,
+ *         step0[e] = step[e] at entry (step == NULL: 0; read only); the padded lanes of the last tile are never read;
+ *   x   = ReLU(fc1 obs + b),  gi = W_ih x + b_ih,  P = sigma(L3 ReLU(L2 ReLU(L1 obs)))  — the first layers as full
+ *         S-column products in macjd_mlp_forward's k order with the bias after the sum;
+ *   then exactly the step of macjd_agent_episode on (gi, P): the same gate and Q-head expressions, the same mask, first
+ *   arg-max and epsilon-greedy rule, the same Philox keying (row n, *counter_base + t + 1).
+ * A T-step launch equals T launches with T = 1 chained through h_final with step + t, eps + t and *counter_base + t, bit
+ * for bit.  The kernel writes hidden, T_out, P_out and h_final only: no staging observation rows (they do not depend on
+ * the actions: the caller fills them once) and nothing of the env.  Rows past n_envs in the last workgroup are computed
+ * from clamped addresses and never stored.  The caller guarantees 0 <= position_columns[p] < S.
+ * Supported: H = 64, actor_hidden = 128, (J, R, A) in {(3, 4, 9), (2, 2, 5)}; MACJD_EUNSUPPORTED otherwise.
+ * MACJD_EINVAL, before any launch: a NULL required member (everything but h0, avail, step, counter_base, h_final, and eps
+ * under greedy_only); T < 1; n_frames < 1; n_pos != 2R + 2J; tile < 1; st_se < S; S outside 1..48; avail_elem_size not 4 / 8
+ * with a mask; w1_ld < H + A + 1; w_hh, w_ih or a2_w not 16-byte aligned (their rows are contiguous).
+ */
+typedef struct macjd_agent_episode_moving_pe_io {
+    int64_t n_envs;            /* E */
+    int32_t T, J, R, H, A, S;  /* steps, agents, radars, rnn_hidden_dim, n_actions, state / observation width */
+    int32_t actor_hidden, greedy_only;
+    /* agent */
+    const float* h0;                                  /* [E*J, H] initial hidden state or NULL = zeros */
+    const float* fc1_w; const float* fc1_b;           /* fc1 [H, S], [H] */
+    const float* w_ih;  const float* b_ih;            /* rnn.weight_ih [3H, H], rnn.bias_ih [3H] */
+    const float* w_hh;  const float* b_hh;            /* rnn.weight_hh [3H, H], rnn.bias_hh [3H] */
+    const float* a1_w;  const float* a1_b;            /* actor.0 [128, S] */
+    const float* a2_w;  const float* a2_b;            /* actor.2 [128, 128] */
+    const float* a3_w;  const float* a3_b;            /* actor.4 [A, 128] */
+    const float* W1;    int64_t w1_ld;                /* fc2_q_head.0.weight [H, H+A+1] */
+    const float* b1;    const float* w2; const float* b2;
+    const void* avail;  int32_t avail_elem_size, reserved;   /* optional mask (static), int32 / int64 elements */
+    int64_t av_se, av_sj, av_sa;
+    const float* eps;          /* [T] exploration probability of every step (device memory) */
+    uint64_t seed;             /* exploration draws */
+    const uint64_t* counter_base;
+    /* observation */
+    const float* state; int64_t st_se;      /* [E, S] every env's own state row, row stride st_se; position columns ignored */
+    const int32_t* step;                    /* [E] step counters at entry, read only; NULL = zeros */
+    const float* positions;                 /* [n_tiles, F + 1, n_pos, tile] (macjd_motion_pe_io) */
+    const int32_t* position_columns;        /* int32 [n_pos] */
+    int32_t n_frames, n_pos, tile, reserved2;   /* F >= 1, 2R + 2J, envs per tile >= 1 */
+    /* outputs, time-major staging rows of the batched runner */
+    float*   hidden;    /* [T(+1), E, J, H] row t = post-update h_t */
+    int32_t* T_out;     /* [T, E, J] */
+    float*   P_out;     /* [T, E, J] */
+    float*   h_final;   /* [E*J, H] optional */
+} macjd_agent_episode_moving_pe_io;
+
+int macjd_agent_episode_moving_pe_supported(int32_t J, int32_t R, int32_t H, int32_t A);
+int macjd_agent_episode_moving_pe(const macjd_agent_episode_moving_pe_io* io, void* hip_stream);
+
+/*
  * Double-DQN target values straight from the unrolled hidden states (reference core/qmix.py:138-147): for every row n
  *   a* = argmax_a Q_eval(h_e[n], a, P_e[n,a])   (no availability mask there, qmix.py:141-142)
  *   out[n] = Q_target(h_t[n], a*, P_t[n,a*])

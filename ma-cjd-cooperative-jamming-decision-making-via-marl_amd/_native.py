@@ -36,6 +36,7 @@ EXPORTS = [
     "macjd_agent_env_episode_scan_supported", "macjd_agent_env_episode_scan",
     "macjd_agent_env_episode_scan_pe_supported", "macjd_agent_env_episode_scan_pe",
     "macjd_agent_env_episode_moving_scan_supported", "macjd_agent_env_episode_moving_scan",
+    "macjd_agent_episode_moving_pe_supported", "macjd_agent_episode_moving_pe",
     "macjd_scenario_set_scan_pattern",
     "macjd_gru_sequence_backward_supported", "macjd_gru_sequence_backward",
     "macjd_prefetch_batch_supported", "macjd_prefetch_batch",
@@ -325,6 +326,28 @@ class AgentEnvEpisodeMovingScanIO(ctypes.Structure):
     _fields_ = [("base", AgentEnvEpisodeScanIO), ("motion", MotionIO), ("motion_scan", MotionScanIO)]
 
 
+class AgentEpisodeMovingPeIO(ctypes.Structure):
+    """ctypes mirror of ``macjd_agent_episode_moving_pe_io`` (include/macjd_nets.h): the agent side of an episode batch on
+    per-env moving frames — a flat block, the agent's members named as in ``AgentEnvEpisodeScanIO``."""
+    _fields_ = [
+        ("n_envs", ctypes.c_int64),
+        ("T", ctypes.c_int32), ("J", ctypes.c_int32), ("R", ctypes.c_int32), ("H", ctypes.c_int32), ("A", ctypes.c_int32),
+        ("S", ctypes.c_int32), ("actor_hidden", ctypes.c_int32), ("greedy_only", ctypes.c_int32),
+        ("h0", ctypes.c_void_p), ("fc1_w", ctypes.c_void_p), ("fc1_b", ctypes.c_void_p),
+        ("w_ih", ctypes.c_void_p), ("b_ih", ctypes.c_void_p), ("w_hh", ctypes.c_void_p), ("b_hh", ctypes.c_void_p),
+        ("a1_w", ctypes.c_void_p), ("a1_b", ctypes.c_void_p), ("a2_w", ctypes.c_void_p), ("a2_b", ctypes.c_void_p),
+        ("a3_w", ctypes.c_void_p), ("a3_b", ctypes.c_void_p),
+        ("W1", ctypes.c_void_p), ("w1_ld", ctypes.c_int64), ("b1", ctypes.c_void_p), ("w2", ctypes.c_void_p), ("b2", ctypes.c_void_p),
+        ("avail", ctypes.c_void_p), ("avail_elem_size", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("av_se", ctypes.c_int64), ("av_sj", ctypes.c_int64), ("av_sa", ctypes.c_int64),
+        ("eps", ctypes.c_void_p), ("seed", ctypes.c_uint64), ("counter_base", ctypes.c_void_p),
+        ("state", ctypes.c_void_p), ("st_se", ctypes.c_int64), ("step", ctypes.c_void_p),
+        ("positions", ctypes.c_void_p), ("position_columns", ctypes.c_void_p),
+        ("n_frames", ctypes.c_int32), ("n_pos", ctypes.c_int32), ("tile", ctypes.c_int32), ("reserved2", ctypes.c_int32),
+        ("hidden", ctypes.c_void_p), ("T_out", ctypes.c_void_p), ("P_out", ctypes.c_void_p), ("h_final", ctypes.c_void_p),
+    ]
+
+
 class DoubleQIO(ctypes.Structure):
     """ctypes mirror of ``macjd_doubleq_io`` (include/macjd_nets.h)."""
     _fields_ = [
@@ -607,6 +630,10 @@ def load() -> ctypes.CDLL:
     lib.macjd_agent_env_episode_moving_scan_supported.argtypes = [ctypes.c_int32] * 4
     lib.macjd_agent_env_episode_moving_scan.restype = ctypes.c_int
     lib.macjd_agent_env_episode_moving_scan.argtypes = [ctypes.c_void_p, ctypes.POINTER(AgentEnvEpisodeMovingScanIO), ctypes.c_void_p]
+    lib.macjd_agent_episode_moving_pe_supported.restype = ctypes.c_int
+    lib.macjd_agent_episode_moving_pe_supported.argtypes = [ctypes.c_int32] * 4
+    lib.macjd_agent_episode_moving_pe.restype = ctypes.c_int
+    lib.macjd_agent_episode_moving_pe.argtypes = [ctypes.POINTER(AgentEpisodeMovingPeIO), ctypes.c_void_p]
     lib.macjd_env_step_many.restype = ctypes.c_int
     lib.macjd_env_step_many.argtypes = [ctypes.c_void_p, ctypes.POINTER(StepIO), ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p]
     lib.macjd_env_step_many_timed.restype = ctypes.c_int

@@ -857,3 +857,6 @@ extern "C" int macjd_agent_episode_seq(const macjd_agent_episode_seq_io* sio, vo
 
 // closed-loop episode launch for scanning radars: agent and env in one kernel (macjd_agent_env_episode_scan)
 #include "macjd_episode_scan.h"
+
+// the agent side of an episode batch on per-env moving frames (macjd_agent_episode_moving_pe)
+#include "macjd_episode_moving_pe.h"

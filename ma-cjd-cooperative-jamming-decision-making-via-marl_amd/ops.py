@@ -563,6 +563,87 @@ def agent_env_episode_moving_scan(agent, env_args: dict, n_envs: int, n_agents: 
     del keep
 
 
+def agent_episode_moving_pe_supported(J: int, R: int, H: int, A: int) -> bool:
+    return bool(_native.load().macjd_agent_episode_moving_pe_supported(int(J), int(R), int(H), int(A)))
+
+
+def agent_episode_moving_pe(agent, env_args: dict, n_envs: int, n_agents: int, T: int, avail, eps_sched, greedy_only: bool,
+                            seed: int, counter_base, stage: dict, h0=None, h_final=None):
+    """The agent side of an episode batch on PER-ENV moving frames as one launch (csrc/macjd_episode_moving_pe.h;
+    include/macjd_nets.h, macjd_agent_episode_moving_pe_io): step t of env e observes its own state row with the position
+    columns of its own frame min(step[e] + t, F); the observation-only work (fc1, the GRU input transform, the actor) is
+    done in the kernel, once per env.  ``agent`` is the stock RNNAgent on the device, ``env_args`` what
+    ``BatchedElectromagneticEnvironment.episode_moving_pe_args()`` hands over, ``stage`` the runner's time-major staging
+    tensors, of which hidden_state, actions_discrete and actions_continuous are written (the state / obs rows are the
+    caller's).  ``eps_sched`` float32 [>= T] and ``counter_base`` int64 / uint64 [1] live on the device."""
+    keep = []
+
+    def f32(t):
+        t = t.detach()
+        t = t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
+        keep.append(t)
+        return t
+
+    io = _native.AgentEpisodeMovingPeIO()
+    H, A, S = agent.rnn_hidden_dim, agent.n_actions, agent.input_shape
+    E, J = int(n_envs), int(n_agents)
+    io.n_envs = E
+    io.T, io.J, io.R, io.H, io.A, io.S = int(T), J, int(env_args["n_radars"]), int(H), int(A), int(S)
+    io.actor_hidden, io.greedy_only = int(agent.actor_hidden_dim), 1 if greedy_only else 0
+    if h0 is not None:
+        io.h0 = f32(h0).data_ptr()
+    a, l1, l2 = agent.actor, agent.fc2_q_head[0], agent.fc2_q_head[2]
+    for name, t_ in (("fc1_w", agent.fc1.weight), ("fc1_b", agent.fc1.bias), ("w_ih", agent.rnn.weight_ih),
+                     ("b_ih", agent.rnn.bias_ih), ("w_hh", agent.rnn.weight_hh), ("b_hh", agent.rnn.bias_hh),
+                     ("a1_w", a[0].weight), ("a1_b", a[0].bias), ("a2_w", a[2].weight), ("a2_b", a[2].bias),
+                     ("a3_w", a[4].weight), ("a3_b", a[4].bias), ("b1", l1.bias), ("w2", l2.weight.reshape(-1)),
+                     ("b2", l2.bias.reshape(-1))):
+        setattr(io, name, f32(t_).data_ptr())
+    W1 = l1.weight.detach()
+    W1 = W1 if (W1.dtype == torch.float32 and W1.stride(-1) == 1) else W1.float().contiguous()
+    keep.append(W1)
+    io.W1, io.w1_ld = W1.data_ptr(), W1.stride(0)
+    dev = W1.device
+    if avail is not None:
+        if avail.dtype not in (torch.int32, torch.int64):
+            avail = avail.to(torch.int32)
+        keep.append(avail)
+        io.avail, io.avail_elem_size = avail.data_ptr(), avail.element_size()
+        io.av_se, io.av_sj, io.av_sa = avail.stride(0), avail.stride(1), avail.stride(2)
+    if eps_sched is not None:
+        assert eps_sched.dtype == torch.float32 and eps_sched.numel() >= T and eps_sched.is_contiguous()
+        io.eps = eps_sched.data_ptr()
+    io.seed = int(seed) & (2 ** 64 - 1)
+    if counter_base is not None:
+        assert counter_base.dtype in (torch.int64, torch.uint64) and counter_base.numel() >= 1
+        io.counter_base = counter_base.data_ptr()
+    state, step, pos, cols = env_args["state"], env_args["step"], env_args["positions"], env_args["position_columns"]
+    F, n_pos, tile = int(env_args["n_frames"]), int(env_args["n_pos"]), int(env_args["tile"])
+    assert state.dtype == torch.float32 and state.dim() == 2 and state.shape[0] >= E and state.shape[1] >= S \
+        and state.stride(1) == 1 and state.device == dev
+    assert pos.dtype == torch.float32 and pos.is_contiguous() and pos.device == dev \
+        and pos.numel() >= ((E + tile - 1) // tile) * (F + 1) * n_pos * tile
+    assert cols.dtype == torch.int32 and cols.is_contiguous() and cols.numel() == n_pos and cols.device == dev
+    io.state, io.st_se = state.data_ptr(), state.stride(0)
+    if step is not None:
+        assert step.dtype == torch.int32 and step.is_contiguous() and step.numel() >= E and step.device == dev
+        io.step = step.data_ptr()
+    io.positions, io.position_columns = pos.data_ptr(), cols.data_ptr()
+    io.n_frames, io.n_pos, io.tile = F, n_pos, tile
+    sizes = {"hidden_state": (T * E * J * H, torch.float32), "actions_discrete": (T * E * J, torch.int32),
+             "actions_continuous": (T * E * J, torch.float32)}
+    for k, (n, dt) in sizes.items():
+        t_ = stage[k]
+        assert t_.is_contiguous() and t_.device == dev and t_.numel() >= n and t_.dtype == dt, k
+    io.hidden, io.T_out, io.P_out = stage["hidden_state"].data_ptr(), stage["actions_discrete"].data_ptr(), stage["actions_continuous"].data_ptr()
+    if h_final is not None:
+        assert h_final.is_contiguous() and h_final.dtype == torch.float32 and h_final.numel() == E * J * H
+        io.h_final = h_final.data_ptr()
+    with torch.cuda.device(dev):
+        _native.check(_native.load().macjd_agent_episode_moving_pe(ctypes.byref(io), _stream(W1)), "macjd_agent_episode_moving_pe")
+    del keep
+
+
 def gru_sequence_reference(gi: torch.Tensor, w_hh: torch.Tensor, b_hh: torch.Tensor,
                            h0: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Step-by-step GRU recurrence with stock torch ops (host tensors / numerics tests).

@@ -354,6 +354,9 @@ class BatchedEpisodeRunner:
         if device_schedule and self.closed_loop_moving_rollout and self.closed_loop_moving_available():
             self._closed_loop_launch(T)   # moving scenario under scanning radars: one launch on the frame tables
             return
+        if device_schedule and self.moving_pe_episode_rollout and self.moving_pe_rollout_available():
+            self._moving_pe_launches(T)   # per-env moving batch: the agent's steps on every env's own frames, the env's steps
+            return
         for t in range(T):
             if device_schedule:
                 self.mac.device_schedule = (self._eps_sched[t:t + 1], self._ctr_base, t + 1)
@@ -578,7 +581,7 @@ class BatchedEpisodeRunner:
             return False
         if getattr(env, "scenario_batch", None) is not None or getattr(env, "kernel_flags", 0) != 0:
             return False
-        if getattr(env, "moving_batch", None) is not None:   # per-env frames: no one state row per step; the step loop only
+        if getattr(env, "moving_batch", None) is not None:   # per-env frames: no one state row per step (rollout_moving_pe's ground)
             return False
         if not (hasattr(env, "step_many_has_production_form") and env.step_many_has_production_form()):
             return False
@@ -640,6 +643,80 @@ class BatchedEpisodeRunner:
         env.step_many(st["actions_discrete"][:n], st["actions_continuous"][:n], st["reward"][:n], st["terminated"][:n],
                       self._rdpj_steps[:n], rdpj_sum=self._rdpj_sum)
 
+    # ---- per-env moving batches: the agent's T steps on every env's own frames as one launch, the env's T steps as another ----
+    moving_pe_episode_rollout = _OptionSwitch("MOVING_PE_EPISODE_ROLLOUT")   # default off (MACJD_MOVING_PE_EPISODE_ROLLOUT=1)
+
+    def moving_pe_rollout_available(self) -> bool:
+        """The env is a per-env moving scenario batch whose many-step launch has a production form at this size,
+        ``kernel_flags == 0``, the MAC is the stock RNNAgent on a HIP device, and the episode kernel on per-env frames
+        covers the size (``ops.agent_episode_moving_pe_supported``).  The observation of env e at step t is its own state
+        row with the positions of its own frame min(t, F), whatever the agents did, so — as on shared frames — nothing the
+        agent computes depends on the env's outputs."""
+        env = self.env
+        if self.device.type != "cuda" or getattr(env, "moving_batch", None) is None or not hasattr(env, "episode_moving_pe_args"):
+            return False
+        if getattr(env, "kernel_flags", 0) != 0:
+            return False
+        if not (hasattr(env, "step_many_has_production_form") and env.step_many_has_production_form()):
+            return False
+        agent = getattr(self.mac, "agent", None)
+        if agent is None or not hasattr(agent, "fc2_q_head") or not hasattr(agent, "actor") or not next(agent.parameters()).is_cuda:
+            return False
+        from .. import ops
+        return (getattr(agent, "actor_hidden_dim", 0) == 128 and agent.input_shape == env.state_dim and env.state_dim <= 48
+                and ops.agent_episode_moving_pe_supported(self.n_agents, env.num_radars, agent.rnn_hidden_dim, agent.n_actions))
+
+    def rollout_moving_pe(self, test_mode=False, n_steps=None):
+        """One episode batch (or its first ``n_steps`` steps) of a per-env moving scenario batch in TWO launches (+ the
+        counter update): ``ops.agent_episode_moving_pe`` (the agent's steps, env e's step t on its own frame min(t, F), the
+        observation-only work inside the kernel) and ``env.step_many`` (the per-env moving many-step launch).  Same staging
+        rows, exploration draws (row, episode * (T + 1) + t + 1) and Monte-Carlo streams as the step-by-step path; hidden
+        states / Q-values / powers differ from it by the summation order of the matrix products (~1e-7), which can flip an
+        arg-max only on a near-tie."""
+        if not self.moving_pe_rollout_available():
+            raise RuntimeError("rollout_moving_pe: not available for this environment / agent (moving_pe_rollout_available())")
+        T = self.episode_limit
+        n = T if n_steps is None else int(n_steps)
+        if not 1 <= n <= T:
+            raise ValueError(f"rollout_moving_pe: n_steps must be in 1..{T}, got {n_steps}")
+        if getattr(self, "_eps_sched", None) is None:
+            self._eps_sched = torch.zeros(T, dtype=torch.float32, device=self.device)
+            self._ctr_base = torch.zeros(1, dtype=torch.int64, device=self.device)
+        if not test_mode and n in (getattr(self, "_graphs", None) or {}):
+            return self.rollout_graphed(n)
+        self._upload_eps_schedule(self._eps_schedule(n, test_mode))
+        self.begin_episodes()                       # episode index, zero hidden state, env reset (every env's frame 0)
+        self._ctr_base.fill_(self._ep * (T + 1))
+        self._moving_pe_launches(n, test_mode=test_mode)
+        self.t_env += n
+
+    def _moving_pe_launches(self, n, test_mode=False):
+        """The launches of ``rollout_moving_pe`` for the first ``n`` steps (behind ``begin_episodes``).  Every rollout starts
+        from a reset, so state / obs row t of env e is always its state row with ``frame_positions()[e, min(t, F)]`` and the
+        availability rows are constant: the staging rows are filled once (rows below the largest ``n`` so far).  Nothing is
+        cached from the weights."""
+        from .. import ops
+        st, mac, env = self.stage, self.mac, self.env
+        E, J, T = self.batch_envs, self.n_agents, self.episode_limit
+        env_args = env.episode_moving_pe_args()
+        done = getattr(self, "_pe_frames_filled", 0)
+        if n > done:
+            fp = env.frame_positions()                                # [E, F + 1, n_pos]
+            cols = env_args["position_columns"].to(torch.int64)
+            k = torch.clamp(torch.arange(done, n, device=self.device), max=env_args["n_frames"])
+            rows = env.get_state().unsqueeze(0).repeat(n - done, 1, 1)   # [n - done, E, S]: the static columns
+            rows[:, :, cols] = fp[:, k].permute(1, 0, 2)
+            st["state"][done:n] = rows
+            st["obs"][done:n] = rows.unsqueeze(2)
+            st["avail_actions"][done:n] = env.get_avail_actions()
+            self._pe_frames_filled = n
+        if getattr(self, "_rdpj_steps", None) is None:
+            self._rdpj_steps = torch.zeros((T, E, 3), dtype=torch.float32, device=self.device)
+        ops.agent_episode_moving_pe(mac.agent, env_args, E, J, n, self._avail, self._eps_sched, bool(test_mode), mac.select_seed,
+                                    self._ctr_base, st, h_final=mac.hidden_states)
+        env.step_many(st["actions_discrete"][:n], st["actions_continuous"][:n], st["reward"][:n], st["terminated"][:n],
+                      self._rdpj_steps[:n], rdpj_sum=self._rdpj_sum)
+
     def run(self, test_mode=False, store=True, sync_stats=True):
         """One batch of E episodes.  Returns the reference's ``run_info`` keys as means over the E
         episodes (one host sync at the very end; pass ``sync_stats=False`` to get 0-dim tensors)."""
@@ -655,6 +732,8 @@ class BatchedEpisodeRunner:
             self.rollout_moving(test_mode=test_mode)
         elif self.closed_loop_moving_rollout and self.closed_loop_moving_available():
             self.rollout_closed_loop_moving(test_mode=test_mode)
+        elif self.moving_pe_episode_rollout and self.moving_pe_rollout_available():
+            self.rollout_moving_pe(test_mode=test_mode)
         elif getattr(self, "_graph", None) is not None and not test_mode:
             self.rollout_graphed()
         else:

@@ -636,12 +636,37 @@ class BatchedElectromagneticEnvironment:
                 "motion_scan_io": self._motion_scan_io, "track": self._track, "step": self._step, "episode": self._episode,
                 "seed": self.seed, "env_offset": self.env_offset, "n_radars": self.num_radars, "pe_tables": None}
 
+    def _need_moving_batch(self, what: str) -> None:
+        if self._motion_pe_io is None:
+            raise RuntimeError(f"{what}: needs a per-env moving scenario batch (moving_batch=...)")
+
+    def episode_moving_pe_args(self) -> Dict[str, Any]:
+        """What the agent's episode launch on per-env moving frames (``ops.agent_episode_moving_pe``) needs from a per-env
+        moving scenario batch: every env's own state row (the position columns are ignored), the step counters, the tiled
+        positions table f32 [n_tiles, F + 1, n_pos, tile] with its state columns, F, n_pos and the tile width."""
+        self._need_moving_batch("episode_moving_pe_args")
+        keep, mp = self._motion_keep, self._motion_pe_io
+        return {"state": self._state_dyn, "step": self._step, "positions": keep["positions"],
+                "position_columns": keep["position_columns"], "n_frames": int(mp.n_frames), "n_pos": int(mp.n_pos),
+                "tile": int(mp.tile), "n_radars": self.num_radars}
+
+    def frame_positions(self) -> torch.Tensor:
+        """f32 [E, F + 1, n_pos] on the device (per-env moving batches only): env e's position columns at step counter k in
+        state order, untiled from the positions table — the bits the per-env moving step writes.  Built once."""
+        self._need_moving_batch("frame_positions")
+        if getattr(self, "_frame_positions", None) is None:
+            pos = self._motion_keep["positions"]                    # [n_tiles, F + 1, n_pos, tile]
+            n_tiles, F1, n_pos, w = pos.shape
+            self._frame_positions = pos.permute(0, 3, 1, 2).reshape(n_tiles * w, F1, n_pos)[:self.batch_envs].contiguous()
+        return self._frame_positions
+
     MANY_STEP_MOVING_SIZES = ((2, 2), (3, 4), (6, 8))   # (J, R) of csrc/macjd_env_motion.hip, motion_size_compiled
 
     def step_many_has_production_form(self) -> bool:
         """A moving env's ``step_many`` exists in the production form only (the lane kernel at a compiled size; any other
-        size is refused by the launch): True when this env moves and its size is one of them."""
-        return (self._motion_io is not None and self._motion_scan_io is None
+        size is refused by the launch): True when this env moves — on shared frames or as a per-env moving batch, whose
+        many-step launch is compiled at the same sizes — and its size is one of them."""
+        return ((self._motion_io is not None or self._motion_pe_io is not None) and self._motion_scan_io is None
                 and (self.num_jammers, self.num_radars) in self.MANY_STEP_MOVING_SIZES)
 
     def _refuse_scanning(self, what: str) -> None:
