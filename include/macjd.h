@@ -379,6 +379,57 @@ typedef struct macjd_motion_pe_compile_desc {
     float*   positions;
 } macjd_motion_pe_compile_desc;
 
+/*
+ * PER-ENV moving scenarios under SCANNING radars (opt-in): the beam tables of macjd_motion_scan_io in the tiled per-env layout
+ * of macjd_motion_pe_io, the frame index between tile and row (tile = macjd_motion_pe_io.tile, F = its n_frames):
+ *   scan_frames    float64 [n_tiles, F, MACJD_PE_SCAN_ROWS(R,J), tile], rows in the order of macjd_scan_pe_io.tables;
+ *   pattern_frames float64 [n_tiles, F, MACJD_PE_SCAN_PATTERN_ROWS(R,L), tile], rows in the order of
+ *                  macjd_scan_pe_pattern_io.tables; given exactly when n_levels > 0.
+ * Row t of frame f of env e at table[(((e / tile) * F + f) * ROWS + t) * tile + e % tile]; the last tile is padded.
+ */
+typedef struct macjd_motion_scan_pe_io {
+    const double* scan_frames;
+    const double* pattern_frames;   /* optional */
+    int32_t n_levels, reserved;     /* L, 0 without pattern_frames */
+} macjd_motion_scan_pe_io;
+
+/*
+ * The device compiler of the beam frames (macjd_motion_scan_pe_compile): ONE launch, item (e, f) for f in 0..F-1 writes the
+ * scan rows (and, L > 0, the level rows) of frame f of env e.  It runs AFTER macjd_motion_pe_compile on the same stream and
+ * reads that compiler's outputs — the GaPs, Pn, pd_no and gr rows of `frames` and `frame_snr_no` (required here) — its
+ * input `in_tables` (the float64 start positions and v dt rows), and one more column per env, scan_in, float64
+ * [n_tiles, MACJD_MOTION_SCAN_PE_IN_ROWS(R,L), tile] in the same tiled layout, rows in the order
+ *   half_beam[R] | sweep[R] | sweep_mod[R] | az0[R] | rho | inv_width[R] | rho_lvl[L]      (the last two blocks only when L > 0)
+ * with rho = 10^(sidelobe_db / 10), rho_lvl[k] = 10^(gain_db[k] / 10) and inv_width as the host's scan compiler forms them.
+ * Arithmetic of an item, plain IEEE float64 in this order (no fused multiply-add), fd = (double)f:
+ *   position per axis  p = p0 + fd * vdt   (macjd_motion_pe_compile's expression: the same bits);
+ *   bearing of object o from radar r:  a = atan2(oy - ry, ox - rx);  d = a * deg_per_rad;  b = d - 360.0 * floor(d / 360.0);
+ *             bear_tgt[r] takes the target, bear_jam[j * R + r] jammer j;
+ *   side lobe: gr_side = gr * rho;  GaPs_side = GaPs * (rho * rho);  snr_no_side = max(0, Pn > 1e-18 ? GaPs_side / Pn : 0);
+ *             pd_no_side = the all-float64 detection probability of the step kernels;
+ *   levels k = 1..L: the same four expressions with rho_lvl[k - 1];
+ *   copies, bits unchanged: level 0 = the main rows (GaPs, frame_snr_no, pd_no, gr), level L + 1 = the side rows; half_beam,
+ *             sweep, sweep_mod, az0 and inv_width copied through; the snr_no row = the frame's frame_snr_no.
+ * The device library's atan2 is the only step IEEE 754 does not pin: bearings agree with the host within rounding, every
+ * other row but the pd_no rows bit for bit.  Lanes of the last tile's padding and bytes outside the tables are not written.
+ */
+#define MACJD_MOTION_SCAN_PE_IN_ROWS(R, L) (4 * (R) + 1 + ((L) > 0 ? (R) + (L) : 0))
+typedef struct macjd_motion_scan_pe_compile_desc {
+    int64_t n_envs;                /* E */
+    int32_t n_radars, n_jammers;   /* R, J */
+    int32_t n_frames;              /* F, 1..65534 */
+    int32_t tile;                  /* >= 1 */
+    int32_t n_levels, reserved;    /* L, 0..MACJD_MAX_PATTERN_LEVELS */
+    double  deg_per_rad;           /* 180 / pi as the host evaluates it */
+    double  pd_A, pd_c1, pd_denB;  /* the Pd constants of macjd_scenario_desc */
+    const double* in_tables;       /* macjd_motion_pe_compile_desc.in_tables */
+    const double* scan_in;
+    const double* frames;          /* written by macjd_motion_pe_compile */
+    const double* frame_snr_no;    /* likewise; required */
+    double* scan_frames;
+    double* pattern_frames;        /* exactly when n_levels > 0 */
+} macjd_motion_scan_pe_compile_desc;
+
 /* library / device */
 int         macjd_abi_version(void);
 const char* macjd_last_error(void);
@@ -504,6 +555,27 @@ int macjd_motion_pe_compile(const macjd_motion_pe_compile_desc* desc, void* hip_
    One lane per env; sizes and variants as macjd_env_step_moving. */
 int macjd_env_step_moving_scan(const macjd_scenario* s, const macjd_step_io* io, const macjd_motion_io* motion,
                                const macjd_scan_io* scan, const macjd_motion_scan_io* motion_scan, void* hip_stream);
+
+/* macjd_env_step_moving_scan on PER-ENV frame tables (see macjd_motion_pe_io, macjd_motion_scan_pe_io): env e runs frame
+   f_e = min(step[e], F - 1) of its OWN tables — the step's rows from motion_pe->frames / frame_flags, every scan row from
+   scan_frames, the level rows from pattern_frames — with bear_tgt of that frame, and the same launch writes (float)theta_a'
+   into scan->state's theta_a columns (when given), positions of frame min(step[e] + 1, F) into the position columns of
+   motion_pe->state and the per-step SNR without jamming into scan->snr_no (when given).  io->pe_tables and
+   motion_pe->snr_no must be NULL; scan->state, when given, must equal motion_pe->state; the handle must be a scanning handle
+   (pattern levels of the handle are accepted only if their L equals n_levels, and are never read).  Results are bit-identical
+   to macjd_env_step_scan_pe(_pattern) on per-env tables whose column for env e holds env e's frame f_e, in the same
+   (production or general all-float64) form.  The outcome depends on the past through theta_a: there is no many-step form.
+   One lane per env; sizes and variants as macjd_env_step_moving. */
+int macjd_env_step_moving_scan_pe(const macjd_scenario* s, const macjd_step_io* io, const macjd_motion_pe_io* motion_pe,
+                                  const macjd_scan_io* scan, const macjd_motion_scan_pe_io* motion_scan_pe, void* hip_stream);
+/* beam part of a reset on per-env beam frames, issued next to macjd_env_reset and macjd_env_reset_moving_pe with the same
+   mask: theta_a[e,r] = the az0 row of env e's frame 0 (and the state columns = (float)az0) for envs with mask != 0 */
+int macjd_env_reset_moving_scan_pe(const macjd_scenario* s, int64_t n_envs, const macjd_scan_io* scan,
+                                   const macjd_motion_scan_pe_io* motion_scan_pe, int32_t n_frames, int32_t tile,
+                                   const uint8_t* mask, void* hip_stream);
+/* the device compiler of the beam frames (see macjd_motion_scan_pe_compile_desc): one launch after macjd_motion_pe_compile
+   on the same stream, no handle */
+int macjd_motion_scan_pe_compile(const macjd_motion_scan_pe_compile_desc* desc, void* hip_stream);
 
 /* timing helper for bench.py: `iters` back-to-back env_step launches, replayed from one HIP graph on a private
    stream after the work queued on `hip_stream` has finished (as the benchmark's rollout replays them, so the

@@ -47,6 +47,7 @@ EXPORTS = [
     "macjd_env_step_moving", "macjd_env_step_many_moving", "macjd_env_reset_moving", "macjd_env_step_moving_scan",
     "macjd_agent_episode_seq_supported", "macjd_agent_episode_seq",
     "macjd_env_step_moving_pe", "macjd_env_step_many_moving_pe", "macjd_env_reset_moving_pe", "macjd_motion_pe_compile",
+    "macjd_env_step_moving_scan_pe", "macjd_env_reset_moving_scan_pe", "macjd_motion_scan_pe_compile",
 ]
 
 
@@ -157,6 +158,25 @@ class MotionScanIO(ctypes.Structure):
     with scanning beams."""
     _fields_ = [("scan_frames", ctypes.c_void_p), ("pattern_frames", ctypes.c_void_p),
                 ("n_levels", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class MotionScanPeIO(ctypes.Structure):
+    """ctypes mirror of ``macjd_motion_scan_pe_io`` (include/macjd.h): the scan and pattern frames of a per-env moving scenario
+    batch under scanning radars, in the tiled per-env layout (frame index between tile and row)."""
+    _fields_ = [("scan_frames", ctypes.c_void_p), ("pattern_frames", ctypes.c_void_p),
+                ("n_levels", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class MotionScanPeCompileDesc(ctypes.Structure):
+    """ctypes mirror of ``macjd_motion_scan_pe_compile_desc`` (include/macjd.h): the arguments of the device compiler of the
+    beam frames."""
+    _fields_ = [
+        ("n_envs", ctypes.c_int64), ("n_radars", ctypes.c_int32), ("n_jammers", ctypes.c_int32),
+        ("n_frames", ctypes.c_int32), ("tile", ctypes.c_int32), ("n_levels", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("deg_per_rad", ctypes.c_double), ("pd_A", ctypes.c_double), ("pd_c1", ctypes.c_double), ("pd_denB", ctypes.c_double),
+        ("in_tables", ctypes.c_void_p), ("scan_in", ctypes.c_void_p), ("frames", ctypes.c_void_p),
+        ("frame_snr_no", ctypes.c_void_p), ("scan_frames", ctypes.c_void_p), ("pattern_frames", ctypes.c_void_p),
+    ]
 
 
 class QheadIO(ctypes.Structure):
@@ -587,6 +607,15 @@ def load() -> ctypes.CDLL:
     lib.macjd_env_step_moving_scan.restype = ctypes.c_int
     lib.macjd_env_step_moving_scan.argtypes = [ctypes.c_void_p, ctypes.POINTER(StepIO), ctypes.POINTER(MotionIO),
                                                ctypes.POINTER(ScanIO), ctypes.POINTER(MotionScanIO), ctypes.c_void_p]
+    lib.macjd_env_step_moving_scan_pe.restype = ctypes.c_int
+    lib.macjd_env_step_moving_scan_pe.argtypes = [ctypes.c_void_p, ctypes.POINTER(StepIO), ctypes.POINTER(MotionPeIO),
+                                                  ctypes.POINTER(ScanIO), ctypes.POINTER(MotionScanPeIO), ctypes.c_void_p]
+    lib.macjd_env_reset_moving_scan_pe.restype = ctypes.c_int
+    lib.macjd_env_reset_moving_scan_pe.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ScanIO),
+                                                   ctypes.POINTER(MotionScanPeIO), ctypes.c_int32, ctypes.c_int32,
+                                                   ctypes.c_void_p, ctypes.c_void_p]
+    lib.macjd_motion_scan_pe_compile.restype = ctypes.c_int
+    lib.macjd_motion_scan_pe_compile.argtypes = [ctypes.POINTER(MotionScanPeCompileDesc), ctypes.c_void_p]
     lib.macjd_env_step.argtypes = [ctypes.c_void_p, ctypes.POINTER(StepIO), ctypes.c_void_p]
     lib.macjd_env_step_timed.restype = ctypes.c_int
     lib.macjd_env_step_timed.argtypes = [ctypes.c_void_p, ctypes.POINTER(StepIO), ctypes.c_int, ctypes.c_void_p,

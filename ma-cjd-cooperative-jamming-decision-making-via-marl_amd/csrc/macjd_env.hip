@@ -1247,6 +1247,109 @@ int macjd_env_step_moving_scan(const macjd_scenario* s, const macjd_step_io* io,
     return launch_step_moving_scan(s, io, motion, scan, motion_scan, (hipStream_t)hip_stream, me);
 }
 
+// ---- per-env moving scenarios under scanning radars (include/macjd.h, macjd_motion_scan_pe_io; kernels in
+// macjd_env_motion_scan_pe.hip) ----
+
+static int validate_motion_scan_pe(const macjd_scenario* s, const macjd_motion_scan_pe_io* ms, const char* me) {
+    if (!ms || !ms->scan_frames) return set_err(MACJD_EINVAL, "%s: NULL motion scan io / scan_frames", me);
+    if (ms->n_levels < 0 || ms->n_levels > MACJD_MAX_PATTERN_LEVELS)
+        return set_err(MACJD_EINVAL, "%s: n_levels outside 0..MACJD_MAX_PATTERN_LEVELS", me);
+    if (s->host.pat_levels > 0 && s->host.pat_levels != ms->n_levels)
+        return set_err(MACJD_EINVAL, "%s: n_levels differs from the pattern levels of the scenario handle", me);
+    if ((ms->pattern_frames != nullptr) != (ms->n_levels > 0))
+        return set_err(MACJD_EINVAL, "%s: pattern_frames and n_levels > 0 go together (both or neither)", me);
+    return MACJD_OK;
+}
+
+// Always the lane kernel on the per-env frame tables: the production variant or the general one at the compiled sizes, the
+// generic-size kernel for the others
+static int launch_step_moving_scan_pe(const macjd_scenario* s, const macjd_step_io* io, const macjd_motion_io* mo, int32_t tile,
+                                      const macjd_scan_io* sc, const macjd_motion_scan_pe_io* mp, hipStream_t stream, const char* who) {
+    const int64_t E = io->n_envs;
+    const int J = s->host.J, R = s->host.R;
+    const LaneGrid lg = lane_grid(E);
+    const dim3 gf((unsigned)lg.blocks), g(lg.strided), b(lg.block);
+    const bool fast = macjd::motion_size_compiled(J, R) && production_io(io, J, R, lg.blocks, 0, 0) && scan_spans_ok(sc, E, R) &&
+                      motion_spans_ok(mo, E, R) && E < ((int64_t)1 << 31);
+    macjd_motion_scan_io ms{};   // the shared-frame block with the same members: fill_motion_scan serves both
+    ms.scan_frames = mp->scan_frames; ms.pattern_frames = mp->pattern_frames; ms.n_levels = mp->n_levels;
+    if (ms.pattern_frames) {
+        if (fast) {
+            macjd::MotionScanPeStepIO<macjd::ScanPePatStepIO<macjd::FastStepIO>> f{};
+            fill_fast(f, io, 0, 0);
+            fill_motion_scan(f, mo, sc, &ms);
+            fill_motion_scan_pattern(f, &ms);
+            f.mv_tile = tile;
+            (void)macjd::launch_motion_scan_pe_pattern_fast(J, R, gf, b, stream, s->dev, f);
+        } else {
+            macjd::MotionScanPeStepIO<macjd::ScanPePatStepIO<macjd_step_io>> w{};
+            static_cast<macjd_step_io&>(w) = *io;
+            fill_motion_scan(w, mo, sc, &ms);
+            fill_motion_scan_pattern(w, &ms);
+            w.mv_tile = tile;
+            macjd::launch_motion_scan_pe_pattern_general(J, R, g, b, stream, s->dev, w);
+        }
+    } else if (fast) {
+        macjd::MotionScanPeStepIO<macjd::ScanPeStepIO<macjd::FastStepIO>> f{};
+        fill_fast(f, io, 0, 0);
+        fill_motion_scan(f, mo, sc, &ms);
+        f.mv_tile = tile;
+        (void)macjd::launch_motion_scan_pe_fast(J, R, gf, b, stream, s->dev, f);
+    } else {
+        macjd::MotionScanPeStepIO<macjd::ScanPeStepIO<macjd_step_io>> w{};
+        static_cast<macjd_step_io&>(w) = *io;
+        fill_motion_scan(w, mo, sc, &ms);
+        w.mv_tile = tile;
+        macjd::launch_motion_scan_pe_general(J, R, g, b, stream, s->dev, w);
+    }
+    return launch_status(who);
+}
+
+int macjd_env_step_moving_scan_pe(const macjd_scenario* s, const macjd_step_io* io, const macjd_motion_pe_io* motion_pe,
+                                  const macjd_scan_io* scan, const macjd_motion_scan_pe_io* motion_scan_pe, void* hip_stream) {
+    const char* me = "macjd_env_step_moving_scan_pe";
+    int rc = validate_io(s, io);
+    if (rc != MACJD_OK) return rc;
+    macjd_motion_io mo;
+    rc = validate_motion_pe(s, motion_pe, &mo, me);
+    if (rc != MACJD_OK) return rc;
+    rc = validate_scan(s, scan, me);   // (refuses a handle that is not a scanning handle)
+    if (rc != MACJD_OK) return rc;
+    rc = validate_motion_scan_pe(s, motion_scan_pe, me);
+    if (rc != MACJD_OK) return rc;
+    if (io->pe_tables) return set_err(MACJD_EINVAL, "%s: io->pe_tables must be NULL (the frames are the tables)", me);
+    if (mo.snr_no)
+        return set_err(MACJD_EINVAL, "%s: motion_pe->snr_no must be NULL (the per-step value travels in scan->snr_no)", me);
+    if (scan->state && scan->state != mo.state)
+        return set_err(MACJD_EINVAL, "%s: scan->state and motion_pe->state must be the same rows", me);
+    if (scan->state && scan->st_se != mo.st_se)
+        return set_err(MACJD_EINVAL, "%s: scan->st_se and motion_pe->st_se must be the same row stride", me);
+    if (io->flags & MACJD_STEP_SLOT_KERNEL)
+        return set_err(MACJD_EUNSUPPORTED, "%s: the (env x slot) kernel has no moving variant (one lane per env only)", me);
+    if (io->n_envs == 0) return MACJD_OK;
+    return launch_step_moving_scan_pe(s, io, &mo, motion_pe->tile, scan, motion_scan_pe, (hipStream_t)hip_stream, me);
+}
+
+int macjd_env_reset_moving_scan_pe(const macjd_scenario* s, int64_t n_envs, const macjd_scan_io* scan,
+                                   const macjd_motion_scan_pe_io* motion_scan_pe, int32_t n_frames, int32_t tile,
+                                   const uint8_t* mask, void* hip_stream) {
+    const char* me = "macjd_env_reset_moving_scan_pe";
+    if (!s || n_envs < 0) return set_err(MACJD_EINVAL, "%s: bad argument", me);
+    int rc = validate_scan(s, scan, me);
+    if (rc != MACJD_OK) return rc;
+    rc = validate_motion_scan_pe(s, motion_scan_pe, me);
+    if (rc != MACJD_OK) return rc;
+    if (n_frames < 1) return set_err(MACJD_EINVAL, "%s: n_frames < 1", me);
+    if (tile < 1) return set_err(MACJD_EINVAL, "%s: tile < 1", me);
+    if (n_envs == 0) return MACJD_OK;
+    int64_t grid = (n_envs + 255) / 256;
+    if (grid > 4096) grid = 4096;
+    macjd::launch_motion_scan_pe_reset(dim3((unsigned)grid), dim3(256), (hipStream_t)hip_stream, n_envs, s->host.R, s->host.J,
+                                       n_frames, tile, motion_scan_pe->scan_frames, scan->theta_a, scan->a_se, scan->a_sx,
+                                       scan->state, scan->st_se, scan->st_col0, scan->st_col_step, mask);
+    return launch_status(me);
+}
+
 static int env_step_timed_impl(const macjd_scenario* s, const macjd_step_io* io, int iters, void* hip_stream,
                                float* ms_per_launch, int32_t many_T, int64_t t_stride);
 

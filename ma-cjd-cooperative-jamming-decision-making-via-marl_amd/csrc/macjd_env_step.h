@@ -1,5 +1,5 @@
 // The one-lane-per-env step kernel (env_step_kernel) with its argument blocks: a header, so that a second translation unit
-// (macjd_env_scan_pe.hip, macjd_env_motion.hip, macjd_env_motion_pe.hip, macjd_env_motion_scan.hip) can instantiate it with another unrolling directive on its size-bounded
+// (macjd_env_scan_pe.hip, macjd_env_motion.hip, macjd_env_motion_pe.hip, macjd_env_motion_scan.hip, macjd_env_motion_scan_pe.hip) can instantiate it with another unrolling directive on its size-bounded
 // loops.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -161,12 +161,22 @@ template <class Base>
 struct MotionPeStepIO : MotionStepIO<Base> {
     int32_t mv_tile, mv_reserved;
 };
+// Argument block of a MOVING SCANNING launch on PER-ENV frame tables (include/macjd.h, macjd_motion_scan_pe_io):
+// MotionScanStepIO's members with every table — frames, flags, positions, scan rows, pattern rows — in the tiled per-env
+// layout, the frame index between tile and row; mv_tile = envs per tile.  A type of its own: the shared-frame moving-scanning
+// instantiations keep their argument block and code (their scan / pattern column strides stay the constant 1).
+template <class ScanBase>
+struct MotionScanPeStepIO : MotionScanStepIO<ScanBase> {
+    int32_t mv_tile, mv_reserved;
+};
 template <class IO> struct io_moves : std::false_type {};
 template <class Base> struct io_moves<MotionStepIO<Base>> : std::true_type {};
 template <class Base> struct io_moves<MotionPeStepIO<Base>> : std::true_type {};
 template <class IO> struct io_moves_pe : std::false_type {};
 template <class Base> struct io_moves_pe<MotionPeStepIO<Base>> : std::true_type {};
 template <class ScanBase> struct io_moves<MotionScanStepIO<ScanBase>> : std::true_type {};
+template <class ScanBase> struct io_moves<MotionScanPeStepIO<ScanBase>> : std::true_type {};
+template <class ScanBase> struct io_moves_pe<MotionScanPeStepIO<ScanBase>> : std::true_type {};
 
 // Per-lane pattern state of an env-step: the number of levels and the target's level at each radar, four bits per radar
 // in 64-bit words (word r >> 4; shifts only, so the per-lane index of the PD32 re-evaluation loop — compiled sizes,
@@ -241,7 +251,8 @@ __global__ void __launch_bounds__(256) env_step_kernel(const DevTables* __restri
     // position columns of the env's state row.
     static_assert(!MOV || PE, "MOV: the per-env-table path of the step");
     // MOV on per-env frame tables (IO = MotionPeStepIO<...>; include/macjd.h, macjd_motion_pe_io): the same path with MotionStepIO
-    // generalised by an env tile — row stride = tile, tile index (e / tile) * F + f, column e % tile.
+    // generalised by an env tile — row stride = tile, tile index (e / tile) * F + f, column e % tile.  With SCAN
+    // (IO = MotionScanPeStepIO<...>; macjd_motion_scan_pe_io) the scan and pattern rows take the same stride, tile and column.
     constexpr bool MVPE = io_moves_pe<IO>::value;
     constexpr int NJ = JT ? JT : MAXJ;
     constexpr int NR = RT ? RT : MAXR;
@@ -422,7 +433,8 @@ __global__ void __launch_bounds__(256) env_step_kernel(const DevTables* __restri
         const double* __restrict__ sp = nullptr;
         int64_t sps = 0;
         if constexpr (SPE) {
-            if constexpr (MOV) sps = 1;   // frame-major: one contiguous block per frame
+            if constexpr (MVPE) sps = mv_ps;   // per-env frames: row stride = the env tile
+            else if constexpr (MOV) sps = 1;   // frame-major: one contiguous block per frame
             else sps = io.pe_tile > 0 ? (int64_t)io.pe_tile : io.sp_stride;
             sp = io.sp_tables + pe_tile_idx * (10 * R + J * R) * sps + pe_col;
         }
@@ -436,7 +448,8 @@ __global__ void __launch_bounds__(256) env_step_kernel(const DevTables* __restri
         const double* __restrict__ pp = nullptr;
         int64_t pps = 0, pp_lv = 0;   // pp_lv = (L + 2) R: rows of one level table
         if constexpr (SPP) {
-            if constexpr (MOV) pps = 1;
+            if constexpr (MVPE) pps = mv_ps;
+            else if constexpr (MOV) pps = 1;
             else pps = io.pe_tile > 0 ? (int64_t)io.pe_tile : io.pp_stride;
             pp_lv = (int64_t)(io.pat_levels + 2) * R;
             pp = io.pp_tables + pe_tile_idx * (R + 4 * pp_lv) * pps + pe_col;
@@ -1006,5 +1019,20 @@ bool launch_motion_scan_pattern_fast(int J, int R, dim3 grid, dim3 block, hipStr
                                      const MotionScanStepIO<ScanPePatStepIO<FastStepIO>>& io);
 void launch_motion_scan_pattern_general(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
                                         const MotionScanStepIO<ScanPePatStepIO<macjd_step_io>>& io);
+
+// macjd_env_motion_scan_pe.hip: the MOV && SCAN instantiations on per-env frame tables (include/macjd.h,
+// macjd_motion_scan_pe_io), with and without PAT, the beam part of their reset and the device compiler of the beam frames.
+// Same sizes and return convention as the launchers of macjd_env_motion.hip.
+bool launch_motion_scan_pe_fast(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
+                                const MotionScanPeStepIO<ScanPeStepIO<FastStepIO>>& io);
+void launch_motion_scan_pe_general(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
+                                   const MotionScanPeStepIO<ScanPeStepIO<macjd_step_io>>& io);
+bool launch_motion_scan_pe_pattern_fast(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
+                                        const MotionScanPeStepIO<ScanPePatStepIO<FastStepIO>>& io);
+void launch_motion_scan_pe_pattern_general(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
+                                           const MotionScanPeStepIO<ScanPePatStepIO<macjd_step_io>>& io);
+void launch_motion_scan_pe_reset(dim3 grid, dim3 block, hipStream_t stream, int64_t n_envs, int R, int J, int n_frames, int tile,
+                                 const double* scan_frames, double* theta_a, int64_t a_se, int64_t a_sx, float* state,
+                                 int64_t st_se, int32_t st_col0, int32_t st_col_step, const uint8_t* mask);
 
 }  // namespace macjd

@@ -28,6 +28,10 @@ What is added (build flags, all optional):
                   threat levels, powers and, with ``randomize_velocity_jitter`` / ``--randomize-velocity-jitter X``
                   (m/s, default 0), velocities; its frame tables are compiled on the device
                   (``scenario.MovingScenarioBatch``).
+  ``randomize_moving_scan_scenarios`` / ``--randomize-moving-scan-scenarios`` (batched runs on a sim-config with ``motion``
+                  AND ``radar_scan`` on one clock): the same for a moving scenario under scanning radars, with
+                  ``randomize_velocity_jitter`` and ``randomize_azimuth_jitter``; frame tables and beam frames are compiled on
+                  the device (``scenario.MovingScanScenarioBatch``); the rollout is the step loop.
   ``--resume DIR`` restores agent, mixer, optimiser and ``trainer_state.json`` (env steps, episodes, epsilon
                   clock, learner step counters, and the positions of the three random streams: exploration counter,
                   replay sampler, per-env Monte-Carlo episode index) — the reference saves the optimiser but never
@@ -119,7 +123,24 @@ def build_components(args, sim_config_path):
     if batch_envs > 1:
         from .simulation.environment import BatchedElectromagneticEnvironment
         off = int(getattr(args, "env_offset", 0))
-        batch = moving_batch = None
+        batch = moving_batch = moving_scan_batch = None
+        velocity_jitter = float(getattr(args, "randomize_velocity_jitter", 0.0) or 0.0)
+        if getattr(args, "randomize_moving_scan_scenarios", False):   # ... of the MOVING scenario under SCANNING radars
+            import yaml
+            from .scenario import MovingScanScenarioBatch
+            if getattr(args, "randomize_scenarios", False) or getattr(args, "randomize_moving_scenarios", False):
+                raise ValueError("--randomize-moving-scan-scenarios, --randomize-moving-scenarios and --randomize-scenarios "
+                                 "are exclusive")
+            with open(sim_config_path) as f:
+                base = yaml.safe_load(f)
+            env_params = (base or {}).get("environment_params") or {}
+            if env_params.get("motion") is None or env_params.get("radar_scan") is None:
+                raise ValueError(f"--randomize-moving-scan-scenarios needs a scenario that both moves and scans on one clock "
+                                 f"({sim_config_path} lacks environment_params.motion or environment_params.radar_scan); "
+                                 f"--randomize-moving-scenarios / --randomize-scenarios take the others")
+            moving_scan_batch = MovingScanScenarioBatch.randomized(
+                base, batch_envs, seed=args.seed, config=args, env_offset=off, velocity_jitter=velocity_jitter,
+                azimuth_jitter=float(getattr(args, "randomize_azimuth_jitter", 0.0) or 0.0), compile="device")
         if getattr(args, "randomize_moving_scenarios", False):   # every env its own variation of the MOVING scenario
             import yaml
             from .scenario import MovingScenarioBatch
@@ -137,8 +158,8 @@ def build_components(args, sim_config_path):
             moving_batch = MovingScenarioBatch.randomized(
                 base, batch_envs, seed=args.seed, config=args, env_offset=off,
                 velocity_jitter=float(getattr(args, "randomize_velocity_jitter", 0.0) or 0.0), compile="device")
-        elif float(getattr(args, "randomize_velocity_jitter", 0.0) or 0.0) != 0.0:
-            raise ValueError("--randomize-velocity-jitter needs --randomize-moving-scenarios")
+        elif velocity_jitter != 0.0 and moving_scan_batch is None:
+            raise ValueError("--randomize-velocity-jitter needs --randomize-moving-scenarios (or --randomize-moving-scan-scenarios)")
         if getattr(args, "randomize_scenarios", False):   # every env its own variation of the scenario file
             import yaml
             from .scenario import ScenarioBatch
@@ -151,11 +172,15 @@ def build_components(args, sim_config_path):
             batch = ScenarioBatch.randomized(base, batch_envs, seed=args.seed, config=args, env_offset=off,
                                              azimuth_jitter=float(getattr(args, "randomize_azimuth_jitter", 0.0) or 0.0))
         env = BatchedElectromagneticEnvironment(args, sim_config_path, batch_envs=batch_envs, seed=args.seed,
-                                                env_offset=off, verbose=True, scenario_batch=batch, moving_batch=moving_batch)
+                                                env_offset=off, verbose=True, scenario_batch=batch, moving_batch=moving_batch,
+                                                moving_scan_batch=moving_scan_batch)
     else:
         if getattr(args, "randomize_moving_scenarios", False) or float(getattr(args, "randomize_velocity_jitter", 0.0) or 0.0):
             raise ValueError("--randomize-moving-scenarios needs a batched run (batch_envs > 1): the single-env facade "
                              "takes no per-env moving batch")
+        if getattr(args, "randomize_moving_scan_scenarios", False):
+            raise ValueError("--randomize-moving-scan-scenarios needs a batched run (batch_envs > 1): the single-env facade "
+                             "takes no per-env moving scanning batch")
         from .simulation.environment import ElectromagneticEnvironment
         env = ElectromagneticEnvironment(config=args, sim_config_path=sim_config_path)
     env_info = env.get_env_info()
@@ -419,8 +444,12 @@ def main(argv=None):
     parser.add_argument("--randomize-moving-scenarios", action="store_true",
                         help="batched runs on a moving scenario (environment_params.motion, no radar_scan): every env gets its "
                              "own random variation; the per-env frame tables are compiled on the device")
+    parser.add_argument("--randomize-moving-scan-scenarios", action="store_true",
+                        help="batched runs on a sim-config with motion and radar_scan on one clock: every env its own random "
+                             "variation of the moving scanning scenario (frame and beam tables compiled on the device)")
     parser.add_argument("--randomize-velocity-jitter", type=float, default=0.0, metavar="X",
-                        help="with --randomize-moving-scenarios: N(0, X) m/s per axis on every velocity (default 0)")
+                        help="with --randomize-moving-scenarios / --randomize-moving-scan-scenarios: N(0, X) m/s per axis on "
+                             "every velocity (default 0)")
     parser.add_argument("--train-agent-body", action="store_true",
                         help="also train fc1 and the GRU of the agent (back-propagation through the unrolled episode); "
                              "eager updates, the actor stays frozen unless --train-actor is given")
@@ -440,6 +469,8 @@ def main(argv=None):
         config.randomize_scenarios = True
     if a.randomize_moving_scenarios:
         config.randomize_moving_scenarios = True
+    if a.randomize_moving_scan_scenarios:
+        config.randomize_moving_scan_scenarios = True
     if a.randomize_velocity_jitter:
         config.randomize_velocity_jitter = a.randomize_velocity_jitter
     if a.train_agent_body:

@@ -176,6 +176,13 @@ class EpisodeRunner:
         self.env.close()
 
 
+def _per_env_moving_scan(env) -> bool:
+    """``env`` is a per-env moving scenario batch under scanning radars (``moving_scan_batch=...``): theta_a depends on the
+    detections and every env has its own frames, so no whole-episode launch applies — every availability predicate of the
+    batched runner answers False and the rollout is the step loop on its dynamic-observation path."""
+    return getattr(env, "moving_scan_batch", None) is not None
+
+
 class BatchedEpisodeRunner:
     """E environments per rollout, device-resident, no per-step host sync.
 
@@ -383,6 +390,8 @@ class BatchedEpisodeRunner:
         RNNAgent on a HIP device at a size the episode kernel covers, and the env offers the many-step launch."""
         if not (self.fused_rollout and self.hoist_static_obs and self.device.type == "cuda" and hasattr(self.env, "step_many")):
             return False
+        if _per_env_moving_scan(self.env):   # per-env moving scanning batch: the step loop only
+            return False
         agent = getattr(self.mac, "agent", None)
         if agent is None or not hasattr(self.mac, "prepare_static_obs") or not next(agent.parameters()).is_cuda:
             return False
@@ -487,6 +496,8 @@ class BatchedEpisodeRunner:
         return self._closed_loop_conditions(per_env=False, moving=True)
 
     def _closed_loop_conditions(self, per_env: bool, moving: bool = False) -> bool:
+        if _per_env_moving_scan(self.env):   # per-env moving scanning batch: the step loop only
+            return False
         env = self.env
         args_name = "episode_moving_scan_args" if moving else ("episode_scan_pe_args" if per_env else "episode_scan_args")
         if self.device.type != "cuda" or not hasattr(env, args_name) or not getattr(env.scenario, "scanning", False):
@@ -577,6 +588,8 @@ class BatchedEpisodeRunner:
         env = self.env
         if self.device.type != "cuda" or not getattr(env.scenario, "moving", False) or not hasattr(env, "frame_states"):
             return False
+        if _per_env_moving_scan(self.env):   # per-env moving scanning batch: the step loop only
+            return False
         if getattr(env.scenario, "scanning", False):   # the state rows depend on detections (theta_a): the step loop only
             return False
         if getattr(env, "scenario_batch", None) is not None or getattr(env, "kernel_flags", 0) != 0:
@@ -654,6 +667,8 @@ class BatchedEpisodeRunner:
         agent computes depends on the env's outputs."""
         env = self.env
         if self.device.type != "cuda" or getattr(env, "moving_batch", None) is None or not hasattr(env, "episode_moving_pe_args"):
+            return False
+        if _per_env_moving_scan(self.env):   # per-env moving scanning batch: the step loop only
             return False
         if getattr(env, "kernel_flags", 0) != 0:
             return False

@@ -15,7 +15,9 @@ tables become per-step frames (``Scenario.motion_tables``; include/macjd.h, ``ma
 (``motion_tables["scan_frames"]`` / ``["pattern_frames"]``; ``macjd_motion_scan_io``).
 ``MovingScenarioBatch`` is the per-env batch of moving scenarios (``macjd_motion_pe_io``): every env's own frame tables,
 stacked from host compiles or written by the device frame compiler from one input column per env
-(``Scenario.motion_compile_inputs``; ``macjd_motion_pe_compile``).
+(``Scenario.motion_compile_inputs``; ``macjd_motion_pe_compile``).  ``MovingScanScenarioBatch`` is the same for scenarios
+that both move and scan (``macjd_motion_scan_pe_io``): the beam frames per env too, from the host or from a second device
+compiler (``macjd_motion_scan_pe_compile``).
 
 Validation and error behaviour follow environment.py:44-79 and :133-199 (same exception types and
 messages for the cases the reference checks).
@@ -938,6 +940,155 @@ class MovingScenarioBatch:
         ins = [_motion_compile_inputs(sc0, m) for sc0, m in zip(starts, motions)]
         out.compile_inputs = np.ascontiguousarray(np.stack([i["column"] for i in ins]))
         out.compile_weak = np.ascontiguousarray(np.stack([i["weak"] for i in ins]))
+        return out
+
+
+DEG_PER_RAD = float(180.0 / np.pi)   # np.degrees multiplies by this constant
+
+
+def motion_scan_pe_in_rows(n_radars: int, n_levels: int) -> int:
+    """MACJD_MOTION_SCAN_PE_IN_ROWS(R, L) of include/macjd.h."""
+    return 4 * n_radars + 1 + (n_radars + n_levels if n_levels > 0 else 0)
+
+
+def _scan_compile_inputs(sc: "Scenario") -> np.ndarray:
+    """The beam-frame compiler's input column (include/macjd.h, macjd_motion_scan_pe_compile_desc) from ``sc``, a SCANNING
+    scenario compiled at the start positions: half_beam | sweep | sweep_mod | az0 | rho | inv_width | rho_lvl, every value
+    ``Scenario._compile_scan``'s own (copied from its ``scan_tables``)."""
+    st = sc.scan_tables
+    parts = [st["half_beam"], st["sweep"], st["sweep_mod"], st["az0"], [st["rho"]]]
+    if sc.scan_pattern_levels:
+        parts += [st["pat_inv_width"], st["pat_rho"]]
+    col = np.concatenate([np.asarray(a, dtype=np.float64).reshape(-1) for a in parts])
+    assert col.shape == (motion_scan_pe_in_rows(sc.num_radars, sc.scan_pattern_levels),)
+    return col
+
+
+class MovingScanScenarioBatch(MovingScenarioBatch):
+    """E scenarios of one shape that both MOVE and SCAN on one clock (``float(motion.step_seconds) ==
+    float(radar_scan.step_seconds)``): the per-env batch of ``config/scenario_3j4r_moving_scan.yaml``-like scenarios
+    (include/macjd.h, macjd_motion_pe_io + macjd_motion_scan_pe_io).  ``MovingScenarioBatch`` keeps refusing ``radar_scan``.
+
+    Shared by the batch: everything ``MovingScenarioBatch`` shares, the pattern's ``level_width`` and its number of levels L;
+    ``sidelobe_db`` and the pattern's ``gain_db`` may differ per env (their values travel in each env's own columns).
+
+    Host path (``MovingScanScenarioBatch(scenarios)``): every scenario's own ``motion_tables`` stacked, bit for bit —
+    ``MovingScenarioBatch``'s four arrays plus ``scan_frames`` f64 [E, F, 10R + JR] and, L > 0, ``pattern_frames`` f64
+    [E, F, R + 4(L+2)R].  Device path (``randomized(..., compile="device")``): ``compile_inputs`` / ``compile_weak`` of the first
+    compiler plus ``scan_compile_inputs`` f64 [E, MACJD_MOTION_SCAN_PE_IN_ROWS(R, L)]; the environment runs
+    macjd_motion_pe_compile, then macjd_motion_scan_pe_compile."""
+
+    def __init__(self, scenarios: List[Scenario]):
+        if not scenarios:
+            raise ValueError("MovingScanScenarioBatch needs at least one scenario")
+        for i, sc in enumerate(scenarios):
+            if not sc.moving:
+                raise ValueError(f"MovingScanScenarioBatch: scenario {i} does not move (no environment_params.motion); "
+                                 f"ScenarioBatch(..., scan=True) takes static scanning scenarios")
+            if not sc.scanning:
+                raise ValueError(f"MovingScanScenarioBatch: scenario {i} has no scanning radars (no environment_params.radar_scan); "
+                                 f"MovingScenarioBatch takes moving scenarios without them")
+        self._check_shared(scenarios, [sc.motion["step_seconds"] for sc in scenarios])
+        self._check_scan_shared([sc.radar_scan for sc in scenarios])
+        self._init_common(scenarios[0], len(scenarios), np.stack([sc.state_vector() for sc in scenarios]))
+        self.scenarios = list(scenarios)
+        mt = [sc.motion_tables for sc in scenarios]
+        self.frames = np.ascontiguousarray(np.stack([m["frames"] for m in mt]), dtype=np.float64)
+        self.flags = np.ascontiguousarray(np.stack([m["flags"] for m in mt]), dtype=np.uint8)
+        self.snr_no = np.ascontiguousarray(np.stack([m["snr_no"] for m in mt]), dtype=np.float64)
+        self.positions = np.ascontiguousarray(np.stack([m["positions"] for m in mt]), dtype=np.float32)
+        self.scan_frames = np.ascontiguousarray(np.stack([m["scan_frames"] for m in mt]), dtype=np.float64)
+        self.pattern_frames = (np.ascontiguousarray(np.stack([m["pattern_frames"] for m in mt]), dtype=np.float64)
+                               if self.scan_pattern_levels else None)
+        self.state_vectors[:, self.position_columns] = self.positions[:, 0]
+        self.compile_inputs = self.compile_weak = self.scan_compile_inputs = None
+
+    @staticmethod
+    def _check_scan_shared(scans: List[Dict[str, Any]]) -> None:
+        """``scans``: every env's parsed ``radar_scan`` block."""
+        p0 = scans[0].get("pattern")
+        for i, rs in enumerate(scans):
+            p = rs.get("pattern")
+            if (p is None) != (p0 is None) or (p is not None and len(p["gain_db"]) != len(p0["gain_db"])):
+                raise ValueError(f"MovingScanScenarioBatch: scenario {i}'s stepped antenna pattern has another number of levels "
+                                 f"than scenario 0's (L is shared by the whole batch)")
+            if p is not None and float(p["level_width"]) != float(p0["level_width"]):
+                raise ValueError(f"MovingScanScenarioBatch: scenario {i}'s radar_scan.pattern.level_width ({p['level_width']!r}) "
+                                 f"differs from scenario 0's ({p0['level_width']!r}) (it is shared by the whole batch)")
+
+    @property
+    def scan_pattern_levels(self) -> int:
+        """L of the batch's stepped antenna pattern, 0 without one."""
+        return int(self.base.scan_pattern_levels)
+
+    def tiled(self, tile: int) -> Dict[str, np.ndarray]:
+        """``MovingScenarioBatch.tiled`` plus ``scan_frames`` [n_tiles, F, 10R + JR, tile] and, L > 0, ``pattern_frames``
+        [n_tiles, F, R + 4(L+2)R, tile] (include/macjd.h, macjd_motion_scan_pe_io).  Host-compiled batches only."""
+        out = super().tiled(tile)
+        out["scan_frames"] = tile_envs(self.scan_frames, tile)
+        if self.pattern_frames is not None:
+            out["pattern_frames"] = tile_envs(self.pattern_frames, tile)
+        return out
+
+    def tiled_compile_inputs(self, tile: int) -> Dict[str, np.ndarray]:
+        """``MovingScenarioBatch.tiled_compile_inputs`` plus ``scan_in`` f64 [n_tiles, scan_in_rows, tile]."""
+        out = super().tiled_compile_inputs(tile)
+        out["scan_in"] = tile_envs(self.scan_compile_inputs, tile)
+        return out
+
+    def table_bytes(self, tile: int) -> int:
+        """Bytes of the device tables at env tile ``tile``: ``MovingScenarioBatch``'s four plus the scan and pattern frames."""
+        R, J, F, L = self.base.num_radars, self.base.num_jammers, self.n_frames, self.scan_pattern_levels
+        n_pad = ((self.n_envs + tile - 1) // tile) * tile
+        beam_rows = pe_scan_rows(R, J) + (pe_scan_pattern_rows(R, L) if L else 0)
+        return super().table_bytes(tile) + n_pad * F * beam_rows * 8
+
+    @classmethod
+    def randomized(cls, base_dict: dict, n_envs: int, seed: int = 0, config: Any = None, env_offset: int = 0,
+                   velocity_jitter: float = 0.0, compile: str = "device", **jitter) -> "MovingScanScenarioBatch":
+        """``MovingScenarioBatch.randomized`` for a base that both moves and scans on one clock (``azimuth_jitter`` among the
+        jitters moves every radar's initial beam azimuth); env e is variation ``env_offset + e`` of the stream keyed by
+        ``seed``.  ``compile="device"`` compiles only the static scanning scenario of frame 0 per env and carries the two
+        compilers' input columns."""
+        if compile not in ("device", "host"):
+            raise ValueError(f"MovingScanScenarioBatch.randomized: compile must be 'device' or 'host', got {compile!r}")
+        env_params = (base_dict or {}).get("environment_params") or {}
+        mo0, rs0 = parse_motion(env_params), parse_radar_scan(env_params)
+        if mo0 is None:
+            raise ValueError("MovingScanScenarioBatch.randomized: the base scenario does not move (no environment_params.motion); "
+                             "ScenarioBatch.randomized takes static scenarios")
+        if rs0 is None:
+            raise ValueError("MovingScanScenarioBatch.randomized: the base scenario has no scanning radars (no "
+                             "environment_params.radar_scan); MovingScenarioBatch.randomized takes moving scenarios without them")
+        nr = getattr(config, "num_radars", None)
+        nj = getattr(config, "num_jammers", None)
+        dicts = []
+        for e in range(n_envs):
+            rng = np.random.default_rng([int(seed), int(env_offset) + e])
+            dicts.append(randomized_moving_scenario_dict(base_dict, rng, velocity_jitter=velocity_jitter, num_radars=nr,
+                                                         num_jammers=nj, **jitter))
+        if compile == "host":
+            return cls([Scenario.from_dict(d, config=config, source=f"<randomized moving scan {seed}:{env_offset + e}>")
+                        for e, d in enumerate(dicts)])
+        # the shared handle and shape come from a moving scanning Scenario of env 0 (one scenario's host compile; it also
+        # applies the one-clock rule with the existing wording)
+        base = Scenario.from_dict(dicts[0], config=config, source=f"<randomized moving scan {seed}:{env_offset}>")
+        starts, motions = [], []
+        for e, d in enumerate(dicts):
+            sc0 = Scenario.from_dict(motion_frame_dict(d, 0), config=config,
+                                     source=f"<randomized moving scan {seed}:{env_offset + e}>[frame 0]")
+            starts.append(sc0)
+            motions.append(parse_motion(d["environment_params"], sc0.num_radars, sc0.num_jammers))
+        cls._check_shared(starts, [m["step_seconds"] for m in motions])
+        cls._check_scan_shared([sc0.radar_scan for sc0 in starts])
+        out = object.__new__(cls)
+        out._init_common(base, n_envs, np.stack([sc0.state_vector() for sc0 in starts]))
+        out.scenarios = None
+        out.frames = out.flags = out.snr_no = out.positions = out.scan_frames = out.pattern_frames = None
+        ins = [_motion_compile_inputs(sc0, m) for sc0, m in zip(starts, motions)]
+        out.compile_inputs = np.ascontiguousarray(np.stack([i["column"] for i in ins]))
+        out.compile_weak = np.ascontiguousarray(np.stack([i["weak"] for i in ins]))
+        out.scan_compile_inputs = np.ascontiguousarray(np.stack([_scan_compile_inputs(sc0) for sc0 in starts]))
         return out
 
 

@@ -27,7 +27,8 @@ import numpy as np
 import torch
 
 from .. import _native
-from ..scenario import DEFAULT_SIM_CONFIG_PATH, FOUR_PI_CUBED, MovingScenarioBatch, Scenario, ScenarioBatch
+from ..scenario import (DEFAULT_SIM_CONFIG_PATH, DEG_PER_RAD, FOUR_PI_CUBED, MovingScanScenarioBatch, MovingScenarioBatch,
+                        Scenario, ScenarioBatch)
 
 RADAR_STATE_SEARCH = "SEARCH"  # core/radar.py:5-7
 RADAR_STATE_TRACK = "TRACK"
@@ -65,12 +66,20 @@ class BatchedElectromagneticEnvironment:
     pe_tiled = True          # A/B hook: False keeps the plain [rows, E] SoA on the device
     moving_batch = None      # the per-env moving scenario batch (moving_batch=...), None otherwise
     _motion_pe_io = None     # ... and its argument block (include/macjd.h, macjd_motion_pe_io)
+    moving_scan_batch = None   # the per-env moving scanning scenario batch (moving_scan_batch=...), None otherwise
+    _motion_scan_pe_io = None  # ... and its beam-frame block (include/macjd.h, macjd_motion_scan_pe_io)
 
     def __init__(self, config: Any = None, sim_config_path: str = DEFAULT_SIM_CONFIG_PATH,
                  batch_envs: Optional[int] = None, device=None, seed: Optional[int] = None,
                  env_offset: int = 0, scenario: Optional[Scenario] = None, verbose: bool = False,
-                 scenario_batch: Optional[ScenarioBatch] = None, moving_batch: Optional[MovingScenarioBatch] = None):
-        """``moving_batch``: one MOVING scenario per env (``MovingScenarioBatch``; exclusive with ``scenario_batch``): every
+                 scenario_batch: Optional[ScenarioBatch] = None, moving_batch: Optional[MovingScenarioBatch] = None,
+                 moving_scan_batch: Optional[MovingScanScenarioBatch] = None):
+        """``moving_scan_batch``: one scenario that both MOVES and SCANS per env (``MovingScanScenarioBatch``; exclusive with
+        ``moving_batch``, ``scenario_batch`` and ``scenario``): every env steps on its own frame tables AND its own beam frames
+        (include/macjd.h, macjd_motion_pe_io + macjd_motion_scan_pe_io), uploaded from the batch's host frames or compiled on the
+        device by macjd_motion_pe_compile and macjd_motion_scan_pe_compile back to back.  Single steps and resets only.
+
+        ``moving_batch``: one MOVING scenario per env (``MovingScenarioBatch``; exclusive with ``scenario_batch``): every
         env steps on its own frame tables (include/macjd.h, macjd_motion_pe_io), uploaded from the batch's host frames or
         compiled on the device from its input columns (macjd_motion_pe_compile).
 
@@ -81,6 +90,19 @@ class BatchedElectromagneticEnvironment:
         ``pattern=True`` each env's stepped antenna pattern tables are streamed too (macjd_env_step_scan_pe_pattern)."""
         self.scenario_batch = scenario_batch
         self.moving_batch = moving_batch
+        self.moving_scan_batch = moving_scan_batch
+        if moving_scan_batch is not None:
+            if moving_batch is not None:
+                raise ValueError("moving_scan_batch and moving_batch are exclusive (a per-env moving batch either scans or does not)")
+            if scenario_batch is not None:
+                raise ValueError("moving_scan_batch and scenario_batch are exclusive (a per-env batch is either static or moving)")
+            if scenario is not None:
+                raise ValueError("moving_scan_batch brings its own scenario (MovingScanScenarioBatch.base): do not pass `scenario` too")
+            scenario = moving_scan_batch.base
+            if batch_envs is None:
+                batch_envs = moving_scan_batch.n_envs
+            if int(batch_envs) != moving_scan_batch.n_envs:
+                raise ValueError(f"batch_envs ({batch_envs}) != scenarios in the moving scanning batch ({moving_scan_batch.n_envs})")
         if moving_batch is not None:
             if scenario_batch is not None:
                 raise ValueError("moving_batch and scenario_batch are exclusive (a per-env batch is either static or moving)")
@@ -126,7 +148,7 @@ class BatchedElectromagneticEnvironment:
         with torch.cuda.device(self.device):
             # a batch under a stepped pattern brings every env's level tables itself: the handle stays pattern-free, so
             # that macjd_env_reset_scan_pe (az0 per env does not depend on the pattern) takes it
-            self._handle = _native.ScenarioHandle(sc, scan_pattern=not pe_pattern)
+            self._handle = _native.ScenarioHandle(sc, scan_pattern=not pe_pattern and moving_scan_batch is None)
         E, R, J = self.batch_envs, self.num_radars, self.num_jammers
         dev = self.device
         self._track = torch.zeros((R, E), dtype=torch.uint8, device=dev)
@@ -183,7 +205,7 @@ class BatchedElectromagneticEnvironment:
                 self._scan_pe_pattern_tables = torch.from_numpy(ptb).to(dev)   # f64 [R + 4(L+2)R, E] or [n_tiles, ..., w]
                 pp = self._scan_pe_pattern_io = _native.ScanPePatternIO()
                 pp.tables, pp.stride, pp.n_levels = self._scan_pe_pattern_tables.data_ptr(), E, scenario_batch.scan_pattern_levels
-        elif sc.scanning:
+        elif sc.scanning and moving_scan_batch is None:
             # beam azimuths f64 [R, E] (radar-major like track), the per-env state rows f32 [E, S] whose theta_a columns the
             # kernel rewrites every step (get_state / get_obs are views of it: one address for captured graphs), and the
             # per-step SNR without jamming (main or side lobe) f32 [R, E]
@@ -194,15 +216,18 @@ class BatchedElectromagneticEnvironment:
             self._state_dyn = st.view(1, -1).repeat(E, 1).contiguous()
             self._snr_no_step = torch.from_numpy(sc.tables["radar_snr_no"]).to(dev).to(torch.float32).view(R, 1).repeat(1, E)
             self._snr_no_step = self._snr_no_step.contiguous()
-        if sc.scanning:
+        if sc.scanning and moving_scan_batch is None:
             si = self._scan_io = _native.ScanIO()
             si.theta_a, si.a_se, si.a_sx = self._theta_a.data_ptr(), 1, E
             si.state, si.st_se = self._state_dyn.data_ptr(), self._state_dyn.stride(0)
             si.st_col0, si.st_col_step = sc.theta_a_col0, sc.theta_a_col_step
             si.snr_no, si.sn_se, si.sn_sx = self._snr_no_step.data_ptr(), 1, E
         self._motion_io = self._motion_keep = self._motion_scan_io = None
-        self._motion_pe_io = None
-        if moving_batch is not None:
+        self._motion_pe_io = self._motion_scan_pe_io = None
+        if moving_scan_batch is not None:
+            self._init_moving_batch(moving_scan_batch)
+            self._init_moving_scan_batch(moving_scan_batch)
+        elif moving_batch is not None:
             self._init_moving_batch(moving_batch)
         elif sc.moving:
             # per-step frame tables (include/macjd.h, macjd_motion_io): f64 [F, rows], u8 [F, J*R], f64 [F, R], the
@@ -287,13 +312,66 @@ class BatchedElectromagneticEnvironment:
         mp.state, mp.st_se = self._state_dyn.data_ptr(), self._state_dyn.stride(0)
         mp.snr_no, mp.sn_se, mp.sn_sx = self._snr_no_step.data_ptr(), 1, E
 
+    def _init_moving_scan_batch(self, mb: MovingScanScenarioBatch) -> None:
+        """After ``_init_moving_batch`` (frame tables, positions, state rows): the per-env beam frames on the device
+        (include/macjd.h, macjd_motion_scan_pe_io) at the same env tile — uploaded from the batch's host frames, or written by
+        ONE launch of the beam-frame compiler right behind the first compiler on the same stream; beams f64 [R, E] and the
+        theta_a columns of the state rows start from each env's own frame-0 az0, the per-step SNR without jamming is carried
+        by the beam block (the motion block's is cleared)."""
+        E, R, J, dev = self.batch_envs, self.num_radars, self.num_jammers, self.device
+        sc, keep, w = self.scenario, self._motion_keep, int(self._pe_tile)
+        F, L = mb.n_frames, mb.scan_pattern_levels
+        n_tiles = (E + w - 1) // w
+        srows, prows = 10 * R + J * R, R + 4 * (L + 2) * R
+        if mb.host_compiled:
+            assert "scan_frames" in keep and (("pattern_frames" in keep) == (L > 0))
+        else:
+            keep["scan_in"] = torch.from_numpy(mb.tiled_compile_inputs(w)["scan_in"]).to(dev)
+            keep["scan_frames"] = torch.zeros((n_tiles, F, srows, w), dtype=torch.float64, device=dev)
+            if L > 0:
+                keep["pattern_frames"] = torch.zeros((n_tiles, F, prows, w), dtype=torch.float64, device=dev)
+            d = _native.MotionScanPeCompileDesc()
+            d.n_envs, d.n_radars, d.n_jammers, d.n_frames, d.tile, d.n_levels = E, R, J, F, w, L
+            d.deg_per_rad = DEG_PER_RAD
+            d.pd_A, d.pd_c1, d.pd_denB = sc.pd_consts
+            d.in_tables, d.scan_in = keep["in_tables"].data_ptr(), keep["scan_in"].data_ptr()
+            d.frames, d.frame_snr_no = keep["frames"].data_ptr(), keep["snr_no"].data_ptr()
+            d.scan_frames = keep["scan_frames"].data_ptr()
+            d.pattern_frames = keep["pattern_frames"].data_ptr() if L > 0 else None
+            with torch.cuda.device(dev):
+                _native.check(self._lib.macjd_motion_scan_pe_compile(ctypes.byref(d), torch.cuda.current_stream(dev).cuda_stream),
+                              "macjd_motion_scan_pe_compile")
+        assert tuple(keep["scan_frames"].shape) == (n_tiles, F, srows, w)
+        assert L == 0 or tuple(keep["pattern_frames"].shape) == (n_tiles, F, prows, w)
+        untile = lambda t: t.permute(0, 2, 1).reshape(n_tiles * w, -1)[:E]      # [n_tiles, k, w] -> [E, k]
+        az0 = untile(keep["scan_frames"][:, 0, 3 * R:4 * R])                    # f64 [E, R]: each env's frame-0 az0
+        self._theta_a = az0.t().contiguous()                                    # f64 [R, E]
+        self._state_dyn[:, sc.theta_a_columns] = az0.to(torch.float32)
+        si = self._scan_io = _native.ScanIO()
+        si.theta_a, si.a_se, si.a_sx = self._theta_a.data_ptr(), 1, E
+        si.state, si.st_se = self._state_dyn.data_ptr(), self._state_dyn.stride(0)
+        si.st_col0, si.st_col_step = sc.theta_a_col0, sc.theta_a_col_step
+        si.snr_no, si.sn_se, si.sn_sx = self._snr_no_step.data_ptr(), 1, E
+        self._motion_pe_io.snr_no = None   # the per-step value travels in the beam block's snr_no
+        ms = self._motion_scan_pe_io = _native.MotionScanPeIO()
+        ms.scan_frames = keep["scan_frames"].data_ptr()
+        ms.pattern_frames = keep["pattern_frames"].data_ptr() if L > 0 else None
+        ms.n_levels = L
+
     @property
     def table_bytes(self) -> int:
-        """Bytes of the per-env frame tables on the device (per-env moving batches only)."""
+        """Bytes of the per-env frame tables on the device (per-env moving batches only; with the beam frames of a per-env
+        moving scanning batch)."""
         if self._motion_pe_io is None:
-            raise AttributeError("table_bytes: not a per-env moving batch (moving_batch=...)")
+            raise AttributeError("table_bytes: not a per-env moving batch (moving_batch=... / moving_scan_batch=...)")
         return int(sum(self._motion_keep[k].numel() * self._motion_keep[k].element_size()
-                       for k in ("frames", "flags", "snr_no", "positions")))
+                       for k in ("frames", "flags", "snr_no", "positions", "scan_frames", "pattern_frames")
+                       if k in self._motion_keep))
+
+    def _refuse_moving_scan_batch(self, what: str) -> None:
+        # theta_a depends on the detections and every env has its own frames: single steps and resets only
+        if self._motion_scan_pe_io is not None:
+            raise RuntimeError(f"{what}: not available on a per-env moving scanning scenario batch (moving_scan_batch=...)")
 
     def _refuse_moving_batch(self, what: str) -> None:
         if self._motion_pe_io is not None:
@@ -348,6 +426,7 @@ class BatchedElectromagneticEnvironment:
         """f32 [F + 1, S] on the device (moving scenarios only): row k is the state row every env shows at step counter k —
         the scenario's state vector with the position columns of frame k (``Scenario.frame_state_rows``), i.e. the bits
         the moving step writes.  Built once."""
+        self._refuse_moving_scan_batch("frame_states")
         self._refuse_moving_batch("frame_states")   # every env has its own frames
         if self._motion_io is None:
             raise AttributeError("frame_states: the scenario does not move (no environment_params.motion)")
@@ -380,7 +459,12 @@ class BatchedElectromagneticEnvironment:
                                                     1, self.batch_envs, self._step.data_ptr(), mptr,
                                                     self._episode.data_ptr(), stream),
                           "macjd_env_reset")
-            if self._scan_pe_io is not None:
+            if self._motion_scan_pe_io is not None:   # beam part on each env's own frame 0 (the position part follows)
+                mp = self._motion_pe_io
+                _native.check(self._lib.macjd_env_reset_moving_scan_pe(
+                    self._handle.ptr, self.batch_envs, ctypes.byref(self._scan_io), ctypes.byref(self._motion_scan_pe_io),
+                    int(mp.n_frames), int(mp.tile), mptr, stream), "macjd_env_reset_moving_scan_pe")
+            elif self._scan_pe_io is not None:
                 _native.check(self._lib.macjd_env_reset_scan_pe(self._handle.ptr, self.batch_envs, ctypes.byref(self._scan_io),
                                                                 ctypes.byref(self._scan_pe_io), self._pe_tile, mptr, stream),
                               "macjd_env_reset_scan_pe")
@@ -480,7 +564,13 @@ class BatchedElectromagneticEnvironment:
                            rdpj_sum)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         with torch.cuda.device(self.device):
-            if self._motion_scan_io is not None:
+            if self._motion_scan_pe_io is not None:
+                si = self._scan_io
+                si.snr_no = self._snr_no_step.data_ptr() if want_info else None
+                _native.check(self._lib.macjd_env_step_moving_scan_pe(
+                    self._handle.ptr, ctypes.byref(io), ctypes.byref(self._motion_pe_io), ctypes.byref(si),
+                    ctypes.byref(self._motion_scan_pe_io), stream), "macjd_env_step_moving_scan_pe")
+            elif self._motion_scan_io is not None:
                 si = self._scan_io
                 si.snr_no = self._snr_no_step.data_ptr() if want_info else None
                 _native.check(self._lib.macjd_env_step_moving_scan(
@@ -526,6 +616,7 @@ class BatchedElectromagneticEnvironment:
         all contiguous.  Legal because a step's outcome depends on the env's past only through the step counter (the
         FSM's next state equals `detected`, core/radar.py:102-117) — see include/macjd.h, macjd_env_step_many; meant for
         actions that do not depend on the env's outputs (static observation).  Philox uniforms, no pd / snr outputs."""
+        self._refuse_moving_scan_batch("step_many")
         self._refuse_scanning("step_many")
         E, J = self.batch_envs, self.num_jammers
         n = actions_T.shape[0]
@@ -562,6 +653,7 @@ class BatchedElectromagneticEnvironment:
     def time_step_many_kernel(self, actions_T, actions_P, out_reward, out_terminated, out_rdpj, iters: int) -> float:
         """bench.py helper: average milliseconds per launch of the many-step kernel (n x E work items), ``iters``
         launches replayed from a HIP graph and bracketed by HIP events on the replay stream (macjd_env_step_many_timed)."""
+        self._refuse_moving_scan_batch("time_step_many_kernel")
         self._refuse_scanning("time_step_many_kernel")
         self._refuse_moving("time_step_many_kernel")
         self._refuse_moving_batch("time_step_many_kernel")
@@ -582,6 +674,7 @@ class BatchedElectromagneticEnvironment:
                          uniforms: Optional[torch.Tensor] = None, want_info: bool = True) -> float:
         """bench.py helper: average milliseconds per env_step launch over ``iters`` back-to-back
         launches, measured with HIP events recorded on the launch stream (macjd_env_step_timed)."""
+        self._refuse_moving_scan_batch("time_step_kernel")
         self._refuse_scanning("time_step_kernel")
         self._refuse_moving("time_step_kernel")
         self._refuse_moving_batch("time_step_kernel")
@@ -597,6 +690,7 @@ class BatchedElectromagneticEnvironment:
         """What the closed-loop episode launch (``ops.agent_env_episode_scan``) needs from a scanning environment: the
         scenario handle, the beam / state-row block, the FSM bits, step counters and episode indices it reads and leaves
         as T single steps would, and the Monte-Carlo stream's seed and env offset."""
+        self._refuse_moving_scan_batch("episode_scan_args")
         self._refuse_moving_batch("episode_scan_args")
         if self._scan_io is None:
             raise RuntimeError("episode_scan_args: the scenario's beams do not scan (no environment_params.radar_scan)")
@@ -614,6 +708,7 @@ class BatchedElectromagneticEnvironment:
         scanning scenario batch: the entries of ``episode_scan_args`` plus the batch's scenario tables and flag bytes
         with their tile width, ``n_envs`` (the plain layout's row stride), the per-env scan block and, under a stepped
         pattern, the per-env level tables (else None)."""
+        self._refuse_moving_scan_batch("episode_scan_pe_args")
         self._refuse_moving_batch("episode_scan_pe_args")
         if self._scan_pe_io is None:
             raise RuntimeError("episode_scan_pe_args: needs a per-env scanning scenario batch (ScenarioBatch(..., scan=True)); "
@@ -627,6 +722,7 @@ class BatchedElectromagneticEnvironment:
         """What the closed-loop episode launch on a moving scanning scenario (``ops.agent_env_episode_moving_scan``) needs:
         the entries of ``episode_scan_args`` plus the motion block (frame tables, positions and their state columns) and the
         motion-scan block (per-frame beam tables, under a stepped pattern the per-frame level tables)."""
+        self._refuse_moving_scan_batch("episode_moving_scan_args")
         self._refuse_moving_batch("episode_moving_scan_args")
         if self._motion_io is None or self._motion_scan_io is None:
             raise RuntimeError("episode_moving_scan_args: needs a scenario that both moves and scans (environment_params.motion "
@@ -644,6 +740,7 @@ class BatchedElectromagneticEnvironment:
         """What the agent's episode launch on per-env moving frames (``ops.agent_episode_moving_pe``) needs from a per-env
         moving scenario batch: every env's own state row (the position columns are ignored), the step counters, the tiled
         positions table f32 [n_tiles, F + 1, n_pos, tile] with its state columns, F, n_pos and the tile width."""
+        self._refuse_moving_scan_batch("episode_moving_pe_args")
         self._need_moving_batch("episode_moving_pe_args")
         keep, mp = self._motion_keep, self._motion_pe_io
         return {"state": self._state_dyn, "step": self._step, "positions": keep["positions"],
@@ -653,6 +750,7 @@ class BatchedElectromagneticEnvironment:
     def frame_positions(self) -> torch.Tensor:
         """f32 [E, F + 1, n_pos] on the device (per-env moving batches only): env e's position columns at step counter k in
         state order, untiled from the positions table — the bits the per-env moving step writes.  Built once."""
+        self._refuse_moving_scan_batch("frame_positions")
         self._need_moving_batch("frame_positions")
         if getattr(self, "_frame_positions", None) is None:
             pos = self._motion_keep["positions"]                    # [n_tiles, F + 1, n_pos, tile]
@@ -667,6 +765,7 @@ class BatchedElectromagneticEnvironment:
         size is refused by the launch): True when this env moves — on shared frames or as a per-env moving batch, whose
         many-step launch is compiled at the same sizes — and its size is one of them."""
         return ((self._motion_io is not None or self._motion_pe_io is not None) and self._motion_scan_io is None
+                and self._motion_scan_pe_io is None
                 and (self.num_jammers, self.num_radars) in self.MANY_STEP_MOVING_SIZES)
 
     def _refuse_scanning(self, what: str) -> None:
