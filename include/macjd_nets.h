@@ -295,6 +295,18 @@ typedef struct macjd_wgrad_norm_io {
 
 int32_t macjd_linear_wgrad_many_norm_partials(const macjd_wgrad_io* ios, int32_t n, int32_t ln_problem);   /* < 0: bad argument */
 int macjd_linear_wgrad_many_norm(const macjd_wgrad_io* ios, int32_t n, const macjd_wgrad_norm_io* norm, void* hip_stream);
+/* The same call with flags.  ROW PRODUCTS problems: by default the reduce launch is the STAGED form — blocks of 256
+   consecutive weight items (four 64-item groups, one thread per output) of one such problem with 37 <= N <= 128 form their
+   sums from operand rows staged once per block into LDS; every other 64-item group (bias items, other kinds, heads and
+   tails of a range, other N) is a block of the plain rows kernel's code.  Every output, partials[w] (still the squares of
+   items [64 w, 64 w + 64)) and the step counter are bit-identical to the plain rows kernel for finite operands.
+   MACJD_WGRAD_PLAIN_ROWS selects the plain rows kernel.  macjd_linear_wgrad_many_norm = flags 0. */
+#define MACJD_WGRAD_PLAIN_ROWS 1u
+int macjd_linear_wgrad_many_norm_ex(const macjd_wgrad_io* ios, int32_t n, const macjd_wgrad_norm_io* norm, uint32_t flags,
+                                    void* hip_stream);
+/* workgroups of that call's reduce launch (<= macjd_linear_wgrad_many_norm_partials: a staged block stands for four
+   groups); < 0: bad argument */
+int32_t macjd_linear_wgrad_many_norm_blocks(const macjd_wgrad_io* ios, int32_t n, int32_t ln_problem, uint32_t flags);
 /* work items of that call's partial-products launch (0: the launch is not issued); < 0: bad argument */
 int64_t macjd_linear_wgrad_many_norm_work_items(const macjd_wgrad_io* ios, int32_t n, int32_t ln_problem);
 /* floats of `slots` external slots of an [M, N] problem with their bias rows (MACJD_WGRAD_EXT_SLOTS); < 0: bad argument */

@@ -43,6 +43,7 @@ EXPORTS = [
     "macjd_actor_gradient_supported", "macjd_actor_gradient",
     "macjd_linear_wgrad_many_norm", "macjd_linear_wgrad_many_norm_partials", "macjd_clip_adam_step_reduced",
     "macjd_linear_wgrad_many_norm_work_items", "macjd_wgrad_slot_floats",
+    "macjd_linear_wgrad_many_norm_ex", "macjd_linear_wgrad_many_norm_blocks",
     "macjd_prefetch_batches_supported", "macjd_prefetch_batches",
     "macjd_env_step_moving", "macjd_env_step_many_moving", "macjd_env_reset_moving", "macjd_env_step_moving_scan",
     "macjd_agent_episode_seq_supported", "macjd_agent_episode_seq",
@@ -526,6 +527,7 @@ class WgradIO(ctypes.Structure):
 
 
 WGRAD_ORDINARY, WGRAD_EXT_SLOTS, WGRAD_ROW_PRODUCTS = 0, 1, 2   # macjd_wgrad_io.kind
+WGRAD_PLAIN_ROWS = 1   # macjd_linear_wgrad_many_norm_ex flags: the plain rows kernel instead of the staged form
 
 
 class WgradNormIO(ctypes.Structure):
@@ -736,6 +738,11 @@ def load() -> ctypes.CDLL:
     lib.macjd_linear_wgrad.argtypes = [ctypes.POINTER(WgradIO), ctypes.c_void_p]
     lib.macjd_linear_wgrad_many_norm.restype = ctypes.c_int
     lib.macjd_linear_wgrad_many_norm.argtypes = [ctypes.POINTER(WgradIO), ctypes.c_int32, ctypes.POINTER(WgradNormIO), ctypes.c_void_p]
+    lib.macjd_linear_wgrad_many_norm_ex.restype = ctypes.c_int
+    lib.macjd_linear_wgrad_many_norm_ex.argtypes = [ctypes.POINTER(WgradIO), ctypes.c_int32, ctypes.POINTER(WgradNormIO), ctypes.c_uint32,
+                                                    ctypes.c_void_p]
+    lib.macjd_linear_wgrad_many_norm_blocks.restype = ctypes.c_int32
+    lib.macjd_linear_wgrad_many_norm_blocks.argtypes = [ctypes.POINTER(WgradIO), ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32]
     lib.macjd_linear_wgrad_many_norm_partials.restype = ctypes.c_int32
     lib.macjd_linear_wgrad_many_norm_partials.argtypes = [ctypes.POINTER(WgradIO), ctypes.c_int32, ctypes.c_int32]
     lib.macjd_clip_adam_step_reduced.restype = ctypes.c_int

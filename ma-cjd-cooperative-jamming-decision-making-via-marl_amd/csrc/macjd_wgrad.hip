@@ -15,13 +15,18 @@
 //   * wgrad_reduce_kernel sums the chunks in index order (deterministic, no float atomics).
 // The grouped pair exists a second time (wgrad_*_many_norm_kernel, macjd_linear_wgrad_many_norm) for the learner's update:
 // one problem contracted with a weight matrix into LayerNorm-parameter gradients in the partial launch's epilogue, the
-// squares of every stored gradient and the optimiser's step counter in the reduce launch.
+// squares of every stored gradient and the optimiser's step counter in the reduce launch.  Its reduce launch has three
+// kernels: slot sums only (wgrad_reduce_many_norm_kernel), with ROW PRODUCTS problems two global loads per lane and term
+// (wgrad_reduce_many_rows_kernel) or — the default — blocks of 256 outputs on LDS-staged operand rows beside plain blocks
+// (wgrad_reduce_rows_staged_kernel, block map in macjd_wgrad_map.h); the last two give the same bits.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #include "../../include/macjd.h"
 #include "../../include/macjd_nets.h"
 #include "macjd_err.h"
+#include "macjd_wgrad_map.h"
 
 namespace macjd {
 
@@ -499,13 +504,15 @@ __device__ __forceinline__ float wgrad_sum_rounds_rows(const float* __restrict__
     return ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
 }
 
-template <bool ROWS>
-__device__ __forceinline__ void wgrad_reduce_norm_body(const WgradBatch& b, const WgradNorm& ln, const unsigned rows_mask) {
+// MAPPED (the staged kernel's plain blocks): the body runs as block `mblock` of `mblocks`; else as its workgroup of the grid
+template <bool ROWS, bool MAPPED = false>
+__device__ __forceinline__ void wgrad_reduce_norm_body(const WgradBatch& b, const WgradNorm& ln, const unsigned rows_mask,
+                                                       const unsigned mblock = 0, const unsigned mblocks = 0) {
     __shared__ float part[4][WG_RED];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t total_all = b.out_start[b.n];
     float sq = 0.0f;
-    for (int64_t g0 = (int64_t)blockIdx.x * WG_RED; g0 < total_all; g0 += (int64_t)gridDim.x * WG_RED) {
+    for (int64_t g0 = (int64_t)(MAPPED ? mblock : blockIdx.x) * WG_RED; g0 < total_all; g0 += (int64_t)(MAPPED ? mblocks : gridDim.x) * WG_RED) {
         const int64_t g = g0 + lane < total_all ? g0 + lane : total_all - 1;
         int M = b.io[0].M, N = b.io[0].N, Mp = b.Mp[0], Np = b.Np[0], n_chunks = b.chunks[0], prob = 0;
         int64_t start = 0, dw_ld = b.io[0].dw_ld;
@@ -557,8 +564,8 @@ __device__ __forceinline__ void wgrad_reduce_norm_body(const WgradBatch& b, cons
     if (wave == 0) {
         sq = wgrad_wave_sum(sq);
         if (lane == 0) {
-            ln.partials[blockIdx.x] = sq;
-            if (blockIdx.x == 0) ln.step[0] += 1.0f;   // nothing in this launch reads it; the optimiser launch reads the advanced value
+            ln.partials[MAPPED ? mblock : blockIdx.x] = sq;
+            if ((MAPPED ? mblock : blockIdx.x) == 0) ln.step[0] += 1.0f;   // nothing in this launch reads it; the optimiser launch reads the advanced value
         }
     }
 }
@@ -570,6 +577,188 @@ __global__ void __launch_bounds__(256) wgrad_reduce_many_norm_kernel(const Wgrad
 __global__ void __launch_bounds__(256) wgrad_reduce_many_rows_kernel(const WgradBatch b, const WgradNorm ln, const unsigned rows_mask) {
     wgrad_reduce_norm_body<true>(b, ln, rows_mask);
 }
+
+// ---- ROWS reduce, staged form (wgrad_reduce_rows_staged_kernel; block map: macjd_wgrad_map.h) ----
+// A FAST block owns 256 consecutive weight items of one ROW PRODUCTS problem = four groups of 64, thread = item.  The `inp`
+// rows [k][0, N) and the <= WGMAP_GCOLS `gout` columns of the block's items are staged once per block into LDS in slices
+// of RS_KS terms (compact: row pitch N resp. WGMAP_GCOLS), so a term costs two ds_read_b32 and one fmaf per lane instead of
+// two global loads behind a per-lane 64-bit address.  The slice behind the one being consumed is in flight in registers.
+// Arithmetic per output is that of wgrad_sum_rounds_rows + wgrad_meet: term t goes into accumulator t % 32 (= "wave"
+// (t / 8) % 4, slot t % 8) in increasing t, each eight combine as ((a0 + a1) + (a2 + a3)) + ((a4 + a5) + (a6 + a7)), the
+// four sums meet as (p0 + p1) + (p2 + p3); one thread holds all 32.  Terms past K are SKIPPED; the plain kernel adds
+// fmaf(0, last row's value, acc) there, which for finite operands leaves the same bits (acc + (+-0) = acc; an acc of -0
+// would turn +0, and -0 == +0 in every later sum's value).  Wave j stores groups0 + j and writes its partial like wave 0
+// of a plain block: fmaf(v, v, 0) per lane, wgrad_wave_sum.
+// Global reads: element (k, col) only for k < K and col < N resp. inside the block's columns — lanes without an element
+// re-read the slice's last valid row (no branch around a load) and do not write LDS; the products never read an LDS word
+// that was not written for the current slice.  16-byte loads only where the host found base, ld and N multiples of 16
+// bytes (vec, uniform per problem); else dwords.
+#ifndef MACJD_RS_KS
+#define MACJD_RS_KS 32      // terms per staged slice (a multiple of 32).  Measured on the benchmark's seven problems (K = 224), one visit:
+                            //   32: 115 VGPRs, 17 KB of LDS, reduce launch alone back to back 10.2 us, 77.4 us per update
+                            //   64: 144 VGPRs, 34 KB, 9.8 us alone, 77.7 us per update;  96: 227 VGPRs, 51 KB, 10.0 us, 78.3
+                            // (the plain rows kernel: 14.6 us alone, 81.0 us per update; timing-only builds of the 64-term form whose
+                            // fast blocks skipped their products, or their global loads: 10.0 each — what is left is the plain
+                            // blocks' slot sums).  224, the whole K in flight, needs more than 256 registers
+#endif
+constexpr int RS_KS = MACJD_RS_KS;                          // at 32: 16 KB + 1 KB of LDS, 16 + 1 registers in flight
+constexpr int RS_NIT = RS_KS * WGMAP_N_CAP / 256;           // floats of `inp` per thread and slice at N = WGMAP_N_CAP
+constexpr int RS_GIT = (RS_KS * WGMAP_GCOLS + 255) / 256;   // floats of `gout` per thread and slice
+constexpr int RS_LDS_BYTES = RS_KS * (WGMAP_N_CAP + WGMAP_GCOLS) * 4;
+static_assert(RS_KS % 32 == 0 && WGMAP_N_CAP == 128 && WGMAP_GCOLS == 8, "a slice starts on accumulator 0; the staging maps");
+static_assert(RS_LDS_BYTES <= 64 * 1024, "above the default limit of dynamic LDS the launch would need hipFuncSetAttribute");
+
+struct RowsFastProb {
+    const float* gout; const float* inp; float* dW;
+    int64_t gout_ld, inp_ld, dw_ld, start;
+    int K, N;
+};
+
+// VEC: 16-byte staging loads; WIDE (dword staging only): N > 64, a second column per lane
+template <bool VEC, bool WIDE>
+__device__ __forceinline__ void wgrad_rows_staged_body(const RowsFastProb& p, const int group0, const WgradNorm& ln,
+                                                       float* __restrict__ sx, float* __restrict__ sg) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int N = p.N, K = p.K;
+    const int i0 = group0 * WG_RED - (int)p.start;   // the block's first item inside the problem (uniform; < 64 * 8192)
+    const int m_lo = i0 / N, gcols = (i0 + WGMAP_FAST_ITEMS - 1) / N - m_lo + 1;
+    const int m = (i0 + tid) / N, n = i0 + tid - m * N;
+    // Staging of a slice goes by rows, so no lane divides.  VEC: a float4 per lane, two rows per wave and load (lanes
+    // 0..31 / 32..63), row 8 it + 2 wave + (lane >> 5); else a float per lane at columns lane and lane + 64, one row per wave
+    // and load, row 4 it + wave.  Every load is unconditional (a load under a condition, even a uniform one, makes hipcc
+    // copy the register array behind it and wait for the load first): a row past the slice's last is re-read from the last
+    // valid row, a column past N from column N - 1; neither is written to LDS.
+    const int W = N >> 2, half = lane >> 5, c4 = lane & 31;
+    float pre[RS_NIT], gpre[RS_GIT];
+    auto load_slice = [&](const int k0) {
+        const int rows = K - k0 < RS_KS ? K - k0 : RS_KS;
+        if constexpr (VEC) {
+            const int cc = c4 < W ? c4 : W - 1;
+#pragma unroll
+            for (int it = 0; it < RS_KS / 8; ++it) {
+                const int r = it * 8 + wave * 2 + half, rc = r < rows ? r : rows - 1;
+                const float4 v = *reinterpret_cast<const float4*>(p.inp + (int64_t)(k0 + rc) * p.inp_ld + 4 * cc);
+                pre[4 * it] = v.x; pre[4 * it + 1] = v.y; pre[4 * it + 2] = v.z; pre[4 * it + 3] = v.w;
+            }
+        } else {
+            const int ca = lane < N ? lane : N - 1, cb = lane + 64 < N ? lane + 64 : N - 1;
+#pragma unroll
+            for (int it = 0; it < RS_KS / 4; ++it) {
+                const int r = it * 4 + wave, rc = r < rows ? r : rows - 1;
+                const float* row = p.inp + (int64_t)(k0 + rc) * p.inp_ld;
+                pre[2 * it] = row[ca];
+                if constexpr (WIDE) pre[2 * it + 1] = row[cb];
+            }
+        }
+#pragma unroll
+        for (int it = 0; it < RS_GIT; ++it) {
+            const int e = it * 256 + tid, gr = e / WGMAP_GCOLS, gc = e % WGMAP_GCOLS;
+            const int rc = gr < rows ? gr : rows - 1, cc = gc < gcols ? gc : gcols - 1;
+            gpre[it] = p.gout[(int64_t)(k0 + rc) * p.gout_ld + m_lo + cc];
+        }
+    };
+    auto store_slice = [&](const int k0) {
+        const int rows = K - k0 < RS_KS ? K - k0 : RS_KS;
+        if constexpr (VEC) {
+#pragma unroll
+            for (int it = 0; it < RS_KS / 8; ++it) {
+                const int r = it * 8 + wave * 2 + half;
+                if (r < rows && c4 < W)
+                    reinterpret_cast<float4*>(sx)[r * W + c4] = float4{pre[4 * it], pre[4 * it + 1], pre[4 * it + 2], pre[4 * it + 3]};
+            }
+        } else {
+#pragma unroll
+            for (int it = 0; it < RS_KS / 4; ++it) {
+                const int r = it * 4 + wave;
+                if (r < rows && lane < N) sx[r * N + lane] = pre[2 * it];
+                if constexpr (WIDE) {
+                    if (r < rows && lane + 64 < N) sx[r * N + lane + 64] = pre[2 * it + 1];
+                }
+            }
+        }
+#pragma unroll
+        for (int it = 0; it < RS_GIT; ++it) {
+            const int e = it * 256 + tid;
+            if (e / WGMAP_GCOLS < rows && e % WGMAP_GCOLS < gcols) sg[e] = gpre[it];
+        }
+    };
+    float acc[32];
+#pragma unroll
+    for (int j = 0; j < 32; ++j) acc[j] = 0.0f;
+    const float* px = sx + n;
+    const float* pg = sg + (m - m_lo);
+    auto products = [&](const int t) {   // terms t .. t + 31 of the staged slice (t = 0 mod 32: accumulator j for term t + j)
+#pragma unroll
+        for (int j = 0; j < 32; ++j) acc[j] = fmaf(pg[(t + j) * WGMAP_GCOLS], px[(t + j) * N], acc[j]);
+    };
+    load_slice(0);
+    int k0 = 0;
+    for (; k0 + RS_KS < K; k0 += RS_KS) {   // the whole slices in front of the last one
+        store_slice(k0);
+        __syncthreads();
+        load_slice(k0 + RS_KS);                // in flight during the products below
+#pragma unroll
+        for (int t = 0; t < RS_KS; t += 32) products(t);
+        __syncthreads();                       // every wave is done reading this slice
+    }
+    store_slice(k0);                           // the last slice: 1 .. RS_KS terms
+    __syncthreads();
+    const int rows = K - k0;
+    int t = 0;
+    for (; t + 32 <= rows; t += 32) products(t);
+    const int rem = rows - t;
+#pragma unroll
+    for (int j = 0; j < 32; ++j)
+        if (j < rem) acc[j] = fmaf(pg[(t + j) * WGMAP_GCOLS], px[(t + j) * N], acc[j]);
+    float pw[4];
+#pragma unroll
+    for (int w = 0; w < 4; ++w)
+        pw[w] = ((acc[8 * w] + acc[8 * w + 1]) + (acc[8 * w + 2] + acc[8 * w + 3])) + ((acc[8 * w + 4] + acc[8 * w + 5]) + (acc[8 * w + 6] + acc[8 * w + 7]));
+    const float v = (pw[0] + pw[1]) + (pw[2] + pw[3]);
+    p.dW[(int64_t)m * p.dw_ld + n] = v;
+    const float sq = wgrad_wave_sum(fmaf(v, v, 0.0f));
+    if (lane == 0) {
+        ln.partials[group0 + wave] = sq;
+        if (group0 == 0 && wave == 0) ln.step[0] += 1.0f;
+    }
+}
+
+// `groups` = ceil(items / 64) <= WGMAP_MAX_GROUPS: a plain block runs the plain kernel's body for its one group (block g of
+// `groups` blocks: one trip of its loop); the problem of a fast block is picked with compile-time indices only
+__global__ void __launch_bounds__(256) wgrad_reduce_rows_staged_kernel(const WgradBatch b, const WgradNorm ln, const unsigned rows_mask,
+                                                                       const unsigned vec_mask, const WgradRowsMap map, const unsigned groups) {
+    // (dynamic: RS_LDS_BYTES; one set for the three instantiations of the fast body, 16-byte aligned behind the plain body's 1 KB.
+    // A plain block is given the 17 KB too and never touches them: at 115 VGPRs four blocks per CU still fit, 72 KB of 160.)
+    extern __shared__ __attribute__((aligned(16))) float rs_lds[];
+    const int bid = (int)blockIdx.x;
+    int first = 0, g0 = map.group0[0], prob = map.prob[0];
+#pragma unroll
+    for (int s = 1; s < WGMAP_MAX_SEG; ++s) {
+        if (s < map.n_seg && bid >= map.block_start[s]) { first = map.block_start[s]; g0 = map.group0[s]; prob = map.prob[s]; }
+    }
+    if (prob < 0) {
+        wgrad_reduce_norm_body<true, true>(b, ln, rows_mask, (unsigned)(g0 + (bid - first)), groups);
+        return;
+    }
+    RowsFastProb p;
+#define MACJD_PICK_ROWS(q)                                                                                         \
+    p.gout = b.io[q].gout; p.inp = b.io[q].inp; p.dW = b.io[q].dW; p.gout_ld = b.io[q].gout_ld;                   \
+    p.inp_ld = b.io[q].inp_ld; p.dw_ld = b.io[q].dw_ld; p.start = b.out_start[q]; p.K = (int)b.io[q].K; p.N = b.io[q].N;
+    MACJD_PICK_ROWS(0)
+#pragma unroll
+    for (int q = 1; q < MACJD_WGRAD_MAX_BATCH; ++q) {
+        if (q == prob) { MACJD_PICK_ROWS(q) }
+    }
+#undef MACJD_PICK_ROWS
+    float* sx = rs_lds;
+    float* sg = rs_lds + RS_KS * WGMAP_N_CAP;
+    const int group0 = g0 + WGMAP_FAST_GROUPS * (bid - first);
+    if ((vec_mask >> prob) & 1u) wgrad_rows_staged_body<true, false>(p, group0, ln, sx, sg);
+    else if (p.N > 64) wgrad_rows_staged_body<false, true>(p, group0, ln, sx, sg);
+    else wgrad_rows_staged_body<false, false>(p, group0, ln, sx, sg);
+}
+
+static_assert(WGMAP_MAX_PROBLEMS == MACJD_WGRAD_MAX_BATCH && WGMAP_GROUP == WG_RED, "macjd_wgrad_map.h mirrors these");
 
 }  // namespace macjd
 
@@ -720,9 +909,51 @@ extern "C" int64_t macjd_wgrad_slot_floats(int32_t M, int32_t N, int64_t slots) 
     return slots * Mp * Np + slots * Mp;
 }
 
-extern "C" int macjd_linear_wgrad_many_norm(const macjd_wgrad_io* ios, int32_t n, const macjd_wgrad_norm_io* norm, void* hip_stream) {
+// block map of the staged ROWS reduce for a validated batch; returns its blocks, or -1 where the plain rows kernel runs
+// (the switch, no ROW PRODUCTS problem, the grid-stride case, or no fast block at all)
+static int wgrad_rows_map(const macjd_wgrad_io* ios, const macjd::WgradBatch& b, unsigned rows_mask, uint32_t flags,
+                          macjd::WgradRowsMap* map, unsigned* vec_mask) {
     using namespace macjd;
-    const char* who = "macjd_linear_wgrad_many_norm";
+    if (!rows_mask || (flags & MACJD_WGRAD_PLAIN_ROWS)) return -1;
+    int32_t M[MACJD_WGRAD_MAX_BATCH], N[MACJD_WGRAD_MAX_BATCH];
+    bool fast_ok[MACJD_WGRAD_MAX_BATCH];
+    unsigned vec = 0;
+    for (int p = 0; p < b.n; ++p) {
+        M[p] = b.io[p].M; N[p] = b.io[p].N;
+        fast_ok[p] = ((rows_mask >> p) & 1u) && ios[p].K <= (1 << 30);
+        if ((((uintptr_t)b.io[p].inp) & 15) == 0 && (b.io[p].inp_ld & 3) == 0 && (b.io[p].N & 3) == 0) vec |= 1u << p;
+    }
+    const int blocks = wgmap_build(b.n, b.out_start, M, N, fast_ok, map);
+    bool any_fast = false;
+    for (int s = 0; s < map->n_seg; ++s) any_fast = any_fast || map->prob[s] >= 0;
+    *vec_mask = vec;
+    return any_fast ? blocks : -1;
+}
+
+extern "C" int32_t macjd_linear_wgrad_many_norm_blocks(const macjd_wgrad_io* ios, int32_t n, int32_t ln_problem, uint32_t flags) {
+    macjd::WgradBatch b;
+    unsigned rows_mask = 0, vec_mask = 0;
+    if (wgrad_norm_batch(ios, n, ln_problem, &b, "macjd_linear_wgrad_many_norm_blocks", &rows_mask) != MACJD_OK) return -1;
+    macjd::WgradRowsMap map;
+    const int blocks = wgrad_rows_map(ios, b, rows_mask, flags, &map, &vec_mask);
+    return blocks >= 0 ? blocks : (int32_t)wgrad_reduce_blocks(b.out_start[n]);
+}
+
+static int wgrad_many_norm_launch(const macjd_wgrad_io* ios, int32_t n, const macjd_wgrad_norm_io* norm, uint32_t flags, void* hip_stream,
+                                  const char* who);
+
+extern "C" int macjd_linear_wgrad_many_norm(const macjd_wgrad_io* ios, int32_t n, const macjd_wgrad_norm_io* norm, void* hip_stream) {
+    return wgrad_many_norm_launch(ios, n, norm, 0u, hip_stream, "macjd_linear_wgrad_many_norm");
+}
+
+extern "C" int macjd_linear_wgrad_many_norm_ex(const macjd_wgrad_io* ios, int32_t n, const macjd_wgrad_norm_io* norm, uint32_t flags,
+                                               void* hip_stream) {
+    return wgrad_many_norm_launch(ios, n, norm, flags, hip_stream, "macjd_linear_wgrad_many_norm_ex");
+}
+
+static int wgrad_many_norm_launch(const macjd_wgrad_io* ios, int32_t n, const macjd_wgrad_norm_io* norm, uint32_t flags, void* hip_stream,
+                                  const char* who) {
+    using namespace macjd;
     if (!norm || !norm->partials || !norm->step) return set_err(MACJD_EINVAL, "%s: bad argument", who);
     WgradBatch b;
     unsigned rows_mask = 0;
@@ -743,9 +974,18 @@ extern "C" int macjd_linear_wgrad_many_norm(const macjd_wgrad_io* ios, int32_t n
     hipStream_t s = (hipStream_t)hip_stream;
     if (b.wg_start[n] > 0)   // (no problem of kind 0: nothing to multiply)
         hipLaunchKernelGGL(wgrad_partial_many_norm_kernel, dim3((unsigned)b.wg_start[n]), dim3(256), 0, s, b, ln);
-    if (rows_mask) hipLaunchKernelGGL(wgrad_reduce_many_rows_kernel, dim3(rblocks), dim3(256), 0, s, b, ln, rows_mask);
+    WgradRowsMap map;
+    unsigned vec_mask = 0;
+    const int sblocks = wgrad_rows_map(ios, b, rows_mask, flags, &map, &vec_mask);
+    if (sblocks > 0)
+        hipLaunchKernelGGL(wgrad_reduce_rows_staged_kernel, dim3((unsigned)sblocks), dim3(256), RS_LDS_BYTES, s, b, ln, rows_mask, vec_mask, map, rblocks);
+    else if (rows_mask) hipLaunchKernelGGL(wgrad_reduce_many_rows_kernel, dim3(rblocks), dim3(256), 0, s, b, ln, rows_mask);
     else hipLaunchKernelGGL(wgrad_reduce_many_norm_kernel, dim3(rblocks), dim3(256), 0, s, b, ln);
     hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_linear_wgrad_many_norm: %s", hipGetErrorString(err));
+    if (err != hipSuccess) {
+        char msg[192];
+        snprintf(msg, sizeof msg, "%s: %s", who, hipGetErrorString(err));
+        return set_err(MACJD_EDEVICE, "%s", msg);
+    }
     return MACJD_OK;
 }

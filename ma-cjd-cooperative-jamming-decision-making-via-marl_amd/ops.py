@@ -1723,7 +1723,8 @@ class deferred_wgrad:
         nio.partials, nio.step = partials.data_ptr(), step.data_ptr()
         t0 = pending[0][1][0]
         with torch.cuda.device(t0.device):
-            _native.check(lib.macjd_linear_wgrad_many_norm(arr, len(pending), ctypes.byref(nio), _stream(t0)),
+            flags = 0 if options.on("ROWS_STAGED") else _native.WGRAD_PLAIN_ROWS
+            _native.check(lib.macjd_linear_wgrad_many_norm_ex(arr, len(pending), ctypes.byref(nio), flags, _stream(t0)),
                           "macjd_linear_wgrad_many_norm")
         if int(lib.macjd_linear_wgrad_many_norm_work_items(arr, len(pending), q)) > 0:   # (0: only the reduce went out)
             global wgrad_partial_launches

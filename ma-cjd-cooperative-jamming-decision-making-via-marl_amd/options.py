@@ -31,6 +31,8 @@ for normal operation.
                                          contraction as one slot per tile and the reduce launch forms the mixer's five products from
                                          the compact rows: no partial-products launch (default learner, f32 mixer, H = 64, A <= 15) /
                                          the partial-products launch
+    MACJD_ROWS_STAGED         1 | 0      the reduce launch's row products: blocks of 256 outputs, one per thread, on operand rows
+                                         staged once per block into LDS (bit-identical results) / two global loads per lane and term
     MACJD_PREFETCH_LAUNCH     1 | 0      pipelined group: a later update's draw, gather, mask sum and scan as ONE launch, the
                                          draw read-only at a baked counter offset / the four launches one behind the other
     MACJD_PREFETCH_AHEAD      2 | 1      that launch for the batches of TWO consecutive updates, issued two updates before the
@@ -52,7 +54,7 @@ import os
 _DEFAULTS = {
     "UPDATE_STREAMS": "2", "UPDATES_PER_GRAPH": "1", "PIPELINED_GROUP": "1", "SHARED_BODY": "1",
     "LEARNER_STATIC_OBS": "1", "ACTOR_IN_SCAN": "1", "DEVICE_SAMPLER": "1", "LN_IN_SQNORM": "1", "NORM_IN_REDUCE": "1", "WGRAD_OUTER": "1",
-    "QHEAD_TAKEN": "1", "QHEAD_DOUBLE_Q": "1", "QHEAD_DOUBLE_Q_H128": "0", "PAIRED_HEADS": "1", "MIXER_TRAIN": "1", "MIXER_STATIC_STATE": "1", "WGRAD_IN_TRAIN": "1", "GRAPHED_ALLREDUCE": "0",
+    "QHEAD_TAKEN": "1", "QHEAD_DOUBLE_Q": "1", "QHEAD_DOUBLE_Q_H128": "0", "PAIRED_HEADS": "1", "MIXER_TRAIN": "1", "MIXER_STATIC_STATE": "1", "WGRAD_IN_TRAIN": "1", "ROWS_STAGED": "1", "GRAPHED_ALLREDUCE": "0",
     "PREFETCH_LAUNCH": "1", "PREFETCH_AHEAD": "2",
     "CLOSED_LOOP_ROLLOUT": "0", "MOVING_EPISODE_ROLLOUT": "0", "CLOSED_LOOP_MOVING_ROLLOUT": "0",
     "MOVING_PE_EPISODE_ROLLOUT": "0",
