@@ -225,8 +225,9 @@ int macjd_clip_adam_step_sample(const macjd_adam_io* io, const macjd_sampler_io*
  * Weight and bias gradient of y = x W^T + b over K rows:  dW[M,N] = gout[K,M]^T x inp[K,N],  db[M] = sum_k gout[k,:]
  * (the backward of torch.nn.Linear for its parameters, core/qmix.py:198 loss.backward()).  On this path the outputs
  * are tiny (e.g. [192,128]) and K is 3e3..1e4 rows, so the reduction is split over K: every workgroup computes one
- * 64x64 output tile for one 128-row K-chunk on exact-f32 MFMA into `workspace`, a second launch sums the chunks in
- * fixed order (deterministic).  workspace >= macjd_linear_wgrad_workspace_floats(K, M, N) floats.
+ * 64x64 output tile for one 64-row K-chunk on exact-f32 MFMA into `workspace`, a second launch sums the chunks in
+ * fixed order (deterministic).  workspace >= macjd_linear_wgrad_workspace_floats(K, M, N) floats; the number of chunks is
+ * what that size implies: chunks (Mp Np + Mp) floats with Mp / Np = M / N padded to 64.
  */
 typedef struct macjd_wgrad_io {
     int64_t K;
