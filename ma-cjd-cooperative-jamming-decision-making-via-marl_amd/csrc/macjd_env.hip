@@ -31,6 +31,7 @@
 
 #include "../../include/macjd.h"
 #include "macjd_env_dev.h"
+#include "macjd_env_plan.h"
 #include "macjd_env_step.h"
 #include "macjd_err.h"
 #include "macjd_philox.h"
@@ -376,20 +377,28 @@ __global__ void scenario_derive_kernel(DevTables* t) {
 
 }  // namespace macjd
 
+using macjd::CompiledDim;
 using macjd::DevTables;
+using macjd::LanePlan;
+using macjd::lane_plan;
 using macjd::set_err;
 
 // ---- host side of the env_step_kernel launches: each rule once (templates: outside the extern "C" block) ----
 
-// Geometry of a lane-kernel launch (one lane per work item).  Small batches: one wave per workgroup spreads the envs
-// over more CUs (latency-bound regime); from 2^16 items: 256-lane workgroups, tables staged once per workgroup.
-// `blocks` gives every item a lane of its own (production variants: no grid-stride loop), `strided` is the capped grid
-// of the general variants' grid-stride loop.
-struct LaneGrid { int block; int64_t blocks; unsigned strided; };
-static LaneGrid lane_grid(int64_t items) {
-    const int block = (items >= (1 << 16)) ? 256 : 64;
-    const int64_t blocks = (items + block - 1) / block, cap = (block == 256) ? 256 * 8 : 256 * 16;
-    return {block, blocks, (unsigned)(blocks > cap ? cap : blocks)};
+// Geometry of a lane-kernel launch: macjd::lane_plan (macjd_env_plan.h); the production variants run on its full grid
+static dim3 full_grid(const LanePlan& p) { return dim3((unsigned)p.full_x, (unsigned)p.full_y); }
+
+// Grid of the reset / counter-advance kernels (256 lanes per workgroup, grid-stride loop over n items)
+static dim3 strided_grid_256(int64_t n) {
+    const int64_t grid = (n + 255) / 256;
+    return dim3((unsigned)(grid > 4096 ? 4096 : grid));
+}
+
+// set_err with the entry point's name and a second word (the wordings of two entry points that share a check)
+static int set_err2(int code, const char* fmt, const char* who, const char* word) {
+    char msg[384];
+    snprintf(msg, sizeof(msg), fmt, who, word);
+    return set_err(code, "%s", msg);
 }
 
 // Every byte offset of a strided per-env array ([n_envs] x items elements of `elem` bytes, + extra elements) below 2^32
@@ -435,29 +444,34 @@ static void fill_scan(X& x, const macjd_scan_io* sc) {
     x.snr_no = sc->snr_no; x.sn_se = sc->sn_se; x.sn_sx = sc->sn_sx;
 }
 
-// ... and a MOVING launch's (include/macjd.h, macjd_motion_io)
-template <class X>
-static void fill_motion(X& x, const macjd_motion_io* mo) {
-    x.frames = mo->frames; x.frame_flags = mo->frame_flags; x.frame_snr_no = mo->frame_snr_no;
-    x.positions = mo->positions; x.position_columns = mo->position_columns;
-    x.state = mo->state; x.mv_st_se = mo->st_se;
-    x.mv_snr_no = mo->snr_no; x.mv_sn_se = mo->sn_se; x.mv_sn_sx = mo->sn_sx;
-    x.n_frames = mo->n_frames; x.n_pos = mo->n_pos;
-}
+// What a MOVING launch reads beyond the step's own block, in one shape for the four table modes: the motion block as its
+// shared-frame form (a per-env block is converted once, motion_pe_as_motion) with the env tile (0: shared frames), and under
+// scanning radars the beam block and the per-frame scan / pattern tables (a per-env block converted likewise)
+struct MovingArgs {
+    macjd_motion_io mo;
+    int32_t tile;
+    const macjd_scan_io* sc;
+    macjd_motion_scan_io ms;
+};
 
-// ... and a MOVING SCANNING launch's (include/macjd.h, macjd_motion_scan_io)
-template <class X>
-static void fill_motion_scan(X& x, const macjd_motion_io* mo, const macjd_scan_io* sc, const macjd_motion_scan_io* ms) {
-    fill_scan(x, sc);
-    x.sp_tables = ms->scan_frames; x.sp_stride = 0;   // frame-major: the strides are not read
-    x.frames = mo->frames; x.frame_flags = mo->frame_flags;
-    x.positions = mo->positions; x.position_columns = mo->position_columns;
-    x.mv_state = mo->state; x.mv_st_se = mo->st_se;
-    x.n_frames = mo->n_frames; x.n_pos = mo->n_pos;
-}
-template <class X>
-static void fill_motion_scan_pattern(X& x, const macjd_motion_scan_io* ms) {
-    x.pp_tables = ms->pattern_frames; x.pp_stride = 0; x.pat_levels = ms->n_levels;
+// ... and a MOVING launch's members of the argument block (include/macjd.h, macjd_motion_io, macjd_motion_scan_io).  The
+// scanning blocks name the state rows mv_state (`state` is the beam block's) and have no snr_no output of their own.
+template <bool SCAN, bool PAT, class X>
+static void fill_moving(X& x, const MovingArgs& a) {
+    const macjd_motion_io& mo = a.mo;
+    x.frames = mo.frames; x.frame_flags = mo.frame_flags;
+    x.positions = mo.positions; x.position_columns = mo.position_columns;
+    x.mv_st_se = mo.st_se; x.n_frames = mo.n_frames; x.n_pos = mo.n_pos;
+    if constexpr (SCAN) {
+        fill_scan(x, a.sc);
+        x.sp_tables = a.ms.scan_frames; x.sp_stride = 0;   // frame-major: the strides are not read
+        x.mv_state = mo.state;
+        if constexpr (PAT) { x.pp_tables = a.ms.pattern_frames; x.pp_stride = 0; x.pat_levels = a.ms.n_levels; }
+    } else {
+        x.frame_snr_no = mo.frame_snr_no; x.state = mo.state;
+        x.mv_snr_no = mo.snr_no; x.mv_sn_se = mo.sn_se; x.mv_sn_sx = mo.sn_sx;
+    }
+    if constexpr (macjd::io_moves_pe<X>::value) x.mv_tile = a.tile;
 }
 
 template <int JT, int RT, bool PE, bool FAST, bool REG = false, bool PD32 = false, bool SCAN = false, bool PAT = false, class IO>
@@ -466,9 +480,7 @@ static void launch_lanes(dim3 grid, dim3 block, hipStream_t stream, const macjd_
 }
 
 // The compiled (J, R) sizes of env_step_kernel; every other size runs the generic <0, 0> kernel.  fn(JT, RT) takes the
-// size as two std::integral_constants and picks the variant.
-template <int N>
-using CompiledDim = std::integral_constant<int, N>;
+// size as two std::integral_constants (CompiledDim, macjd_env_step.h) and picks the variant.
 template <class F>
 static int with_compiled_size(int J, int R, F&& fn) {
     if (J == 3 && R == 4) return fn(CompiledDim<3>{}, CompiledDim<4>{});
@@ -488,6 +500,91 @@ static int launch_status(const char* who) {
     char msg[256];
     snprintf(msg, sizeof(msg), "%s launch: %s", who, hipGetErrorString(err));
     return set_err(MACJD_EDEVICE, "%s", msg);
+}
+
+// Argument block of a SCAN launch on per-env tables, with or without the pattern's rows
+template <bool PAT, class Base>
+using ScanPeIO = std::conditional_t<PAT, macjd::ScanPePatStepIO<Base>, macjd::ScanPeStepIO<Base>>;
+
+// SCAN launches on per-env scenario tables, with (PAT) or without a stepped antenna pattern: the lane kernel, single step
+// (include/macjd.h, macjd_env_step_scan_pe, macjd_env_step_scan_pe_pattern).  The production variant or the general one at
+// the sizes scan_pe_compiled covers, the generic-size kernel for the others.  `pp` is NULL without a pattern.
+template <bool PAT>
+static int launch_step_scan_pe(const macjd_scenario* s, const macjd_step_io* io, const macjd_scan_io* sc, const macjd_scan_pe_io* sp,
+                               const macjd_scan_pe_pattern_io* pp, hipStream_t stream, const char* who) {
+    const int64_t E = io->n_envs;
+    const int J = s->host.J, R = s->host.R;
+    const LanePlan lp = lane_plan(E, 0);
+    const dim3 gf = full_grid(lp), g(lp.strided), b(lp.block);
+    const bool fast = production_io(io, J, R, lp.blocks, 0, 0) && scan_spans_ok(sc, E, R);
+    const auto fill_tables = [&](auto& x) {
+        fill_scan(x, sc);
+        x.sp_tables = sp->tables; x.sp_stride = sp->stride;
+        if constexpr (PAT) { x.pp_tables = pp->tables; x.pp_stride = pp->stride; x.pat_levels = pp->n_levels; }
+    };
+    ScanPeIO<PAT, macjd::FastStepIO> f{};
+    ScanPeIO<PAT, macjd_step_io> w{};
+    static_cast<macjd_step_io&>(w) = *io;
+    fill_tables(w);
+    if (fast) {
+        fill_fast(f, io, 0, 0);
+        f.pe_tables = io->pe_tables; f.pe_flags = io->pe_flags; f.pe_stride = io->pe_stride; f.pe_tile = io->pe_tile;
+        fill_tables(f);
+    }
+    // launch_lanes<JT, RT, PE = true, FAST, REG = false, PD32 = false, SCAN = true, PAT>
+    with_compiled_size(J, R, [&](auto jt, auto rt) -> int {
+        constexpr int JT = decltype(jt)::value, RT = decltype(rt)::value;
+        if constexpr (!scan_pe_compiled(JT)) macjd::launch_scan_pe_generic(g, b, stream, s->dev, w);
+        else if (fast) launch_lanes<JT, RT, true, true, false, false, true, PAT>(gf, b, stream, s, f);
+        else launch_lanes<JT, RT, true, false, false, false, true, PAT>(g, b, stream, s, w);
+        return MACJD_OK;
+    });
+    return launch_status(who);
+}
+
+// ---- moving scenarios: ONE dispatch path for the four table modes ("Moving env launches") ----
+
+// The production form's 32-bit offsets into the motion arrays: every state element of a row (the position columns lie below
+// the row stride; the caller's tables say which), the snr_no output
+static bool motion_spans_ok(const macjd_motion_io* mo, int64_t E, int R) {
+    return span_ok(E, mo->st_se, 1, 1, 4, mo->st_se - 1) && (!mo->snr_no || span_ok(E, mo->sn_se, mo->sn_sx, R, 4));
+}
+
+// Argument block of a MOVING launch: (per-env frames, scanning radars, stepped pattern, production or general base)
+template <bool MVPE, bool SCAN, bool PAT, class Base>
+using MovingIO = std::conditional_t<
+    SCAN, std::conditional_t<MVPE, macjd::MotionScanPeStepIO<ScanPeIO<PAT, Base>>, macjd::MotionScanStepIO<ScanPeIO<PAT, Base>>>,
+    std::conditional_t<MVPE, macjd::MotionPeStepIO<Base>, macjd::MotionStepIO<Base>>>;
+
+// MOVING launches: always the lane kernel on the frame tables (include/macjd.h, macjd_env_step_moving and its _pe, _scan,
+// _scan_pe and many-step forms).  The production variant at a compiled moving size in the production configuration whose
+// 32-bit offsets fit; otherwise the general variant (the generic-size kernel at the other sizes), single steps only.
+template <bool MVPE, bool SCAN, bool PAT>
+static int launch_step_moving(const macjd_scenario* s, const macjd_step_io* io, const MovingArgs& a, hipStream_t stream,
+                              int32_t many_T, int64_t t_stride, const char* who) {
+    const int64_t E = io->n_envs;
+    const int J = s->host.J, R = s->host.R;
+    if (many_T > 65535) return set_err(MACJD_EINVAL, "%s: at most 65535 steps per launch", who);
+    const LanePlan lp = lane_plan(E, many_T);
+    bool fast = macjd::motion_size_compiled(J, R) && production_io(io, J, R, lp.blocks, many_T, t_stride) &&
+                motion_spans_ok(&a.mo, E, R);
+    if constexpr (SCAN) fast = fast && scan_spans_ok(a.sc, E, R);
+    if constexpr (MVPE) fast = fast && E < ((int64_t)1 << 31);   // the env index and its tile arithmetic in 32 bits
+    if (fast) {
+        MovingIO<MVPE, SCAN, PAT, macjd::FastStepIO> f{};
+        fill_fast(f, io, many_T, t_stride);
+        fill_moving<SCAN, PAT>(f, a);
+        (void)macjd::launch_motion(J, R, full_grid(lp), dim3(lp.block), stream, s->dev, f);
+    } else {
+        if (many_T > 0)
+            return set_err(MACJD_EUNSUPPORTED, "%s: production configuration at a compiled size (2j/2r, 3j/4r, 6j/8r) only: Philox "
+                           "uniforms, float32 actions, no float64 diagnostics, offsets below 2^32 bytes", who);
+        MovingIO<MVPE, SCAN, PAT, macjd_step_io> w{};
+        static_cast<macjd_step_io&>(w) = *io;
+        fill_moving<SCAN, PAT>(w, a);
+        (void)macjd::launch_motion(J, R, dim3(lp.strided), dim3(lp.block), stream, s->dev, w);
+    }
+    return launch_status(who);
 }
 
 extern "C" {
@@ -591,10 +688,7 @@ int macjd_env_reset(const macjd_scenario* s, int64_t n_envs, uint8_t* track, int
                     int32_t* step, const uint8_t* mask, int32_t* episode, void* hip_stream) {
     if (!s || !track || !step || n_envs < 0) return set_err(MACJD_EINVAL, "macjd_env_reset: bad argument");
     if (n_envs == 0) return MACJD_OK;
-    const int block = 256;
-    int64_t grid = (n_envs + block - 1) / block;
-    if (grid > 4096) grid = 4096;
-    hipLaunchKernelGGL(macjd::env_reset_kernel, dim3((unsigned)grid), dim3(block), 0, (hipStream_t)hip_stream, n_envs,
+    hipLaunchKernelGGL(macjd::env_reset_kernel, strided_grid_256(n_envs), dim3(256), 0, (hipStream_t)hip_stream, n_envs,
                        s->host.R, track, k_se, k_sx, step, mask, episode);
     return launch_status("macjd_env_reset");
 }
@@ -639,11 +733,9 @@ static int launch_step(const macjd_scenario* s, const macjd_step_io* io, hipStre
     }
     // generic sizes (and the A/B hook): one lane per env
     if (many_T > 65535) return set_err(MACJD_EINVAL, "%s", "macjd_env_step_many: at most 65535 steps per launch");
-    const LaneGrid lg = lane_grid(E);
-    // many-step launches: grid = (envs / block, steps)
-    const dim3 gf((unsigned)(many_T > 0 ? (io->n_envs + lg.block - 1) / lg.block : lg.blocks), (unsigned)(many_T > 0 ? many_T : 1));
-    const dim3 g(lg.strided), b(lg.block);
-    const bool fast = production_io(io, J, R, lg.blocks, many_T, t_stride);
+    const LanePlan lp = lane_plan(io->n_envs, many_T);
+    const dim3 gf = full_grid(lp), g(lp.strided), b(lp.block);
+    const bool fast = production_io(io, J, R, lp.blocks, many_T, t_stride);
     macjd::FastStepIO f{};
     if (fast) {
         fill_fast(f, io, many_T, t_stride);
@@ -677,9 +769,9 @@ static int launch_step(const macjd_scenario* s, const macjd_step_io* io, hipStre
 static int launch_step_scan(const macjd_scenario* s, const macjd_step_io* io, const macjd_scan_io* sc, hipStream_t stream) {
     const int64_t E = io->n_envs;
     const int J = s->host.J, R = s->host.R;
-    const LaneGrid lg = lane_grid(E);
-    const dim3 gf((unsigned)lg.blocks), g(lg.strided), b(lg.block);
-    const bool fast = production_io(io, J, R, lg.blocks, 0, 0) && scan_spans_ok(sc, E, R);
+    const LanePlan lp = lane_plan(E, 0);
+    const dim3 gf = full_grid(lp), g(lp.strided), b(lp.block);
+    const bool fast = production_io(io, J, R, lp.blocks, 0, 0) && scan_spans_ok(sc, E, R);
     macjd::ScanStepIO<macjd::FastStepIO> f{};
     macjd::ScanStepIO<macjd_step_io> w{};
     static_cast<macjd_step_io&>(w) = *io;
@@ -812,75 +904,10 @@ int macjd_env_reset_scan(const macjd_scenario* s, int64_t n_envs, const macjd_sc
     int rc = validate_scan(s, scan, "macjd_env_reset_scan");
     if (rc != MACJD_OK) return rc;
     if (n_envs == 0) return MACJD_OK;
-    int64_t grid = (n_envs + 255) / 256;
-    if (grid > 4096) grid = 4096;
-    hipLaunchKernelGGL(macjd::env_reset_scan_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)hip_stream, s->dev, n_envs,
+    hipLaunchKernelGGL(macjd::env_reset_scan_kernel, strided_grid_256(n_envs), dim3(256), 0, (hipStream_t)hip_stream, s->dev, n_envs,
                        s->host.R, scan->theta_a, scan->a_se, scan->a_sx, scan->state, scan->st_se, scan->st_col0,
                        scan->st_col_step, mask);
     return launch_status("macjd_env_reset_scan");
-}
-
-// SCAN launches on per-env scenario tables: the lane kernel, single step (include/macjd.h, macjd_env_step_scan_pe)
-static int launch_step_scan_pe(const macjd_scenario* s, const macjd_step_io* io, const macjd_scan_io* sc, const macjd_scan_pe_io* sp,
-                               hipStream_t stream) {
-    const int64_t E = io->n_envs;
-    const int J = s->host.J, R = s->host.R;
-    const LaneGrid lg = lane_grid(E);
-    const dim3 gf((unsigned)lg.blocks), g(lg.strided), b(lg.block);
-    const bool fast = production_io(io, J, R, lg.blocks, 0, 0) && scan_spans_ok(sc, E, R);
-    macjd::ScanPeStepIO<macjd::FastStepIO> f{};
-    macjd::ScanPeStepIO<macjd_step_io> w{};
-    static_cast<macjd_step_io&>(w) = *io;
-    fill_scan(w, sc);
-    w.sp_tables = sp->tables; w.sp_stride = sp->stride;
-    if (fast) {
-        fill_fast(f, io, 0, 0);
-        f.pe_tables = io->pe_tables; f.pe_flags = io->pe_flags; f.pe_stride = io->pe_stride; f.pe_tile = io->pe_tile;
-        fill_scan(f, sc);
-        f.sp_tables = sp->tables; f.sp_stride = sp->stride;
-    }
-    // launch_lanes<JT, RT, PE = true, FAST, REG = false, PD32 = false, SCAN = true>
-    with_compiled_size(J, R, [&](auto jt, auto rt) -> int {
-        constexpr int JT = decltype(jt)::value, RT = decltype(rt)::value;
-        if constexpr (!scan_pe_compiled(JT)) macjd::launch_scan_pe_generic(g, b, stream, s->dev, w);
-        else if (fast) launch_lanes<JT, RT, true, true, false, false, true>(gf, b, stream, s, f);
-        else launch_lanes<JT, RT, true, false, false, false, true>(g, b, stream, s, w);
-        return MACJD_OK;
-    });
-    return launch_status("macjd_env_step_scan_pe");
-}
-
-// SCAN launches under a stepped antenna pattern on per-env tables (include/macjd.h, macjd_env_step_scan_pe_pattern): the
-// production variant or the general one at the sizes scan_pe_compiled covers, the generic-size kernel for the others
-static int launch_step_scan_pe_pattern(const macjd_scenario* s, const macjd_step_io* io, const macjd_scan_io* sc,
-                                       const macjd_scan_pe_io* sp, const macjd_scan_pe_pattern_io* pp, hipStream_t stream) {
-    const int64_t E = io->n_envs;
-    const int J = s->host.J, R = s->host.R;
-    const LaneGrid lg = lane_grid(E);
-    const dim3 gf((unsigned)lg.blocks), g(lg.strided), b(lg.block);
-    const bool fast = production_io(io, J, R, lg.blocks, 0, 0) && scan_spans_ok(sc, E, R);
-    macjd::ScanPePatStepIO<macjd::FastStepIO> f{};
-    macjd::ScanPePatStepIO<macjd_step_io> w{};
-    static_cast<macjd_step_io&>(w) = *io;
-    fill_scan(w, sc);
-    w.sp_tables = sp->tables; w.sp_stride = sp->stride;
-    w.pp_tables = pp->tables; w.pp_stride = pp->stride; w.pat_levels = pp->n_levels;
-    if (fast) {
-        fill_fast(f, io, 0, 0);
-        f.pe_tables = io->pe_tables; f.pe_flags = io->pe_flags; f.pe_stride = io->pe_stride; f.pe_tile = io->pe_tile;
-        fill_scan(f, sc);
-        f.sp_tables = sp->tables; f.sp_stride = sp->stride;
-        f.pp_tables = pp->tables; f.pp_stride = pp->stride; f.pat_levels = pp->n_levels;
-    }
-    // launch_lanes<JT, RT, PE = true, FAST, REG = false, PD32 = false, SCAN = true, PAT = true>
-    with_compiled_size(J, R, [&](auto jt, auto rt) -> int {
-        constexpr int JT = decltype(jt)::value, RT = decltype(rt)::value;
-        if constexpr (!scan_pe_compiled(JT)) macjd::launch_scan_pe_pattern_generic(g, b, stream, s->dev, w);
-        else if (fast) launch_lanes<JT, RT, true, true, false, false, true, true>(gf, b, stream, s, f);
-        else launch_lanes<JT, RT, true, false, false, false, true, true>(g, b, stream, s, w);
-        return MACJD_OK;
-    });
-    return launch_status("macjd_env_step_scan_pe_pattern");
 }
 
 // `pattern_ok`: the caller brings the pattern's levels per env (macjd_env_step_scan_pe_pattern); the handle's are not read
@@ -921,7 +948,7 @@ int macjd_env_step_scan_pe_pattern(const macjd_scenario* s, const macjd_step_io*
     if (io->flags & MACJD_STEP_SLOT_KERNEL)
         return set_err(MACJD_EUNSUPPORTED, "%s: the (env x slot) kernel has no per-env pattern variant (one lane per env only)", me);
     if (io->n_envs == 0) return MACJD_OK;
-    return launch_step_scan_pe_pattern(s, io, scan, scan_pe, pattern, (hipStream_t)hip_stream);
+    return launch_step_scan_pe<true>(s, io, scan, scan_pe, pattern, (hipStream_t)hip_stream, me);
 }
 
 int macjd_env_step_scan_pe(const macjd_scenario* s, const macjd_step_io* io, const macjd_scan_io* scan, const macjd_scan_pe_io* scan_pe,
@@ -935,7 +962,7 @@ int macjd_env_step_scan_pe(const macjd_scenario* s, const macjd_step_io* io, con
     rc = validate_scan_pe(s, scan_pe, io->n_envs, io->pe_tile, me);
     if (rc != MACJD_OK) return rc;
     if (io->n_envs == 0) return MACJD_OK;
-    return launch_step_scan_pe(s, io, scan, scan_pe, (hipStream_t)hip_stream);
+    return launch_step_scan_pe<false>(s, io, scan, scan_pe, nullptr, (hipStream_t)hip_stream, me);
 }
 
 int macjd_env_reset_scan_pe(const macjd_scenario* s, int64_t n_envs, const macjd_scan_io* scan, const macjd_scan_pe_io* scan_pe,
@@ -947,9 +974,7 @@ int macjd_env_reset_scan_pe(const macjd_scenario* s, int64_t n_envs, const macjd
     rc = validate_scan_pe(s, scan_pe, n_envs, pe_tile, me);
     if (rc != MACJD_OK) return rc;
     if (n_envs == 0) return MACJD_OK;
-    int64_t grid = (n_envs + 255) / 256;
-    if (grid > 4096) grid = 4096;
-    hipLaunchKernelGGL(macjd::env_reset_scan_pe_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)hip_stream, n_envs,
+    hipLaunchKernelGGL(macjd::env_reset_scan_pe_kernel, strided_grid_256(n_envs), dim3(256), 0, (hipStream_t)hip_stream, n_envs,
                        s->host.R, s->host.J, scan_pe->tables, scan_pe->stride, pe_tile, scan->theta_a, scan->a_se, scan->a_sx,
                        scan->state, scan->st_se, scan->st_col0, scan->st_col_step, mask);
     return launch_status(me);
@@ -962,23 +987,39 @@ int macjd_env_step(const macjd_scenario* s, const macjd_step_io* io, void* hip_s
     return launch_step(s, io, (hipStream_t)hip_stream);
 }
 
+// The argument checks of a many-step entry point `me`.  `unwritten` names the per-step outputs such a launch does not write
+// ("pd / snr_with", plus "snr_no" where the entry has a block that carries one: `also_unwritten`).
+static int validate_many(const macjd_step_io* io, int32_t n_steps, int64_t t_stride, const void* also_unwritten,
+                         const char* unwritten, const char* me) {
+    if (n_steps < 1 || t_stride < 0) return set_err(MACJD_EINVAL, "%s: bad n_steps / t_stride", me);
+    if (io->pd || io->snr_with || also_unwritten) return set_err2(MACJD_EINVAL, "%s: %s are not written (pass NULL)", me, unwritten);
+    if (io->r_dpj_sum && !io->r_dpj) return set_err(MACJD_EINVAL, "%s: r_dpj_sum needs the per-step r_dpj buffer", me);
+    return MACJD_OK;
+}
+
+// Second launch of a many-step entry point: the step counters and the reward-component sums (env_advance_kernel)
+static int advance_after_many(const macjd_step_io* io, int32_t n_steps, hipStream_t stream, const char* me) {
+    hipLaunchKernelGGL(macjd::env_advance_kernel, strided_grid_256(io->n_envs * 3), dim3(256), 0, stream, io->n_envs, n_steps,
+                       io->step, io->r_dpj, io->r_dpj_sum);
+    return launch_status(me);
+}
+
 int macjd_env_step_many(const macjd_scenario* s, const macjd_step_io* io, int32_t n_steps, int64_t t_stride, void* hip_stream) {
+    const char* me = "macjd_env_step_many";
     int rc = validate_io(s, io);
     if (rc != MACJD_OK) return rc;
-    if (n_steps < 1 || t_stride < 0) return set_err(MACJD_EINVAL, "%s", "macjd_env_step_many: bad n_steps / t_stride");
-    if (io->pd || io->snr_with) return set_err(MACJD_EINVAL, "%s", "macjd_env_step_many: pd / snr_with are not written (pass NULL)");
-    if (io->r_dpj_sum && !io->r_dpj) return set_err(MACJD_EINVAL, "%s", "macjd_env_step_many: r_dpj_sum needs the per-step r_dpj buffer");
+    rc = validate_many(io, n_steps, t_stride, nullptr, "pd / snr_with", me);
+    if (rc != MACJD_OK) return rc;
     if (io->n_envs == 0) return MACJD_OK;
     rc = launch_step(s, io, (hipStream_t)hip_stream, n_steps, t_stride);
     if (rc != MACJD_OK) return rc;
-    int64_t grid = (io->n_envs * 3 + 255) / 256;
-    if (grid > 4096) grid = 4096;
-    hipLaunchKernelGGL(macjd::env_advance_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)hip_stream, io->n_envs,
-                       n_steps, io->step, io->r_dpj, io->r_dpj_sum);
-    return launch_status("macjd_env_step_many");
+    return advance_after_many(io, n_steps, (hipStream_t)hip_stream, me);
 }
 
-// ---- moving scenarios (include/macjd.h, macjd_motion_io; kernels in macjd_env_motion.hip) ----
+}  // extern "C"
+
+// ---- moving scenarios (include/macjd.h, macjd_motion_io and its _pe, _scan, _scan_pe forms; kernels in macjd_env_motion*.hip,
+// dispatch in launch_step_moving above): the checks the entry points share (templates among them: C++ linkage) ----
 
 static int validate_motion(const macjd_scenario* s, const macjd_motion_io* mo, const char* what) {
     if (!s || !mo) return set_err(MACJD_EINVAL, "%s: NULL scenario / motion io", what);
@@ -994,90 +1035,7 @@ static int validate_motion(const macjd_scenario* s, const macjd_motion_io* mo, c
     return MACJD_OK;
 }
 
-// The production form's 32-bit offsets into the motion arrays: every state element of a row (the position columns lie below
-// the row stride; the caller's tables say which), the snr_no output
-static bool motion_spans_ok(const macjd_motion_io* mo, int64_t E, int R) {
-    return span_ok(E, mo->st_se, 1, 1, 4, mo->st_se - 1) && (!mo->snr_no || span_ok(E, mo->sn_se, mo->sn_sx, R, 4));
-}
-// MOVING launches: always the lane kernel on the frame tables (include/macjd.h, macjd_env_step_moving)
-static int launch_step_moving(const macjd_scenario* s, const macjd_step_io* io, const macjd_motion_io* mo, hipStream_t stream,
-                              int32_t many_T, int64_t t_stride, const char* who) {
-    const int64_t E = io->n_envs * (many_T > 0 ? many_T : 1);   // work items of the launch
-    const int J = s->host.J, R = s->host.R;
-    if (many_T > 65535) return set_err(MACJD_EINVAL, "%s: at most 65535 steps per launch", who);
-    const LaneGrid lg = lane_grid(E);
-    const dim3 gf((unsigned)(many_T > 0 ? (io->n_envs + lg.block - 1) / lg.block : lg.blocks), (unsigned)(many_T > 0 ? many_T : 1));
-    const dim3 g(lg.strided), b(lg.block);
-    const bool fast = macjd::motion_size_compiled(J, R) && production_io(io, J, R, lg.blocks, many_T, t_stride) &&
-                      motion_spans_ok(mo, io->n_envs, R);
-    if (fast) {
-        macjd::MotionStepIO<macjd::FastStepIO> f{};
-        fill_fast(f, io, many_T, t_stride);
-        fill_motion(f, mo);
-        (void)macjd::launch_motion_fast(J, R, gf, b, stream, s->dev, f);
-    } else {
-        if (many_T > 0)
-            return set_err(MACJD_EUNSUPPORTED, "%s: production configuration at a compiled size (2j/2r, 3j/4r, 6j/8r) only: Philox "
-                           "uniforms, float32 actions, no float64 diagnostics, offsets below 2^32 bytes", who);
-        macjd::MotionStepIO<macjd_step_io> w{};
-        static_cast<macjd_step_io&>(w) = *io;
-        fill_motion(w, mo);
-        macjd::launch_motion_general(J, R, g, b, stream, s->dev, w);
-    }
-    return launch_status(who);
-}
-
-int macjd_env_step_moving(const macjd_scenario* s, const macjd_step_io* io, const macjd_motion_io* motion, void* hip_stream) {
-    const char* me = "macjd_env_step_moving";
-    int rc = validate_io(s, io);
-    if (rc != MACJD_OK) return rc;
-    rc = validate_motion(s, motion, me);
-    if (rc != MACJD_OK) return rc;
-    if (io->pe_tables) return set_err(MACJD_EINVAL, "%s: io->pe_tables must be NULL (the frames are the tables)", me);
-    if (io->flags & MACJD_STEP_SLOT_KERNEL)
-        return set_err(MACJD_EUNSUPPORTED, "%s: the (env x slot) kernel has no moving variant (one lane per env only)", me);
-    if (io->n_envs == 0) return MACJD_OK;
-    return launch_step_moving(s, io, motion, (hipStream_t)hip_stream, 0, 0, me);
-}
-
-int macjd_env_step_many_moving(const macjd_scenario* s, const macjd_step_io* io, const macjd_motion_io* motion, int32_t n_steps,
-                               int64_t t_stride, void* hip_stream) {
-    const char* me = "macjd_env_step_many_moving";
-    int rc = validate_io(s, io);
-    if (rc != MACJD_OK) return rc;
-    rc = validate_motion(s, motion, me);
-    if (rc != MACJD_OK) return rc;
-    if (io->pe_tables) return set_err(MACJD_EINVAL, "%s: io->pe_tables must be NULL (the frames are the tables)", me);
-    if (n_steps < 1 || t_stride < 0) return set_err(MACJD_EINVAL, "%s: bad n_steps / t_stride", me);
-    if (io->pd || io->snr_with || motion->snr_no) return set_err(MACJD_EINVAL, "%s: pd / snr_with / snr_no are not written (pass NULL)", me);
-    if (io->r_dpj_sum && !io->r_dpj) return set_err(MACJD_EINVAL, "%s: r_dpj_sum needs the per-step r_dpj buffer", me);
-    if (io->n_envs == 0) return MACJD_OK;
-    rc = launch_step_moving(s, io, motion, (hipStream_t)hip_stream, n_steps, t_stride, me);
-    if (rc != MACJD_OK) return rc;
-    int64_t grid = (io->n_envs * 3 + 255) / 256;
-    if (grid > 4096) grid = 4096;
-    hipLaunchKernelGGL(macjd::env_advance_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)hip_stream, io->n_envs,
-                       n_steps, io->step, io->r_dpj, io->r_dpj_sum);
-    return launch_status(me);
-}
-
-int macjd_env_reset_moving(const macjd_scenario* s, int64_t n_envs, const macjd_motion_io* motion, const uint8_t* mask,
-                           void* hip_stream) {
-    const char* me = "macjd_env_reset_moving";
-    if (n_envs < 0) return set_err(MACJD_EINVAL, "%s: bad argument", me);
-    const int rc = validate_motion(s, motion, me);
-    if (rc != MACJD_OK) return rc;
-    if (n_envs == 0) return MACJD_OK;
-    int64_t grid = (n_envs + 255) / 256;
-    if (grid > 4096) grid = 4096;
-    macjd::launch_motion_reset(dim3((unsigned)grid), dim3(256), (hipStream_t)hip_stream, n_envs, motion->n_pos, motion->positions,
-                               motion->position_columns, motion->state, motion->st_se, mask);
-    return launch_status(me);
-}
-
-// ---- per-env moving scenarios (include/macjd.h, macjd_motion_pe_io; kernels in macjd_env_motion_pe.hip) ----
-
-// The shared-frame block with the same members: validation, span checks and fill_motion serve both
+// A per-env motion block as the shared-frame block with the same members: validation, span checks and fill_moving serve both
 static macjd_motion_io motion_pe_as_motion(const macjd_motion_pe_io* mp) {
     macjd_motion_io mo{};
     mo.frames = mp->frames; mo.frame_flags = mp->frame_flags; mo.frame_snr_no = mp->frame_snr_no;
@@ -1088,246 +1046,185 @@ static macjd_motion_io motion_pe_as_motion(const macjd_motion_pe_io* mp) {
     return mo;
 }
 
-static int validate_motion_pe(const macjd_scenario* s, const macjd_motion_pe_io* mp, macjd_motion_io* mo, const char* what) {
-    if (!s || !mp) return set_err(MACJD_EINVAL, "%s: NULL scenario / motion io", what);
-    *mo = motion_pe_as_motion(mp);
+// The motion block of either kind, checked, into a->mo / a->tile (tile 0: shared frames)
+static int validate_motion_into(const macjd_scenario* s, const macjd_motion_io* mo, MovingArgs* a, const char* what) {
     const int rc = validate_motion(s, mo, what);
+    if (rc == MACJD_OK) { a->mo = *mo; a->tile = 0; }
+    return rc;
+}
+static int validate_motion_into(const macjd_scenario* s, const macjd_motion_pe_io* mp, MovingArgs* a, const char* what) {
+    if (!s || !mp) return set_err(MACJD_EINVAL, "%s: NULL scenario / motion io", what);
+    a->mo = motion_pe_as_motion(mp);
+    a->tile = mp->tile;
+    const int rc = validate_motion(s, &a->mo, what);
     if (rc != MACJD_OK) return rc;
     if (mp->tile < 1) return set_err(MACJD_EINVAL, "%s: tile < 1", what);
     return MACJD_OK;
 }
 
-// MOVING launches on per-env frame tables: always the lane kernel (include/macjd.h, macjd_env_step_moving_pe)
-static int launch_step_moving_pe(const macjd_scenario* s, const macjd_step_io* io, const macjd_motion_io* mo, int32_t tile,
-                                 hipStream_t stream, int32_t many_T, int64_t t_stride, const char* who) {
-    const int64_t E = io->n_envs * (many_T > 0 ? many_T : 1);   // work items of the launch
-    const int J = s->host.J, R = s->host.R;
-    if (many_T > 65535) return set_err(MACJD_EINVAL, "%s: at most 65535 steps per launch", who);
-    const LaneGrid lg = lane_grid(E);
-    const dim3 gf((unsigned)(many_T > 0 ? (io->n_envs + lg.block - 1) / lg.block : lg.blocks), (unsigned)(many_T > 0 ? many_T : 1));
-    const dim3 g(lg.strided), b(lg.block);
-    const bool fast = macjd::motion_size_compiled(J, R) && production_io(io, J, R, lg.blocks, many_T, t_stride) &&
-                      motion_spans_ok(mo, io->n_envs, R) && io->n_envs < ((int64_t)1 << 31);
-    if (fast) {
-        macjd::MotionPeStepIO<macjd::FastStepIO> f{};
-        fill_fast(f, io, many_T, t_stride);
-        fill_motion(f, mo);
-        f.mv_tile = tile;
-        (void)macjd::launch_motion_pe_fast(J, R, gf, b, stream, s->dev, f);
-    } else {
-        if (many_T > 0)
-            return set_err(MACJD_EUNSUPPORTED, "%s: production configuration at a compiled size (2j/2r, 3j/4r, 6j/8r) only: Philox "
-                           "uniforms, float32 actions, no float64 diagnostics, offsets below 2^32 bytes", who);
-        macjd::MotionPeStepIO<macjd_step_io> w{};
-        static_cast<macjd_step_io&>(w) = *io;
-        fill_motion(w, mo);
-        w.mv_tile = tile;
-        macjd::launch_motion_pe_general(J, R, g, b, stream, s->dev, w);
-    }
-    return launch_status(who);
+// Common head of the moving step entry points: the step's own block, then the motion block
+template <class Motion>
+static int validate_moving_step(const macjd_scenario* s, const macjd_step_io* io, const Motion* motion, MovingArgs* a, const char* me) {
+    const int rc = validate_io(s, io);
+    return rc != MACJD_OK ? rc : validate_motion_into(s, motion, a, me);
+}
+static int refuse_pe_tables(const macjd_step_io* io, const char* me) {
+    return io->pe_tables ? set_err(MACJD_EINVAL, "%s: io->pe_tables must be NULL (the frames are the tables)", me) : MACJD_OK;
+}
+static int refuse_slot_kernel(const macjd_step_io* io, const char* me) {
+    return (io->flags & MACJD_STEP_SLOT_KERNEL)
+               ? set_err(MACJD_EUNSUPPORTED, "%s: the (env x slot) kernel has no moving variant (one lane per env only)", me)
+               : MACJD_OK;
+}
+
+// The single-step (n_steps = 0) and many-step entry points on shared (Motion = macjd_motion_io) and per-env frames
+template <class Motion>
+static int env_step_moving(const macjd_scenario* s, const macjd_step_io* io, const Motion* motion, int32_t n_steps, int64_t t_stride,
+                           bool many, hipStream_t stream, const char* me) {
+    constexpr bool MVPE = std::is_same<Motion, macjd_motion_pe_io>::value;
+    MovingArgs a{};
+    int rc = validate_moving_step(s, io, motion, &a, me);
+    if (rc != MACJD_OK) return rc;
+    rc = refuse_pe_tables(io, me);
+    if (rc != MACJD_OK) return rc;
+    rc = many ? validate_many(io, n_steps, t_stride, a.mo.snr_no, "pd / snr_with / snr_no", me) : refuse_slot_kernel(io, me);
+    if (rc != MACJD_OK) return rc;
+    if (io->n_envs == 0) return MACJD_OK;
+    rc = launch_step_moving<MVPE, false, false>(s, io, a, stream, many ? n_steps : 0, many ? t_stride : 0, me);
+    if (rc != MACJD_OK || !many) return rc;
+    return advance_after_many(io, n_steps, stream, me);
+}
+
+// The scan / pattern frame tables of a moving scanning step or reset `me`
+static int validate_motion_scan_levels(const macjd_scenario* s, const macjd_motion_scan_io& ms, const char* me) {
+    if (ms.n_levels < 0 || ms.n_levels > MACJD_MAX_PATTERN_LEVELS)
+        return set_err(MACJD_EINVAL, "%s: n_levels outside 0..MACJD_MAX_PATTERN_LEVELS", me);
+    if (s->host.pat_levels > 0 && s->host.pat_levels != ms.n_levels)
+        return set_err(MACJD_EINVAL, "%s: n_levels differs from the pattern levels of the scenario handle", me);
+    if ((ms.pattern_frames != nullptr) != (ms.n_levels > 0))
+        return set_err(MACJD_EINVAL, "%s: pattern_frames and n_levels > 0 go together (both or neither)", me);
+    return MACJD_OK;
+}
+// `ms` NULL or without scan frames: refused; otherwise a->ms and the level checks
+static int validate_motion_scan(const macjd_scenario* s, const macjd_motion_scan_io* ms, MovingArgs* a, const char* me) {
+    if (!ms || !ms->scan_frames) return set_err(MACJD_EINVAL, "%s: NULL motion scan io / scan_frames", me);
+    a->ms = *ms;
+    return validate_motion_scan_levels(s, a->ms, me);
+}
+// A per-env block as the shared-frame block with the same members (NULL stays NULL)
+static const macjd_motion_scan_io* motion_scan_pe_as_motion_scan(const macjd_motion_scan_pe_io* mp, macjd_motion_scan_io* ms) {
+    if (!mp) return nullptr;
+    ms->scan_frames = mp->scan_frames; ms->pattern_frames = mp->pattern_frames; ms->n_levels = mp->n_levels; ms->reserved = 0;
+    return ms;
+}
+
+// What a moving scanning step refuses of its motion block (`word`: "motion" or "motion_pe", as the entry point names it)
+static int refuse_motion_snr_no(const MovingArgs& a, const char* word, const char* me) {
+    return a.mo.snr_no ? set_err2(MACJD_EINVAL, "%s: %s->snr_no must be NULL (the per-step value travels in scan->snr_no)", me, word)
+                       : MACJD_OK;
+}
+static int validate_same_state_rows(const macjd_scan_io* scan, const MovingArgs& a, const char* word, const char* me) {
+    if (scan->state && scan->state != a.mo.state)
+        return set_err2(MACJD_EINVAL, "%s: scan->state and %s->state must be the same rows", me, word);
+    if (scan->state && scan->st_se != a.mo.st_se)
+        return set_err2(MACJD_EINVAL, "%s: scan->st_se and %s->st_se must be the same row stride", me, word);
+    return MACJD_OK;
+}
+
+// Tail of the two moving scanning step entry points, after their block checks: the pattern-or-plain choice and the launch
+template <bool MVPE>
+static int env_step_moving_scan_tail(const macjd_scenario* s, const macjd_step_io* io, const macjd_scan_io* scan, MovingArgs& a,
+                                     const char* word, hipStream_t stream, const char* me) {
+    int rc = validate_same_state_rows(scan, a, word, me);
+    if (rc != MACJD_OK) return rc;
+    rc = refuse_slot_kernel(io, me);
+    if (rc != MACJD_OK) return rc;
+    if (io->n_envs == 0) return MACJD_OK;
+    a.sc = scan;
+    return a.ms.pattern_frames ? launch_step_moving<MVPE, true, true>(s, io, a, stream, 0, 0, me)
+                               : launch_step_moving<MVPE, true, false>(s, io, a, stream, 0, 0, me);
+}
+
+extern "C" {
+
+int macjd_env_step_moving(const macjd_scenario* s, const macjd_step_io* io, const macjd_motion_io* motion, void* hip_stream) {
+    return env_step_moving(s, io, motion, 0, 0, false, (hipStream_t)hip_stream, "macjd_env_step_moving");
+}
+
+int macjd_env_step_many_moving(const macjd_scenario* s, const macjd_step_io* io, const macjd_motion_io* motion, int32_t n_steps,
+                               int64_t t_stride, void* hip_stream) {
+    return env_step_moving(s, io, motion, n_steps, t_stride, true, (hipStream_t)hip_stream, "macjd_env_step_many_moving");
+}
+
+int macjd_env_reset_moving(const macjd_scenario* s, int64_t n_envs, const macjd_motion_io* motion, const uint8_t* mask,
+                           void* hip_stream) {
+    const char* me = "macjd_env_reset_moving";
+    if (n_envs < 0) return set_err(MACJD_EINVAL, "%s: bad argument", me);
+    const int rc = validate_motion(s, motion, me);
+    if (rc != MACJD_OK) return rc;
+    if (n_envs == 0) return MACJD_OK;
+    macjd::launch_motion_reset(strided_grid_256(n_envs), dim3(256), (hipStream_t)hip_stream, n_envs, motion->n_pos, motion->positions,
+                               motion->position_columns, motion->state, motion->st_se, mask);
+    return launch_status(me);
 }
 
 int macjd_env_step_moving_pe(const macjd_scenario* s, const macjd_step_io* io, const macjd_motion_pe_io* motion_pe, void* hip_stream) {
-    const char* me = "macjd_env_step_moving_pe";
-    int rc = validate_io(s, io);
-    if (rc != MACJD_OK) return rc;
-    macjd_motion_io mo;
-    rc = validate_motion_pe(s, motion_pe, &mo, me);
-    if (rc != MACJD_OK) return rc;
-    if (io->pe_tables) return set_err(MACJD_EINVAL, "%s: io->pe_tables must be NULL (the frames are the tables)", me);
-    if (io->flags & MACJD_STEP_SLOT_KERNEL)
-        return set_err(MACJD_EUNSUPPORTED, "%s: the (env x slot) kernel has no moving variant (one lane per env only)", me);
-    if (io->n_envs == 0) return MACJD_OK;
-    return launch_step_moving_pe(s, io, &mo, motion_pe->tile, (hipStream_t)hip_stream, 0, 0, me);
+    return env_step_moving(s, io, motion_pe, 0, 0, false, (hipStream_t)hip_stream, "macjd_env_step_moving_pe");
 }
 
 int macjd_env_step_many_moving_pe(const macjd_scenario* s, const macjd_step_io* io, const macjd_motion_pe_io* motion_pe,
                                   int32_t n_steps, int64_t t_stride, void* hip_stream) {
-    const char* me = "macjd_env_step_many_moving_pe";
-    int rc = validate_io(s, io);
-    if (rc != MACJD_OK) return rc;
-    macjd_motion_io mo;
-    rc = validate_motion_pe(s, motion_pe, &mo, me);
-    if (rc != MACJD_OK) return rc;
-    if (io->pe_tables) return set_err(MACJD_EINVAL, "%s: io->pe_tables must be NULL (the frames are the tables)", me);
-    if (n_steps < 1 || t_stride < 0) return set_err(MACJD_EINVAL, "%s: bad n_steps / t_stride", me);
-    if (io->pd || io->snr_with || mo.snr_no) return set_err(MACJD_EINVAL, "%s: pd / snr_with / snr_no are not written (pass NULL)", me);
-    if (io->r_dpj_sum && !io->r_dpj) return set_err(MACJD_EINVAL, "%s: r_dpj_sum needs the per-step r_dpj buffer", me);
-    if (io->n_envs == 0) return MACJD_OK;
-    rc = launch_step_moving_pe(s, io, &mo, motion_pe->tile, (hipStream_t)hip_stream, n_steps, t_stride, me);
-    if (rc != MACJD_OK) return rc;
-    int64_t grid = (io->n_envs * 3 + 255) / 256;
-    if (grid > 4096) grid = 4096;
-    hipLaunchKernelGGL(macjd::env_advance_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)hip_stream, io->n_envs,
-                       n_steps, io->step, io->r_dpj, io->r_dpj_sum);
-    return launch_status(me);
+    return env_step_moving(s, io, motion_pe, n_steps, t_stride, true, (hipStream_t)hip_stream, "macjd_env_step_many_moving_pe");
 }
 
 int macjd_env_reset_moving_pe(const macjd_scenario* s, int64_t n_envs, const macjd_motion_pe_io* motion_pe, const uint8_t* mask,
                               void* hip_stream) {
     const char* me = "macjd_env_reset_moving_pe";
     if (n_envs < 0) return set_err(MACJD_EINVAL, "%s: bad argument", me);
-    macjd_motion_io mo;
-    const int rc = validate_motion_pe(s, motion_pe, &mo, me);
+    MovingArgs a{};
+    const int rc = validate_motion_into(s, motion_pe, &a, me);
     if (rc != MACJD_OK) return rc;
     if (n_envs == 0) return MACJD_OK;
-    int64_t grid = (n_envs + 255) / 256;
-    if (grid > 4096) grid = 4096;
-    macjd::launch_motion_pe_reset(dim3((unsigned)grid), dim3(256), (hipStream_t)hip_stream, n_envs, mo.n_pos, mo.n_frames,
-                                  motion_pe->tile, mo.positions, mo.position_columns, mo.state, mo.st_se, mask);
+    macjd::launch_motion_pe_reset(strided_grid_256(n_envs), dim3(256), (hipStream_t)hip_stream, n_envs, a.mo.n_pos, a.mo.n_frames,
+                                  a.tile, a.mo.positions, a.mo.position_columns, a.mo.state, a.mo.st_se, mask);
     return launch_status(me);
-}
-
-// ---- moving scenarios with scanning beams (include/macjd.h, macjd_motion_scan_io; kernels in macjd_env_motion_scan.hip) ----
-
-// Always the lane kernel on the frame tables: the production variant or the general one at the compiled sizes, the
-// generic-size kernel for the others
-static int launch_step_moving_scan(const macjd_scenario* s, const macjd_step_io* io, const macjd_motion_io* mo, const macjd_scan_io* sc,
-                                   const macjd_motion_scan_io* ms, hipStream_t stream, const char* who) {
-    const int64_t E = io->n_envs;
-    const int J = s->host.J, R = s->host.R;
-    const LaneGrid lg = lane_grid(E);
-    const dim3 gf((unsigned)lg.blocks), g(lg.strided), b(lg.block);
-    const bool fast = macjd::motion_size_compiled(J, R) && production_io(io, J, R, lg.blocks, 0, 0) && scan_spans_ok(sc, E, R) &&
-                      motion_spans_ok(mo, E, R);
-    if (ms->pattern_frames) {
-        if (fast) {
-            macjd::MotionScanStepIO<macjd::ScanPePatStepIO<macjd::FastStepIO>> f{};
-            fill_fast(f, io, 0, 0);
-            fill_motion_scan(f, mo, sc, ms);
-            fill_motion_scan_pattern(f, ms);
-            (void)macjd::launch_motion_scan_pattern_fast(J, R, gf, b, stream, s->dev, f);
-        } else {
-            macjd::MotionScanStepIO<macjd::ScanPePatStepIO<macjd_step_io>> w{};
-            static_cast<macjd_step_io&>(w) = *io;
-            fill_motion_scan(w, mo, sc, ms);
-            fill_motion_scan_pattern(w, ms);
-            macjd::launch_motion_scan_pattern_general(J, R, g, b, stream, s->dev, w);
-        }
-    } else if (fast) {
-        macjd::MotionScanStepIO<macjd::ScanPeStepIO<macjd::FastStepIO>> f{};
-        fill_fast(f, io, 0, 0);
-        fill_motion_scan(f, mo, sc, ms);
-        (void)macjd::launch_motion_scan_fast(J, R, gf, b, stream, s->dev, f);
-    } else {
-        macjd::MotionScanStepIO<macjd::ScanPeStepIO<macjd_step_io>> w{};
-        static_cast<macjd_step_io&>(w) = *io;
-        fill_motion_scan(w, mo, sc, ms);
-        macjd::launch_motion_scan_general(J, R, g, b, stream, s->dev, w);
-    }
-    return launch_status(who);
 }
 
 int macjd_env_step_moving_scan(const macjd_scenario* s, const macjd_step_io* io, const macjd_motion_io* motion,
                                const macjd_scan_io* scan, const macjd_motion_scan_io* motion_scan, void* hip_stream) {
     const char* me = "macjd_env_step_moving_scan";
-    int rc = validate_io(s, io);
-    if (rc != MACJD_OK) return rc;
-    rc = validate_motion(s, motion, me);
+    MovingArgs a{};
+    int rc = validate_moving_step(s, io, motion, &a, me);
     if (rc != MACJD_OK) return rc;
     rc = validate_scan(s, scan, me);   // (refuses a handle that is not a scanning handle)
     if (rc != MACJD_OK) return rc;
     if (!motion_scan || !motion_scan->scan_frames) return set_err(MACJD_EINVAL, "%s: NULL motion scan io / scan_frames", me);
-    if (io->pe_tables) return set_err(MACJD_EINVAL, "%s: io->pe_tables must be NULL (the frames are the tables)", me);
-    if (motion->snr_no)
-        return set_err(MACJD_EINVAL, "%s: motion->snr_no must be NULL (the per-step value travels in scan->snr_no)", me);
-    if (motion_scan->n_levels < 0 || motion_scan->n_levels > MACJD_MAX_PATTERN_LEVELS)
-        return set_err(MACJD_EINVAL, "%s: n_levels outside 0..MACJD_MAX_PATTERN_LEVELS", me);
-    if (s->host.pat_levels > 0 && s->host.pat_levels != motion_scan->n_levels)
-        return set_err(MACJD_EINVAL, "%s: n_levels differs from the pattern levels of the scenario handle", me);
-    if ((motion_scan->pattern_frames != nullptr) != (motion_scan->n_levels > 0))
-        return set_err(MACJD_EINVAL, "%s: pattern_frames and n_levels > 0 go together (both or neither)", me);
-    if (scan->state && scan->state != motion->state)
-        return set_err(MACJD_EINVAL, "%s: scan->state and motion->state must be the same rows", me);
-    if (scan->state && scan->st_se != motion->st_se)
-        return set_err(MACJD_EINVAL, "%s: scan->st_se and motion->st_se must be the same row stride", me);
-    if (io->flags & MACJD_STEP_SLOT_KERNEL)
-        return set_err(MACJD_EUNSUPPORTED, "%s: the (env x slot) kernel has no moving variant (one lane per env only)", me);
-    if (io->n_envs == 0) return MACJD_OK;
-    return launch_step_moving_scan(s, io, motion, scan, motion_scan, (hipStream_t)hip_stream, me);
-}
-
-// ---- per-env moving scenarios under scanning radars (include/macjd.h, macjd_motion_scan_pe_io; kernels in
-// macjd_env_motion_scan_pe.hip) ----
-
-static int validate_motion_scan_pe(const macjd_scenario* s, const macjd_motion_scan_pe_io* ms, const char* me) {
-    if (!ms || !ms->scan_frames) return set_err(MACJD_EINVAL, "%s: NULL motion scan io / scan_frames", me);
-    if (ms->n_levels < 0 || ms->n_levels > MACJD_MAX_PATTERN_LEVELS)
-        return set_err(MACJD_EINVAL, "%s: n_levels outside 0..MACJD_MAX_PATTERN_LEVELS", me);
-    if (s->host.pat_levels > 0 && s->host.pat_levels != ms->n_levels)
-        return set_err(MACJD_EINVAL, "%s: n_levels differs from the pattern levels of the scenario handle", me);
-    if ((ms->pattern_frames != nullptr) != (ms->n_levels > 0))
-        return set_err(MACJD_EINVAL, "%s: pattern_frames and n_levels > 0 go together (both or neither)", me);
-    return MACJD_OK;
-}
-
-// Always the lane kernel on the per-env frame tables: the production variant or the general one at the compiled sizes, the
-// generic-size kernel for the others
-static int launch_step_moving_scan_pe(const macjd_scenario* s, const macjd_step_io* io, const macjd_motion_io* mo, int32_t tile,
-                                      const macjd_scan_io* sc, const macjd_motion_scan_pe_io* mp, hipStream_t stream, const char* who) {
-    const int64_t E = io->n_envs;
-    const int J = s->host.J, R = s->host.R;
-    const LaneGrid lg = lane_grid(E);
-    const dim3 gf((unsigned)lg.blocks), g(lg.strided), b(lg.block);
-    const bool fast = macjd::motion_size_compiled(J, R) && production_io(io, J, R, lg.blocks, 0, 0) && scan_spans_ok(sc, E, R) &&
-                      motion_spans_ok(mo, E, R) && E < ((int64_t)1 << 31);
-    macjd_motion_scan_io ms{};   // the shared-frame block with the same members: fill_motion_scan serves both
-    ms.scan_frames = mp->scan_frames; ms.pattern_frames = mp->pattern_frames; ms.n_levels = mp->n_levels;
-    if (ms.pattern_frames) {
-        if (fast) {
-            macjd::MotionScanPeStepIO<macjd::ScanPePatStepIO<macjd::FastStepIO>> f{};
-            fill_fast(f, io, 0, 0);
-            fill_motion_scan(f, mo, sc, &ms);
-            fill_motion_scan_pattern(f, &ms);
-            f.mv_tile = tile;
-            (void)macjd::launch_motion_scan_pe_pattern_fast(J, R, gf, b, stream, s->dev, f);
-        } else {
-            macjd::MotionScanPeStepIO<macjd::ScanPePatStepIO<macjd_step_io>> w{};
-            static_cast<macjd_step_io&>(w) = *io;
-            fill_motion_scan(w, mo, sc, &ms);
-            fill_motion_scan_pattern(w, &ms);
-            w.mv_tile = tile;
-            macjd::launch_motion_scan_pe_pattern_general(J, R, g, b, stream, s->dev, w);
-        }
-    } else if (fast) {
-        macjd::MotionScanPeStepIO<macjd::ScanPeStepIO<macjd::FastStepIO>> f{};
-        fill_fast(f, io, 0, 0);
-        fill_motion_scan(f, mo, sc, &ms);
-        f.mv_tile = tile;
-        (void)macjd::launch_motion_scan_pe_fast(J, R, gf, b, stream, s->dev, f);
-    } else {
-        macjd::MotionScanPeStepIO<macjd::ScanPeStepIO<macjd_step_io>> w{};
-        static_cast<macjd_step_io&>(w) = *io;
-        fill_motion_scan(w, mo, sc, &ms);
-        w.mv_tile = tile;
-        macjd::launch_motion_scan_pe_general(J, R, g, b, stream, s->dev, w);
-    }
-    return launch_status(who);
+    a.ms = *motion_scan;
+    rc = refuse_pe_tables(io, me);
+    if (rc != MACJD_OK) return rc;
+    rc = refuse_motion_snr_no(a, "motion", me);
+    if (rc != MACJD_OK) return rc;
+    rc = validate_motion_scan_levels(s, a.ms, me);   // (this entry point checks the levels after the two refusals)
+    if (rc != MACJD_OK) return rc;
+    return env_step_moving_scan_tail<false>(s, io, scan, a, "motion", (hipStream_t)hip_stream, me);
 }
 
 int macjd_env_step_moving_scan_pe(const macjd_scenario* s, const macjd_step_io* io, const macjd_motion_pe_io* motion_pe,
                                   const macjd_scan_io* scan, const macjd_motion_scan_pe_io* motion_scan_pe, void* hip_stream) {
     const char* me = "macjd_env_step_moving_scan_pe";
-    int rc = validate_io(s, io);
-    if (rc != MACJD_OK) return rc;
-    macjd_motion_io mo;
-    rc = validate_motion_pe(s, motion_pe, &mo, me);
+    MovingArgs a{};
+    macjd_motion_scan_io ms;
+    int rc = validate_moving_step(s, io, motion_pe, &a, me);
     if (rc != MACJD_OK) return rc;
     rc = validate_scan(s, scan, me);   // (refuses a handle that is not a scanning handle)
     if (rc != MACJD_OK) return rc;
-    rc = validate_motion_scan_pe(s, motion_scan_pe, me);
+    rc = validate_motion_scan(s, motion_scan_pe_as_motion_scan(motion_scan_pe, &ms), &a, me);
     if (rc != MACJD_OK) return rc;
-    if (io->pe_tables) return set_err(MACJD_EINVAL, "%s: io->pe_tables must be NULL (the frames are the tables)", me);
-    if (mo.snr_no)
-        return set_err(MACJD_EINVAL, "%s: motion_pe->snr_no must be NULL (the per-step value travels in scan->snr_no)", me);
-    if (scan->state && scan->state != mo.state)
-        return set_err(MACJD_EINVAL, "%s: scan->state and motion_pe->state must be the same rows", me);
-    if (scan->state && scan->st_se != mo.st_se)
-        return set_err(MACJD_EINVAL, "%s: scan->st_se and motion_pe->st_se must be the same row stride", me);
-    if (io->flags & MACJD_STEP_SLOT_KERNEL)
-        return set_err(MACJD_EUNSUPPORTED, "%s: the (env x slot) kernel has no moving variant (one lane per env only)", me);
-    if (io->n_envs == 0) return MACJD_OK;
-    return launch_step_moving_scan_pe(s, io, &mo, motion_pe->tile, scan, motion_scan_pe, (hipStream_t)hip_stream, me);
+    rc = refuse_pe_tables(io, me);
+    if (rc != MACJD_OK) return rc;
+    rc = refuse_motion_snr_no(a, "motion_pe", me);
+    if (rc != MACJD_OK) return rc;
+    return env_step_moving_scan_tail<true>(s, io, scan, a, "motion_pe", (hipStream_t)hip_stream, me);
 }
 
 int macjd_env_reset_moving_scan_pe(const macjd_scenario* s, int64_t n_envs, const macjd_scan_io* scan,
@@ -1335,17 +1232,17 @@ int macjd_env_reset_moving_scan_pe(const macjd_scenario* s, int64_t n_envs, cons
                                    const uint8_t* mask, void* hip_stream) {
     const char* me = "macjd_env_reset_moving_scan_pe";
     if (!s || n_envs < 0) return set_err(MACJD_EINVAL, "%s: bad argument", me);
+    MovingArgs a{};
+    macjd_motion_scan_io ms;
     int rc = validate_scan(s, scan, me);
     if (rc != MACJD_OK) return rc;
-    rc = validate_motion_scan_pe(s, motion_scan_pe, me);
+    rc = validate_motion_scan(s, motion_scan_pe_as_motion_scan(motion_scan_pe, &ms), &a, me);
     if (rc != MACJD_OK) return rc;
     if (n_frames < 1) return set_err(MACJD_EINVAL, "%s: n_frames < 1", me);
     if (tile < 1) return set_err(MACJD_EINVAL, "%s: tile < 1", me);
     if (n_envs == 0) return MACJD_OK;
-    int64_t grid = (n_envs + 255) / 256;
-    if (grid > 4096) grid = 4096;
-    macjd::launch_motion_scan_pe_reset(dim3((unsigned)grid), dim3(256), (hipStream_t)hip_stream, n_envs, s->host.R, s->host.J,
-                                       n_frames, tile, motion_scan_pe->scan_frames, scan->theta_a, scan->a_se, scan->a_sx,
+    macjd::launch_motion_scan_pe_reset(strided_grid_256(n_envs), dim3(256), (hipStream_t)hip_stream, n_envs, s->host.R, s->host.J,
+                                       n_frames, tile, a.ms.scan_frames, scan->theta_a, scan->a_se, scan->a_sx,
                                        scan->state, scan->st_se, scan->st_col0, scan->st_col_step, mask);
     return launch_status(me);
 }

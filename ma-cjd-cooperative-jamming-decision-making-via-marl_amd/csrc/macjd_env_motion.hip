@@ -4,7 +4,8 @@
 // the per-env-table path of the step with the table column chosen by the env's step counter (frame-major tables, one
 // contiguous block of MACJD_PE_ROWS doubles per env-step) and the position columns of the env's state row rewritten with the
 // next frame's positions.  Every kernel built in macjd_env.hip compiles exactly as before.  The host side (validation, span
-// checks, the many-step launch's counter advance) is in macjd_env.hip next to the launches it mirrors.
+// checks, the many-step launch's counter advance) is in macjd_env.hip: launch_step_moving, the one dispatch function of the
+// moving modes.
 #include "macjd_env_step.h"
 
 namespace macjd {
@@ -19,29 +20,9 @@ __global__ void env_reset_motion_kernel(int64_t n_envs, int n_pos, const float* 
     }
 }
 
-bool motion_size_compiled(int J, int R) { return (J == 2 && R == 2) || (J == 3 && R == 4) || (J == 6 && R == 8); }
-
-template <int JT, int RT, bool FAST, class IO>
-static void launch(dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev, const IO& io) {
-    hipLaunchKernelGGL((env_step_kernel<JT, RT, true, FAST, IO>), grid, block, 0, stream, dev, io);
-}
-
-bool launch_motion_fast(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
-                        const MotionStepIO<FastStepIO>& io) {
-    if (J == 3 && R == 4) launch<3, 4, true>(grid, block, stream, dev, io);
-    else if (J == 6 && R == 8) launch<6, 8, true>(grid, block, stream, dev, io);
-    else if (J == 2 && R == 2) launch<2, 2, true>(grid, block, stream, dev, io);
-    else return false;
-    return true;
-}
-
-void launch_motion_general(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
-                           const MotionStepIO<macjd_step_io>& io) {
-    if (J == 3 && R == 4) launch<3, 4, false>(grid, block, stream, dev, io);
-    else if (J == 6 && R == 8) launch<6, 8, false>(grid, block, stream, dev, io);
-    else if (J == 2 && R == 2) launch<2, 2, false>(grid, block, stream, dev, io);
-    else launch<0, 0, false>(grid, block, stream, dev, io);
-}
+// launch_motion_sized<FAST, SCAN = false, PAT = false>
+MACJD_LAUNCH_MOTION(MotionStepIO<FastStepIO>) { return launch_motion_sized<true, false, false>(J, R, grid, block, stream, dev, io); }
+MACJD_LAUNCH_MOTION(MotionStepIO<macjd_step_io>) { return launch_motion_sized<false, false, false>(J, R, grid, block, stream, dev, io); }
 
 void launch_motion_reset(dim3 grid, dim3 block, hipStream_t stream, int64_t n_envs, int n_pos, const float* positions,
                          const int32_t* position_columns, float* state, int64_t st_se, const uint8_t* mask) {

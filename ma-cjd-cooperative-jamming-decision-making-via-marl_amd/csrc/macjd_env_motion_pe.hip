@@ -8,7 +8,8 @@
 //     frame-table path of the moving step with row stride = the env tile, tile index (e / tile) * F + f, column e % tile.
 //   * the position part of a reset on per-env frame tables.
 // Every kernel built in the other translation units compiles exactly as before.  The host side of the step / reset entry
-// points (validation, span checks, the many-step launch's counter advance) is in macjd_env.hip next to the launches it mirrors.
+// points (validation, span checks, the many-step launch's counter advance) is in macjd_env.hip: launch_step_moving, the one
+// dispatch function of the moving modes.
 #include "macjd_env_step.h"
 #include "macjd_err.h"
 
@@ -138,27 +139,9 @@ __global__ void env_reset_motion_pe_kernel(int64_t n_envs, int n_pos, int n_fram
     }
 }
 
-template <int JT, int RT, bool FAST, class IO>
-static void launch(dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev, const IO& io) {
-    hipLaunchKernelGGL((env_step_kernel<JT, RT, true, FAST, IO>), grid, block, 0, stream, dev, io);
-}
-
-bool launch_motion_pe_fast(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
-                           const MotionPeStepIO<FastStepIO>& io) {
-    if (J == 3 && R == 4) launch<3, 4, true>(grid, block, stream, dev, io);
-    else if (J == 6 && R == 8) launch<6, 8, true>(grid, block, stream, dev, io);
-    else if (J == 2 && R == 2) launch<2, 2, true>(grid, block, stream, dev, io);
-    else return false;
-    return true;
-}
-
-void launch_motion_pe_general(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
-                              const MotionPeStepIO<macjd_step_io>& io) {
-    if (J == 3 && R == 4) launch<3, 4, false>(grid, block, stream, dev, io);
-    else if (J == 6 && R == 8) launch<6, 8, false>(grid, block, stream, dev, io);
-    else if (J == 2 && R == 2) launch<2, 2, false>(grid, block, stream, dev, io);
-    else launch<0, 0, false>(grid, block, stream, dev, io);
-}
+// launch_motion_sized<FAST, SCAN = false, PAT = false>
+MACJD_LAUNCH_MOTION(MotionPeStepIO<FastStepIO>) { return launch_motion_sized<true, false, false>(J, R, grid, block, stream, dev, io); }
+MACJD_LAUNCH_MOTION(MotionPeStepIO<macjd_step_io>) { return launch_motion_sized<false, false, false>(J, R, grid, block, stream, dev, io); }
 
 void launch_motion_pe_reset(dim3 grid, dim3 block, hipStream_t stream, int64_t n_envs, int n_pos, int n_frames, int tile,
                             const float* positions, const int32_t* position_columns, float* state, int64_t st_se,

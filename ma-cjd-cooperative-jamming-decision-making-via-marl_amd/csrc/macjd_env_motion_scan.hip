@@ -6,45 +6,18 @@
 // contiguous block each per env-step), and both the theta_a columns and the position columns of the env's state row
 // rewritten.  The size-bounded loops are unrolled by an explicit count, as in macjd_env_scan_pe.hip: with `#pragma unroll`
 // the generic-size kernel keeps them as loops and its per-lane arrays go to scratch.  Every kernel built in the other
-// translation units compiles exactly as before.  The host side (validation, span checks) is in macjd_env.hip.
+// translation units compiles exactly as before.  The host side (validation, span checks) is in macjd_env.hip:
+// launch_step_moving, the one dispatch function of the moving modes.
 #define MACJD_ENV_PRAGMA(x) _Pragma(#x)
 #define MACJD_ENV_UNROLL_SIZED(N) MACJD_ENV_PRAGMA(unroll N)
 #include "macjd_env_step.h"
 
 namespace macjd {
 
-template <int JT, int RT, bool FAST, bool PAT, class IO>
-static void launch(dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev, const IO& io) {
-    hipLaunchKernelGGL((env_step_kernel<JT, RT, true, FAST, IO, false, false, true, PAT>), grid, block, 0, stream, dev, io);
-}
-
-template <bool FAST, bool PAT, class IO>
-static bool launch_compiled(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev, const IO& io) {
-    if (J == 3 && R == 4) launch<3, 4, FAST, PAT>(grid, block, stream, dev, io);
-    else if (J == 6 && R == 8) launch<6, 8, FAST, PAT>(grid, block, stream, dev, io);
-    else if (J == 2 && R == 2) launch<2, 2, FAST, PAT>(grid, block, stream, dev, io);
-    else return false;
-    return true;
-}
-
-bool launch_motion_scan_fast(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
-                             const MotionScanStepIO<ScanPeStepIO<FastStepIO>>& io) {
-    return launch_compiled<true, false>(J, R, grid, block, stream, dev, io);
-}
-
-void launch_motion_scan_general(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
-                                const MotionScanStepIO<ScanPeStepIO<macjd_step_io>>& io) {
-    if (!launch_compiled<false, false>(J, R, grid, block, stream, dev, io)) launch<0, 0, false, false>(grid, block, stream, dev, io);
-}
-
-bool launch_motion_scan_pattern_fast(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
-                                     const MotionScanStepIO<ScanPePatStepIO<FastStepIO>>& io) {
-    return launch_compiled<true, true>(J, R, grid, block, stream, dev, io);
-}
-
-void launch_motion_scan_pattern_general(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
-                                        const MotionScanStepIO<ScanPePatStepIO<macjd_step_io>>& io) {
-    if (!launch_compiled<false, true>(J, R, grid, block, stream, dev, io)) launch<0, 0, false, true>(grid, block, stream, dev, io);
-}
+// launch_motion_sized<FAST, SCAN = true, PAT>
+MACJD_LAUNCH_MOTION(MotionScanStepIO<ScanPeStepIO<FastStepIO>>) { return launch_motion_sized<true, true, false>(J, R, grid, block, stream, dev, io); }
+MACJD_LAUNCH_MOTION(MotionScanStepIO<ScanPeStepIO<macjd_step_io>>) { return launch_motion_sized<false, true, false>(J, R, grid, block, stream, dev, io); }
+MACJD_LAUNCH_MOTION(MotionScanStepIO<ScanPePatStepIO<FastStepIO>>) { return launch_motion_sized<true, true, true>(J, R, grid, block, stream, dev, io); }
+MACJD_LAUNCH_MOTION(MotionScanStepIO<ScanPePatStepIO<macjd_step_io>>) { return launch_motion_sized<false, true, true>(J, R, grid, block, stream, dev, io); }
 
 }  // namespace macjd

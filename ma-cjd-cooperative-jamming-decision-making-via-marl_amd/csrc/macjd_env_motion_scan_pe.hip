@@ -21,7 +21,7 @@
 //     loops are unrolled by an explicit count, as in macjd_env_motion_scan.hip.
 //   * the beam part of a reset on per-env beam frames.
 // Every kernel built in the other translation units compiles exactly as before.  The host side of the step / reset entry
-// points (validation, span checks) is in macjd_env.hip next to the launches it mirrors.
+// points (validation, span checks) is in macjd_env.hip: launch_step_moving, the one dispatch function of the moving modes.
 #define MACJD_ENV_PRAGMA(x) _Pragma(#x)
 #define MACJD_ENV_UNROLL_SIZED(N) MACJD_ENV_PRAGMA(unroll N)
 #include "macjd_env_step.h"
@@ -133,39 +133,11 @@ __global__ void env_reset_motion_scan_pe_kernel(int64_t n_envs, int R, int J, in
     }
 }
 
-template <int JT, int RT, bool FAST, bool PAT, class IO>
-static void launch(dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev, const IO& io) {
-    hipLaunchKernelGGL((env_step_kernel<JT, RT, true, FAST, IO, false, false, true, PAT>), grid, block, 0, stream, dev, io);
-}
-
-template <bool FAST, bool PAT, class IO>
-static bool launch_compiled(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev, const IO& io) {
-    if (J == 3 && R == 4) launch<3, 4, FAST, PAT>(grid, block, stream, dev, io);
-    else if (J == 6 && R == 8) launch<6, 8, FAST, PAT>(grid, block, stream, dev, io);
-    else if (J == 2 && R == 2) launch<2, 2, FAST, PAT>(grid, block, stream, dev, io);
-    else return false;
-    return true;
-}
-
-bool launch_motion_scan_pe_fast(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
-                                const MotionScanPeStepIO<ScanPeStepIO<FastStepIO>>& io) {
-    return launch_compiled<true, false>(J, R, grid, block, stream, dev, io);
-}
-
-void launch_motion_scan_pe_general(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
-                                   const MotionScanPeStepIO<ScanPeStepIO<macjd_step_io>>& io) {
-    if (!launch_compiled<false, false>(J, R, grid, block, stream, dev, io)) launch<0, 0, false, false>(grid, block, stream, dev, io);
-}
-
-bool launch_motion_scan_pe_pattern_fast(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
-                                        const MotionScanPeStepIO<ScanPePatStepIO<FastStepIO>>& io) {
-    return launch_compiled<true, true>(J, R, grid, block, stream, dev, io);
-}
-
-void launch_motion_scan_pe_pattern_general(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
-                                           const MotionScanPeStepIO<ScanPePatStepIO<macjd_step_io>>& io) {
-    if (!launch_compiled<false, true>(J, R, grid, block, stream, dev, io)) launch<0, 0, false, true>(grid, block, stream, dev, io);
-}
+// launch_motion_sized<FAST, SCAN = true, PAT>
+MACJD_LAUNCH_MOTION(MotionScanPeStepIO<ScanPeStepIO<FastStepIO>>) { return launch_motion_sized<true, true, false>(J, R, grid, block, stream, dev, io); }
+MACJD_LAUNCH_MOTION(MotionScanPeStepIO<ScanPeStepIO<macjd_step_io>>) { return launch_motion_sized<false, true, false>(J, R, grid, block, stream, dev, io); }
+MACJD_LAUNCH_MOTION(MotionScanPeStepIO<ScanPePatStepIO<FastStepIO>>) { return launch_motion_sized<true, true, true>(J, R, grid, block, stream, dev, io); }
+MACJD_LAUNCH_MOTION(MotionScanPeStepIO<ScanPePatStepIO<macjd_step_io>>) { return launch_motion_sized<false, true, true>(J, R, grid, block, stream, dev, io); }
 
 void launch_motion_scan_pe_reset(dim3 grid, dim3 block, hipStream_t stream, int64_t n_envs, int R, int J, int n_frames, int tile,
                                  const double* scan_frames, double* theta_a, int64_t a_se, int64_t a_sx, float* state,

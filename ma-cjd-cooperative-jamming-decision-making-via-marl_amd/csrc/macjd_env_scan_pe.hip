@@ -18,8 +18,7 @@ void launch_scan_pe_generic(dim3 grid, dim3 block, hipStream_t stream, const Dev
 }
 
 // the same kernel under a stepped antenna pattern on per-env tables (PAT = true, the level rows loaded where they are used)
-void launch_scan_pe_pattern_generic(dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
-                                    const ScanPePatStepIO<macjd_step_io>& io) {
+void launch_scan_pe_generic(dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev, const ScanPePatStepIO<macjd_step_io>& io) {
     hipLaunchKernelGGL((env_step_kernel<0, 0, true, false, ScanPePatStepIO<macjd_step_io>, false, false, true, true>), grid, block, 0,
                        stream, dev, io);
 }

@@ -984,53 +984,69 @@ MACJD_ENV_UNROLL_SIZED(NR)
 // SCAN = true>, built there with its size-bounded loops unrolled by count (see MACJD_ENV_UNROLL_SIZED)
 void launch_scan_pe_generic(dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev, const ScanPeStepIO<macjd_step_io>& io);
 // ... and its PAT form (ScanPePatStepIO), built there with the same unrolling
-void launch_scan_pe_pattern_generic(dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
-                                    const ScanPePatStepIO<macjd_step_io>& io);
+void launch_scan_pe_generic(dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev, const ScanPePatStepIO<macjd_step_io>& io);
 
+// The moving launches (MOV instantiations, IO = Motion*StepIO<...>) live in four translation units of their own:
+// macjd_env_motion.hip (shared frames), macjd_env_motion_pe.hip (per-env frames), macjd_env_motion_scan.hip (shared frames
+// under scanning radars, with and without PAT) and macjd_env_motion_scan_pe.hip (per-env frames under scanning radars).
+// They share the launcher below and ONE list of compiled sizes.
 
-// macjd_env_motion.hip: the MOV instantiations (moving scenarios), a translation unit of their own.  Compiled sizes 2j/2r,
-// 3j/4r, 6j/8r have a production and a general variant; launch_motion_fast returns false for every other size (no launch),
-// launch_motion_general runs those on the generic-size kernel.
-bool motion_size_compiled(int J, int R);
-bool launch_motion_fast(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
-                        const MotionStepIO<FastStepIO>& io);
-void launch_motion_general(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
-                           const MotionStepIO<macjd_step_io>& io);
+// A compiled (J, R) size as two std::integral_constants: what the size switches hand to their callable
+template <int N>
+using CompiledDim = std::integral_constant<int, N>;
+
+// The compiled moving sizes: fn(JT, RT) runs at the size's constants; false (fn not called) for every other size
+template <class F>
+static bool with_motion_size(int J, int R, F&& fn) {
+    if (J == 3 && R == 4) fn(CompiledDim<3>{}, CompiledDim<4>{});
+    else if (J == 6 && R == 8) fn(CompiledDim<6>{}, CompiledDim<8>{});
+    else if (J == 2 && R == 2) fn(CompiledDim<2>{}, CompiledDim<2>{});
+    else return false;
+    return true;
+}
+inline bool motion_size_compiled(int J, int R) { return with_motion_size(J, R, [](auto, auto) {}); }
+
+template <int JT, int RT, bool PE, bool FAST, bool SCAN, bool PAT, class IO>
+static void launch(dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev, const IO& io) {
+    hipLaunchKernelGGL((env_step_kernel<JT, RT, PE, FAST, IO, false, false, SCAN, PAT>), grid, block, 0, stream, dev, io);
+}
+
+// Body of a unit's launch_motion overloads: the kernel of the compiled size; at every other size the production forms
+// (FAST) launch nothing and return false, the general forms run the generic-size kernel.  The instantiations belong to the
+// unit that calls this (its MACJD_ENV_UNROLL_SIZED).
+template <bool FAST, bool SCAN, bool PAT, class IO>
+static bool launch_motion_sized(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev, const IO& io) {
+    const bool sized = with_motion_size(J, R, [&](auto jt, auto rt) {
+        launch<decltype(jt)::value, decltype(rt)::value, true, FAST, SCAN, PAT>(grid, block, stream, dev, io);
+    });
+    if constexpr (!FAST)
+        if (!sized) launch<0, 0, true, false, SCAN, PAT>(grid, block, stream, dev, io);
+    return sized || !FAST;
+}
+
+// One overload per argument-block type, each defined in the unit that holds the type's kernels.  Returns whether a launch
+// was issued.  The macro is the signature, for the declarations here and the definitions there.
+#define MACJD_LAUNCH_MOTION(IO) \
+    bool launch_motion(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev, const IO& io)
+MACJD_LAUNCH_MOTION(MotionStepIO<FastStepIO>);                                // macjd_env_motion.hip
+MACJD_LAUNCH_MOTION(MotionStepIO<macjd_step_io>);
+MACJD_LAUNCH_MOTION(MotionPeStepIO<FastStepIO>);                              // macjd_env_motion_pe.hip
+MACJD_LAUNCH_MOTION(MotionPeStepIO<macjd_step_io>);
+MACJD_LAUNCH_MOTION(MotionScanStepIO<ScanPeStepIO<FastStepIO>>);              // macjd_env_motion_scan.hip
+MACJD_LAUNCH_MOTION(MotionScanStepIO<ScanPeStepIO<macjd_step_io>>);
+MACJD_LAUNCH_MOTION(MotionScanStepIO<ScanPePatStepIO<FastStepIO>>);
+MACJD_LAUNCH_MOTION(MotionScanStepIO<ScanPePatStepIO<macjd_step_io>>);
+MACJD_LAUNCH_MOTION(MotionScanPeStepIO<ScanPeStepIO<FastStepIO>>);            // macjd_env_motion_scan_pe.hip
+MACJD_LAUNCH_MOTION(MotionScanPeStepIO<ScanPeStepIO<macjd_step_io>>);
+MACJD_LAUNCH_MOTION(MotionScanPeStepIO<ScanPePatStepIO<FastStepIO>>);
+MACJD_LAUNCH_MOTION(MotionScanPeStepIO<ScanPePatStepIO<macjd_step_io>>);
+
+// the resets of the moving modes: the position part (shared / per-env frames) and the beam part on per-env beam frames
 void launch_motion_reset(dim3 grid, dim3 block, hipStream_t stream, int64_t n_envs, int n_pos, const float* positions,
                          const int32_t* position_columns, float* state, int64_t st_se, const uint8_t* mask);
-
-// macjd_env_motion_pe.hip: the MOV instantiations on per-env frame tables (include/macjd.h, macjd_motion_pe_io) and the
-// position part of their reset.  Same sizes and return convention as the launchers of macjd_env_motion.hip.
-bool launch_motion_pe_fast(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
-                           const MotionPeStepIO<FastStepIO>& io);
-void launch_motion_pe_general(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
-                              const MotionPeStepIO<macjd_step_io>& io);
 void launch_motion_pe_reset(dim3 grid, dim3 block, hipStream_t stream, int64_t n_envs, int n_pos, int n_frames, int tile,
                             const float* positions, const int32_t* position_columns, float* state, int64_t st_se,
                             const uint8_t* mask);
-
-// macjd_env_motion_scan.hip: the MOV && SCAN instantiations (moving scenarios with scanning beams), with and without PAT, a
-// translation unit of their own.  Same sizes and return convention as the launchers of macjd_env_motion.hip.
-bool launch_motion_scan_fast(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
-                             const MotionScanStepIO<ScanPeStepIO<FastStepIO>>& io);
-void launch_motion_scan_general(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
-                                const MotionScanStepIO<ScanPeStepIO<macjd_step_io>>& io);
-bool launch_motion_scan_pattern_fast(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
-                                     const MotionScanStepIO<ScanPePatStepIO<FastStepIO>>& io);
-void launch_motion_scan_pattern_general(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
-                                        const MotionScanStepIO<ScanPePatStepIO<macjd_step_io>>& io);
-
-// macjd_env_motion_scan_pe.hip: the MOV && SCAN instantiations on per-env frame tables (include/macjd.h,
-// macjd_motion_scan_pe_io), with and without PAT, the beam part of their reset and the device compiler of the beam frames.
-// Same sizes and return convention as the launchers of macjd_env_motion.hip.
-bool launch_motion_scan_pe_fast(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
-                                const MotionScanPeStepIO<ScanPeStepIO<FastStepIO>>& io);
-void launch_motion_scan_pe_general(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
-                                   const MotionScanPeStepIO<ScanPeStepIO<macjd_step_io>>& io);
-bool launch_motion_scan_pe_pattern_fast(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
-                                        const MotionScanPeStepIO<ScanPePatStepIO<FastStepIO>>& io);
-void launch_motion_scan_pe_pattern_general(int J, int R, dim3 grid, dim3 block, hipStream_t stream, const DevTables* dev,
-                                           const MotionScanPeStepIO<ScanPePatStepIO<macjd_step_io>>& io);
 void launch_motion_scan_pe_reset(dim3 grid, dim3 block, hipStream_t stream, int64_t n_envs, int R, int J, int n_frames, int tile,
                                  const double* scan_frames, double* theta_a, int64_t a_se, int64_t a_sx, float* state,
                                  int64_t st_se, int32_t st_col0, int32_t st_col_step, const uint8_t* mask);
