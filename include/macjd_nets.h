@@ -906,6 +906,44 @@ int macjd_agent_env_episode_moving_scan(const macjd_scenario* scenario, const ma
                                         void* hip_stream);
 
 /*
+ * macjd_agent_env_episode_moving_scan on a PER-ENV moving scanning scenario batch (macjd_motion_pe_io +
+ * macjd_motion_scan_pe_io, with or without a stepped antenna pattern per env): the same launch, outputs and hand-over, with
+ * every frame read taken from the env's own column of the tiled per-env frame tables.  Env e runs step t on its own frame
+ * f = min(step0[e] + t, n_frames - 1), step0[e] = base.step[e] at entry: row k of a table with ROWS rows per frame at
+ * table[(((e / tile) * n_frames + f) * ROWS + k) * tile + e % tile] — the step's own rows from motion_pe.frames /
+ * frame_flags, every scan row from motion_scan_pe.scan_frames, under a pattern inv_width and the level rows from
+ * motion_scan_pe.pattern_frames.  Any tile width >= 1 (also below the 16 envs of a workgroup, and widths that do not
+ * divide 16); the padded lanes of the last tile are never read.
+ *   base            the shared call's block; base.pe_tables must be NULL (the frames are the tables)
+ *   motion_pe       frames, frame_flags, positions, position_columns, n_frames, n_pos, tile and state (= base.scan.state)
+ *                   are read; snr_no must be NULL (the per-step value travels in base.scan.snr_no); frame_snr_no is not read
+ *   motion_scan_pe  scan_frames; pattern_frames together with n_levels = L, or neither
+ * The observation of step t shows the env's positions of frame min(step0[e] + t, n_frames) (the positions table holds
+ * n_frames + 1 frames per tile) at position_columns: besides the theta_a columns the kernel writes these n_pos = 2R + 2J
+ * columns of the staging rows t < T (st_state, st_obs) and nothing else of them; every other column is the caller's.  At
+ * exit theta_a, track, step, rdpj_sum, h_final, the theta_a columns and the position columns (frame
+ * min(step0[e] + T, n_frames)) of the env's state rows hold what T single macjd_env_step_moving_scan_pe steps would have
+ * left, and scan.snr_no the last step's value of the env's own frame: the snr_no / snr_no_side row of scan_frames, or under
+ * a pattern the snr_no_lvl row of the last level in pattern_frames.  The env half is bit-identical to T single
+ * macjd_env_step_moving_scan_pe steps in their general all-float64 form on the actions the agent half chose.
+ * The handle is the batch's scanning handle (R, J, episode_limit, the r_p bounds, the Pd constants).  MACJD_EINVAL: NULL
+ * frames / frame_flags / positions / position_columns / scan_frames / state, n_frames < 1 or not the handle's
+ * episode_limit, n_pos != 2R + 2J, tile < 1, motion_pe.snr_no != NULL, motion_pe.state != base.scan.state (or another row
+ * stride), pattern_frames without n_levels in 1..MACJD_MAX_PATTERN_LEVELS or n_levels without pattern_frames, a handle whose
+ * pattern L is > 0 and differs from n_levels, a handle without scan tables, base.pe_tables != NULL; MACJD_EUNSUPPORTED:
+ * sizes other than those of macjd_agent_env_episode_scan.  Every check returns before any launch.
+ */
+typedef struct macjd_agent_env_episode_moving_scan_pe_io {
+    macjd_agent_env_episode_scan_io base;   /* base.pe_tables must be NULL */
+    macjd_motion_pe_io       motion_pe;
+    macjd_motion_scan_pe_io  motion_scan_pe;
+} macjd_agent_env_episode_moving_scan_pe_io;
+
+int macjd_agent_env_episode_moving_scan_pe_supported(int32_t J, int32_t R, int32_t H, int32_t A);
+int macjd_agent_env_episode_moving_scan_pe(const macjd_scenario* scenario, const macjd_agent_env_episode_moving_scan_pe_io* io,
+                                           void* hip_stream);
+
+/*
  * The agent side of a whole episode batch on PER-ENV moving frames (macjd_motion_pe_io) in ONE launch.  The observation
  * of env e at step t is its own state row with the position columns taken from its own frame min(step0[e] + t, F),
  * whatever the agents did, so — as for macjd_agent_episode_seq — nothing the agent computes depends on the environment's

@@ -49,6 +49,7 @@ EXPORTS = [
     "macjd_agent_episode_seq_supported", "macjd_agent_episode_seq",
     "macjd_env_step_moving_pe", "macjd_env_step_many_moving_pe", "macjd_env_reset_moving_pe", "macjd_motion_pe_compile",
     "macjd_env_step_moving_scan_pe", "macjd_env_reset_moving_scan_pe", "macjd_motion_scan_pe_compile",
+    "macjd_agent_env_episode_moving_scan_pe_supported", "macjd_agent_env_episode_moving_scan_pe",
 ]
 
 
@@ -345,6 +346,11 @@ class AgentEnvEpisodeScanPeIO(ctypes.Structure):
 class AgentEnvEpisodeMovingScanIO(ctypes.Structure):
     """ctypes mirror of ``macjd_agent_env_episode_moving_scan_io`` (include/macjd_nets.h)."""
     _fields_ = [("base", AgentEnvEpisodeScanIO), ("motion", MotionIO), ("motion_scan", MotionScanIO)]
+
+
+class AgentEnvEpisodeMovingScanPeIO(ctypes.Structure):
+    """ctypes mirror of ``macjd_agent_env_episode_moving_scan_pe_io`` (include/macjd_nets.h)."""
+    _fields_ = [("base", AgentEnvEpisodeScanIO), ("motion_pe", MotionPeIO), ("motion_scan_pe", MotionScanPeIO)]
 
 
 class AgentEpisodeMovingPeIO(ctypes.Structure):
@@ -661,6 +667,11 @@ def load() -> ctypes.CDLL:
     lib.macjd_agent_env_episode_moving_scan_supported.argtypes = [ctypes.c_int32] * 4
     lib.macjd_agent_env_episode_moving_scan.restype = ctypes.c_int
     lib.macjd_agent_env_episode_moving_scan.argtypes = [ctypes.c_void_p, ctypes.POINTER(AgentEnvEpisodeMovingScanIO), ctypes.c_void_p]
+    lib.macjd_agent_env_episode_moving_scan_pe_supported.restype = ctypes.c_int
+    lib.macjd_agent_env_episode_moving_scan_pe_supported.argtypes = [ctypes.c_int32] * 4
+    lib.macjd_agent_env_episode_moving_scan_pe.restype = ctypes.c_int
+    lib.macjd_agent_env_episode_moving_scan_pe.argtypes = [ctypes.c_void_p, ctypes.POINTER(AgentEnvEpisodeMovingScanPeIO),
+                                                           ctypes.c_void_p]
     lib.macjd_agent_episode_moving_pe_supported.restype = ctypes.c_int
     lib.macjd_agent_episode_moving_pe_supported.argtypes = [ctypes.c_int32] * 4
     lib.macjd_agent_episode_moving_pe.restype = ctypes.c_int

@@ -42,6 +42,12 @@
 // launched with the argument block EpScanMovIO (MOV below, deduced from the block's type so that the existing variants keep
 // their names) — the env's column is frame f = min(step counter, F - 1) of the frame tables, staged again every step, and
 // the observation's position columns follow positions[min(step counter, F)] (see the comment on the kernel).
+//
+// Per-env moving scenarios under scanning radars (include/macjd_nets.h, macjd_agent_env_episode_moving_scan_pe_io): the MOV
+// variant launched with the argument block EpScanMovPeIO (MVP below, deduced from the block's type again) — every frame
+// read is taken from the env's own column of the tiled per-env frame tables (include/macjd.h, macjd_motion_pe_io /
+// macjd_motion_scan_pe_io).  The twelve earlier variants keep their names and code,
+// profiles/episode_moving_scan_pe_isa_check.txt.
 #pragma once
 
 #include <type_traits>
@@ -97,6 +103,20 @@ struct EpScanMovIO : macjd_agent_env_episode_scan_io {
     int32_t n_frames, pat_levels;
 };
 
+// Argument block of the launch on a per-env moving scanning scenario batch (include/macjd_nets.h,
+// macjd_agent_env_episode_moving_scan_pe_io): EpScanMovIO's members, the tables in the tiled per-env frame layout of
+// macjd_motion_pe_io / macjd_motion_scan_pe_io (row t of frame f of env e at
+// table[(((e / tile) * F + f) * ROWS + t) * tile + e % tile]; positions with F + 1 frames per tile), and the tile width.
+struct EpScanMovPeIO : macjd_agent_env_episode_scan_io {
+    const double* frames;
+    const uint8_t* frame_flags;
+    const double* scan_frames;
+    const double* pattern_frames;
+    const float* positions;
+    const int32_t* position_columns;
+    int32_t n_frames, pat_levels, tile;
+};
+
 // Rows of the per-env LDS block [row][16] of the PE variants (lane er reads [row * 16 + er]): the env's pe_tables rows in
 // their own order, then the scan rows the step reads, then (PAT) inv_width.
 template <int J, int R>
@@ -133,10 +153,18 @@ struct EpScanPeRows {
 // columns: waves 1 - 3, idle during S5, copy positions[min(step0 + t + 1, F)] into the LDS observation tile for step t + 1
 // (wave 0 writes the theta_a columns there: disjoint columns), S1 copies them from the tile into the staging rows next to
 // the theta_a columns, and the env lane leaves positions[min(step0 + T, F)] in the env's state row at exit.
+//
+// MVP (IO = EpScanMovPeIO; MOV's code with other addresses): every frame table is per env in the tiled layout.  Thread tid
+// owns env column tid & 15 in every role that reads a table (staging, position columns, env lane), so the tile arithmetic
+// (e / tile, e % tile) is done once per launch: the thread keeps its env's tile index and its lane in the tile, and inside
+// the loop only the frame index changes.  Any tile width >= 1: the 16 envs of a workgroup may span several tiles; rows past
+// E use env E - 1's column, so the last tile's padding lanes are never read.  With tile % 16 == 0 the 16 envs of a row are
+// 128 contiguous bytes.
 template <int J, int R, int A, int SQ, bool PAT, bool PE = false, class IO = macjd_agent_env_episode_scan_io>
 __global__ void __launch_bounds__(256) agent_env_episode_scan_kernel(const DevTables* __restrict__ tb, const IO io) {
     static_assert(J <= 4, "one wave per agent tile in the Q-head phase");
-    constexpr bool MOV = std::is_same_v<IO, EpScanMovIO>;
+    constexpr bool MVP = std::is_same_v<IO, EpScanMovPeIO>;   // MOV on per-env frame tables
+    constexpr bool MOV = std::is_same_v<IO, EpScanMovIO> || MVP;
     static_assert(PE == (std::is_same_v<IO, EpScanPeIO> || MOV), "PE: the argument block with the per-env tables");
     constexpr int NPOS = 2 * R + 2 * J;   // MOV: position columns of a state row
     static_assert(!PAT || R <= 8, "PAT: the target's levels are packed four bits per radar into 32 bits");
@@ -359,6 +387,16 @@ __global__ void __launch_bounds__(256) agent_env_episode_scan_kernel(const DevTa
     }
     int32_t step_ctr = io.step[ee];
     const int32_t step0 = step_ctr;   // MOV: env (lane & 15)'s counter at entry, in every wave
+    // MVP: env (lane & 15)'s place in the tiled tables — the only division of the launch; element offset of row 0 of frame f
+    // of a table with `frames` frames per tile and `rows` rows per frame (consecutive rows are mv_w elements apart)
+    int64_t mv_tl = 0, mv_w = 1;
+    int mv_cl = 0;
+    if constexpr (MVP) {
+        mv_w = io.tile;
+        mv_tl = ee / mv_w;
+        mv_cl = (int)(ee - mv_tl * mv_w);
+    }
+    auto mv_off = [&](int64_t frames, int64_t f, int rows) -> int64_t { return ((mv_tl * frames + f) * rows) * mv_w + mv_cl; };
     const uint32_t episode = io.episode ? (uint32_t)io.episode[ee] : 0u;
     float rsum[3] = {0.0f, 0.0f, 0.0f};
     if (io.rdpj_sum) {
@@ -375,7 +413,12 @@ __global__ void __launch_bounds__(256) agent_env_episode_scan_kernel(const DevTa
     __syncthreads();
     if constexpr (MOV) {   // the first step's position columns of the observation tile, from the table like every later step's
         const int k = step0 < io.n_frames ? step0 : io.n_frames;
+        if constexpr (MVP) {
+            const float* __restrict__ ps = io.positions + mv_off((int64_t)io.n_frames + 1, k, NPOS);
+            for (int i = tid; i < 16 * NPOS; i += 256) Ol[er * OLD + pcol[i >> 4]] = ps[(int64_t)(i >> 4) * mv_w];
+        } else {
         for (int i = tid; i < 16 * NPOS; i += 256) Ol[er * OLD + pcol[i >> 4]] = io.positions[(int64_t)k * NPOS + (i >> 4)];
+        }
         __syncthreads();
     }
     const PdConsts pdk = pd_consts(tab.pd_A, tab.pd_c1, tab.pd_denB);
@@ -416,13 +459,27 @@ __global__ void __launch_bounds__(256) agent_env_episode_scan_kernel(const DevTa
         pp_lane = io.pp_tables + tl * (R + 4 * (int64_t)(pat_L + 2) * R) * pps + (tiled ? ee - tl * io.pe_tile : ee);
     }
     auto pp_row = [&](int lt, int k, int r) -> double {
-        if constexpr (MOV) return mv_pp[R + (lt * (pat_L + 2) + k) * R + r];
+        if constexpr (MVP) return mv_pp[(int64_t)(R + (lt * (pat_L + 2) + k) * R + r) * mv_w];
+        else if constexpr (MOV) return mv_pp[R + (lt * (pat_L + 2) + k) * R + r];
         else return pp_lane[(int64_t)(R + (lt * (pat_L + 2) + k) * R + r) * pps];
     };
 
     for (int t = 0; t < T; ++t) {
         const int cur = t & 1, nxt = cur ^ 1;
-        if constexpr (MOV) {
+        if constexpr (MVP) {
+            // frame f of env (tid & 15)'s own column -> the [row][16] block and the flag bytes, in place (read next in S5)
+            const int64_t f = (step0 + t < io.n_frames ? step0 + t : io.n_frames - 1);
+            const double* __restrict__ pe = io.frames + mv_off(io.n_frames, f, PR::NPE);
+            const double* __restrict__ sp = io.scan_frames + mv_off(io.n_frames, f, PR::NSP);
+            for (int row = tid >> 4; row < PR::INVW; row += 16)
+                pt[row * 16 + er] = row < PR::NPE ? pe[(int64_t)row * mv_w] : sp[(int64_t)PR::sp_src(row - PR::NPE) * mv_w];
+            if ((tid >> 4) < J * R) pfl[(tid >> 4) * 16 + er] = io.frame_flags[mv_off(io.n_frames, f, J * R) + (int64_t)(tid >> 4) * mv_w];
+            if constexpr (PAT) {   // inv_width: the first R rows of the env's pattern column of the frame
+                if (tid < 16 * R)
+                    pt[(PR::INVW + (tid >> 4)) * 16 + er] =
+                        io.pattern_frames[mv_off(io.n_frames, f, R + 4 * (pat_L + 2) * R) + (int64_t)(tid >> 4) * mv_w];
+            }
+        } else if constexpr (MOV) {
             // frame f of env column (tid & 15) -> the [row][16] block and the flag bytes, in place (read next in S5)
             const int64_t f = (step0 + t < io.n_frames ? step0 + t : io.n_frames - 1);
             const double* __restrict__ pe = io.frames + f * PR::NPE;
@@ -674,7 +731,9 @@ __global__ void __launch_bounds__(256) agent_env_episode_scan_kernel(const DevTa
         if (wave == 0) {
             constexpr int NP = R + J, NBLK = (NP + 3) / 4;
             const uint32_t step_before = (uint32_t)step_ctr;
-            if constexpr (MOV && PAT)   // the level rows of this step's frame (wave 0's counter is step0 + t here)
+            if constexpr (MVP && PAT)   // the level rows of this step's frame in the env's own column
+                mv_pp = io.pattern_frames + mv_off(io.n_frames, step_ctr < io.n_frames ? step_ctr : io.n_frames - 1, R + 4 * (pat_L + 2) * R);
+            else if constexpr (MOV && PAT)   // the level rows of this step's frame (wave 0's counter is step0 + t here)
                 mv_pp = io.pattern_frames + (int64_t)(step_ctr < io.n_frames ? step_ctr : io.n_frames - 1) * (R + 4 * (int64_t)(pat_L + 2) * R);
             uint32_t rw[NBLK * 4];
 #pragma unroll
@@ -825,6 +884,10 @@ __global__ void __launch_bounds__(256) agent_env_episode_scan_kernel(const DevTa
         } else if constexpr (MOV) {
             // waves 1 - 3: the position columns of step t + 1's observation (row = tid & 15: the env whose step0 the thread holds)
             const int k = step0 + t + 1 < io.n_frames ? step0 + t + 1 : io.n_frames;
+            if constexpr (MVP) {
+                const float* __restrict__ ps = io.positions + mv_off((int64_t)io.n_frames + 1, k, NPOS);
+                for (int i = tid - 64; i < 16 * NPOS; i += 192) Ol[er * OLD + pcol[i >> 4]] = ps[(int64_t)(i >> 4) * mv_w];
+            } else
             for (int i = tid - 64; i < 16 * NPOS; i += 192) Ol[er * OLD + pcol[i >> 4]] = io.positions[(int64_t)k * NPOS + (i >> 4)];
         }
         __syncthreads();
@@ -843,6 +906,9 @@ __global__ void __launch_bounds__(256) agent_env_episode_scan_kernel(const DevTa
                         v = pp_row(PP_SNR_NO, (int)((lv_last >> (4 * r)) & 15u), r);
                     } else if constexpr (MOV) {   // the last step's frame: its snr_no | snr_no_side row
                         const int64_t fl = step_ctr - 1 < io.n_frames ? step_ctr - 1 : io.n_frames - 1;
+                        if constexpr (MVP)
+                            v = io.scan_frames[mv_off(io.n_frames, fl, PR::NSP) + (int64_t)((((in_t_last >> r) & 1u) ? 6 : 7) * R + r) * mv_w];
+                        else
                         v = io.scan_frames[fl * PR::NSP + (((in_t_last >> r) & 1u) ? 6 : 7) * R + r];
                     } else {
                         const bool tiled = io.pe_tile > 0;
@@ -865,6 +931,11 @@ __global__ void __launch_bounds__(256) agent_env_episode_scan_kernel(const DevTa
         }
         if constexpr (MOV) {   // the positions the next step's agents see
             const int k = step_ctr < io.n_frames ? step_ctr : io.n_frames;
+            if constexpr (MVP) {
+                const float* __restrict__ ps = io.positions + mv_off((int64_t)io.n_frames + 1, k, NPOS);
+#pragma unroll
+                for (int p = 0; p < NPOS; ++p) io.scan.state[ee * io.scan.st_se + pcol[p]] = ps[(int64_t)p * mv_w];
+            } else
 #pragma unroll
             for (int p = 0; p < NPOS; ++p) io.scan.state[ee * io.scan.st_se + pcol[p]] = io.positions[(int64_t)k * NPOS + p];
         }
@@ -1030,5 +1101,57 @@ extern "C" int macjd_agent_env_episode_moving_scan(const macjd_scenario* s, cons
     else hipLaunchKernelGGL((agent_env_episode_scan_kernel<2, 2, 5, 3, false, true, EpScanMovIO>), grid, block, 0, st, s->dev, k);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_agent_env_episode_moving_scan: %s", hipGetErrorString(err));
+    return MACJD_OK;
+}
+
+extern "C" int macjd_agent_env_episode_moving_scan_pe_supported(int32_t J, int32_t R, int32_t H, int32_t A) {
+    return macjd_agent_env_episode_scan_supported(J, R, H, A);
+}
+
+// The closed-loop launch on a per-env moving scanning scenario batch's tiled frame tables (include/macjd_nets.h,
+// macjd_agent_env_episode_moving_scan_pe_io); its argument errors mirror macjd_env_step_moving_scan_pe's and
+// macjd_agent_env_episode_moving_scan's, and all of them return before any launch
+extern "C" int macjd_agent_env_episode_moving_scan_pe(const macjd_scenario* s, const macjd_agent_env_episode_moving_scan_pe_io* mio,
+                                                      void* hip_stream) {
+    using namespace macjd;
+    const char* me = "macjd_agent_env_episode_moving_scan_pe";
+    if (mio && mio->base.pe_tables) return set_err(MACJD_EINVAL, "%s: base.pe_tables must be NULL (the frames are the tables)", me);
+    const int rc = episode_scan_check(s, mio ? &mio->base : nullptr, me, false);
+    if (rc != MACJD_OK) return rc;
+    const macjd_agent_env_episode_scan_io* io = &mio->base;
+    const macjd_motion_pe_io* mo = &mio->motion_pe;
+    const macjd_motion_scan_pe_io* ms = &mio->motion_scan_pe;
+    if (!mo->frames || !mo->frame_flags || !mo->positions || !mo->position_columns || !mo->state)
+        return set_err(MACJD_EINVAL, "%s: frames / frame_flags / positions / position_columns / state is NULL", me);
+    if (!ms->scan_frames) return set_err(MACJD_EINVAL, "%s: NULL scan_frames", me);
+    if (mo->n_frames < 1) return set_err(MACJD_EINVAL, "%s: n_frames < 1", me);
+    if (mo->n_frames != s->host.episode_limit) return set_err(MACJD_EINVAL, "%s: n_frames must equal the scenario's episode_limit", me);
+    if (mo->n_pos != 2 * io->R + 2 * io->J) return set_err(MACJD_EINVAL, "%s: n_pos must equal 2R + 2J", me);
+    if (mo->tile < 1) return set_err(MACJD_EINVAL, "%s: tile must be >= 1", me);
+    if (mo->snr_no) return set_err(MACJD_EINVAL, "%s: motion_pe.snr_no must be NULL (the per-step value travels in base.scan.snr_no)", me);
+    if (mo->state != io->scan.state || mo->st_se != io->scan.st_se)
+        return set_err(MACJD_EINVAL, "%s: base.scan.state and motion_pe.state must be the same rows with the same row stride", me);
+    if (ms->n_levels < 0 || ms->n_levels > MACJD_MAX_PATTERN_LEVELS)
+        return set_err(MACJD_EINVAL, "%s: n_levels outside 0..MACJD_MAX_PATTERN_LEVELS", me);
+    if (s->host.pat_levels > 0 && s->host.pat_levels != ms->n_levels)
+        return set_err(MACJD_EINVAL, "%s: n_levels differs from the pattern levels of the scenario handle", me);
+    if ((ms->pattern_frames != nullptr) != (ms->n_levels > 0))
+        return set_err(MACJD_EINVAL, "%s: pattern_frames and n_levels > 0 go together (both or neither)", me);
+    if (io->n_envs == 0) return MACJD_OK;
+    const bool pat = ms->pattern_frames != nullptr;
+    EpScanMovPeIO k{};
+    static_cast<macjd_agent_env_episode_scan_io&>(k) = *io;
+    k.frames = mo->frames; k.frame_flags = mo->frame_flags; k.scan_frames = ms->scan_frames; k.pattern_frames = ms->pattern_frames;
+    k.positions = mo->positions; k.position_columns = mo->position_columns;
+    k.n_frames = mo->n_frames; k.pat_levels = pat ? ms->n_levels : 0; k.tile = mo->tile;
+    const dim3 grid((unsigned)((io->n_envs + 15) / 16)), block(256);
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (pat) {
+        if (io->J == 3) hipLaunchKernelGGL((agent_env_episode_scan_kernel<3, 4, 9, 3, true, true, EpScanMovPeIO>), grid, block, 0, st, s->dev, k);
+        else hipLaunchKernelGGL((agent_env_episode_scan_kernel<2, 2, 5, 3, true, true, EpScanMovPeIO>), grid, block, 0, st, s->dev, k);
+    } else if (io->J == 3) hipLaunchKernelGGL((agent_env_episode_scan_kernel<3, 4, 9, 3, false, true, EpScanMovPeIO>), grid, block, 0, st, s->dev, k);
+    else hipLaunchKernelGGL((agent_env_episode_scan_kernel<2, 2, 5, 3, false, true, EpScanMovPeIO>), grid, block, 0, st, s->dev, k);
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return set_err(MACJD_EDEVICE, "macjd_agent_env_episode_moving_scan_pe: %s", hipGetErrorString(err));
     return MACJD_OK;
 }

@@ -31,7 +31,8 @@ What is added (build flags, all optional):
   ``randomize_moving_scan_scenarios`` / ``--randomize-moving-scan-scenarios`` (batched runs on a sim-config with ``motion``
                   AND ``radar_scan`` on one clock): the same for a moving scenario under scanning radars, with
                   ``randomize_velocity_jitter`` and ``randomize_azimuth_jitter``; frame tables and beam frames are compiled on
-                  the device (``scenario.MovingScanScenarioBatch``); the rollout is the step loop.
+                  the device (``scenario.MovingScanScenarioBatch``); the rollout is the step loop, or with
+                  ``MACJD_CLOSED_LOOP_MOVING_PE_ROLLOUT=1`` (no further flag) the closed-loop launch on every env's own frames.
   ``--resume DIR`` restores agent, mixer, optimiser and ``trainer_state.json`` (env steps, episodes, epsilon
                   clock, learner step counters, and the positions of the three random streams: exploration counter,
                   replay sampler, per-env Monte-Carlo episode index) — the reference saves the optimiser but never

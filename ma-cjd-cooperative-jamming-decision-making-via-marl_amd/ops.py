@@ -563,6 +563,32 @@ def agent_env_episode_moving_scan(agent, env_args: dict, n_envs: int, n_agents: 
     del keep
 
 
+def agent_env_episode_moving_scan_pe_supported(J: int, R: int, H: int, A: int) -> bool:
+    return bool(_native.load().macjd_agent_env_episode_moving_scan_pe_supported(int(J), int(R), int(H), int(A)))
+
+
+def agent_env_episode_moving_scan_pe(agent, env_args: dict, n_envs: int, n_agents: int, T: int, avail, eps_sched,
+                                     greedy_only: bool, seed: int, counter_base, stage: dict, rdpj_sum=None, h0=None,
+                                     h_final=None):
+    """``agent_env_episode_moving_scan`` on a per-env moving scanning scenario batch (include/macjd_nets.h,
+    macjd_agent_env_episode_moving_scan_pe_io): the same launch with every frame read taken from the env's own column of the
+    tiled per-env frame tables.  ``env_args`` is what ``BatchedElectromagneticEnvironment.episode_moving_scan_pe_args()``
+    hands over: the shared call's entries plus the per-env motion and motion-scan blocks."""
+    lib = _native.load()
+    mio = _native.AgentEnvEpisodeMovingScanPeIO()
+    keep, W1 = _fill_episode_scan_io(mio.base, agent, env_args, n_envs, n_agents, T, avail, eps_sched, greedy_only, seed,
+                                     counter_base, stage, rdpj_sum, h0, h_final)
+    ctypes.memmove(ctypes.addressof(mio) + _native.AgentEnvEpisodeMovingScanPeIO.motion_pe.offset,
+                   ctypes.addressof(env_args["motion_pe_io"]), ctypes.sizeof(_native.MotionPeIO))
+    ctypes.memmove(ctypes.addressof(mio) + _native.AgentEnvEpisodeMovingScanPeIO.motion_scan_pe.offset,
+                   ctypes.addressof(env_args["motion_scan_pe_io"]), ctypes.sizeof(_native.MotionScanPeIO))
+    mio.motion_pe.snr_no = None   # the per-step value travels in the beam block's snr_no
+    with torch.cuda.device(W1.device):
+        _native.check(lib.macjd_agent_env_episode_moving_scan_pe(env_args["handle"], ctypes.byref(mio), _stream(W1)),
+                      "macjd_agent_env_episode_moving_scan_pe")
+    del keep
+
+
 def agent_episode_moving_pe_supported(J: int, R: int, H: int, A: int) -> bool:
     return bool(_native.load().macjd_agent_episode_moving_pe_supported(int(J), int(R), int(H), int(A)))
 

@@ -46,6 +46,8 @@ for normal operation.
                                          episode batch in one launch on the frame tables
     MACJD_MOVING_PE_EPISODE_ROLLOUT 0 | 1   per-env moving scenario batches: step-by-step rollout / the agent's steps of an
                                          episode batch as one launch on every env's own frames, the env's steps as another
+    MACJD_CLOSED_LOOP_MOVING_PE_ROLLOUT 0 | 1   per-env moving scanning scenario batches: step-by-step rollout / agent and env of
+                                         an episode batch in one launch on every env's own frame tables
 """
 from __future__ import annotations
 
@@ -57,7 +59,7 @@ _DEFAULTS = {
     "QHEAD_TAKEN": "1", "QHEAD_DOUBLE_Q": "1", "QHEAD_DOUBLE_Q_H128": "0", "PAIRED_HEADS": "1", "MIXER_TRAIN": "1", "MIXER_STATIC_STATE": "1", "WGRAD_IN_TRAIN": "1", "ROWS_STAGED": "1", "GRAPHED_ALLREDUCE": "0",
     "PREFETCH_LAUNCH": "1", "PREFETCH_AHEAD": "2",
     "CLOSED_LOOP_ROLLOUT": "0", "MOVING_EPISODE_ROLLOUT": "0", "CLOSED_LOOP_MOVING_ROLLOUT": "0",
-    "MOVING_PE_EPISODE_ROLLOUT": "0",
+    "MOVING_PE_EPISODE_ROLLOUT": "0", "CLOSED_LOOP_MOVING_PE_ROLLOUT": "0",
 }
 _values = None
 

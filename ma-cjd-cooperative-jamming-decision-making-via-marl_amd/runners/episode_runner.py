@@ -178,8 +178,9 @@ class EpisodeRunner:
 
 def _per_env_moving_scan(env) -> bool:
     """``env`` is a per-env moving scenario batch under scanning radars (``moving_scan_batch=...``): theta_a depends on the
-    detections and every env has its own frames, so no whole-episode launch applies — every availability predicate of the
-    batched runner answers False and the rollout is the step loop on its dynamic-observation path."""
+    detections and every env has its own frames, so no open-loop whole-episode launch applies — every earlier availability
+    predicate of the batched runner answers False; its rollout is the step loop on the dynamic-observation path or, under
+    its own switch, the closed-loop launch on per-env frames (``closed_loop_moving_pe_available``)."""
     return getattr(env, "moving_scan_batch", None) is not None
 
 
@@ -364,6 +365,9 @@ class BatchedEpisodeRunner:
         if device_schedule and self.moving_pe_episode_rollout and self.moving_pe_rollout_available():
             self._moving_pe_launches(T)   # per-env moving batch: the agent's steps on every env's own frames, the env's steps
             return
+        if device_schedule and self.closed_loop_moving_pe_rollout and self.closed_loop_moving_pe_available():
+            self._closed_loop_launch(T)   # per-env moving scanning batch: one launch on every env's own frame tables
+            return
         for t in range(T):
             if device_schedule:
                 self.mac.device_schedule = (self._eps_sched[t:t + 1], self._ctr_base, t + 1)
@@ -534,6 +538,37 @@ class BatchedEpisodeRunner:
                                "(closed_loop_moving_available())")
         self._rollout_closed_loop(test_mode, n_steps, "rollout_closed_loop_moving")
 
+    # default off (MACJD_CLOSED_LOOP_MOVING_PE_ROLLOUT=1)
+    closed_loop_moving_pe_rollout = _OptionSwitch("CLOSED_LOOP_MOVING_PE_ROLLOUT")
+
+    def closed_loop_moving_pe_available(self) -> bool:
+        """``closed_loop_moving_available`` for a per-env moving scanning scenario batch (``moving_scan_batch=...``): a HIP
+        device, ``kernel_flags == 0``, the stock RNNAgent with actor width 128 and ``input_shape == state_dim <= 48`` at a
+        size the closed-loop kernel covers (``episode_moving_scan_pe_args``,
+        ``ops.agent_env_episode_moving_scan_pe_supported``)."""
+        env = self.env
+        if self.device.type != "cuda" or not _per_env_moving_scan(env) or not hasattr(env, "episode_moving_scan_pe_args"):
+            return False
+        if getattr(env, "kernel_flags", 0) != 0:
+            return False
+        agent = getattr(self.mac, "agent", None)
+        if agent is None or not hasattr(agent, "fc2_q_head") or not hasattr(agent, "actor") or not next(agent.parameters()).is_cuda:
+            return False
+        from .. import ops
+        return (getattr(agent, "actor_hidden_dim", 0) == 128 and agent.input_shape == env.state_dim and env.state_dim <= 48
+                and ops.agent_env_episode_moving_scan_pe_supported(self.n_agents, env.num_radars, agent.rnn_hidden_dim,
+                                                                   agent.n_actions))
+
+    def rollout_closed_loop_moving_pe(self, test_mode=False, n_steps=None):
+        """``rollout_closed_loop_moving`` on a per-env moving scanning scenario batch
+        (``ops.agent_env_episode_moving_scan_pe``): one launch in which env e runs step t on its own frame
+        min(step[e] + t, F - 1) and the observation's position columns follow its own frames; its env half is bit-identical
+        to the per-env moving scanning step kernel's all-float64 form."""
+        if not self.closed_loop_moving_pe_available():
+            raise RuntimeError("rollout_closed_loop_moving_pe: not available for this environment / agent "
+                               "(closed_loop_moving_pe_available())")
+        self._rollout_closed_loop(test_mode, n_steps, "rollout_closed_loop_moving_pe")
+
     def rollout_closed_loop(self, test_mode=False, n_steps=None):
         """One episode batch (or its first ``n_steps`` steps) of a scanning scenario in ONE launch
         (``ops.agent_env_episode_scan``): per step the observation-only work once per env, the agent step of
@@ -568,7 +603,9 @@ class BatchedEpisodeRunner:
         from .. import ops
         if not self._static_filled:
             self._fill_static()   # (a per-env batch: each env's own state row)
-        if getattr(self.env.scenario, "moving", False):   # moving under scanning radars: the frame tables
+        if _per_env_moving_scan(self.env):   # per-env moving scanning batch: every env reads its own frame tables
+            launch, env_args = ops.agent_env_episode_moving_scan_pe, self.env.episode_moving_scan_pe_args()
+        elif getattr(self.env.scenario, "moving", False):   # moving under scanning radars: the frame tables
             launch, env_args = ops.agent_env_episode_moving_scan, self.env.episode_moving_scan_args()
         elif getattr(self.env, "scenario_batch", None) is not None:   # per-env scenario batch: every env reads its own tables
             launch, env_args = ops.agent_env_episode_scan_pe, self.env.episode_scan_pe_args()
@@ -749,6 +786,8 @@ class BatchedEpisodeRunner:
             self.rollout_closed_loop_moving(test_mode=test_mode)
         elif self.moving_pe_episode_rollout and self.moving_pe_rollout_available():
             self.rollout_moving_pe(test_mode=test_mode)
+        elif self.closed_loop_moving_pe_rollout and self.closed_loop_moving_pe_available():
+            self.rollout_closed_loop_moving_pe(test_mode=test_mode)
         elif getattr(self, "_graph", None) is not None and not test_mode:
             self.rollout_graphed()
         else:

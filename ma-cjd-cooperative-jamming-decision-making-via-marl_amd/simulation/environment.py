@@ -732,6 +732,20 @@ class BatchedElectromagneticEnvironment:
                 "motion_scan_io": self._motion_scan_io, "track": self._track, "step": self._step, "episode": self._episode,
                 "seed": self.seed, "env_offset": self.env_offset, "n_radars": self.num_radars, "pe_tables": None}
 
+    def episode_moving_scan_pe_args(self) -> Dict[str, Any]:
+        """What the closed-loop episode launch on a per-env moving scanning scenario batch
+        (``ops.agent_env_episode_moving_scan_pe``) needs: the entries of ``episode_scan_args`` plus the per-env motion block
+        (tiled frame tables, positions and their state columns, tile width) and the per-env motion-scan block (tiled beam
+        frames, under a stepped pattern the tiled level frames)."""
+        if self._motion_scan_pe_io is None:
+            raise RuntimeError("episode_moving_scan_pe_args: needs a per-env moving scanning scenario batch "
+                               "(moving_scan_batch=...); episode_moving_scan_args serves shared frame tables")
+        self._scan_io.snr_no = self._snr_no_step.data_ptr()   # (a step with want_info=False clears it)
+        return {"handle": self._handle.ptr, "scan_io": self._scan_io, "motion_pe_io": self._motion_pe_io,
+                "motion_scan_pe_io": self._motion_scan_pe_io, "track": self._track, "step": self._step,
+                "episode": self._episode, "seed": self.seed, "env_offset": self.env_offset, "n_radars": self.num_radars,
+                "pe_tables": None}
+
     def _need_moving_batch(self, what: str) -> None:
         if self._motion_pe_io is None:
             raise RuntimeError(f"{what}: needs a per-env moving scenario batch (moving_batch=...)")
