@@ -179,6 +179,34 @@ int macjd_td_loss(const macjd_tdloss_io* io, void* hip_stream);
 int macjd_td_mask_sum(const macjd_tdloss_io* io, float* out, void* hip_stream);
 
 /*
+ * TD(lambda) targets: the loss of macjd_td_loss against lambda-returns instead of the one-step target.  For a batch of B
+ * episodes and Tm1 loss-carrying steps, with the inputs of macjd_td_loss (tq[b, t] = the target network's Q_tot of step
+ * t + 1), per episode:
+ *   boot[t] = gamma * (1 - terminated[t])
+ *   cont[t] = (t + 1 < Tm1) and filled[t + 1] and not terminated[t]          -- a select, never a multiply
+ *   lam[t]  = lambda if cont[t] else 0
+ *   G[t]    = reward[t] + boot[t] * ((1 - lam[t]) * tq[t] + lam[t] * G[t + 1])          -- G[Tm1] is never read
+ *   loss    = sum((filled (y - G))^2) / sum(filled)
+ *   gy      = 2 filled (y - G) / sum(filled)
+ *   stats   = loss, mean(y), mean(G) over all B * Tm1, sum(filled)
+ * The chain stops on termination, at the last step and in front of an unfilled step; what sits behind a stop never
+ * reaches a G in front of it (the select: not even as 0 * inf).  lambda = 0 is macjd_td_loss's target term for term;
+ * lambda = 1 is the discounted reward-to-go with one bootstrap where the chain stops.  G[t] is defined at unfilled t by
+ * the same recursion, so mean(G) keeps the meaning mean(target) has in macjd_td_loss.
+ * One single-workgroup launch.  td: every field as in macjd_td_loss (strides, gy_cols, gy == NULL = the sums only:
+ * stats[0..2] written, stats[3] left alone; ret is written either way).
+ */
+typedef struct macjd_tdlambda_io {
+    macjd_tdloss_io td;
+    float lambda;              /* 0 <= lambda <= 1 */
+    float reserved;            /* the padding in front of ret made explicit (as in macjd_tdloss_io): not read, set 0 */
+    float* ret;                /* out, required: G, element (b, t) at ret[b * ret_sb + t], t < Tm1 */
+    int64_t ret_sb;            /* >= Tm1 */
+} macjd_tdlambda_io;
+
+int macjd_td_lambda_loss(const macjd_tdlambda_io* io, void* hip_stream);
+
+/*
  * Gradient clipping + Adam over ONE flat parameter vector (reference core/qmix.py:199-200:
  * torch.nn.utils.clip_grad_norm_(params, max_norm) followed by torch.optim.Adam.step()):
  *   total_norm = ||grad||_2 ; coef = min(1, max_norm / (total_norm + 1e-6)) ; g = coef * grad

@@ -50,6 +50,7 @@ EXPORTS = [
     "macjd_env_step_moving_pe", "macjd_env_step_many_moving_pe", "macjd_env_reset_moving_pe", "macjd_motion_pe_compile",
     "macjd_env_step_moving_scan_pe", "macjd_env_reset_moving_scan_pe", "macjd_motion_scan_pe_compile",
     "macjd_agent_env_episode_moving_scan_pe_supported", "macjd_agent_env_episode_moving_scan_pe",
+    "macjd_td_lambda_loss",
 ]
 
 
@@ -470,6 +471,14 @@ class TdLossIO(ctypes.Structure):
     ]
 
 
+class TdLambdaIO(ctypes.Structure):
+    """ctypes mirror of ``macjd_tdlambda_io`` (include/macjd_nets.h)."""
+    _fields_ = [
+        ("td", TdLossIO), ("lam", ctypes.c_float), ("reserved", ctypes.c_float),
+        ("ret", ctypes.c_void_p), ("ret_sb", ctypes.c_int64),
+    ]
+
+
 class AdamIO(ctypes.Structure):
     """ctypes mirror of ``macjd_adam_io`` (include/macjd_nets.h)."""
     _fields_ = [
@@ -724,6 +733,8 @@ def load() -> ctypes.CDLL:
     lib.macjd_mlp_forward_pair.argtypes = [ctypes.POINTER(MlpIO), ctypes.POINTER(MlpIO), ctypes.c_void_p]
     lib.macjd_mlp_forward.restype = ctypes.c_int
     lib.macjd_mlp_forward.argtypes = [ctypes.POINTER(MlpIO), ctypes.c_void_p]
+    lib.macjd_td_lambda_loss.restype = ctypes.c_int
+    lib.macjd_td_lambda_loss.argtypes = [ctypes.POINTER(TdLambdaIO), ctypes.c_void_p]
     lib.macjd_td_loss.restype = ctypes.c_int
     lib.macjd_td_loss.argtypes = [ctypes.POINTER(TdLossIO), ctypes.c_void_p]
     lib.macjd_clip_adam_step.restype = ctypes.c_int

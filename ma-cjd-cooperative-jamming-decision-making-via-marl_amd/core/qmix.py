@@ -28,6 +28,12 @@ and Adam step; the actor reads the observation alone, so the whole gradient is t
 (ops.actor_gradient) and three split-K weight gradients.  ``train`` then also returns ``actor_q_avg`` =
 ``sum_n m_n sum_a Q_na / actor_loss_coef``.  Eager updates only, like ``train_agent_body``.
 
+Opt-in departure, ``args.td_lambda`` (absent / None by default; main.py ``--td-lambda X``, 0 <= X <= 1): the loss chases
+lambda-returns instead of the one-step target (include/macjd_nets.h, ``macjd_tdlambda_io``: the definition; 0 is the
+reference's target term for term, 1 the discounted reward-to-go with one bootstrap where the chain stops).  Only the
+target moves, so it combines with the two options above; ``target_qtot_avg`` is then the mean lambda-return.  Eager
+updates only: ``enable_graphs`` refuses.
+
 What changes is the schedule of the work, not the algebra.  The reference unrolls
 ``for t: for a:`` in Python — 2 x T x (3 + 5A) small launches per call (qmix.py:241-274).  Everything
 except the GRU recurrence is time-parallel, so here: fc1 / actor / GRU input transform / Q-head base are
@@ -73,6 +79,9 @@ class QMixLearner:
         self.train_actor = bool(getattr(args, "train_actor", False))             # module docstring
         self.actor_loss_coef = float(getattr(args, "actor_loss_coef", 1.0))
         self._last_actor_q = None
+        self.td_lambda = self._checked_td_lambda(getattr(args, "td_lambda", None))   # module docstring
+        # read once, here (the captured updates never look at it); _forward_backward's loss call branches on this flag and
+        # looks ops.td_loss / ops.td_lambda_loss up at call time, as the default path always has
 
         self.eval_qmix_net = QMixer(args)
         self.target_mac = copy.deepcopy(mac)
@@ -97,6 +106,18 @@ class QMixLearner:
             self._flatten_trainable()
         self._body_versions = None
         self._mark_body_shared()   # target_mac is a deep copy of mac (qmix.py:53)
+
+    @staticmethod
+    def _checked_td_lambda(value):
+        if value is None:
+            return None
+        try:
+            lam = float(value)
+        except (TypeError, ValueError):
+            raise ValueError(f"td_lambda must be a number in [0, 1], got {value!r}") from None
+        if isinstance(value, bool) or not 0.0 <= lam <= 1.0:   # (a NaN fails both comparisons)
+            raise ValueError(f"td_lambda must be a number in [0, 1], got {value!r}")
+        return lam
 
     # ------------------------------------------------------------------ frozen agent body
     @staticmethod
@@ -335,8 +356,12 @@ class QMixLearner:
 
         # targets = r + gamma (1 - terminated) Q_tot'(s', a')            qmix.py:155
         # loss = sum((filled (Q_tot - targets))^2) / sum(filled)          qmix.py:190-194   (one fused launch)
-        loss, eval_mean, target_mean = ops.td_loss(eval_q_mixer, target_q_mixer, rewards[:, :-1], terminated[:, :-1],
-                                                   filled[:, :-1], self.args.gamma)
+        if self.td_lambda is None:
+            loss, eval_mean, target_mean = ops.td_loss(eval_q_mixer, target_q_mixer, rewards[:, :-1], terminated[:, :-1],
+                                                       filled[:, :-1], self.args.gamma)
+        else:   # the same against lambda-returns (module docstring)
+            loss, eval_mean, target_mean = ops.td_lambda_loss(eval_q_mixer, target_q_mixer, rewards[:, :-1], terminated[:, :-1],
+                                                              filled[:, :-1], self.args.gamma, self.td_lambda)
 
         for p in self.params:   # autograd then ASSIGNS fresh gradients (no accumulate-add kernels, no memset);
             p.grad = None       # parameters the graph never reaches keep grad None, as in the reference
@@ -842,6 +867,9 @@ class QMixLearner:
         if self.train_actor:
             raise RuntimeError("enable_graphs: train_actor is an eager-mode option (the captured, static-observation and "
                                "shared-body updates are built on the frozen actor); use train()")
+        if self.td_lambda is not None:
+            raise RuntimeError("enable_graphs: td_lambda is an eager-mode option (the captured update forms the TD gradient "
+                               "inside the mixer training launch, before any target row of a later step exists); use train()")
         self.release_graphs()   # a re-capture destroys the previous graphs first, explicitly and at a quiet point
         self._verify_body_shared()   # (values, not version counters: catches writes made through .data)
         same_buffer = getattr(self, "_g_buffer", None) is buffer

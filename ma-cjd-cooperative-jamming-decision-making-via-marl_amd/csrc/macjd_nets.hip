@@ -27,6 +27,7 @@
 #include "../../include/macjd_nets.h"
 #include "macjd_err.h"
 #include "macjd_tdloss.h"
+#include "macjd_tdlambda.h"
 #include "macjd_philox.h"
 #include "macjd_gru_math.h"   // gru_sigmoid / gru_tanh
 
@@ -828,6 +829,84 @@ extern "C" int macjd_td_loss(const macjd_tdloss_io* io, void* hip_stream) {
     if (io->y_sb < io->Tm1 || io->tq_sb < io->Tm1 || (io->gy && (io->gy_cols < io->Tm1 || io->gy_sb < io->gy_cols)))
         return set_nets_err(MACJD_EINVAL, "macjd_td_loss: bad strides");
     hipLaunchKernelGGL(td_loss_kernel, dim3(1), dim3(1024), 0, (hipStream_t)hip_stream, *io);
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return set_nets_err(MACJD_EDEVICE, hipGetErrorString(err));
+    return MACJD_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// TD(lambda): td_loss_kernel against lambda-returns (macjd_tdlambda_io).  One workgroup of 16 waves; the returns of an
+// episode are a suffix scan over affine maps, 64 steps per wave pass (macjd_tdlambda.h states the order of every sum).
+// Pass 1: returns -> io.ret, the four block sums from registers; pass 2 (behind the sums' barriers, which also order the
+// stores to ret in front of the loads below): dL/dy from y and the stored returns, as td_loss_kernel's second pass.
+namespace macjd {
+
+__global__ void __launch_bounds__(1024) td_lambda_loss_kernel(const macjd_tdlambda_io io) {
+    const macjd_tdloss_io& td = io.td;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n_chunks = (td.Tm1 + 63) >> 6;
+    const int n_items = wave < td.B ? ((td.B - wave + 15) >> 4) * n_chunks : 0;   // (episode, chunk) items of this wave
+    const float lam = io.lambda, one_m_lam = 1.0f - io.lambda;
+    float q[4] = {0.0f, 0.0f, 0.0f, 0.0f};   // filled, e^2, y, G
+    float carry_g = 0.0f, carry_m = 0.0f;    // G / filled of the first step of the chunk behind
+    tdl_chunk cur = n_items > 0 ? tdl_load(td, 0, n_chunks, wave, lane) : tdl_chunk{};
+    for (int item = 0; item < n_items; ++item) {
+        // the next item's loads do not depend on this item's scan: in flight across it
+        const tdl_chunk nxt = item + 1 < n_items ? tdl_load(td, item + 1, n_chunks, wave, lane) : tdl_chunk{};
+        if (cur.t - lane == 64 * (n_chunks - 1)) { carry_g = 0.0f; carry_m = 0.0f; }   // last chunk: a new episode
+        float m_next = __shfl_down(cur.m, 1, 64);
+        if (lane == 63) m_next = carry_m;
+        const float boot = cur.term ? 0.0f : td.gamma;                 // gamma (1 - terminated)
+        const bool cont = m_next != 0.0f && !cur.term;                 // (t + 1 < Tm1: m is 0 past the end)
+        float a = cur.r + (cont ? boot * one_m_lam : boot) * cur.tq;
+        float c = cont ? boot * lam : 0.0f;
+        tdl_scan(a, c, lane);
+        const float g = c != 0.0f ? fmaf(c, carry_g, a) : a;
+        carry_g = __shfl(g, 0, 64);
+        carry_m = __shfl(cur.m, 0, 64);
+        if (cur.valid) {
+            io.ret[(int64_t)cur.b * io.ret_sb + cur.t] = g;
+            const float e = (cur.y - g) * cur.m;
+            q[0] += cur.m; q[1] += e * e; q[2] += cur.y; q[3] += g;
+        }
+        cur = nxt;
+    }
+    __shared__ float s4[4][16], tot4[4];
+    tdl_block_sums(q, s4, tot4);
+    const int M = td.B * td.Tm1;
+    const float tot_m = tot4[0];
+    if (threadIdx.x == 0) {
+        td.stats[0] = tot4[1] / tot_m;
+        td.stats[1] = tot4[2] / (float)M;
+        td.stats[2] = tot4[3] / (float)M;
+        if (td.gy) td.stats[3] = tot_m;
+    }
+    if (!td.gy) return;
+    const float scale = 2.0f / tot_m;
+    const int cols = (int)td.gy_cols;
+    for (int i = threadIdx.x; i < td.B * cols; i += blockDim.x) {
+        const int b = i / cols, t = i - b * cols;
+        float g = 0.0f;   // columns past Tm1 (full-length rows) carry no loss
+        if (t < td.Tm1) {
+            const float m = td.filled[b * td.f_sb + t * td.f_st] ? 1.0f : 0.0f;
+            g = scale * m * (td.y[b * td.y_sb + t] - io.ret[b * io.ret_sb + t]);
+        }
+        td.gy[b * td.gy_sb + t] = g;
+    }
+}
+
+}  // namespace macjd
+
+extern "C" int macjd_td_lambda_loss(const macjd_tdlambda_io* io, void* hip_stream) {
+    using namespace macjd;
+    if (!io || io->td.B < 1 || io->td.Tm1 < 1) return set_nets_err(MACJD_EINVAL, "macjd_td_lambda_loss: bad B / Tm1");
+    const macjd_tdloss_io& td = io->td;
+    if (!td.y || !td.tq || !td.reward || !td.terminated || !td.filled || !td.stats || !io->ret)
+        return set_nets_err(MACJD_EINVAL, "macjd_td_lambda_loss: NULL pointer");
+    if (td.y_sb < td.Tm1 || td.tq_sb < td.Tm1 || io->ret_sb < td.Tm1 || (td.gy && (td.gy_cols < td.Tm1 || td.gy_sb < td.gy_cols)))
+        return set_nets_err(MACJD_EINVAL, "macjd_td_lambda_loss: bad strides");
+    if (!(io->lambda >= 0.0f && io->lambda <= 1.0f)) return set_nets_err(MACJD_EINVAL, "macjd_td_lambda_loss: lambda outside [0, 1]");
+    hipLaunchKernelGGL(td_lambda_loss_kernel, dim3(1), dim3(1024), 0, (hipStream_t)hip_stream, *io);
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return set_nets_err(MACJD_EDEVICE, hipGetErrorString(err));
     return MACJD_OK;

@@ -303,8 +303,10 @@ def run(args):
     batch_envs = int(getattr(args, "batch_envs", 1) or 1)
     episodes_per_run = batch_envs
     use_graphs = bool(getattr(args, "hip_graphs", True)) and args.use_cuda and batch_envs > 1
-    if getattr(args, "train_agent_body", False) or getattr(args, "train_actor", False):
+    if (getattr(args, "train_agent_body", False) or getattr(args, "train_actor", False)
+            or getattr(args, "td_lambda", None) is not None):
         use_graphs = False   # these updates are eager (learner.train); the captured update is built on the frozen body
+                             # and on the one-step target
     # config/default.yaml is scaled for batch_envs = 4096 (epsilon annealed over 2500 steps PER ENV, 200 M collected steps);
     # the reference's own protocol (one env) anneals over 100 000 of its 2 M steps (reference config/default.yaml:21-23,60)
     if batch_envs == 1 and (args.epsilon_anneal_time < 20000 or args.total_env_steps > 20_000_000):
@@ -432,6 +434,14 @@ def run(args):
     return {"episodes": episode, "total_steps": total_steps, "log_dir": log_dir, "train_steps": learner.train_step}
 
 
+def _unit_interval(text):
+    """argparse type of --td-lambda: a float in [0, 1] (a NaN fails the comparison)."""
+    x = float(text)
+    if not 0.0 <= x <= 1.0:
+        raise argparse.ArgumentTypeError(f"{text!r} is not in [0, 1]")
+    return x
+
+
 def main(argv=None):
     parser = argparse.ArgumentParser(description="MA-CJD QMix Training (MI355X hot path)")
     parser.add_argument("--config", type=str, default="default")
@@ -459,6 +469,9 @@ def main(argv=None):
                              "with the Q-head held fixed); eager updates; combines with --train-agent-body")
     parser.add_argument("--actor-loss-coef", type=float, default=None, metavar="X",
                         help="weight of the actor objective in the one clipped Adam step (default 1.0)")
+    parser.add_argument("--td-lambda", type=_unit_interval, default=None, metavar="X",
+                        help="train against TD(lambda) returns, 0 <= X <= 1 (0: the one-step target, 1: reward-to-go with "
+                             "one bootstrap); eager updates; combines with --train-agent-body / --train-actor")
     a = parser.parse_args(argv)
     config = load_config(config_name=a.config, config_dir=a.config_dir)
     config.config, config.env_config, config.device_request = a.config, a.env_config, a.device
@@ -480,6 +493,8 @@ def main(argv=None):
         config.train_actor = True
     if a.actor_loss_coef is not None:
         config.actor_loss_coef = a.actor_loss_coef
+    if a.td_lambda is not None:
+        config.td_lambda = a.td_lambda
     return run(config)
 
 

@@ -1497,6 +1497,101 @@ def td_loss(y, tq, reward, terminated, filled, gamma):
 
 
 # ---------------------------------------------------------------------------------------------
+# TD(lambda) targets (macjd_tdlambda_io in include/macjd_nets.h: the definition)
+def _lambda_returns_reference(tq, reward, terminated, filled, gamma, lam):
+    """G [B,Tm1,1] by the reverse recursion, a select (``torch.where``) where the chain stops."""
+    Tm1 = tq.shape[1]
+    term, fill = terminated != 0, filled != 0
+    boot = gamma * (1 - term.to(tq.dtype))
+    out, nxt = [None] * Tm1, None
+    for t in reversed(range(Tm1)):
+        mix = tq[:, t]
+        if t + 1 < Tm1:
+            mix = torch.where(fill[:, t + 1] & ~term[:, t], (1 - lam) * tq[:, t] + lam * nxt, mix)
+        nxt = reward[:, t] + boot[:, t] * mix
+        out[t] = nxt
+    return torch.stack(out, dim=1) if Tm1 else torch.zeros_like(tq)
+
+
+def td_lambda_reference(y, tq, reward, terminated, filled, gamma, lam):
+    """Stock-torch form of the loss against lambda-returns.  Shapes as ``td_loss_reference``; ``lam`` = 0 is its target.
+    Returns (loss, mean(y), mean(G)), loss differentiable in y."""
+    targets = _lambda_returns_reference(tq, reward, terminated, filled, gamma, lam)
+    m = (filled != 0).to(y.dtype)
+    td = (y - targets.detach()) * m
+    return (td ** 2).sum() / m.sum(), y.detach().mean(), targets.mean()
+
+
+def _unit_step_rows(x):
+    """x [B, T, 1] -> (float32 tensor whose steps are adjacent elements, its batch stride): views pass as they are."""
+    x = x.detach()
+    if x.dtype != torch.float32:
+        x = x.float()
+    B, T = x.shape[0], x.shape[1]
+    if (T > 1 and x.stride(1) != 1) or (B > 1 and x.stride(0) < T):
+        x = x.contiguous()
+    return x, (x.stride(0) if B > 1 else T)
+
+
+class _TdLambdaHip(torch.autograd.Function):
+    """y, tq [B, Tm1, 1] (views with adjacent steps are read in place); reward / terminated / filled [B, Tm1, 1] views.
+    One launch: loss, the logged means, dL/dy (saved for backward) and the returns."""
+
+    @staticmethod
+    def forward(ctx, y, tq, reward, terminated, filled, gamma, lam):
+        lib = _native.load()
+        B, Tm1 = y.shape[0], y.shape[1]
+        (yc, y_sb), (tqc, tq_sb) = _unit_step_rows(y), _unit_step_rows(tq)
+        stats = torch.empty(4, dtype=torch.float32, device=yc.device)
+        gy = torch.empty((B, Tm1, 1), dtype=torch.float32, device=yc.device)
+        ret = torch.empty((B, Tm1, 1), dtype=torch.float32, device=yc.device)
+        io = _native.TdLambdaIO()
+        td = io.td
+        td.B, td.Tm1, td.gamma = B, Tm1, float(gamma)
+        td.y, td.y_sb, td.tq, td.tq_sb = yc.data_ptr(), y_sb, tqc.data_ptr(), tq_sb
+        td.gy, td.gy_sb, td.gy_cols = gy.data_ptr(), Tm1, Tm1
+        td.reward, td.r_sb, td.r_st = reward.data_ptr(), reward.stride(0), reward.stride(1)
+        td.terminated, td.t_sb, td.t_st = terminated.data_ptr(), terminated.stride(0), terminated.stride(1)
+        td.filled, td.f_sb, td.f_st = filled.data_ptr(), filled.stride(0), filled.stride(1)
+        td.stats = stats.data_ptr()
+        io.lam, io.ret, io.ret_sb = float(lam), ret.data_ptr(), Tm1
+        with torch.cuda.device(yc.device):
+            _native.check(lib.macjd_td_lambda_loss(ctypes.byref(io), _stream(yc)), "macjd_td_lambda_loss")
+        ctx.save_for_backward(gy)
+        ctx.mark_non_differentiable(stats)
+        stats.saved_gy, stats.saved_ret = gy, ret      # plain attributes (autograd does not look at them)
+        return stats[0], stats
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_stats):
+        (gy,) = ctx.saved_tensors
+        return gy * g_loss, None, None, None, None, None, None
+
+
+def _td_lambda_on_device(y, reward, terminated, filled):
+    return (y.is_cuda and reward.dtype == torch.float32 and terminated.dtype == torch.bool and filled.dtype == torch.bool
+            and y.shape[1] > 0)
+
+
+def td_lambda_loss(y, tq, reward, terminated, filled, gamma, lam):
+    """(loss, mean(y), mean(G)) against lambda-returns, loss differentiable in y.  One fused launch on a HIP device; the
+    stock-torch form under the conditions under which ``td_loss`` takes its own."""
+    if not _td_lambda_on_device(y, reward, terminated, filled):
+        return td_lambda_reference(y, tq, reward, terminated, filled, gamma, lam)
+    loss, stats = _TdLambdaHip.apply(y, tq, reward, terminated, filled, gamma, lam)
+    return loss, stats[1], stats[2]
+
+
+def td_lambda_returns(tq, reward, terminated, filled, gamma, lam):
+    """The lambda-returns G [B, Tm1, 1] themselves (the same launch on a HIP device: the returns do not depend on y)."""
+    if not _td_lambda_on_device(tq, reward, terminated, filled):
+        return _lambda_returns_reference(tq, reward, terminated, filled, gamma, lam).detach()
+    with torch.no_grad():
+        _, stats = _TdLambdaHip.apply(tq, tq, reward, terminated, filled, gamma, lam)
+    return stats.saved_ret
+
+
+# ---------------------------------------------------------------------------------------------
 # Fused clip_grad_norm_ + Adam on flat vectors (reference core/qmix.py:199-200)
 def _sampler_io(idx_out, n_stored, counter, seed, offset=0):
     assert idx_out.dtype == torch.int64 and idx_out.is_contiguous() and n_stored.dtype == torch.int32 and counter.dtype == torch.int64
